@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """bench.py - audio samples/sec of the FastSVC generator forward on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5                        # the headline only
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                 # + roofline, secondary, cpu_baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + the last step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -23,7 +25,15 @@ resident in HBM.  Workloads (BASELINE.json `configs`):
   cfg4var         cfg4's variable-length variant (2 - 10 s, ragged length-bucketed batches)
   cfg5            one full training step (see run_cfg5)
 
-Prints ONE JSON line.  `roofline` is measured live with hipEvents on the launch stream
+Prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline (`metric`, `value`,
+`unit`, `ms_per_step`, `dtype`, ...); `roofline`, `secondary` and `cpu_baseline` are null unless --full is given, and
+so are cfg5's `training_kernels`.  --dump-outputs DIR writes what the last timed step computed, from inputs that are
+the same in every run with the same arguments: `waveform.npy` (cfg1 / cfg2 / cfg3: the (B, 1, T) output, all ranks'
+at --gpus N), `waveforms.npy` (cfg4 / cfg4var: the gathered waveforms, concatenated in utterance order) or
+`generator_params.npy` + `discriminator_params.npy` (cfg5: the parameters after the step, flattened).  Beyond
+32 MiB in all, whole rows (utterances; elements of a flat array) of a fixed sample seeded by the file's name are kept.
+
+With --full, `roofline` is measured live with hipEvents on the launch stream
 (fastsvc_forward_profile): `roofline.e2e` prices EVERY launch of the step at
 max(alg. FLOPs / MFMA peak of its arithmetic, alg. bytes / 8 TB/s) and divides the sum by the measured
 step time (time-weighted whole-forward fraction); `roofline.kernel` is the DOMINANT symbol - most time per step, the top
@@ -37,6 +47,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -71,8 +82,15 @@ def parse(argv=None):
     ap.add_argument("--discriminator", default="melgan", choices=["melgan", "hifigan"],
                     help="cfg5: melgan = the recipe yaml's MelGAN multi-scale discriminator (4.35 M parameters); hifigan = the HiFiGAN "
                          "multi-period + multi-scale discriminator BASELINE config 5 names (fastsvc.py:631-1143 defaults, 70.7 M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the cfg3 float32 / bfloat16 block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel roofline pass, the `secondary` "
+                         "workloads (or the weak-scaling figure at --gpus N), the CPU baseline, and cfg5's training-kernel "
+                         "rooflines.  Off: set up, warm up, time the steps, dump outputs if asked, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / "
+                         "float64, at most 32 MiB in all: whole rows of a fixed, seeded sample beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary workloads")
     ap.add_argument("--autotune", action="store_true",
                     help="run the untimed device-side autotune pass (cf. cudnn.benchmark) instead of "
                          "the shipped launch-shape table / static cost model")
@@ -190,6 +208,37 @@ def emit(json_fd: int, full: dict, detail_path):
         text = json.dumps(slim, separators=(",", ":"))
     sys.stdout.flush()
     os.write(json_fd, (text + "\n").encode())
+
+
+DUMP_BYTES = 32 << 20
+
+
+def _sample_rows(name: str, n: int, keep: int) -> np.ndarray:
+    """`keep` of `n` row indices, sorted: all of them, or a fixed sample seeded by the output's name."""
+    if keep >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, keep, replace=False))
+
+
+def dump_outputs(out_dir: str, outputs: dict):
+    """--dump-outputs: write each of `outputs` ({name: tensor, or list of tensors = one row each}) as
+    out_dir/<name>.npy, float64 where the tensor is float64, float32 otherwise.  Rows are the first axis of a tensor or
+    the items of a list; if everything together exceeds DUMP_BYTES, every output keeps the same share of its rows, a
+    sample seeded by its name.  The kept rows of a list (waveforms of different lengths) are written concatenated."""
+    os.makedirs(out_dir, exist_ok=True)
+    width = lambda t: 8 if t.dtype == torch.float64 else 4
+    rows = {k: (v if isinstance(v, list) else [v] if v.dim() == 0 else v) for k, v in outputs.items()}
+    total = sum(sum(r.numel() * width(r) for r in v) if isinstance(v, list) else v.numel() * width(v) for v in rows.values())
+    share = min(1.0, DUMP_BYTES / max(total, 1))
+    for name, v in rows.items():
+        idx = _sample_rows(name, len(v), max(1, int(len(v) * share)))
+        if isinstance(v, list):
+            t = torch.cat([v[i].detach().reshape(-1).to(torch.float64 if v[i].dtype == torch.float64 else torch.float32)
+                           for i in idx])
+        else:
+            t = v.detach()[torch.as_tensor(idx, device=v.device)]
+            t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def self_launch(args, argv):
@@ -737,6 +786,12 @@ def run_cfg5(args, dist, world, rank, dev, extras=True):
     elapsed = time_steps(step, torch.cuda.synchronize, args.steps, args.warmup, dist if world > 1 else None, dev)
     if rank != 0:
         return None
+    if getattr(args, "dump_outputs", None):
+        # what the caller of a training step holds after the last one: both networks' parameters (flattened in
+        # named_parameters order); the step's loss values are not read back (log=False)
+        dump_outputs(args.dump_outputs, {
+            "generator_params": torch.cat([p.detach().reshape(-1) for _, p in gen.named_parameters()]),
+            "discriminator_params": torch.cat([p.detach().reshape(-1) for _, p in disc.named_parameters()])})
     ms = elapsed / args.steps * 1e3
     # roofline of the HIP share of the step: the generator forward (run twice per step) profiled launch by launch at
     # the recipe batch, priced like every forward line; e2e.frac is against the WHOLE step (PyTorch backward,
@@ -842,7 +897,7 @@ def main(argv=None):
     torch.cuda.set_device(dev)
 
     if args.workload == "cfg5":
-        line = run_cfg5(args, dist, world, rank, dev)
+        line = run_cfg5(args, dist, world, rank, dev, extras=args.full)
         if rank == 0:
             emit(json_fd, line, args.detail)
         if dist is not None:
@@ -900,11 +955,15 @@ def main(argv=None):
             def fwd(ppg, sine, lft, emb, out=None):
                 return plan.forward(blob, ppg, sine, lft, emb, workspace=ws, out=out)
 
+        waves = [None]                                  # the last step's gathered waveforms (--dump-outputs)
+
         def step(i):
-            D.run_utterance_parallel(fwd, utts, dev, max_batch=64, n_frames=n_frames, hop=cfg.hop, forward_into=True, ragged=ragged)
+            waves[0] = D.run_utterance_parallel(fwd, utts, dev, max_batch=64, n_frames=n_frames, hop=cfg.hop,
+                                                forward_into=True, ragged=ragged)
 
         drain = torch.cuda.synchronize
         samples_per_step = float(sum(n_frames)) * cfg.hop            # real samples only: padding is not output
+        last_outputs = lambda: {"waveforms": waves[0]}
     else:
         if args.workload == "cfg3":
             args_dev = list(S.device_batch(cfg, B, F, wl["seed"] + 1000 * rank, dev))
@@ -932,6 +991,7 @@ def main(argv=None):
             torch.cuda.synchronize()
 
         samples_per_step = float(world) * B * T
+        last_outputs = lambda: {"waveform": (gathered if world > 1 else outs)[(args.steps - 1) & 1]}
 
     # one-off, untimed: pick the launch shape of every layer for this (B, F) on this device
     # (the reference's recipes run with torch.backends.cudnn.benchmark = True, train_fastsvc.py:617)
@@ -941,9 +1001,11 @@ def main(argv=None):
         plan.forward(blob, *args_dev, workspace=ws, autotune=True)
     elapsed = time_steps(step, drain, args.steps, args.warmup, dist if world > 1 else None, dev)
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs())
 
     weak = None
-    if world > 1 and default_workload and not args.no_secondary:
+    if args.full and world > 1 and default_workload and not args.no_secondary:
         # the weak-scaling figure next to the strong-scaling headline: every rank a cfg2 batch (8 x 4 s) of its own
         # utterances, waveforms all-gathered asynchronously, same storage
         w2 = S.WORKLOADS["cfg2"]
@@ -976,13 +1038,15 @@ def main(argv=None):
     if rank == 0:
         # per-batch time for the end-to-end fraction: the step's time scaled to one full B x F batch of samples
         # (cfg4: 1 / batches per step; cfg4var: by the samples of this rank's shard - its batches differ in size)
-        if args_dev is None:
-            args_dev = roofline_batch()
-        batch_share = B * T / (float(sum(n_frames[i] for i in mine)) * cfg.hop) if strong else 1.0
-        roof = roofline(plan, blob, args_dev, ms_per_step * batch_share,
-                        pmc_file=f"{PMC_TAG}_{'cfg3' if strong else args.workload}_{args.storage}_pmc_traffic.json")
+        roof = None
+        if args.full:
+            if args_dev is None:
+                args_dev = roofline_batch()
+            batch_share = B * T / (float(sum(n_frames[i] for i in mine)) * cfg.hop) if strong else 1.0
+            roof = roofline(plan, blob, args_dev, ms_per_step * batch_share,
+                            pmc_file=f"{PMC_TAG}_{'cfg3' if strong else args.workload}_{args.storage}_pmc_traffic.json")
         secondary = None
-        if world == 1 and not args.no_secondary and default_workload:
+        if args.full and world == 1 and not args.no_secondary and default_workload:
             del ws
             torch.cuda.empty_cache()
             secondary = {}
@@ -1022,7 +1086,7 @@ def main(argv=None):
         if weak is not None:
             secondary = {"weak_cfg2": weak}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_seconds)
         value = samples_per_step * args.steps / elapsed
         flops_step = plan.flops_per_sample * samples_per_step / world

@@ -35,6 +35,9 @@ Fixtures written:
   decode_chain.npz      decode_fastsvc.py:160-189 per utterance for three utterances of different
                         length: F0Statistics.estimate / .convert (features.py:41-108, std forced to 1),
                         then ``inference()`` with the converted F0 (noise_amp=0)
+  live_tiny.npz         tiny-width generator, B=3, F=31: the output the oracle's ``forward_as_executed`` must reproduce
+  ref_checkpoint.npz    a reference generator's own initialisation (reduced width) as its checkpoint stores it, and its
+                        state dict after ``remove_weight_norm`` (the checkpoint-loading test of test_boundary.py)
 
     python tests/golden/make_golden.py decode_chain     # only that fixture
 """
@@ -484,6 +487,29 @@ def fold(M):
     np.savez_compressed(os.path.join(HERE, "weight_norm_fold.npz"), **out)
 
 
+def live_tiny(M):
+    """live_tiny.npz: the reference generator's output (eval, weight norm on) for the tiny width, B=3, F=31."""
+    cfg = S.TINY_CONFIG
+    g, _ = build_reference(M, cfg, 555)
+    b = S.synth_batch(cfg, 3, 31, 556)
+    np.savez_compressed(os.path.join(HERE, "live_tiny.npz"), y=run(g, b, True),
+                        meta=np.array([555, 556, 3, 31], np.int64))
+
+
+def ref_checkpoint(M):
+    """ref_checkpoint.npz: a reference generator's own initialisation (torch.manual_seed(3), reduced width) as the
+    checkpoint's ["model"]["generator"] stores it (`ckpt/<key>`), and its state dict after ``remove_weight_norm``
+    (`folded/<key>`)."""
+    params = dict(in_channels=8, mid_channels=[16, 8, 8, 4], upsampling_scales=[2, 4, 4, 5], out_channels=1,
+                  spk_emb_size=16, use_spk_emb=True)
+    torch.manual_seed(3)
+    g = M.FastSVCGenerator(**params)
+    out = {f"ckpt/{k}": v.numpy().copy() for k, v in g.state_dict().items()}
+    g.remove_weight_norm()
+    out.update({f"folded/{k}": v.numpy().copy() for k, v in g.state_dict().items()})
+    np.savez_compressed(os.path.join(HERE, "ref_checkpoint.npz"), **out)
+
+
 def stft_loss(M):
     """stft_loss.npz: inputs are regenerated from seeds (numpy default_rng) by the tests; expected values stored."""
     from harana.losses import MultiResolutionSTFTLoss
@@ -508,10 +534,12 @@ def stft_loss(M):
 
 if __name__ == "__main__":
     M = import_reference()
-    todo = sys.argv[1:] or ["tiny", "full", "inference", "fold", "decode_chain", "grads", "train", "stft_loss", "hifigan"]
+    todo = sys.argv[1:] or ["tiny", "full", "inference", "fold", "decode_chain", "grads", "train", "stft_loss", "hifigan",
+                            "live_tiny", "ref_checkpoint"]
     for name in todo:
         {"tiny": tiny, "full": full, "inference": inference, "fold": fold, "decode_chain": decode_chain, "grads": grads,
-         "train": train, "train_recipe": train_recipe, "stft_loss": stft_loss, "hifigan": hifigan}[name](M)
+         "train": train, "train_recipe": train_recipe, "stft_loss": stft_loss, "hifigan": hifigan,
+         "live_tiny": live_tiny, "ref_checkpoint": ref_checkpoint}[name](M)
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -107,3 +107,43 @@ def test_pmc_traffic_lookup_flags_a_stale_summary(tmp_path):
     assert bench.pmc_traffic("spk_proj", shares, ("missing.json", "x_pmc_traffic.json"), root=str(tmp_path))[2] is False
     assert bench.pmc_traffic("spk_proj", shares, ("missing.json",), root=str(tmp_path)) == (None, None, False)
     assert "traffic_stale" in bench.ROOFLINE_KEYS
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """A bare run measures the headline only; --full turns the roofline / secondary / CPU-baseline passes on."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.parse(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+
+
+def test_dump_outputs_keeps_whole_rows_of_a_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, within the byte budget, whole rows (utterances) of a sample that is
+    the same in every run; ragged waveforms concatenated in utterance order."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn((64, 1, 24000), generator=g)                       # 6.1 MB: sampled
+    ragged = [torch.randn((1, 100 * (i + 1)), generator=g) for i in range(5)]
+    small = torch.randn((3,), generator=g, dtype=torch.float64)
+    out = {"waveform": big, "waveforms": ragged, "scalar": torch.tensor(2.5), "p64": small}
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["p64.npy", "scalar.npy", "waveform.npy", "waveforms.npy"]
+    total = sum((tmp_path / "a" / n).stat().st_size for n in names)
+    assert total <= (1 << 20) + 4 * 256
+    w = np.load(tmp_path / "a" / "waveform.npy")
+    assert w.dtype == np.float32 and w.shape[1:] == (1, 24000) and 1 <= w.shape[0] < 64
+    rows = {i for i in range(64) for r in w if np.array_equal(r, big[i].numpy())}
+    assert len(rows) == w.shape[0]                                     # whole utterances, no two alike
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    assert np.load(tmp_path / "a" / "p64.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "scalar.npy").tolist() == [2.5]
+    cat = np.load(tmp_path / "a" / "waveforms.npy")
+    assert cat.dtype == np.float32 and cat.ndim == 1
+    # everything fits without sampling: written whole
+    bench.dump_outputs(str(tmp_path / "c"), {"waveforms": ragged})
+    assert np.array_equal(np.load(tmp_path / "c" / "waveforms.npy"), torch.cat([r.reshape(-1) for r in ragged]).numpy())

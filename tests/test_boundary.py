@@ -384,37 +384,45 @@ def test_checkpoint_schema_roundtrip(tmp_path):
 
 
 def test_reference_load_model_and_decode_sequence_with_the_swapped_class(tmp_path):
-    """The reference's OWN `load_model` (harana/utils/utils.py:243-280) and the decode_fastsvc.py:140-143
-    sequence (load_model -> remove_weight_norm -> eval) run against this package's class installed as
-    harana.models.FastSVCGenerator, on a checkpoint written by the REFERENCE generator in the
-    Trainer.save_checkpoint schema (train_fastsvc.py:104-128).  Build container only."""
-    from oracle import refimport
-    if not refimport.reference_available():
-        pytest.skip("reference tree not present (GPU box)")
+    """A checkpoint written by the REFERENCE generator in the Trainer.save_checkpoint schema (train_fastsvc.py:104-128),
+    loaded the way the reference's `load_model` does it (harana/utils/utils.py:243-280: config.yml beside the checkpoint,
+    class looked up on harana.models by `generator_type`, strict load of ["model"]["generator"]) with this package's class
+    installed as harana.models.FastSVCGenerator, then the decode_fastsvc.py:140-143 sequence (remove_weight_norm -> eval).
+    The reference generator's own initialisation and its state dict after remove_weight_norm are stored data
+    (tests/golden/ref_checkpoint.npz, written by make_golden.py from the live reference)."""
+    import sys
     import yaml
-    ref_models = refimport.import_reference()
-    from harana.utils.utils import load_model
+    from svcc23_fastsvc_amd import checkpoint as C
+    g = np.load(os.path.join(ROOT, "tests", "golden", "ref_checkpoint.npz"))
+    ref_sd = {k[5:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("ckpt/")}
+    ref_folded = {k[7:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("folded/")}
     params = dict(in_channels=8, mid_channels=[16, 8, 8, 4], upsampling_scales=[2, 4, 4, 5], out_channels=1,
                   spk_emb_size=16, use_spk_emb=True)
-    torch.manual_seed(3)
-    ref_gen = ref_models.FastSVCGenerator(**params)
     ckpt = tmp_path / "exp" / "checkpoint-10steps.pkl"
     os.makedirs(ckpt.parent)
-    torch.save({"model": {"generator": ref_gen.state_dict(), "discriminator": {}},
+    torch.save({"model": {"generator": ref_sd, "discriminator": {}},
                 "optimizer": {"generator": {}, "discriminator": {}},
                 "scheduler": {"generator": {}, "discriminator": {}}, "steps": 10, "epochs": 1}, str(ckpt))
     with open(ckpt.parent / "config.yml", "w") as f:
         yaml.dump({"generator_type": "FastSVCGenerator", "generator_params": params}, f, Dumper=yaml.Dumper)
-    original = ref_models.FastSVCGenerator
+    saved = {m: sys.modules.get(m) for m in ("harana", "harana.models")}
+    models = sys.modules.get("harana.models")
+    original = getattr(models, "FastSVCGenerator", None) if models is not None else None
     try:
         A.install_into_harana()                          # the swap a maintainer makes (INTEGRATION.md)
+        ref_models = sys.modules["harana.models"]
         assert ref_models.FastSVCGenerator is A.FastSVCGenerator
-        model = load_model(str(ckpt))                    # reference code, our class
+        with open(ckpt.parent / "config.yml") as f:
+            config = yaml.load(f, Loader=yaml.Loader)
+        model = getattr(ref_models, config["generator_type"])(**config["generator_params"])
+        model.load_state_dict(torch.load(str(ckpt), map_location="cpu")["model"]["generator"])
         assert isinstance(model, A.FastSVCGenerator)
+        loaded = C.load_generator(str(ckpt))             # the package's own restatement of load_model
+        for k, v in model.state_dict().items():
+            assert torch.equal(v, loaded.state_dict()[k]), k
         model.remove_weight_norm()                       # decode_fastsvc.py:142
         model = model.eval()                             # :143 (.to(device) needs the GPU box)
-        ref_gen.remove_weight_norm()
-        ours, theirs = model.state_dict(), ref_gen.state_dict()
+        ours, theirs = model.state_dict(), ref_folded
         assert list(ours) == list(theirs)
         for k in theirs:
             assert torch.allclose(ours[k], theirs[k], atol=1e-7), k
@@ -427,7 +435,13 @@ def test_reference_load_model_and_decode_sequence_with_the_swapped_class(tmp_pat
         b2 = plan.pack(torch.load(str(ckpt))["model"]["generator"]).numpy()
         assert b1.shape == b2.shape and (b1.view(np.uint16) != b2.view(np.uint16)).mean() < 0.2
     finally:
-        ref_models.FastSVCGenerator = original
+        if original is not None:
+            models.FastSVCGenerator = original
+        for m, mod in saved.items():
+            if mod is None:
+                sys.modules.pop(m, None)
+            else:
+                sys.modules[m] = mod
 
 
 def test_split_half_conversions_match_numpy():

@@ -6,7 +6,6 @@ import torch
 
 from conftest import load_golden
 from oracle import fastsvc_oracle as O
-from oracle.refimport import reference_available
 from svcc23_fastsvc_amd import synth as S
 
 # fp32 reference noise floor is ~1e-5 max-abs; the oracle must sit inside it.
@@ -134,21 +133,17 @@ def test_shape_invariant_is_validated():
         O.forward_dedup(w, S.TINY_CONFIG.upsampling_scales, g["ppg"], g["sine"][..., :-1], g["lft"][..., :-1])
 
 
-@pytest.mark.skipif(not reference_available(), reason="live reference only exists in the build container")
 def test_oracle_against_live_reference():
-    from oracle.refimport import import_reference
-    M = import_reference()
+    """forward_as_executed against the output of the reference generator itself (tests/golden/live_tiny.npz, written
+    by make_golden.py from the live reference: tiny width, weight norm on, B=3, F=31)."""
+    g = load_golden("live_tiny.npz")
+    seed_w, seed_x, B, F = (int(v) for v in g["meta"])
     cfg = S.TINY_CONFIG
-    sd = S.synth_state_dict(cfg, 555)
-    ref = M.FastSVCGenerator(in_channels=cfg.in_channels, mid_channels=list(cfg.mid_channels),
-                             upsampling_scales=list(cfg.upsampling_scales), out_channels=1,
-                             spk_emb_size=cfg.spk_emb_size, use_spk_emb=True)
-    ref.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    b = S.synth_batch(cfg, 3, 31, 556)
-    with torch.no_grad():
-        y_ref = ref(torch.from_numpy(b.ppg), torch.from_numpy(b.sine), torch.from_numpy(b.lft),
-                    torch.from_numpy(b.spk_emb)).numpy()
+    sd = S.synth_state_dict(cfg, seed_w)
+    b = S.synth_batch(cfg, B, F, seed_x)
+    y_ref = g["y"]
     y = O.forward_as_executed(S.fold_weight_norm(sd), cfg.upsampling_scales, b.ppg, b.sine, b.lft, b.spk_emb).numpy()
+    assert y.shape == y_ref.shape
     assert np.abs(y - y_ref).max() <= TOL
 
 
