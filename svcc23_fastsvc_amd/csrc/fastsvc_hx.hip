@@ -1083,7 +1083,7 @@ void conv_hx_kernel(const ConvParams p0) {
                 pos_next(xl_tl, xl_ch);
                 const int t_start = (tile0 + tl) * NT - halo_al;                  // >= -8
                 const int j = ((((t_start + 8 * S) / S) - 8) & ~3) + 4 * xg4;     // floor(t_start / S), down to a multiple of 4
-                // (row ends are multiples of 4 in these instances: a group lies inside the utterance or outside it)
+                // (row ends are multiples of 4 in these instances - conv_hx_x2_rows_ok: a group lies inside the utterance or outside it)
                 const bool ok = ((unsigned)j < (unsigned)x2T) & (un < nunits);
                 const int rows_left = p.CIN - ch * HX_KC;
                 #pragma unroll
@@ -1896,6 +1896,7 @@ static hipError_t hx_launch_shape(const ConvParams& p, int nsig, hipStream_t str
             if (kind != EPI_AFF || p.res || p.x2_T * p.s2 != p.T || (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)))
                 return hipErrorInvalidValue;
             if (w8 && p.s2 == 2 && W / p.s2 + 5 > 128) return hipErrorInvalidValue;   // (the second operand's 32 groups of 4 columns per tile)
+            if (w8 && !conv_hx_x2_rows_ok(p)) return hipErrorInvalidValue;
 #define FASTSVC_HXX(sv, stat) if (p.s2 == sv) return hx_launch_instance<&conv_hx_kernel<MW, NW, WM, WN, MODE_DIRECT, EPI_AFF, sv, stat>>(grid, smem + est, stream, p);
             if constexpr (MW * NW <= 12) {                                         // (larger tiles spill with this epilogue)
                 if constexpr (MW == 2) { if (p.nch32 == 1) { FASTSVC_HXX(5, true) } }
@@ -1958,6 +1959,7 @@ hipError_t launch_conv_hx(const ConvParams& p, const ConvLaunch& cfg, hipStream_
 
 #ifndef FASTSVC_ACT_BF16      // storage-independent host query: defined once
 bool conv_hx_x2_ok(int MW, int nch32, int s2) { return MW == 2 ? (nch32 == 1 && s2 == 5) : MW == 3 ? (s2 == 2 || s2 == 4) : false; }
+bool conv_hx_x2_rows_ok(const ConvParams& p) { return p.s2 != 2 || ((p.lens ? p.x2len_mul : p.x2_T) & 3) == 0; }
 bool conv_hx_tail_ok(int mode, int MW, int epi_kind, int S) { return hx_tail_instance(MW, mode, epi_kind, S); }
 
 bool conv_hx_shape(int mode, int MW, int NW, int WM, int WN) {

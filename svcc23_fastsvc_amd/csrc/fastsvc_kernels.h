@@ -300,12 +300,22 @@ bool conv_hx_tail_ok(int mode, int MW, int epi_kind, int S);
 // whether the MODE_DIRECT instances with a second, stretched operand (ConvParams::x2) exist for this channel-tile count,
 // number of K chunks and stretch factor
 bool conv_hx_x2_ok(int MW, int nch32, int s2);
+// ... and whether the 16-byte-window instances (bfloat16 storage) may take this launch's second operand: at S = 2 they
+// request 4 of its columns at once and test the row end once per group, so its rows (every utterance's own row of a
+// ragged batch: lens[b] * x2len_mul) must be a multiple of 4 long - else the columns past the end reach the last outputs
+bool conv_hx_x2_rows_ok(const ConvParams& p);
 
 // the wide-layer kernel in which every wave multiplies (fastsvc_wx.hip): MODE_DIRECT, 48-channel groups (MW = 3), the
 // weights once per workgroup and unit through LDS; bfloat16 storage.  cfg.pipe is ignored; same ConvParams as launch_conv_hx.
 hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream);
 bool conv_wx_shape(int mode, int MW, int NW, int WM, int WN);
 bool conv_wx_fits(int nch32, int dil);      // window buffers + two units of weights + patches fit the CU's LDS
+// whether launch_conv_wx has an instance for this launch, whatever its workgroup shape: a direct k = 3 conv without a
+// second operand, rank-1 term, fused conv_last, split input or input affine; rows a multiple of 4 long (each utterance's
+// own row of a ragged batch); C_in a multiple of 8 and <= WX_NT (= 512) channels; dilation 1..28; the LDS fit; and a
+// compiled (prologue, epilogue) pair - a FiLM-affine epilogue only behind the InstanceNorm prologue.  p.nch32 / p.dil /
+// p.CIN / p.flags must be set.  The route (run_conv) asks the same before it offers the kernel a launch.
+bool conv_wx_supported(const ConvParams& p);
 
 // down-sampling stage 0, first conv (C_in = 1, k = 3, d = 1, LeakyReLU on the input):
 //   y[sig][b][co][t] = bias[co] + sum_tap w[co][tap] * lrelu(x[sig][b][t + tap - 1])

@@ -1700,7 +1700,8 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
     p.ldx = p.x_T; p.ldy = p.T; p.ldx2 = p.x2_T;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; p.x2len_mul = p.x2_T / p.frames_ld; }
     if (!hx_env || !x_env || g_exact_f32 || p.no_hx || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T || (long)p.x2_T * p.s2 != p.T ||
-        (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)) || !conv_hx_x2_ok(c.MW, c.nch32, p.s2) || c.dil > 28)
+        (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)) || !conv_hx_x2_ok(c.MW, c.nch32, p.s2) || c.dil > 28 ||
+        (act_bf16 && !conv_hx_x2_rows_ok(p)))
         return hipSuccess;
     p.mode = MODE_DIRECT; p.s = 1;
     p.CIN = c.cin; p.KC = c.KC; p.nchunks = c.nchunks; p.w = blob + c.w_off; p.Q = c.Q;
@@ -2158,8 +2159,10 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         // the 48-channel-group layers (C >= 96) in bfloat16 storage with a plain / residual / FiLM-affine epilogue.
         // FASTSVC_WX = 0: off, 2: wherever it exists (A/B, tests), else by the launch table / tuning
         static const int wx_env = std::getenv("FASTSVC_WX") ? std::atoi(std::getenv("FASTSVC_WX")) : 1;
-        const bool wx_ok = hx_ok && wx_env != 0 && act_bf16 && p.mode == MODE_DIRECT && c.MW == 3 && !ragged_tail && !p.last_w &&
-                           !p.r1x && !p.x2 && !p.xsplit && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4);
+        ConvParams pw = p;
+        pw.nch32 = c.nch32;                              // (what geometry() sets for the candidate)
+        const bool wx_ok = hx_ok && wx_env != 0 && act_bf16 && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
+                           conv_wx_supported(pw);
         bool wx_have = false;                            // ... and the layer has a shape of it
         if (wx_ok) {
             static const int wshapes[][3] = {{6, 4, 2}};

@@ -534,18 +534,17 @@ hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_
 #ifndef FASTSVC_ACT_BF16
     return hipErrorInvalidValue;                               // (float32 storage: not built)
 #else
-    if (p.mode != MODE_DIRECT || p.ntaps != 3 || (p.T & 3) || !p.whx || p.nch32 * HX_KC > WX_NT || p.dil < 1 || p.dil > 28 ||
-        p.x2 || p.r1x || p.last_w || p.xsplit || (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)) || (p.CIN & 7) ||
-        (p.flags & F_PRE_AFFINE) || cfg.MW != WX_MW || cfg.NW != WX_NW || cfg.WM != WX_WM || cfg.WN != WX_WN || p.ngroups % WX_WM != 0)
+    if (!conv_wx_supported(p) || (p.T & 3) || !p.whx || cfg.MW != WX_MW || cfg.NW != WX_NW || cfg.WM != WX_WM || cfg.WN != WX_WN ||
+        p.ngroups % WX_WM != 0)
         return hipErrorInvalidValue;
     const size_t smem = wx_smem(p);
-    if (smem + WX_STATIC_LDS > 160 * 1024) return hipErrorInvalidValue;
     const int ntx = (p.T + WX_TILE - 1) / WX_TILE;
     const int tpw = p.tpw > 0 ? p.tpw : 1;
     dim3 grid((ntx + tpw - 1) / tpw, p.ngroups / WX_WM, cfg.nsig * p.B);
     const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
     const int kind = aff ? EPI_AFF : p.res ? EPI_RES : EPI_PLAIN;
     const int pro = (p.flags & F_PRE_NORM) ? 2 : (p.flags & F_PRE_LRELU) ? 1 : 0;
+    // (the instances conv_wx_supported admits)
 #define FASTSVC_WX(pr, k) if (pro == pr && kind == k) return wx_launch_instance<&conv_wx_kernel<pr, k>>(grid, smem, stream, p);
     FASTSVC_WX(0, EPI_PLAIN) FASTSVC_WX(0, EPI_RES)
     FASTSVC_WX(1, EPI_PLAIN) FASTSVC_WX(1, EPI_RES)
@@ -558,6 +557,15 @@ hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_
 #ifndef FASTSVC_ACT_BF16      // storage-independent host queries: defined once
 bool conv_wx_shape(int mode, int MW, int NW, int WM, int WN) {
     return mode == MODE_DIRECT && MW == WX_MW && NW == WX_NW && WM == WX_WM && WN == WX_WN;
+}
+bool conv_wx_supported(const ConvParams& p) {
+    if (p.mode != MODE_DIRECT || p.ntaps != 3 || p.nch32 * HX_KC > WX_NT || p.dil < 1 || p.dil > 28 || p.x2 || p.r1x ||
+        p.last_w || p.xsplit || (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)) || (p.CIN & 7) || (p.flags & F_PRE_AFFINE))
+        return false;
+    if (wx_smem(p, 1) + WX_STATIC_LDS > 160 * 1024) return false;
+    // compiled (prologue, epilogue) pairs: {none, LeakyReLU, norm + LeakyReLU} x {plain, residual}, (norm + LeakyReLU, FiLM affine)
+    const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
+    return !aff || (p.flags & F_PRE_NORM) != 0;
 }
 // whether the window buffers (dilation dil), the two units of weights and the patches fit the CU's LDS
 bool conv_wx_fits(int nch32, int dil) {

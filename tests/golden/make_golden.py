@@ -36,6 +36,8 @@ Fixtures written:
                         length: F0Statistics.estimate / .convert (features.py:41-108, std forced to 1),
                         then ``inference()`` with the converted F0 (noise_amp=0)
   live_tiny.npz         tiny-width generator, B=3, F=31: the output the oracle's ``forward_as_executed`` must reproduce
+  live_configs.npz      every generator of tests/config_matrix.py, B=2, F=9: the reference's output with a speaker
+                        embedding (`<name>/y`) and, where the generator has one, without (`<name>/y_nospk`)
   ref_checkpoint.npz    a reference generator's own initialisation (reduced width) as its checkpoint stores it, and its
                         state dict after ``remove_weight_norm`` (the checkpoint-loading test of test_boundary.py)
 
@@ -496,6 +498,21 @@ def live_tiny(M):
                         meta=np.array([555, 556, 3, 31], np.int64))
 
 
+def live_configs(M):
+    """live_configs.npz: the reference generator's output (eval, weight norm on) for every configuration of
+    tests/config_matrix.py, B=2, F=9, with and (where use_spk_emb) without a speaker embedding."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import config_matrix as CM
+    out = {"meta": np.array([CM.SEED_W, CM.SEED_X, CM.B, CM.F], np.int64)}
+    for name in CM.NAMES:
+        cfg = CM.config(name)
+        g, _ = build_reference(M, cfg, CM.SEED_W)
+        b = S.synth_batch(cfg, CM.B, CM.F, CM.SEED_X)
+        for spk in CM.speaker_modes(name):
+            out[f"{name}/y" if spk else f"{name}/y_nospk"] = run(g, b, spk)
+    np.savez_compressed(os.path.join(HERE, "live_configs.npz"), **out)
+
+
 def ref_checkpoint(M):
     """ref_checkpoint.npz: a reference generator's own initialisation (torch.manual_seed(3), reduced width) as the
     checkpoint's ["model"]["generator"] stores it (`ckpt/<key>`), and its state dict after ``remove_weight_norm``
@@ -535,11 +552,11 @@ def stft_loss(M):
 if __name__ == "__main__":
     M = import_reference()
     todo = sys.argv[1:] or ["tiny", "full", "inference", "fold", "decode_chain", "grads", "train", "stft_loss", "hifigan",
-                            "live_tiny", "ref_checkpoint"]
+                            "live_tiny", "live_configs", "ref_checkpoint"]
     for name in todo:
         {"tiny": tiny, "full": full, "inference": inference, "fold": fold, "decode_chain": decode_chain, "grads": grads,
          "train": train, "train_recipe": train_recipe, "stft_loss": stft_loss, "hifigan": hifigan,
-         "live_tiny": live_tiny, "ref_checkpoint": ref_checkpoint}[name](M)
+         "live_tiny": live_tiny, "live_configs": live_configs, "ref_checkpoint": ref_checkpoint}[name](M)
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

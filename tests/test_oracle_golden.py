@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import config_matrix as CM
 from conftest import load_golden
 from oracle import fastsvc_oracle as O
 from svcc23_fastsvc_amd import synth as S
@@ -145,6 +146,29 @@ def test_oracle_against_live_reference():
     y = O.forward_as_executed(S.fold_weight_norm(sd), cfg.upsampling_scales, b.ppg, b.sine, b.lft, b.spk_emb).numpy()
     assert y.shape == y_ref.shape
     assert np.abs(y - y_ref).max() <= TOL
+
+
+@pytest.mark.parametrize("name", CM.NAMES)
+def test_oracle_against_live_reference_on_the_config_matrix(name):
+    """forward_as_executed and forward_dedup against the reference generator's own output for every configuration the
+    GPU matrix runs (tests/config_matrix.py; tests/golden/live_configs.npz: weight norm on, B=2, F=9), with and - where
+    the generator has a speaker embedding - without one: the oracle those tests trust is pinned at their scales."""
+    g = load_golden("live_configs.npz")
+    seed_w, seed_x, B, F = (int(v) for v in g["meta"])
+    cfg = CM.config(name)
+    w = S.fold_weight_norm(S.synth_state_dict(cfg, seed_w))
+    b = S.synth_batch(cfg, B, F, seed_x)
+    checked = 0
+    for spk in CM.speaker_modes(name):
+        y_ref = g[f"{name}/y" if spk else f"{name}/y_nospk"]
+        assert y_ref.shape == (B, cfg.out_channels, F * cfg.hop)
+        scale = 1.0 if spk else max(1.0, float(np.abs(y_ref).max()))
+        for fn in (O.forward_as_executed, O.forward_dedup):
+            y = fn(w, cfg.upsampling_scales, b.ppg, b.sine, b.lft, b.spk_emb if spk else None).numpy()
+            assert y.shape == y_ref.shape
+            assert np.abs(y - y_ref).max() <= TOL * scale, (fn.__name__, spk, float(np.abs(y - y_ref).max()))
+            checked += 1
+    assert checked == 2 * len(CM.speaker_modes(name))
 
 
 @pytest.mark.parametrize("s", [2, 4, 5])
