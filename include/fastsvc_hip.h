@@ -84,7 +84,26 @@ void fastsvc_plan_destroy(fastsvc_plan* plan);
  * halves the traffic of the HBM-bound layers and the workspace; arithmetic (fp32 MFMA), weights,
  * InstanceNorm sums, inputs and output stay float32.  Accuracy is that of bf16 activations (about 1e-2
  * of the output range), so this is the mode for BASELINE config 3, not for the 1e-3 parity bar.
- * Set it before fastsvc_workspace_bytes / fastsvc_forward; needs F % 4 == 0 and the yaml channel counts. */
+ * Set it before fastsvc_workspace_bytes / fastsvc_forward; needs F % 4 == 0 and the yaml channel counts.
+ *
+ * 2 = float16 (IEEE binary16): the same tensors, the same 2 bytes per element (workspace size, layout, taps and
+ * HBM traffic are those of bfloat16 storage) with 11 significand bits instead of 8; one
+ * v_mfma_f32_16x16x32_f16 per product on binary16-rounded weights and activations, every store rounds to nearest
+ * even.  What stays float32 / float64 is what stays so in bfloat16 storage: accumulators, InstanceNorm sums, FiLM
+ * arithmetic, the inputs (ppg is copied to binary16 in the workspace; sine, lft, spk_emb are read as they are) and
+ * the output.  Accuracy (measured on an MI355X against the float64 oracle, DESIGN.md "float16 activation storage"):
+ * 8 x 600 frames of the yaml generator, mean-abs 8.7e-4 and max-abs 1.3e-2 on a waveform of range 4.1, i.e. 2.1e-4 /
+ * 3.1e-3 of the range - 7 to 8 times less than bfloat16 storage on the same inputs (6.8e-3 / 9.0e-2), about 30 PCM-16
+ * steps where bfloat16 storage is off by 220; float32 storage stays two orders of magnitude closer still.
+ * RANGE CONTRACT: the format is unscaled, so every workspace tensor of the call must stay below 65504 in magnitude,
+ * and values under 2^-14 lose relative precision (subnormals, floor 2^-24).  Outside the contract nothing faults and
+ * the call still returns FASTSVC_OK: an element past the ceiling is stored as an infinity, and infinities / NaNs
+ * propagate to the output; no state survives the call (the next forward on the same workspace is unaffected).
+ * The contract covers the WEIGHTS too: this mode multiplies unscaled binary16 copies of the folded weights, so a weight
+ * above 65504 in magnitude is packed as an infinity and weights under 2^-14 lose relative precision (float32 storage
+ * scales its binary16 weight pieces per output channel, bfloat16 has float32's range: neither has this limit).
+ * float32 storage (0) scales its binary16 operands by measured maxima and has no such contract; bfloat16 storage has
+ * float32's range.  Same needs as bfloat16 storage (F % 4 == 0, the yaml channel counts). */
 int fastsvc_plan_set_storage(fastsvc_plan* plan, int32_t dtype);
 int fastsvc_plan_get_storage(const fastsvc_plan* plan);
 
@@ -169,7 +188,8 @@ int fastsvc_autotune(const fastsvc_plan* plan, const void* dev_blob,
 
 /* Launch-shape table.  fastsvc_autotune stores its winners in the plan under keys
  * "<layer>|<B>|<T>" ("<layer>|<B>|<T>|b" while the plan uses bfloat16 activation storage, whose variants
- * compile under different register budgets); these entry points export them and load them back (a table measured once on an
+ * compile under different register budgets; "...|h" in float16 storage, whose instances have bfloat16's shapes and
+ * budgets: a float16 plan looks "|h" up first and falls back to the "|b" entry); these entry points export them and load them back (a table measured once on an
  * MI355X ships as svcc23_fastsvc_amd/tuned_mi355x.json, so production runs need no trial launches).
  * An entry whose shape is not compiled for that layer is ignored at launch time (cost model instead).
  *   fastsvc_tuned_count: number of entries;

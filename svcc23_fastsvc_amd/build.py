@@ -37,18 +37,22 @@ def needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-# (source, extra flags, object name): fastsvc_kernels.hip is compiled twice - float32 and bfloat16
-# activation storage (namespace fastsvc / fastsvc::bf16) - the objects are built in parallel
+# (source, extra flags, object name): the four convolution kernel files are compiled three times - float32, bfloat16
+# and binary16 activation storage (namespace fastsvc / fastsvc::bf16 / fastsvc::f16) - the objects are built in parallel
 UNITS = [
     ("fastsvc_kernels.hip", [], "kernels_f32.o"),
     ("fastsvc_kernels.hip", ["-DFASTSVC_ACT_BF16=1"], "kernels_bf16.o"),
+    ("fastsvc_kernels.hip", ["-DFASTSVC_ACT_F16=1"], "kernels_f16.o"),
     ("fastsvc_hx.hip", [], "hx_f32.o"),
     ("fastsvc_hx.hip", ["-DFASTSVC_ACT_BF16=1"], "hx_bf16.o"),
+    ("fastsvc_hx.hip", ["-DFASTSVC_ACT_F16=1"], "hx_f16.o"),
     ("fastsvc_wx.hip", [], "wx_f32.o"),
     ("fastsvc_wx.hip", ["-DFASTSVC_ACT_BF16=1"], "wx_bf16.o"),
+    ("fastsvc_wx.hip", ["-DFASTSVC_ACT_F16=1"], "wx_f16.o"),
     # (-fno-honor-nans: LeakyReLU as max(v, 0.2 v) without the canonicalising v_max v, v, v in front of it)
     ("fastsvc_cond.hip", ["-fno-honor-nans"], "cond_f32.o"),
     ("fastsvc_cond.hip", ["-fno-honor-nans", "-DFASTSVC_ACT_BF16=1"], "cond_bf16.o"),
+    ("fastsvc_cond.hip", ["-fno-honor-nans", "-DFASTSVC_ACT_F16=1"], "cond_f16.o"),
     ("fastsvc_plan.cpp", [], "plan.o"),
     ("fastsvc_signal.hip", [], "signal.o"),
     ("fastsvc_loudness.hip", [], "loudness.o"),

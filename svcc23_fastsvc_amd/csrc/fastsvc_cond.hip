@@ -28,14 +28,18 @@
 #include "fastsvc_kernels.h"
 
 namespace fastsvc {
-#ifdef FASTSVC_ACT_BF16
-namespace bf16 {
+#ifdef FASTSVC_ACT_2B
+namespace FASTSVC_ACT_NS {
 #endif
 
 #include "fastsvc_device.inc"
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
+#ifdef FASTSVC_ACT_F16
+typedef _Float16 cs_t;
+#else
 typedef __bf16 cs_t;
+#endif
 constexpr int CS_NP = 1;
 #else
 typedef _Float16 cs_t;
@@ -46,7 +50,7 @@ typedef cs_t cs4 __attribute__((ext_vector_type(4)));
 typedef unsigned cs_u2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f32x4 cs_mfma(cs8 a, cs8 b, f32x4 c) {
-#ifdef FASTSVC_ACT_BF16
+#if defined(FASTSVC_ACT_2B) && !defined(FASTSVC_ACT_F16)
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 #else
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
@@ -114,7 +118,7 @@ __device__ __forceinline__ f32x4 cs_lrelu4(f32x4 v) {
 // back, subtract, convert (e - hi is exact in float32), 1 instruction per value instead of 2.5 (same as hx_lo_pair of
 // fastsvc_hx.hip; the split is 40 % of a float32-storage epilogue's VALU work).
 __device__ __forceinline__ unsigned cs_lo_pair(unsigned hi_pair, float e0, float e1) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
     (void)hi_pair; (void)e0; (void)e1;
     return 0u;
 #else
@@ -357,7 +361,7 @@ void cond_stage0_kernel(const CondStage0Params p) {
         }
     };
     xfetch(tile_begin * NT);
-#if defined(FASTSVC_COND_TRACE) && defined(FASTSVC_ACT_BF16)
+#if defined(FASTSVC_COND_TRACE) && defined(FASTSVC_ACT_2B)
     unsigned long long* trace = (p.amax_hd && blockIdx.x == 1 && blockIdx.z == 0 && lane == 0)
         ? reinterpret_cast<unsigned long long*>(p.amax_hd) + wave * 64 : nullptr;
     int tri = 0;
@@ -448,7 +452,7 @@ void cond_stage0_kernel(const CondStage0Params p) {
                 const unsigned char* bo[4];                  // the row's four slots (swizzled): immediates do the rest
                 #pragma unroll
                 for (int o = 0; o < 4; ++o) bo[o] = bufA + cs_off(row, o);
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                 unsigned short v[NR];
 #else
                 float v[NR];
@@ -459,7 +463,7 @@ void cond_stage0_kernel(const CondStage0Params p) {
                     const int sc = wave + CS_NWAVES * k;               // (wave-uniform)
                     const int s = sc >= CS_C ? 1 : 0, c = sc - s * CS_C;
                     const unsigned char* src = bo[c >> 3] + s * PLANE + (c & 7) * 2;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     v[k] = *reinterpret_cast<const unsigned short*>(src);
 #else
                     v[k] = ((float)*reinterpret_cast<const _Float16*>(src) + (float)*reinterpret_cast<const _Float16*>(src + lo_off)) * (s ? ih1 : ih0);
@@ -470,7 +474,7 @@ void cond_stage0_kernel(const CondStage0Params p) {
                 for (int k = 0; k < NR; ++k) {
                     const int sc = wave + CS_NWAVES * k;
                     const int s = sc >= CS_C ? 1 : 0, c = sc - s * CS_C;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     __builtin_amdgcn_raw_buffer_store_b16(v[k], s ? hdr1 : hdr0, j * 2, c * p.hd_ld * 2, 0);
 #else
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[k]), s ? hdr1 : hdr0, j * 4, c * p.hd_ld * 4, 0);
@@ -516,7 +520,7 @@ void cond_stage0_kernel(const CondStage0Params p) {
                     f32x4 v = acc[ii];
                     if constexpr (CS_NP == 2) v = v * oinv;
                     unsigned char* dst = srow + (i0 + ii) * 16 * (int)sizeof(act_t);
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     *reinterpret_cast<cs4*>(dst) = __builtin_convertvector(v, cs4);
 #else
                     // (not __builtin_bit_cast(unsigned, v.y): on a vector-element lvalue this hipcc reads element 0)
@@ -1011,7 +1015,7 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
                             #pragma unroll
                             for (int ii = 0; ii < 2; ++ii) acc[ii] = cs_prod<false>(W5[ch][tap], a[ii][tap], acc[ii]);
                     }
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     cs_u2 outv[2];
 #else
                     f32x4 outv[2];
@@ -1021,7 +1025,7 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
                         f32x4 v = acc[ii];
                         if constexpr (CS_NP == 2) v = v * oinv;
                         unsigned char* dst = sb + (i0 + ii) * 16 * (int)sizeof(act_t);
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                         outv[ii] = __builtin_bit_cast(cs_u2, __builtin_convertvector(v, cs4));
                         *reinterpret_cast<cs_u2*>(dst) = outv[ii];
 #else
@@ -1048,7 +1052,7 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
         float hmax[2] = {0.f, 0.f};
         const int jj = lane & 15, q = lane >> 4;               // hd: lane = (decimated column, 12 channels of one signal)
         const int hs = q >> 1, hc0 = (q & 1) * 12;
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
         const float ih = 1.0f / sc[2][hs];                     // (exact: powers of two)
 #endif
         p0_steps(nsteps, [&](auto jc, int s) {
@@ -1086,7 +1090,7 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
                             const int c = hc0 + 4 * e;
                             hv[e] = *reinterpret_cast<const cs_u2*>(src + cs_off(row, c >> 3) + (c & 7) * 2);
                         }
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                         #pragma unroll
                         for (int e = 0; e < 3; ++e)
                             #pragma unroll
@@ -1145,7 +1149,7 @@ static hipError_t cond_stage0_pipe_instance(const CondStage0Params& p, hipStream
 
 // p.small: 1 = the 112-column tile variant (more, shorter workgroups: batches that do not fill the chip with 240-column
 // tiles); 2 = the layer pipeline (long runs of chunks per workgroup; tpw = chunks per workgroup)
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 constexpr int P0_N = 4;
 #else
 constexpr int P0_N = 2;
@@ -1159,8 +1163,8 @@ hipError_t launch_cond_stage0(const CondStage0Params& p, hipStream_t stream) {
     return p.small ? cond_stage0_instance<8>(p, stream) : cond_stage0_instance<16>(p, stream);
 }
 
-#ifndef FASTSVC_ACT_BF16
-// columns per tile (small = 0 / 1) or per chunk of the pipeline (small = 2: float32 storage; 3: bfloat16 storage)
+#ifndef FASTSVC_ACT_2B
+// columns per tile (small = 0 / 1) or per chunk of the pipeline (small = 2: float32 storage; 3: 2-byte storage)
 int cond_stage0_tile_columns(int small) {
     return small == 2 ? 16 * 2 : small == 3 ? 16 * 4 : small ? CsGeom<8>::NT : CsGeom<16>::NT;
 }
@@ -1480,7 +1484,7 @@ void cond_stage1_kernel(const CondStage1Params p) {
                 const unsigned char* bo[4];                  // the row's four slots (swizzled): immediates do the rest
                 #pragma unroll
                 for (int o = 0; o < 4; ++o) bo[o] = bufA + cs_off(row, o);
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                 unsigned short v[NR];
 #else
                 float v[NR];
@@ -1491,7 +1495,7 @@ void cond_stage1_kernel(const CondStage1Params p) {
                     const int scn = wave + C1_NWAVES * k;
                     const int s = scn >= C1_C ? 1 : 0, c = scn - s * C1_C;
                     const unsigned char* src = bo[(c & 31) >> 3] + (s * C1_NC + (c >> 5)) * PLANE + (c & 7) * 2;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     v[k] = *reinterpret_cast<const unsigned short*>(src);
 #else
                     v[k] = ((float)*reinterpret_cast<const _Float16*>(src) + (float)*reinterpret_cast<const _Float16*>(src + lo_off)) * (s ? ih1 : ih0);
@@ -1502,7 +1506,7 @@ void cond_stage1_kernel(const CondStage1Params p) {
                 for (int k = 0; k < NR; ++k) {
                     const int scn = wave + C1_NWAVES * k;
                     const int s = scn >= C1_C ? 1 : 0, c = scn - s * C1_C;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     __builtin_amdgcn_raw_buffer_store_b16(v[k], s ? hdr1 : hdr0, j * 2, c * p.hd_ld * 2, 0);
 #else
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[k]), s ? hdr1 : hdr0, j * 4, c * p.hd_ld * 4, 0);
@@ -1544,7 +1548,7 @@ void cond_stage1_kernel(const CondStage1Params p) {
                     f32x4 v = acc[ii];
                     if constexpr (CS_NP == 2) v = v * oinv;
                     unsigned char* dst = srow + (i0 + ii) * 16 * (int)sizeof(act_t);
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     *reinterpret_cast<cs4*>(dst) = __builtin_convertvector(v, cs4);
 #else
                     *reinterpret_cast<f32x4*>(dst) = v;
@@ -1611,9 +1615,9 @@ static hipError_t cond_stage1_instance(const CondStage1Params& p, hipStream_t st
     return hipGetLastError();
 }
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 // =====================================================================================================================
-// Stage 1 (C = 48, C_in = 24) as a LAYER PIPELINE - bfloat16 storage only (the float32 instance's hi + lo planes do not fit
+// Stage 1 (C = 48, C_in = 24) as a LAYER PIPELINE - 2-byte storage only (the float32 instance's hi + lo planes do not fit
 // three-chunk rings).  Same scheme as cond_stage0_pipe_kernel; what differs:
 //   * 12 waves: 0-1 stage-in of a signal's compact input (raw -> a 6-chunk ring for the 1x1 residual conv, LeakyReLU'd -> the
 //     3-chunk ring c1 reads; loads requested two steps ahead) AND its c1; 2-3 c2; 4-5 c3 (starts from the 1x1 residual conv of
@@ -1792,8 +1796,8 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
                         f32x4 lo4, hi4;
                         #pragma unroll
                         for (int c = 0; c < 4; ++c) {
-                            lo4[c] = __builtin_bit_cast(float, (unsigned)e[c] << 16);
-                            hi4[c] = __builtin_bit_cast(float, (unsigned)e[4 + c] << 16);
+                            lo4[c] = a16_lo((unsigned)e[c]);
+                            hi4[c] = a16_lo((unsigned)e[4 + c]);
                         }
                         const CsPk8 act = cs_pack8(cs_lrelu4(lo4), cs_lrelu4(hi4), 0xffffffffu);
                         const int rr = 4 * it_q + j;
@@ -1977,7 +1981,7 @@ static hipError_t cond_stage1_pipe_instance(const CondStage1Params& p, hipStream
 hipError_t launch_cond_stage1(const CondStage1Params& p, hipStream_t stream) {
     if (p.C != C1_C || p.Cin != C1_CIN || (p.T % 8) != 0 || (p.ld % 8) != 0 || (p.ldx % 4) != 0 || (p.tpw & 0xffff) < 1 ||
         (p.hd && p.hd_s < 2)) return hipErrorInvalidValue;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
     if (p.small == 2) return cond_stage1_pipe_instance(p, stream);
 #else
     if (p.small == 2) return hipErrorInvalidValue;         // (bfloat16 storage only: Q1Geom)
@@ -1985,11 +1989,11 @@ hipError_t launch_cond_stage1(const CondStage1Params& p, hipStream_t stream) {
     return p.small ? cond_stage1_instance<4>(p, stream) : cond_stage1_instance<8>(p, stream);
 }
 
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
 int cond_stage1_tile_columns(int small) { return small == 2 ? 32 : small ? C1Geom<4>::NT : C1Geom<8>::NT; }
 #endif
 
-#ifdef FASTSVC_ACT_BF16
-}  // namespace bf16
+#ifdef FASTSVC_ACT_2B
+}  // namespace FASTSVC_ACT_NS
 #endif
 }  // namespace fastsvc

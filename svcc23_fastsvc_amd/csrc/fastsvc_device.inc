@@ -1,6 +1,6 @@
 // fastsvc_device.inc - device helpers shared by the convolution kernel files (fastsvc_kernels.hip: f32-input
 // MFMA kernels; fastsvc_hx.hip: f16 split-product / bf16 MFMA kernels).  Included INSIDE namespace fastsvc
-// (and fastsvc::bf16 for the bfloat16-storage compilation): buffer-descriptor loads / stores, the activation
+// (and fastsvc::bf16 / fastsvc::f16 for the 2-byte-storage compilations): buffer-descriptor loads / stores, the activation
 // storage type, and the tile epilogues (bias, LeakyReLU, residual, FiLM affine + InstanceNorm partial sums).
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -97,11 +97,12 @@ __device__ __forceinline__ int row_valid(int t, int T) { return min(4, max(0, T 
 // The variants that sit at the 128-VGPR limit are compiled WITHOUT the row-end handling (they are the
 // full-rate shapes, whose rows are 160 F long); run_conv only launches them when T % 4 == 0.
 // ---- activation storage type ------------------------------------------------------------------
-// The file is compiled twice: as is (activations float32 in HBM: the parity path) and with
-// -DFASTSVC_ACT_BF16 (namespace fastsvc::bf16: every workspace tensor - conv outputs, FiLM-affined
-// tensors, scale / shift - is stored as bfloat16, halving the traffic of the HBM-bound layers; the
-// arithmetic, the LDS windows, the weights and the InstanceNorm sums stay float32 / float64).
-// All offsets in the kernels are written in "float bytes" (elements * 4); the bf16 helpers halve them.
+// The file is compiled three times: as is (activations float32 in HBM: the parity path) and with
+// -DFASTSVC_ACT_BF16 / -DFASTSVC_ACT_F16 (namespace fastsvc::bf16 / fastsvc::f16; both set FASTSVC_ACT_2B, see
+// fastsvc_kernels.h: every workspace tensor - conv outputs, FiLM-affined tensors, scale / shift - is stored as
+// bfloat16 / binary16, halving the traffic of the HBM-bound layers; the arithmetic, the LDS windows, the weights
+// and the InstanceNorm sums stay float32 / float64).
+// All offsets in the kernels are written in "float bytes" (elements * 4); the 2-byte helpers halve them.
 // Sum over the wave's four 16-lane rows, every lane ending with a[l & 15] + a[(l & 15) + 16] + ... (the order of
 // `a += __shfl_xor(a, 16); a += __shfl_xor(a, 32)`, bit for bit) on the VALU: gfx950's v_permlane{16,32}_swap instead of two
 // ds_bpermute_b32 round trips through the LDS queue per value (the per-tile InstanceNorm sums of the narrow layers: 0.7k of
@@ -117,29 +118,47 @@ __device__ __forceinline__ float row_xsum(float a) {
     return a + b;
 }
 double row_xsum(double) = delete;                        // (float64 sums: __shfl_xor - a silent narrowing would cost the sums their precision)
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 typedef unsigned short act_t;
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned f32_to_bf16_bits(float x) {            // round to nearest even
+// ---- the element format: the ONLY code that knows whether the 2-byte element is bfloat16 or binary16 ----
+//   a16_lo / a16_hi : the low / high half of a dword as float       a16_bits : float -> the element's bits, round to nearest even
+//   a16_pack2       : two floats -> one dword (low half first), round to nearest even
+// Each is one VALU instruction per value in both formats (gfx950): shift / mask against v_cvt_f32_f16 (+ sdwa WORD_1),
+// v_cvt_pk_bf16_f32 against v_cvt_pk_f16_f32 (NOT v_cvt_pkrtz: values pass through a dozen layers, a biased rounding adds up).
+#ifdef FASTSVC_ACT_F16
+__device__ __forceinline__ float a16_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)w); }
+__device__ __forceinline__ float a16_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+__device__ __forceinline__ unsigned a16_bits(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x); }
+__device__ __forceinline__ unsigned a16_pack2(float a, float b) {
+    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{a, b}, h2v));
+}
+#else
+__device__ __forceinline__ float a16_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float a16_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+__device__ __forceinline__ unsigned a16_bits(float x) {                    // round to nearest even
     const unsigned u = __builtin_bit_cast(unsigned, x);
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
-// two values -> one dword of bfloat16 (low half first), round to nearest even: ONE v_cvt_pk_bf16_f32 (gfx950) where the
-// integer form above costs 3-4 instructions per value - the epilogues of the narrow layers are bound by their VALU
-// instruction count (timeline of up.3.d9: 4.1k of 5.8k cycles per tile in the epilogue with four waves per SIMD)
-__device__ __forceinline__ unsigned bf16_pack2(float a, float b) {
+// ONE v_cvt_pk_bf16_f32 (gfx950) where the integer form above costs 3-4 instructions per value - the epilogues of the
+// narrow layers are bound by their VALU instruction count (timeline of up.3.d9: 4.1k of 5.8k cycles per tile in the
+// epilogue with four waves per SIMD)
+__device__ __forceinline__ unsigned a16_pack2(float a, float b) {
     typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
     typedef float f2v __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{a, b}, bf2v));
 }
+#endif
+__device__ __forceinline__ f32x4 a16_unpack4(unsigned lo, unsigned hi) { return f32x4{a16_lo(lo), a16_hi(lo), a16_lo(hi), a16_hi(hi)}; }
 __device__ __forceinline__ f32x4 act_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     const u32x2v w = __builtin_amdgcn_raw_buffer_load_b64(r, voff >> 1, soff >> 1, FASTSVC_LD_AUX);
-    return f32x4{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                 __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
+    return a16_unpack4(w.x, w.y);
 }
 __device__ __forceinline__ float act_load1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     const unsigned short h = __builtin_amdgcn_raw_buffer_load_b16(r, voff >> 1, soff >> 1, 0);
-    return __builtin_bit_cast(float, (unsigned)h << 16);
+    return a16_lo((unsigned)h);
 }
 // The same loads WITHOUT the conversion: what a prefetching wave keeps in registers between the request and the use.
 // (A converted value is an instruction on the loaded register, i.e. a wait for the load where the conversion stands -
@@ -150,8 +169,7 @@ __device__ __forceinline__ act4_t act_load4_raw(__amdgpu_buffer_rsrc_t r, int vo
     return __builtin_amdgcn_raw_buffer_load_b64(r, voff >> 1, soff >> 1, FASTSVC_LD_AUX);
 }
 __device__ __forceinline__ f32x4 act_unpack4(act4_t w) {
-    return f32x4{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                 __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
+    return a16_unpack4(w.x, w.y);
 }
 __device__ __forceinline__ act4_t act_pack4_raw(act1_t a, act1_t b, act1_t c, act1_t d) {
     return act4_t{(a & 0xffffu) | (b << 16), (c & 0xffffu) | (d << 16)};
@@ -159,11 +177,11 @@ __device__ __forceinline__ act4_t act_pack4_raw(act1_t a, act1_t b, act1_t c, ac
 __device__ __forceinline__ act1_t act_load1_raw(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, voff >> 1, soff >> 1, 0);
 }
-__device__ __forceinline__ float act_unpack1(act1_t h) { return __builtin_bit_cast(float, h << 16); }
+__device__ __forceinline__ float act_unpack1(act1_t h) { return a16_lo(h); }
 __device__ __forceinline__ void act_store4(__amdgpu_buffer_rsrc_t r, int voff, f32x4 v) {
     u32x2v w;
-    w.x = bf16_pack2(v.x, v.y);
-    w.y = bf16_pack2(v.z, v.w);
+    w.x = a16_pack2(v.x, v.y);
+    w.y = a16_pack2(v.z, v.w);
     __builtin_amdgcn_raw_buffer_store_b64(w, r, voff >> 1, 0, FASTSVC_ST_AUX);
 }
 __device__ __forceinline__ void act_store4_n(__amdgpu_buffer_rsrc_t r, int voff, f32x4 v, int nv) {
@@ -172,9 +190,9 @@ __device__ __forceinline__ void act_store4_n(__amdgpu_buffer_rsrc_t r, int voff,
     } else {
         const float e0 = v[0], e1 = v[1], e2 = v[2];
         const int far = 0x7ffffff0, o = voff >> 1;
-        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)f32_to_bf16_bits(e0), r, nv >= 1 ? o : far, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)f32_to_bf16_bits(e1), r, nv >= 2 ? o + 2 : far, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)f32_to_bf16_bits(e2), r, nv >= 3 ? o + 4 : far, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)a16_bits(e0), r, nv >= 1 ? o : far, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)a16_bits(e1), r, nv >= 2 ? o + 2 : far, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)a16_bits(e2), r, nv >= 3 ? o + 4 : far, 0, 0);
     }
 }
 #else
@@ -232,8 +250,8 @@ struct EpiRsrc {
 constexpr int AMAX_W = 8;
 constexpr int AMAX_STRIDE = 32;          // floats between slots
 constexpr int AMAX_ENTRY = AMAX_W * AMAX_STRIDE;
-#if defined(FASTSVC_ACT_BF16) || defined(FASTSVC_EXP_NOTRACK)
-constexpr bool AMAX_TRACK = false;       // bfloat16 storage: bf16 has float32's exponent range, nothing to scale
+#if defined(FASTSVC_ACT_2B) || defined(FASTSVC_EXP_NOTRACK)
+constexpr bool AMAX_TRACK = false;       // 2-byte storage: bf16 has float32's exponent range; binary16 storage is unscaled (range contract, fastsvc_hip.h)
 #else
 constexpr bool AMAX_TRACK = true;
 #endif
@@ -414,7 +432,7 @@ __device__ __forceinline__ void lds_dma4(__amdgpu_buffer_rsrc_t r, unsigned lds_
 // One 16 x 16 item of an activation tensor (this lane's four consecutive elements) into the wave's slot.
 // float32: one 16-byte piece per lane (1 KB slot).  bfloat16 storage: the lane's 8 bytes go as two
 // dword pieces (LDS-DMA has no 8-byte form): elements 0-1 in the first 256 B of the slot, 2-3 in the second.
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 constexpr int EST_ITEM_FLOATS = 128;
 constexpr int EST_DMA_PER_ITEM = 2;                         // LDS-DMA instructions of one item (what a counted wait skips)
 __device__ __forceinline__ void est_fetch(__amdgpu_buffer_rsrc_t r, unsigned slot_byte, int off, int soff) {
@@ -423,8 +441,7 @@ __device__ __forceinline__ void est_fetch(__amdgpu_buffer_rsrc_t r, unsigned slo
 }
 __device__ __forceinline__ f32x4 est_read(const float* slot, int lane) {
     const unsigned w0 = __builtin_bit_cast(unsigned, slot[lane]), w1 = __builtin_bit_cast(unsigned, slot[64 + lane]);
-    return f32x4{__builtin_bit_cast(float, w0 << 16), __builtin_bit_cast(float, w0 & 0xffff0000u),
-                 __builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
+    return a16_unpack4(w0, w1);
 }
 #else
 constexpr int EST_ITEM_FLOATS = 256;

@@ -21,6 +21,9 @@
 //       tests/test_dynamic_range_gpu.py holds that over inputs / weights scaled by 2^-20 .. 2^8.
 //   bfloat16 storage (namespace fastsvc::bf16, -DFASTSVC_ACT_BF16):  ONE v_mfma_f32_16x16x32_bf16 product
 //       of the bf16-rounded operands - BASELINE config 3's "bf16 generator forward".
+//   float16 storage (namespace fastsvc::f16, -DFASTSVC_ACT_F16):  the same code with ONE v_mfma_f32_16x16x32_f16
+//       product of the binary16-rounded, unscaled operands.  Both flags set FASTSVC_ACT_2B (fastsvc_kernels.h), which is
+//       what the kernel bodies below test: "2-byte elements"; the format shows in hx_t / hx_mfma / the a16_* helpers only.
 //
 // Data movement (what bounds these kernels: with the matrix work this cheap every layer is HBM-side):
 //   * workgroup = 4 consumer + 4 producer waves, one barrier per unit = (time tile, 32-channel K chunk),
@@ -42,8 +45,8 @@
 #include "fastsvc_kernels.h"
 
 namespace fastsvc {
-#ifdef FASTSVC_ACT_BF16
-namespace bf16 {
+#ifdef FASTSVC_ACT_2B
+namespace FASTSVC_ACT_NS {
 #endif
 
 #include "fastsvc_device.inc"
@@ -232,7 +235,7 @@ __device__ __forceinline__ void hx_chain_store(const f32x4 (&acc)[NA][MW], int n
     }
 }
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 // Polyphase epilogue in bfloat16 storage: a lane's 4 S consecutive output samples go out as 16-byte pieces
 // (8 samples; one 8-byte piece left over for odd S) instead of S 8-byte ones (see ws_epilogue_poly).
 template <int MW, int NW, int EPI, int S, bool TAILK = false, class KT>
@@ -351,8 +354,8 @@ __device__ __forceinline__ void hx_poly_pass1(const ConvParams& p, const f32x4 (
             #pragma unroll
             for (int q = 0; q < S; ++q) {                   // 4 S samples = S pieces of 8 bytes
                 u32x2v w;
-                w.x = bf16_pack2(phase_value(4 * q), phase_value(4 * q + 1));
-                w.y = bf16_pack2(phase_value(4 * q + 2), phase_value(4 * q + 3));
+                w.x = a16_pack2(phase_value(4 * q), phase_value(4 * q + 1));
+                w.y = a16_pack2(phase_value(4 * q + 2), phase_value(4 * q + 3));
                 *reinterpret_cast<u32x2v*>(dst + q * 8) = w;
             }
         }
@@ -410,12 +413,12 @@ struct HxPolyPass2 {
             for (int c = 0; c < NCH; ++c) {
                 const int col = c * 32 + piece * 8;
                 if (EPI == EPI_AFF) {
-                    const f32x8 v = bf8_unpack(*reinterpret_cast<const u32x4*>(src + (col < NC ? c * 64 : 0)));
+                    const f32x8 v = a16_unpack8(*reinterpret_cast<const u32x4*>(src + (col < NC ? c * 64 : 0)));
                     f32x8 u;
-                    const f32x8 sc = bf8_unpack(l1[sl][c]), sh = bf8_unpack(l2[sl][c]);
+                    const f32x8 sc = a16_unpack8(l1[sl][c]), sh = a16_unpack8(l2[sl][c]);
                     u.lo = sc.lo * v.lo + sh.lo; u.hi = sc.hi * v.hi + sh.hi;
                     u = keep8_exact(u, nv[sl][c]);
-                    yw[c] = bf8_pack(u);
+                    yw[c] = a16_pack8(u);
                     a1 += ((u.lo.x + u.lo.y) + (u.lo.z + u.lo.w)) + ((u.hi.x + u.hi.y) + (u.hi.z + u.hi.w));
                     a2 += ((u.lo.x * u.lo.x + u.lo.y * u.lo.y) + (u.lo.z * u.lo.z + u.lo.w * u.lo.w)) +
                           ((u.hi.x * u.hi.x + u.hi.y * u.hi.y) + (u.hi.z * u.hi.z + u.hi.w * u.hi.w));
@@ -468,8 +471,8 @@ __device__ __forceinline__ void hx_epilogue_dec2_staged(const ConvParams& p, con
             unsigned char* dst = Pw + (m * 16 + (lane & 15)) * PB + (n * 16 + (lane >> 4) * 4) * 2;
             const f32x4 a = KT::finish(acc[0][n][m], iv, bias), b = KT::finish(acc[1][n][m], iv2, bias2);
             u32x2v wa, wb;
-            wa.x = bf16_pack2(a.x, a.y); wa.y = bf16_pack2(a.z, a.w);
-            wb.x = bf16_pack2(b.x, b.y); wb.y = bf16_pack2(b.z, b.w);
+            wa.x = a16_pack2(a.x, a.y); wa.y = a16_pack2(a.z, a.w);
+            wb.x = a16_pack2(b.x, b.y); wb.y = a16_pack2(b.z, b.w);
             *reinterpret_cast<u32x2v*>(dst) = wa;
             *reinterpret_cast<u32x2v*>(dst + TB) = wb;
         }
@@ -533,7 +536,7 @@ constexpr bool hx_est2() { return hx_estage<MW, NW, MODE, EPI>() && MW * NW <= 4
 
 template <int MW, int NW, int MODE, int EPI, int S = 1>
 constexpr int hx_min_waves() {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
     // ... and the C = 24 middle conv with its second operand (bfloat16 storage): it sits at the edge of the budget, and
     // past it the CU holds one workgroup instead of two (measured 948 -> 1147 us at 64 x 240000)
     if (MODE == MODE_DIRECT && MW == 2 && NW == 2 && EPI == EPI_AFF && S > 1) return 4;     // (it fits without a spill: checked)
@@ -871,7 +874,7 @@ void conv_hx_kernel(const ConvParams p0) {
             const int soff = ch * HX_KC * p.ldx * 4;
             const int rows_left = p.CIN - ch * HX_KC;
             tokmask = 0;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
             if constexpr (W8) {
                 #pragma unroll
                 for (int i = 0; i < ITEMS; ++i) {
@@ -960,7 +963,7 @@ void conv_hx_kernel(const ConvParams p0) {
                 }
                 return;
             }
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
             if constexpr (W8) {
                 const bool row_end = (p.T & 7) != 0;           // (wave-uniform) the last item of a row holds 4 rows of it
                 #pragma unroll
@@ -989,15 +992,15 @@ void conv_hx_kernel(const ConvParams p0) {
                         const int off = hx_lds_off(8 * it_q[i] + j, it_oct[i] >> 1) + (it_oct[i] & 1) * 8;
                         if constexpr (DEC2) {                  // the raw copy for the 1x1 residual conv (see below)
                             u32x2v hr;
-                            hr.x = bf16_pack2(e[0], e[1]);
-                            hr.y = bf16_pack2(e[2], e[3]);
+                            hr.x = a16_pack2(e[0], e[1]);
+                            hr.y = a16_pack2(e[2], e[3]);
                             *reinterpret_cast<u32x2v*>(tile + raw_off + off) = hr;
                         }
                         #pragma unroll
                         for (int c = 0; c < 4; ++c) e[c] = fmaxf(e[c], e[c] * slope);
                         u32x2v h;
-                        h.x = bf16_pack2(e[0], e[1]);
-                        h.y = bf16_pack2(e[2], e[3]);
+                        h.x = a16_pack2(e[0], e[1]);
+                        h.y = a16_pack2(e[2], e[3]);
                         *reinterpret_cast<u32x2v*>(tile + off) = h;
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -1077,7 +1080,7 @@ void conv_hx_kernel(const ConvParams p0) {
         constexpr bool XW = XR && W8 && S == 2;
         const int xq4 = ptid & 7, xg4 = ptid >> 3;
         auto ploadX = [&](int un, act1_t (&px)[XJ][8]) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
             if constexpr (XW) {
                 const int tl = xl_tl, ch = xl_ch;
                 pos_next(xl_tl, xl_ch);
@@ -1117,7 +1120,7 @@ void conv_hx_kernel(const ConvParams p0) {
             }
         };
         auto pcommitX = [&](int un, const act1_t (&pw)[XJ][8], unsigned char* tile) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
             if constexpr (XW) {
                 const int tl = xc_tl;
                 pos_next(xc_tl, xc_ch);
@@ -1221,7 +1224,7 @@ void conv_hx_kernel(const ConvParams p0) {
             Rp.res = Rp.y; Rp.r1x = Rp.y;
         }
         auto ppass2 = [&](int un) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
             if constexpr (PSPLIT) {
                 const int etl = e_tl, ech = e_ch;
                 pos_next(e_tl, e_ch);
@@ -1582,7 +1585,7 @@ void conv_hx_kernel(const ConvParams p0) {
                     if constexpr (EST) {
                         // the epilogue's scale / shift pieces, two units ahead of it
                         if (active && ch + 1 == nch) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                             if constexpr (PAIRS) hx_epilogue8_stage<MW, NW / 2, EPI>(p, R, Ew, mg, tcolw, lane);
                             else
 #endif
@@ -1609,7 +1612,7 @@ void conv_hx_kernel(const ConvParams p0) {
                         #pragma unroll
                         for (int m = 0; m < MW; ++m) { s1[m] = 0.f; s2[m] = 0.f; }
                         if constexpr (EST) { if (active) ws_epilogue_stage_wait<NSLOT>(!WSTATIC); }
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                         if constexpr (PAIRS) hx_epilogue8<MW, NW / 2, EPI, EST, false, false>(p, R, acc, s1, s2, sig, mg, tcolw, active, lane, K, Ew, Xw);
                         else
 #endif
@@ -1640,7 +1643,7 @@ void conv_hx_kernel(const ConvParams p0) {
         for (int tl = 0; tl < ntiles; ++tl) {
             auto est_stage = [&](const float* slots, int tile) {
                 if constexpr (EST) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                     if constexpr (PAIRS) hx_epilogue8_stage<MW, NW / 2, EPI>(p, R, slots, mg, tile * NT + wave_n * (NW * 16), lane);
                     else
 #endif
@@ -1697,7 +1700,7 @@ void conv_hx_kernel(const ConvParams p0) {
                     if constexpr (EST) { if (active) ws_epilogue_stage_wait<NSLOT>(!WSTATIC && !(FASTSVC_DBG_ON(p, DBG_NO_MFMA))); }
                     stamp(10);                         // (timeline build: the staged operands have landed)
                     if constexpr (POLY) {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                         if constexpr (hx_poly_staged<MW, NW, MODE, EPI, S>()) {
                             // pass 1, workgroup barrier, then this wave's share of pass 2 (the staging partner runs the rest)
                             const int tcolw = (tile0 + tl) * NT + wave_n * (NW * 16);
@@ -1717,7 +1720,7 @@ void conv_hx_kernel(const ConvParams p0) {
                     }
                     else if constexpr (DEC2)
                     {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                         if constexpr (hx_dec2_staged<MW, NW, MODE>())
                             hx_epilogue_dec2_staged<MW, NW>(p, R, acc2, sig, mg, (tile0 + tl) * NT + wave_n * (NW * 16), active, lane, K,
                                                             tiles + 2 * bufsz + cw * hx_dec2_patch_bytes<MW, NW>());
@@ -1726,7 +1729,7 @@ void conv_hx_kernel(const ConvParams p0) {
                         ws_epilogue_dec2<MW, NW>(p, R, acc2, sig, mg, (tile0 + tl) * NT + wave_n * (NW * 16), active, lane, K);
                     }
                     else {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
                         if constexpr (PAIRS) {
                             if (!(FASTSVC_DBG_ON(p, DBG_NO_EPILOGUE)))
                                 hx_epilogue8<MW, NW / 2, EPI, EST, TAILK>(p, R, acc, s1, s2, sig, mg,
@@ -1842,7 +1845,7 @@ static hipError_t hx_launch_shape(const ConvParams& p, int nsig, hipStream_t str
                         (CHAIN ? (size_t)(MODE == MODE_UPHEAD ? 2 : 1) * p.nch32b * HX_NP * (NT + 16) * HX_ROW : 0);
     const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
     if constexpr (MODE == MODE_UPHEAD) {
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
         if (!(p.flags & F_AFF_OUT) || !p.y || !p.y2 || !p.bias2 || smem + HX_STATIC_LDS > 160 * 1024) return hipErrorInvalidValue;
 #define FASTSVC_HXU(sv) if (p.s == sv) return hx_launch_kind<MW, NW, WM, WN, MODE_UPHEAD, EPI_AFF, sv>(grid, smem, stream, p);
         FASTSVC_HXU(2) FASTSVC_HXU(4) FASTSVC_HXU(5)
@@ -1957,7 +1960,7 @@ hipError_t launch_conv_hx(const ConvParams& p, const ConvLaunch& cfg, hipStream_
     return hipErrorInvalidValue;
 }
 
-#ifndef FASTSVC_ACT_BF16      // storage-independent host query: defined once
+#ifndef FASTSVC_ACT_2B      // storage-independent host query: defined once
 bool conv_hx_x2_ok(int MW, int nch32, int s2) { return MW == 2 ? (nch32 == 1 && s2 == 5) : MW == 3 ? (s2 == 2 || s2 == 4) : false; }
 bool conv_hx_x2_rows_ok(const ConvParams& p) { return p.s2 != 2 || ((p.lens ? p.x2len_mul : p.x2_T) & 3) == 0; }
 bool conv_hx_tail_ok(int mode, int MW, int epi_kind, int S) { return hx_tail_instance(MW, mode, epi_kind, S); }
@@ -1985,7 +1988,7 @@ bool conv_hx_shape(int mode, int MW, int NW, int WM, int WN) {
 }
 #endif
 
-#ifdef FASTSVC_ACT_BF16
-}  // namespace bf16
+#ifdef FASTSVC_ACT_2B
+}  // namespace FASTSVC_ACT_NS
 #endif
 }  // namespace fastsvc

@@ -1,11 +1,15 @@
 // fastsvc_hx_common.inc - pieces shared by the half-precision-MFMA kernel files (fastsvc_hx.hip: wave-specialised kernels;
 // fastsvc_wx.hip: the wide-layer kernel in which every wave multiplies): operand types, the MFMA wrapper, the LDS tile
 // swizzle, fragment reads / products, the staging commit, and (bfloat16 storage) the 8-wide pair epilogue.
-// Included INSIDE namespace fastsvc (and fastsvc::bf16), after fastsvc_device.inc.
+// Included INSIDE namespace fastsvc (and fastsvc::bf16 / fastsvc::f16), after fastsvc_device.inc.
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
+#ifdef FASTSVC_ACT_F16
+typedef _Float16 hx_t;
+#else
 typedef __bf16 hx_t;
-constexpr int HX_NP = 1;                 // operand pieces: bf16 product of the rounded operands
+#endif
+constexpr int HX_NP = 1;                 // operand pieces: one product of the operands rounded to the storage format
 #else
 typedef _Float16 hx_t;
 constexpr int HX_NP = 2;                 // hi + lo binary16 pieces, three products
@@ -14,7 +18,7 @@ typedef hx_t hx8 __attribute__((ext_vector_type(8)));
 typedef hx_t hx2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f32x4 hx_mfma(hx8 a, hx8 b, f32x4 c) {
-#ifdef FASTSVC_ACT_BF16
+#if defined(FASTSVC_ACT_2B) && !defined(FASTSVC_ACT_F16)
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 #else
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
@@ -158,10 +162,10 @@ __device__ __forceinline__ void hx_commit_slot(unsigned char* tile, int off, int
     }
 }
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 // ---------------------------------------------------------------------------------------------------------
-// bfloat16 storage: 8-wide tile epilogue.  In the MFMA result layout a lane owns 4 consecutive time steps of
-// one channel = 8 BYTES of bf16, so every epilogue access of a wave was 16 rows x 32-byte segments (measured:
+// 2-byte storage: 8-wide tile epilogue.  In the MFMA result layout a lane owns 4 consecutive time steps of
+// one channel = 8 BYTES of bf16 / binary16, so every epilogue access of a wave was 16 rows x 32-byte segments (measured:
 // 4.2 TB/s for that shape against 5.8 TB/s for 16-byte lanes, tools/micro/rw_pattern.hip, and twice the
 // memory instructions).  Two neighbouring 16-column tiles are therefore re-laid through a wave-private LDS
 // patch so that a lane owns 8 consecutive time steps (16 B): lane (co = lane & 15, g = lane >> 4) of the pair
@@ -169,25 +173,23 @@ __device__ __forceinline__ void hx_commit_slot(unsigned char* tile, int off, int
 // ---------------------------------------------------------------------------------------------------------
 struct f32x8 { f32x4 lo, hi; };
 
-__device__ __forceinline__ f32x8 bf8_unpack(u32x4 w) {
+__device__ __forceinline__ f32x8 a16_unpack8(u32x4 w) {
     f32x8 r;
-    r.lo = f32x4{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                 __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
-    r.hi = f32x4{__builtin_bit_cast(float, w.z << 16), __builtin_bit_cast(float, w.z & 0xffff0000u),
-                 __builtin_bit_cast(float, w.w << 16), __builtin_bit_cast(float, w.w & 0xffff0000u)};
+    r.lo = a16_unpack4(w.x, w.y);
+    r.hi = a16_unpack4(w.z, w.w);
     return r;
 }
-__device__ __forceinline__ u32x4 bf8_pack(const f32x8& v) {
+__device__ __forceinline__ u32x4 a16_pack8(const f32x8& v) {
     u32x4 w;
-    w.x = bf16_pack2(v.lo.x, v.lo.y);
-    w.y = bf16_pack2(v.lo.z, v.lo.w);
-    w.z = bf16_pack2(v.hi.x, v.hi.y);
-    w.w = bf16_pack2(v.hi.z, v.hi.w);
+    w.x = a16_pack2(v.lo.x, v.lo.y);
+    w.y = a16_pack2(v.lo.z, v.lo.w);
+    w.z = a16_pack2(v.hi.x, v.hi.y);
+    w.w = a16_pack2(v.hi.z, v.hi.w);
     return w;
 }
 // boff: BYTE offset of the lane's first element inside the descriptor
 __device__ __forceinline__ f32x8 act_load8(__amdgpu_buffer_rsrc_t r, int boff, int soff) {
-    return bf8_unpack(__builtin_amdgcn_raw_buffer_load_b128(r, boff, soff, FASTSVC_LD_AUX));
+    return a16_unpack8(__builtin_amdgcn_raw_buffer_load_b128(r, boff, soff, FASTSVC_LD_AUX));
 }
 // nv: valid elements of the lane (0, 4 or 8 - rows are a multiple of 4 long)
 __device__ __forceinline__ void act_store8_raw(__amdgpu_buffer_rsrc_t r, int boff, const u32x4& w, int nv) {
@@ -201,7 +203,7 @@ __device__ __forceinline__ void act_store8_raw(__amdgpu_buffer_rsrc_t r, int bof
     }
 }
 __device__ __forceinline__ void act_store8(__amdgpu_buffer_rsrc_t r, int boff, const f32x8& v, int nv) {
-    act_store8_raw(r, boff, bf8_pack(v), nv);
+    act_store8_raw(r, boff, a16_pack8(v), nv);
 }
 __device__ __forceinline__ f32x8 keep8_exact(f32x8 v, int nv) {       // zero the elements at and past index nv (any nv)
     #pragma unroll
@@ -300,11 +302,11 @@ __device__ __forceinline__ void hx_epilogue8(const ConvParams& p, const EpiRsrc&
                 w0[g] = w1[g] = w2[g] = u32x4{0u, 0u, 0u, 0u};
                 if constexpr (EST) {
                     const u32x4* slot = reinterpret_cast<const u32x4*>(Ew) + (m * NP2 + k) * 64 + lane;
-                    if (EPI == EPI_RES) l0[g] = bf8_unpack(slot[0]);
+                    if (EPI == EPI_RES) l0[g] = a16_unpack8(slot[0]);
                     if (EPI == EPI_AFF) {
-                        l1[g] = bf8_unpack(slot[0]);
-                        l2[g] = bf8_unpack(slot[MW * NP2 * 64]);
-                        if (p.res) l0[g] = bf8_unpack(slot[2 * MW * NP2 * 64]);
+                        l1[g] = a16_unpack8(slot[0]);
+                        l2[g] = a16_unpack8(slot[MW * NP2 * 64]);
+                        if (p.res) l0[g] = a16_unpack8(slot[2 * MW * NP2 * 64]);
                     }
                 } else {
                     if (EPI == EPI_RES) w0[g] = __builtin_amdgcn_raw_buffer_load_b128(R.res, boff[g], 0, FASTSVC_LD_AUX);
@@ -323,8 +325,8 @@ __device__ __forceinline__ void hx_epilogue8(const ConvParams& p, const EpiRsrc&
             for (int g = 0; g < G; ++g) {
                 f32x8 v = hx_pair(acc[2 * (k0 + g)][m], acc[2 * (k0 + g) + 1][m], Xw, lane);
                 if constexpr (!EST) {
-                    if (EPI == EPI_RES || EPI == EPI_AFF) l0[g] = bf8_unpack(w0[g]);
-                    if (EPI == EPI_AFF) { l1[g] = bf8_unpack(w1[g]); l2[g] = bf8_unpack(w2[g]); }
+                    if (EPI == EPI_RES || EPI == EPI_AFF) l0[g] = a16_unpack8(w0[g]);
+                    if (EPI == EPI_AFF) { l1[g] = a16_unpack8(w1[g]); l2[g] = a16_unpack8(w2[g]); }
                 }
                 v.lo += bias; v.hi += bias;
                 if (!LRB || (p.flags & F_POST_LRELU)) {            // (wave-uniform)

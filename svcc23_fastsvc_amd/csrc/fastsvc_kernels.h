@@ -4,6 +4,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// Activation storage of a compilation of the kernel files (build.py): nothing = float32, -DFASTSVC_ACT_BF16 = bfloat16
+// (namespace fastsvc::bf16), -DFASTSVC_ACT_F16 = binary16 (namespace fastsvc::f16).  The switch has two meanings and the
+// sources test them apart: FASTSVC_ACT_2B = "an element is 2 bytes" (halved offsets, 16-byte requests of 8 elements, the
+// 8-wide epilogues, the launch geometry, one product per MFMA step), which is all a kernel body knows; which 2-byte format
+// it is shows only in the conversion helpers of fastsvc_device.inc (a16_*) and in the MFMA operand type (hx_t, cs_t).
+#if defined(FASTSVC_ACT_BF16) && defined(FASTSVC_ACT_F16)
+#error "FASTSVC_ACT_BF16 and FASTSVC_ACT_F16 exclude each other"
+#endif
+#if defined(FASTSVC_ACT_BF16)
+#define FASTSVC_ACT_2B 1
+#define FASTSVC_ACT_NS bf16
+#elif defined(FASTSVC_ACT_F16)
+#define FASTSVC_ACT_2B 1
+#define FASTSVC_ACT_NS f16
+#endif
+
 namespace fastsvc {
 
 // input index modes of the generic convolution (how output-rate column t maps to the source row)
@@ -358,21 +374,24 @@ struct SpkBlock {
 hipError_t launch_spk_proj(const float* emb, const SpkBlock* blocks, int nblocks, int B, int E,
                            hipStream_t stream);
 
-// The same launchers compiled with bfloat16 activation storage (fastsvc_kernels.hip built with
-// -DFASTSVC_ACT_BF16): every pointer to an activation tensor then addresses bfloat16 elements (strides
+// The same launchers compiled with 2-byte activation storage (the kernel files built with -DFASTSVC_ACT_BF16 /
+// -DFASTSVC_ACT_F16): every pointer to an activation tensor then addresses bfloat16 / binary16 elements (strides
 // stay in elements); weights, biases, the raw signals (r1x), statistics and speaker biases stay float32.
-namespace bf16 {
-hipError_t launch_conv(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream);
-hipError_t launch_conv_hx(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream);
-hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream);
-hipError_t launch_in1_conv(const float* x, long x_sig, const float* w, const float* bias, long w_sig, long b_sig,
-                           float* y, int nsig, int B, int C, int T, const int* lens, int len_mul, hipStream_t stream,
-                           float* amax_out = nullptr);
-hipError_t launch_pointwise_out(const float* x, const float* w, const float* bias, float* y,
-                                int B, int C, int O, int T, const int* lens, int len_mul, hipStream_t stream);
-hipError_t launch_act_convert(const float* src, float* dst_bf16, long n, hipStream_t stream);
-hipError_t launch_cond_stage0(const CondStage0Params& p, hipStream_t stream);
-hipError_t launch_cond_stage1(const CondStage1Params& p, hipStream_t stream);
-}  // namespace bf16
+#define FASTSVC_ACT_LAUNCHERS \
+hipError_t launch_conv(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream); \
+hipError_t launch_conv_hx(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream); \
+hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream); \
+hipError_t launch_in1_conv(const float* x, long x_sig, const float* w, const float* bias, long w_sig, long b_sig, \
+                           float* y, int nsig, int B, int C, int T, const int* lens, int len_mul, hipStream_t stream, \
+                           float* amax_out = nullptr); \
+hipError_t launch_pointwise_out(const float* x, const float* w, const float* bias, float* y, \
+                                int B, int C, int O, int T, const int* lens, int len_mul, hipStream_t stream); \
+hipError_t launch_act_convert(const float* src, float* dst_act, long n, hipStream_t stream); \
+hipError_t launch_cond_stage0(const CondStage0Params& p, hipStream_t stream); \
+hipError_t launch_cond_stage1(const CondStage1Params& p, hipStream_t stream); \
+
+namespace bf16 { FASTSVC_ACT_LAUNCHERS }
+namespace f16 { FASTSVC_ACT_LAUNCHERS }
+#undef FASTSVC_ACT_LAUNCHERS
 
 }  // namespace fastsvc

@@ -22,8 +22,8 @@
 #include "fastsvc_kernels.h"
 
 namespace fastsvc {
-#ifdef FASTSVC_ACT_BF16
-namespace bf16 {          // second compilation of this file: bfloat16 activation storage (see act_t below)
+#ifdef FASTSVC_ACT_2B
+namespace FASTSVC_ACT_NS {          // second / third compilation of this file: bfloat16 / binary16 activation storage (see act_t below)
 #endif
 
 #include "fastsvc_device.inc"
@@ -639,12 +639,17 @@ constexpr bool ws_estage() {
 }
 template <int MW, int NW, int MODE, int EPI>
 constexpr int ws_min_waves() {
-#ifdef FASTSVC_ACT_BF16
-    // bfloat16 storage: the pack / unpack temporaries push these variants over 128 registers
+#ifdef FASTSVC_ACT_2B
+    // 2-byte storage: the pack / unpack temporaries push these variants over 128 registers
     if (MODE == MODE_POLY && EPI == EPI_AFF) return 2;
     if (MODE == MODE_DEC2 && NW == 2) return 2;
     if (MW == 2 && NW == 4 && (EPI == EPI_AFF || EPI == EPI_RANK1)) return 2;
     if (MW == 3 && NW == 2) return 2;
+#endif
+#ifdef FASTSVC_ACT_F16
+    // binary16: the conversions of both halves of a loaded dword (v_cvt_f32_f16, + sdwa) keep the dword live where
+    // bfloat16's shift / mask overwrite it - the decimating NW = 4 instances, at 128 registers in bfloat16, spilled 42-44
+    if (MW == 2 && NW == 4 && MODE == MODE_DECIMATE) return 2;
 #endif
     if (MODE == MODE_POLY) return (MW <= 2 && NW == 1) ? 4 : 2;
     if (MODE == MODE_WINO) return (MW == 2 && NW == 1) ? 4 : 2;   // four accumulator sets + a 24-slot weight ring
@@ -919,8 +924,8 @@ void conv_mfma_ws_kernel(const ConvParams p0) {
             R.r1x = make_rsrc(p.r1x ? p.r1x + (long)sig * p.r1x_sig + (long)b * p.r1x_b : nul, p.r1x ? p.ldy : 0);
         }
         // (variants already at their register budget fetch them per tile instead)
-#ifdef FASTSVC_ACT_BF16
-        constexpr bool HOIST_OK = false;        // the bf16 pack / unpack temporaries take those registers
+#ifdef FASTSVC_ACT_2B
+        constexpr bool HOIST_OK = false;        // the 2-byte pack / unpack temporaries take those registers
 #else
         constexpr bool HOIST_OK = true;
 #endif
@@ -1045,7 +1050,7 @@ void conv_mfma_ws_kernel(const ConvParams p0) {
     }
 }
 
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
 template <int MW, int NW>
 static hipError_t launch_conv_generic(const ConvParams& p, int nsig, hipStream_t stream) {
     constexpr int WM = 1, WN = 4;
@@ -1064,7 +1069,7 @@ static hipError_t launch_conv_generic(const ConvParams& p, int nsig, hipStream_t
 template <int MW, int NW, int WM, int WN>
 constexpr bool poly_shape() { return WM != 4 && ((MW == 3 && NW == 1) || (MW == 2 && NW <= 2)); }
 
-#ifndef FASTSVC_ACT_BF16      // storage-independent host queries: defined once
+#ifndef FASTSVC_ACT_2B      // storage-independent host queries: defined once
 int conv_ws_resident(int MW, int NW, int mode, int epi_kind) {
     // workgroups per CU the register budget of the compiled variant allows (see ws_min_waves)
     if (mode == MODE_POLY) return (MW <= 2 && NW == 1) ? 2 : 1;
@@ -1202,7 +1207,7 @@ static hipError_t launch_conv_pipe(const ConvParams& p, int nsig, hipStream_t st
     return hipGetLastError();
 }
 
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
 bool conv_pipe_supported(const ConvParams& p) {
     if (p.KC != 24) return false;                              // 6 k-steps per tap per chunk, compiled in
     if (p.flags & F_PRE_AFFINE) return false;                  // only the generic kernel fuses the affine
@@ -1233,7 +1238,7 @@ hipError_t launch_conv(const ConvParams& p, const ConvLaunch& cfg, hipStream_t s
 #undef FASTSVC_PIPE
         return hipErrorInvalidValue;
     }
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
 #define FASTSVC_CASE(mw, nw) if (cfg.MW == mw && cfg.NW == nw) return launch_conv_generic<mw, nw>(p, cfg.nsig, stream);
     FASTSVC_CASE(1, 1) FASTSVC_CASE(1, 2) FASTSVC_CASE(1, 4)
     FASTSVC_CASE(2, 1) FASTSVC_CASE(2, 2) FASTSVC_CASE(2, 4)
@@ -1248,7 +1253,7 @@ hipError_t launch_conv(const ConvParams& p, const ConvLaunch& cfg, hipStream_t s
 // K = 3 only: a VALU kernel; every thread produces 4 consecutive samples for all C channels.
 // HBM-write bound (C floats written per float read).
 // ---------------------------------------------------------------------------------------------
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 constexpr int IN1_SPT = 8;          // samples per thread: 16-byte bf16 stores
 #else
 constexpr int IN1_SPT = 4;          // 16-byte float stores
@@ -1281,16 +1286,16 @@ void in1_conv_kernel(const float* __restrict__ x, long x_sig, const float* __res
         #pragma unroll
         for (int i = 0; i < SPT; ++i) { o[i] = bb + (w0 * xv[i] + w1 * xv[i + 1]) + w2 * xv[i + 2]; amx = fmaxf(amx, fabsf(o[i])); }
         act_t* yr = yb + (long)co * ld + t;
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
         if (full) {
             u32x4 q;
-            q.x = bf16_pack2(o[0], o[1]);
-            q.y = bf16_pack2(o[2], o[3]);
-            q.z = bf16_pack2(o[4], o[5]);
-            q.w = bf16_pack2(o[6], o[7]);
+            q.x = a16_pack2(o[0], o[1]);
+            q.y = a16_pack2(o[2], o[3]);
+            q.z = a16_pack2(o[4], o[5]);
+            q.w = a16_pack2(o[6], o[7]);
             *reinterpret_cast<u32x4*>(yr) = q;
         } else {
-            for (int i = 0; i < SPT && t + i < T; ++i) yr[i] = (act_t)f32_to_bf16_bits(o[i]);
+            for (int i = 0; i < SPT && t + i < T; ++i) yr[i] = (act_t)a16_bits(o[i]);
         }
 #else
         if (full) {
@@ -1314,7 +1319,7 @@ hipError_t launch_in1_conv(const float* x, long x_sig, const float* w, const flo
     return hipGetLastError();
 }
 
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
 // ---------------------------------------------------------------------------------------------
 // Largest magnitude of every input row (fastsvc_kernels.h, launch_amax_inputs): what the split-binary16 kernels
 // scale their staged activations by.  gridDim = (AMAX_W, 3 B input rows + zeroing rows): block x of an input row scans
@@ -1440,17 +1445,16 @@ void pointwise_out_kernel(const float* __restrict__ x, const float* __restrict__
     const act_t* xb = reinterpret_cast<const act_t*>(x) + (long)b * C * ld;
     const bool full = (t + 3 < T) && ((ld & 3) == 0);
     auto ld1 = [&](long idx) -> float {
-#ifdef FASTSVC_ACT_BF16
-        return __builtin_bit_cast(float, (unsigned)xb[idx] << 16);
+#ifdef FASTSVC_ACT_2B
+        return a16_lo((unsigned)xb[idx]);
 #else
         return xb[idx];
 #endif
     };
     auto ld4 = [&](long idx) -> f32x4 {
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
         const u32x2v v = *reinterpret_cast<const u32x2v*>(xb + idx);
-        return f32x4{__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xffff0000u),
-                     __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xffff0000u)};
+        return a16_unpack4(v.x, v.y);
 #else
         return *reinterpret_cast<const f32x4*>(xb + idx);
 #endif
@@ -1481,12 +1485,12 @@ hipError_t launch_pointwise_out(const float* x, const float* w, const float* bia
     return hipGetLastError();
 }
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 // float32 -> bfloat16 copy of an external input (the PPG) into the workspace
 __global__ __launch_bounds__(256)
 void act_convert_kernel(const float* __restrict__ src, act_t* __restrict__ dst, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = (act_t)f32_to_bf16_bits(src[i]);
+    if (i < n) dst[i] = (act_t)a16_bits(src[i]);
 }
 
 hipError_t launch_act_convert(const float* src, float* dst, long n, hipStream_t stream) {
@@ -1558,7 +1562,7 @@ hipError_t launch_spk_proj(const float* emb, const SpkBlock* blocks, int nblocks
 
 #endif   // speaker projection: storage independent, defined once
 
-#ifdef FASTSVC_ACT_BF16
-}  // namespace bf16
+#ifdef FASTSVC_ACT_2B
+}  // namespace FASTSVC_ACT_NS
 #endif
 }  // namespace fastsvc

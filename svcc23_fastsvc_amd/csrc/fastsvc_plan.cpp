@@ -70,16 +70,19 @@ struct PackedConv {
     long b2_pair = 0;
     // half-precision-MFMA kernels (fastsvc_hx.hip): pre-split fragments [group][32-channel chunk][tap]
     // [16-channel tile][piece][lane][8 halves]; index 0 = binary16 hi + lo pieces (float32 storage),
-    // 1 = bfloat16 (bfloat16 storage).  Offsets in floats, pair strides (lft -> sine) in bytes.
+    // 1 = bfloat16 (bfloat16 storage), 2 = binary16, one piece, unscaled (float16 storage: the twin of set 1, same size
+    // and order; allocated behind everything else - add_f16_twins - so that no offset of sets 0 / 1 depends on it).
+    // Offsets in floats, pair strides (lft -> sine) in bytes.
     bool hx = false;
     int nch32 = 0;
-    size_t hx_off[2] = {0, 0};
-    long hx_pair[2] = {0, 0};
-    size_t hxp_off[2] = {0, 0};       // the polyphase taps W0 | W0+W1+W2 | W2 in the same format (stretch convs)
+    size_t hx_off[3] = {0, 0, 0};
+    long hx_pair[3] = {0, 0, 0};
+    size_t hxp_off[3] = {0, 0, 0};    // the polyphase taps W0 | W0+W1+W2 | W2 in the same format (stretch convs)
+    size_t hx_fl = 0, hxp_fl = 0, hxc_fl = 0;      // floats of set 1 of each (= of its twin, set 2)
     // MODE_CHAIN (this conv fused behind its predecessor, fastsvc_hx.hip): per group [pred's nch32 units |
     // this conv's nch32 units] of 3 slots x MW fragments each; bias of the predecessor at bmid_off
-    size_t hxc_off[2] = {0, 0};
-    long hxc_pair[2] = {0, 0};
+    size_t hxc_off[3] = {0, 0, 0};
+    long hxc_pair[3] = {0, 0, 0};
     size_t bmid_off = 0;
     long bmid_pair = 0;
     // inverse per-output-channel weight scales of the split-binary16 fragments (ConvParams::whx_inv; float offsets,
@@ -210,7 +213,7 @@ struct fastsvc_plan {
     std::vector<RawParam*> raw_jobs;
     std::vector<int> cond_bound_jobs;   // conditioning stages with cbnd tables
     double flops_per_sample = 0.0;
-    int storage = 0;                    // activation storage in the workspace: 0 float32, 1 bfloat16
+    int storage = 0;                    // activation storage in the workspace: 0 float32, 1 bfloat16, 2 float16 (binary16)
     bool compact = false;               // workspace layout: intermediates of different stages share buffers (fastsvc_plan_set_workspace_mode)
     // autotuned launch choices (fastsvc_autotune), keyed by "layer|B|T"; guarded by tune_mu
     struct Choice { int NW, WM, WN, tpw, algo; };    // algo: 0 direct / as launched, 1 Winograd F(2,3)
@@ -223,7 +226,7 @@ struct fastsvc_plan {
 
     // |ln work ratio| + a quarter of |ln row-length ratio|: what a launch shape trades off (workgroups against tiles
     // per workgroup against columns per tile) depends on B * T first and on the row length second
-    bool prior_for(const char* layer, int B, int T, bool bf16, Choice& out) const {     // tune_mu held
+    bool prior_for(const char* layer, int B, int T, bool two_byte, Choice& out) const {     // tune_mu held; two_byte: entries with a storage tail ("|b", "|h")
         const size_t ln = std::strlen(layer);
         double best = 1e30;
         bool found = false;
@@ -233,7 +236,7 @@ struct fastsvc_plan {
             int b = 0, t = 0;
             char tail = 0;
             const int n = std::sscanf(k.c_str() + ln + 1, "%d|%d|%c", &b, &t, &tail);
-            if (n < 2 || b <= 0 || t <= 0 || (n == 3) != bf16) continue;
+            if (n < 2 || b <= 0 || t <= 0 || (n == 3) != two_byte) continue;
             const double d = std::fabs(std::log((double)b * t / ((double)B * T))) + 0.25 * std::fabs(std::log((double)t / T));
             if (d < best) { best = d; out = kv.second; found = true; }
         }
@@ -285,7 +288,7 @@ struct fastsvc_plan {
             for (int i = 0; i < npair; ++i) { c[i].hx = true; c[i].nch32 = (cin + 31) / 32; }
             for (int prec = 0; prec < 2; ++prec) {
                 const size_t fl = (size_t)c[0].ngroups * c[0].nch32 * 3 * c[0].MW * (prec == 0 ? 2 : 1) * 256;   // 1 KB fragments
-                for (int i = 0; i < npair; ++i) c[i].hx_off[prec] = alloc(fl);
+                for (int i = 0; i < npair; ++i) { c[i].hx_off[prec] = alloc(fl); if (prec == 1) c[i].hx_fl = fl; }
                 if (npair == 2) c[0].hx_pair[prec] = (long)(c[1].hx_off[prec] - c[0].hx_off[prec]) * 4;
             }
             for (int i = 0; i < npair; ++i) c[i].hx_inv_off = alloc(c[i].b_floats);
@@ -313,7 +316,7 @@ struct fastsvc_plan {
             for (int i = 0; i < 2; ++i) { c[i].hx = true; c[i].nch32 = (cin + 31) / 32; }
             for (int prec = 0; prec < 2; ++prec) {
                 const size_t fl = (size_t)c[0].ngroups * c[0].nch32 * 4 * c[0].MW * (prec == 0 ? 2 : 1) * 256;
-                for (int i = 0; i < 2; ++i) c[i].hx_off[prec] = alloc(fl);
+                for (int i = 0; i < 2; ++i) { c[i].hx_off[prec] = alloc(fl); if (prec == 1) c[i].hx_fl = fl; }
                 c[0].hx_pair[prec] = (long)(c[1].hx_off[prec] - c[0].hx_off[prec]) * 4;
             }
             for (int i = 0; i < 2; ++i) c[i].hx_inv_off = alloc(2 * c[i].b_floats);       // k=3 conv | 1x1 conv
@@ -335,7 +338,7 @@ struct fastsvc_plan {
             c[0].ngroups > 2 || a[0].dil > 4 || c[0].dil > 4) return;
         for (int prec = 0; prec < 2; ++prec) {
             const size_t fl = (size_t)c[0].ngroups * (a[0].nch32 + c[0].nch32) * 3 * c[0].MW * (prec == 0 ? 2 : 1) * 256;
-            for (int i = 0; i < 2; ++i) c[i].hxc_off[prec] = alloc(fl);
+            for (int i = 0; i < 2; ++i) { c[i].hxc_off[prec] = alloc(fl); if (prec == 1) c[i].hxc_fl = fl; }
             c[0].hxc_pair[prec] = (long)(c[1].hxc_off[prec] - c[0].hxc_off[prec]) * 4;
         }
         for (int i = 0; i < 2; ++i) c[i].bmid_off = a[i].b_off;
@@ -351,8 +354,11 @@ struct fastsvc_plan {
         plan_conv(c, 2 * C, 2 * C, 3, 1);
         if (c.MW < 2 || c.ngroups > 2) return;
         c.hx = true; c.nch32 = (2 * C + 31) / 32;
-        for (int prec = 0; prec < 2; ++prec)
-            c.hxc_off[prec] = alloc((size_t)c.ngroups * 2 * c.nch32 * 3 * c.MW * (prec == 0 ? 2 : 1) * 256);
+        for (int prec = 0; prec < 2; ++prec) {
+            const size_t fl = (size_t)c.ngroups * 2 * c.nch32 * 3 * c.MW * (prec == 0 ? 2 : 1) * 256;
+            c.hxc_off[prec] = alloc(fl);
+            if (prec == 1) c.hxc_fl = fl;
+        }
         c.b_off = heads.b_off;
         c.bmid_off = alloc(c.b_floats);
         c.hxc_inv_off = alloc(2 * c.b_floats + 4);
@@ -365,7 +371,8 @@ struct fastsvc_plan {
         PackedConv& c = u.head;
         if (!u.first.hx || !u.res.hx || !u.up.hx || !u.res.poly || !u.up.poly || u.first.MW != u.res.MW) return;
         c = u.res;                                     // geometry of the C -> C convs (MW, ngroups, biases of the residual conv)
-        c.hx_off[0] = c.hx_off[1] = 0; c.hxp_off[0] = c.hxp_off[1] = 0; c.hx_inv_off = c.hxp_inv_off = 0;
+        c.hx_off[0] = c.hx_off[1] = c.hx_off[2] = 0; c.hxp_off[0] = c.hxp_off[1] = c.hxp_off[2] = 0; c.hx_inv_off = c.hxp_inv_off = 0;
+        c.hx_fl = c.hxp_fl = c.hxc_fl = 0;
         if (c.ngroups > 4) return;
         c.nch32 = u.first.nch32;                       // units of the first conv; the polyphase convs have ceil(C / 32) each
         const int nchb = (u.C + 31) / 32;
@@ -382,11 +389,24 @@ struct fastsvc_plan {
     void add_xr_fuse(UpStage& u, const std::string& prefix) {
         PackedConv& c = u.d3;
         if (!c.hx || !u.res.hx || c.cin != c.cout || u.res.cin != c.cin || u.res.cout != c.cout || u.res.MW != c.MW) return;
-        for (int prec = 0; prec < 2; ++prec)
-            c.hxc_off[prec] = alloc((size_t)c.ngroups * 2 * c.nch32 * 3 * c.MW * (prec == 0 ? 2 : 1) * 256);
+        for (int prec = 0; prec < 2; ++prec) {
+            const size_t fl = (size_t)c.ngroups * 2 * c.nch32 * 3 * c.MW * (prec == 0 ? 2 : 1) * 256;
+            c.hxc_off[prec] = alloc(fl);
+            if (prec == 1) c.hxc_fl = fl;
+        }
         c.hxc_inv_off = alloc(2 * c.b_floats);
         c.b2_off = u.res.b_off;
         xr_jobs.push_back(XrJob{&c, prefix + ".conv_block1.1", prefix + ".residual_block.1"});
+    }
+
+    // float16 storage: the single-piece binary16 twin (set 2) of every bfloat16 fragment set of one conv or lft / sine
+    // pair.  Called once, after every other allocation (build_plan): the blob grows at its end only.
+    void add_f16_twins(PackedConv* c, int npair) {
+        for (int i = 0; i < npair; ++i) if (c[i].hx_off[1]) c[i].hx_off[2] = alloc(c[i].hx_fl);
+        if (npair == 2 && c[0].hx_off[2]) c[0].hx_pair[2] = (long)(c[1].hx_off[2] - c[0].hx_off[2]) * 4;
+        for (int i = 0; i < npair; ++i) if (c[i].hxp_off[1]) c[i].hxp_off[2] = alloc(c[i].hxp_fl);
+        for (int i = 0; i < npair; ++i) if (c[i].hxc_off[1]) c[i].hxc_off[2] = alloc(c[i].hxc_fl);
+        if (npair == 2 && c[0].hxc_off[2]) c[0].hxc_pair[2] = (long)(c[1].hxc_off[2] - c[0].hxc_off[2]) * 4;
     }
 
     void add_raw(RawParam* r, int npair, const std::vector<std::string>& layers, size_t wf, size_t bf) {
@@ -486,8 +506,11 @@ int build_plan(fastsvc_plan& P) {
                 pc->poly = true;
                 pc->wp_off = P.alloc(pc->w_floats);
                 if (pc->hx) {
-                    for (int prec = 0; prec < 2; ++prec)
-                        pc->hxp_off[prec] = P.alloc((size_t)pc->ngroups * pc->nch32 * 3 * pc->MW * (prec == 0 ? 2 : 1) * 256);
+                    for (int prec = 0; prec < 2; ++prec) {
+                        const size_t fl = (size_t)pc->ngroups * pc->nch32 * 3 * pc->MW * (prec == 0 ? 2 : 1) * 256;
+                        pc->hxp_off[prec] = P.alloc(fl);
+                        if (prec == 1) pc->hxp_fl = fl;
+                    }
                     pc->hxp_inv_off = P.alloc(pc->b_floats);
                 }
             }
@@ -504,6 +527,17 @@ int build_plan(fastsvc_plan& P) {
         cin = u.C;
     }
     P.add_raw(&P.last, 1, {"conv_last"}, (size_t)c.out_channels * cin, c.out_channels);
+    // ---- binary16 fragment sets of float16 storage: behind everything above, in plan order ----
+    for (int k = 0; k < n; ++k) {
+        DownStage& d = P.down[k];
+        for (PackedConv* pr : {d.r, d.c1, d.rc1, d.c2, d.c3, d.film}) P.add_f16_twins(pr, 2);
+        P.add_f16_twins(&d.heads, 1);
+        P.add_f16_twins(&d.filmc, 1);
+    }
+    for (int i = 0; i < n; ++i) {
+        UpStage& u = P.up[i];
+        for (PackedConv* pc : {&u.first, &u.res, &u.up, &u.d3, &u.d9, &u.d27, &u.head}) P.add_f16_twins(pc, 1);
+    }
     flops += 2.0 * cin * c.out_channels;
     P.flops_per_sample = flops;
     return FASTSVC_OK;
@@ -614,8 +648,8 @@ int fastsvc_pack_weights(const fastsvc_plan* plan, const fastsvc_tensor* tensors
     // says which output a fragment feeds (MODE_DEC2: slot 3 = the 1x1 conv; fused pair: the second conv's units).
     // (generic over the accessors: through std::function the per-element calls made this the longest part of a pack)
     struct OneTable { int operator()(int, int) const { return 0; } };
-    auto pack_hx = [&](const PackedConv& c, const size_t (&off)[2], int nslots, auto&& wt, size_t inv_off, int ntables,
-                       auto&& table_of_, int precs = 3 /* bit 0: binary16 pieces (+ the scale tables), bit 1: bfloat16 */,
+    auto pack_hx = [&](const PackedConv& c, const size_t (&off)[3], int nslots, auto&& wt, size_t inv_off, int ntables,
+                       auto&& table_of_, int precs = 3 /* bit 0: binary16 pieces (+ the scale tables), bit 1: bfloat16 and its binary16 twin */,
                        int gpart = 0, int gparts = 1 /* this call's share of the channel groups */) {
         const int g0 = c.ngroups * gpart / gparts, g1 = c.ngroups * (gpart + 1) / gparts;
         constexpr bool has_tables = !std::is_same<std::decay_t<decltype(table_of_)>, OneTable>::value;
@@ -637,8 +671,8 @@ int fastsvc_pack_weights(const fastsvc_plan* plan, const fastsvc_tensor* tensors
                     inv[(size_t)t * n16 + co] = std::ldexp(1.0f, -e);
                 }
         }
-        for (int prec = 0; prec < 2; ++prec) {
-            if (!off[prec] || !(precs & (1 << prec))) continue;   // (a fragment set that exists for one storage type only)
+        for (int prec = 0; prec < 3; ++prec) {
+            if (!off[prec] || !(precs & (1 << (prec == 2 ? 1 : prec)))) continue;   // (a fragment set that exists for one storage type only)
             const int np = prec == 0 ? 2 : 1;
             uint16_t* hp = reinterpret_cast<uint16_t*>(blob + off[prec]);
             for (int grp = g0; grp < g1; ++grp)
@@ -656,8 +690,10 @@ int fastsvc_pack_weights(const fastsvc_plan* plan, const fastsvc_tensor* tensors
                                         const uint16_t hi = f32_to_f16(v);
                                         frag[lane * 8 + e] = hi;
                                         frag[512 + lane * 8 + e] = f32_to_f16(v - f16_to_f32(hi));
-                                    } else {
+                                    } else if (prec == 1) {
                                         frag[lane * 8 + e] = f32_to_bf16(v);
+                                    } else {
+                                        frag[lane * 8 + e] = f32_to_f16(v);        // (unscaled: the kernels of 2-byte storage apply no inverse table)
                                     }
                                 }
                         }
@@ -1188,8 +1224,8 @@ Workspace layout_workspace(const fastsvc_plan& P, int B, int F) {
     int64_t hop = 1;
     for (int i = 0; i < n; ++i) hop *= P.cfg.upsampling_scales[i];
     const int64_t T = hop * F;
-    const size_t ae = P.storage == 1 ? 2 : sizeof(float);      // activation element size
-    if (P.storage == 1) ws.add("ppg_act", B, P.cfg.in_channels, F, ae);
+    const size_t ae = P.storage != 0 ? 2 : sizeof(float);      // activation element size
+    if (P.storage != 0) ws.add("ppg_act", B, P.cfg.in_channels, F, ae);
     // stages that run as whole-stage launches keep their intermediates in LDS: zero-sized placeholders (the amax rows
     // are indexed by buffer, taps of those names are empty)
     const bool whole[2] = {cond_stage_whole(P, 0, F), cond_stage_whole(P, 0, F) && cond_stage_whole(P, 1, F)};
@@ -1484,6 +1520,25 @@ bool timeline_launch(const char* layer, ConvParams p, long wgs, int nchunks, con
 hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int nsig, long pair_w_stride,
                     long pair_b_stride, hipStream_t stream, Profiler* prof, const char* layer);
 
+// Launch-table keys end in nothing (float32 storage), "|b" (bfloat16) or "|h" (float16).  The float16 objects have
+// bfloat16's instance set and register budgets, so a float16 plan that has no "|h" entry runs on the "|b" one.
+inline const char* key_suffix(int storage) { return storage == 2 ? "|h" : storage == 1 ? "|b" : ""; }
+template <class Map>
+inline auto tuned_find(Map& tuned, const char* key) -> decltype(tuned.find(key)) {
+    auto it = tuned.find(key);
+    const size_t n = std::strlen(key);
+    if (it == tuned.end() && n >= 2 && key[n - 2] == '|' && key[n - 1] == 'h') {
+        std::string kb(key);
+        kb[n - 1] = 'b';
+        it = tuned.find(kb);
+    }
+    return it;
+}
+// profile names: operand pieces and format of the products (x3 split binary16, x1 bfloat16, h1 binary16)
+inline const char* prod_tag(int storage) { return storage == 2 ? "h1" : storage == 1 ? "x1" : "x3"; }
+// a launcher of the plan's activation storage
+#define FASTSVC_BY_STORAGE(storage, fn) ((storage) == 2 ? f16::fn : (storage) == 1 ? bf16::fn : fn)
+
 hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob, ConvParams p, int nsig,
                      long pair_b_stride, hipStream_t stream, Profiler* prof, const char* layer, double sep_ms, bool& done,
                      const RawParam* in1 = nullptr) {
@@ -1492,8 +1547,9 @@ hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob
     done = false;
     static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
     static const int chain_env = std::getenv("FASTSVC_CHAIN") ? std::atoi(std::getenv("FASTSVC_CHAIN")) : 1;
-    const bool act_bf16 = g_tune.plan && g_tune.plan->storage == 1;
-    const int prec = act_bf16 ? 1 : 0;
+    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
+    const int prec = stg;                   // fragment set = storage
     p.ldx = p.x_T; p.ldy = p.T;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; }
     if (!hx_env || !chain_env || g_exact_f32 || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T ||
@@ -1516,12 +1572,12 @@ hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob
         p.dbg = dbg;
     }
     auto launch = [&](const ConvParams& q, const ConvLaunch& Lq) {
-        return act_bf16 ? bf16::launch_conv_hx(q, Lq, stream) : launch_conv_hx(q, Lq, stream);
+        return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, stream);
     };
     struct Cand { int NW, WM, WN; };
     std::vector<Cand> cands;
     static const int shapes[][3] = {{6, 2, 2}, {4, 2, 2}, {3, 1, 4}, {2, 1, 4}};
-    const int np = act_bf16 ? 1 : 2;
+    const int np = act_2b ? 1 : 2;
     for (const auto& sh : shapes) {
         if (!conv_hx_shape(p.mode, c.MW, sh[0], sh[1], sh[2]) || c.ngroups != sh[1]) continue;
         const int NT = 16 * sh[0] * sh[2];
@@ -1530,12 +1586,12 @@ hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob
     }
     if (cands.empty()) return hipSuccess;
     char key[96];
-    std::snprintf(key, sizeof(key), act_bf16 ? "%s|%d|%d|b" : "%s|%d|%d", layer, p.B, p.T);
+    std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
     bool have = false, fused = true;
     Cand best = cands[0];
     if (g_tune.plan) {
         std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        auto it = g_tune.plan->tuned.find(key);
+        auto it = tuned_find(g_tune.plan->tuned, key);
         if (it != g_tune.plan->tuned.end()) {
             if (it->second.algo != 3 && chain_env != 2) { have = true; fused = false; }      // FASTSVC_CHAIN=2: fused regardless (A/B)
             for (const Cand& cd : cands)
@@ -1596,11 +1652,11 @@ hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob
         double el = (in1 ? 1.0 : (double)a.cin) * p.T + (double)c.cout * p.T;
         if (p.res) el += (double)c.cout * p.T;
         if (p.r1x) el += (double)p.T;
-        const double bytes = (act_bf16 ? 2.0 : 4.0) * el * p.B * nsig +
+        const double bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig +
                              4.0 * (double)(a.w_floats + a.b_floats + c.w_floats + c.b_floats) * nsig;
         char kname[48];
         std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,%d,%d,1,%s>", L.MW, L.NW, L.WM, L.WN, p.mode,
-                      p.r1x ? 3 : p.res ? 2 : 1, act_bf16 ? "x1" : "x3");
+                      p.r1x ? 3 : p.res ? 2 : 1, prod_tag(stg));
         hipError_t e = prof->begin(stream, layer, kname, flops, bytes);
         if (e != hipSuccess) return e;
         e = launch(p, L);
@@ -1628,8 +1684,9 @@ hipError_t run_uphead(const UpStage& u, const float* blob, ConvParams p, hipStre
     static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
     static const int head_env = std::getenv("FASTSVC_UPHEAD") ? std::atoi(std::getenv("FASTSVC_UPHEAD")) : 1;
     const PackedConv& c = u.head;
-    const bool act_bf16 = g_tune.plan && g_tune.plan->storage == 1;
-    if (!hx_env || !head_env || g_exact_f32 || act_bf16 || !c.hxc_off[0] || (p.x_T & 3) || g_tune.tuning) return hipSuccess;
+    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
+    if (!hx_env || !head_env || g_exact_f32 || act_2b || !c.hxc_off[0] || (p.x_T & 3) || g_tune.tuning) return hipSuccess;
     p.T = p.x_T;
     p.ldx = p.x_T; p.ldy = p.x_T * u.scale;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; if ((p.len_mul & 3) != 0) return hipSuccess; }
@@ -1658,7 +1715,7 @@ hipError_t run_uphead(const UpStage& u, const float* blob, ConvParams p, hipStre
     bool fused = head_env == 2;
     if (g_tune.plan) {
         std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        auto it = g_tune.plan->tuned.find(key);
+        auto it = tuned_find(g_tune.plan->tuned, key);
         if (it != g_tune.plan->tuned.end()) {
             fused = it->second.algo == 3 || (head_env == 2 && it->second.algo != 0);
             if (it->second.algo == 0) fused = false;                     // table says: separate launches
@@ -1695,13 +1752,14 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
     static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
     static const int x_env = std::getenv("FASTSVC_D3X") ? std::atoi(std::getenv("FASTSVC_D3X")) : 1;     // 0: never, 2: wherever it exists (A/B)
     const PackedConv& c = u.d3;
-    const bool act_bf16 = g_tune.plan && g_tune.plan->storage == 1;
-    const int prec = act_bf16 ? 1 : 0;
+    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
+    const int prec = stg;                   // fragment set = storage
     p.ldx = p.x_T; p.ldy = p.T; p.ldx2 = p.x2_T;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; p.x2len_mul = p.x2_T / p.frames_ld; }
     if (!hx_env || !x_env || g_exact_f32 || p.no_hx || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T || (long)p.x2_T * p.s2 != p.T ||
         (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)) || !conv_hx_x2_ok(c.MW, c.nch32, p.s2) || c.dil > 28 ||
-        (act_bf16 && !conv_hx_x2_rows_ok(p)))
+        (act_2b && !conv_hx_x2_rows_ok(p)))
         return hipSuccess;
     p.mode = MODE_DIRECT; p.s = 1;
     p.CIN = c.cin; p.KC = c.KC; p.nchunks = c.nchunks; p.w = blob + c.w_off; p.Q = c.Q;
@@ -1718,7 +1776,7 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
         p.dbg = dbg;
     }
     auto launch = [&](const ConvParams& q, const ConvLaunch& Lq) {
-        return act_bf16 ? bf16::launch_conv_hx(q, Lq, stream) : launch_conv_hx(q, Lq, stream);
+        return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, stream);
     };
     struct Cand { int NW, WM, WN; };
     std::vector<Cand> cands;
@@ -1728,12 +1786,12 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
             cands.push_back(Cand{sh[0], sh[1], sh[2]});
     if (cands.empty()) return hipSuccess;
     char key[96];
-    std::snprintf(key, sizeof(key), act_bf16 ? "%s|%d|%d|b" : "%s|%d|%d", layer, p.B, p.T);
+    std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
     bool have = false, fused = true;
     Cand best = cands[0];
     if (g_tune.plan) {
         std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        auto it = g_tune.plan->tuned.find(key);
+        auto it = tuned_find(g_tune.plan->tuned, key);
         if (it != g_tune.plan->tuned.end()) {
             if (it->second.algo != 3 && x_env != 2) { have = true; fused = false; }
             for (const Cand& cd : cands)
@@ -1786,7 +1844,7 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
         if (g_tune.plan) {
             fastsvc_plan::Choice pr{0, 0, 0, 0, -1};
             std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-            if (g_tune.plan->prior_for(layer, p.B, p.T, act_bf16, pr)) {
+            if (g_tune.plan->prior_for(layer, p.B, p.T, act_2b, pr)) {
                 if (pr.algo != 3 && x_env != 2) fused = false;
                 for (const Cand& cd : cands) if (cd.NW == pr.NW && cd.WM == pr.WM && cd.WN == pr.WN) best = cd;
             }
@@ -1809,9 +1867,9 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
         const double cols = (double)p.T * p.B;
         const double flops = 2.0 * 2.0 * 3.0 * c.cin * c.cout * cols;      // both convs at the OUTPUT rate, as the reference runs them
         const double el = (double)c.cin * p.T + (double)c.cin * p.x2_T + 4.0 * c.cout * p.T;   // u1, a | xmid, u2, scale, shift
-        const double bytes = (act_bf16 ? 2.0 : 4.0) * el * p.B + 4.0 * 2.0 * (double)(c.w_floats + c.b_floats);
+        const double bytes = (act_2b ? 2.0 : 4.0) * el * p.B + 4.0 * 2.0 * (double)(c.w_floats + c.b_floats);
         char kname[48];
-        std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,0,4,%d,%s>", L.MW, L.NW, L.WM, L.WN, p.s2, act_bf16 ? "x1" : "x3");
+        std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,0,4,%d,%s>", L.MW, L.NW, L.WM, L.WN, p.s2, prod_tag(stg));
         hipError_t e = prof->begin(stream, layer, kname, flops, bytes);
         if (e != hipSuccess) return e;
         e = launch(p, L);
@@ -1841,7 +1899,7 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
     if (!cond_stage_whole(P, 0, F) || g_exact_f32 || (P.storage == 0 && (!amax_in || !amax_hd))) return hipSuccess;
     const DownStage& d = P.down[0];
     const DownStage& d1 = P.down[1];
-    const int prec = P.storage == 1 ? 1 : 0;
+    const int prec = P.storage;             // fragment set = storage
     CondStage0Params q;
     std::memset(&q, 0, sizeof(q));
     q.x = sig; q.x_sig = sig_stride; q.x_b = T;
@@ -1869,7 +1927,7 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
     // tiles per workgroup: the grid runs in whole rounds of the 2 x 256 resident workgroups, at most ~32 tiles each
     // (a workgroup's start - 24 KB of weight fragments per wave, zeroed tiles - costs about two tiles)
     // short tiles where the long ones would leave CUs without a workgroup (a batch below one round of them)
-    const long slots_all = P.storage == 1 ? 512 : 256;
+    const long slots_all = P.storage != 0 ? 512 : 256;
     static const int small_env = std::getenv("FASTSVC_COND_SMALL") ? std::atoi(std::getenv("FASTSVC_COND_SMALL")) : -1;
     {
         const int NTb = cond_stage0_tile_columns(0);
@@ -1883,14 +1941,14 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
     int pipe_mode = pipe_env;
     {
         char key[96];
-        std::snprintf(key, sizeof(key), P.storage == 1 ? "cond.0|%d|%ld|b" : "cond.0|%d|%ld", B, (long)T);
+        std::snprintf(key, sizeof(key), "cond.0|%d|%ld%s", B, (long)T, key_suffix(P.storage));
         std::lock_guard<std::mutex> lock(P.tune_mu);
-        auto it = P.tuned.find(key);
+        auto it = tuned_find(P.tuned, key);
         if (it != P.tuned.end() && it->second.algo == 4) pipe_mode = 0;
         if (it != P.tuned.end() && it->second.algo == 5) pipe_mode = 2;
     }
     if (pipe_mode && small_env < 0) {
-        const int NTp = cond_stage0_tile_columns(P.storage == 1 ? 3 : 2);
+        const int NTp = cond_stage0_tile_columns(P.storage != 0 ? 3 : 2);
         const long nchunks = (T + NTp - 1) / NTp;
         long kc = 0;
         {   // ONE round of the 256 resident workgroups (two rounds of half the run measured 1-3 % slower: tools/cond_pipe_tpw.sh)
@@ -1899,7 +1957,7 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
             if (k >= 24 || pipe_mode == 2) kc = k;
         }
         // (the pipeline addresses both signals' hd rows of an utterance through ONE 32-bit-offset descriptor)
-        const bool hd_fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * (P.storage == 1 ? 2L : 4L) < (1L << 31);
+        const bool hd_fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * (P.storage != 0 ? 2L : 4L) < (1L << 31);
         if (kc && hd_fits) { q.small = 2; q.tpw = (int)std::min<long>(tpw_env > 0 ? tpw_env : kc, 0xffff); }
     }
     const int NT = q.small == 2 ? 0 : cond_stage0_tile_columns(q.small);
@@ -1907,7 +1965,7 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
     if (q.small == 2) {}
     else if (tpw_env > 0) q.tpw = tpw_env;
     else {
-        const long slots = P.storage == 1 ? 512 : 256, total = ntx * B;     // workgroups resident at a time (LDS: two per CU in bfloat16 storage, one in float32)
+        const long slots = P.storage != 0 ? 512 : 256, total = ntx * B;     // workgroups resident at a time (LDS: two per CU in 2-byte storage, one in float32)
         const long rounds = std::max<long>(1, (total + slots * 32 - 1) / (slots * 32));
         long tpw = std::max<long>(1, (total + slots * rounds - 1) / (slots * rounds));
         // (per-utterance rounding: ceil(ntx / tpw) * B workgroups must not spill into one more round)
@@ -1930,15 +1988,14 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
         q.amax_hd = reinterpret_cast<float*>(trace_buf);
     }
     done = true;
-    auto launch = [&]() { return P.storage == 1 ? bf16::launch_cond_stage0(q, stream) : launch_cond_stage0(q, stream); };
+    auto launch = [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage0)(q, stream); };
     if (prof) {
         const double C = d.C, cols = (double)T * B;
         const double flops = (2.0 * (2.0 * (3.0 * C + C) + 2.0 * 3.0 * 3.0 * C * C) + 2.0 * 3.0 * 4.0 * C * C) * cols;
-        const double ae = P.storage == 1 ? 2.0 : 4.0;
+        const double ae = P.storage != 0 ? 2.0 : 4.0;
         const double bytes = (2.0 * 4.0 + 2.0 * C * ae + 2.0 * C * ae / d1.scale) * cols +
                              4.0 * (double)(2 * (d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
-        hipError_t e = prof->begin(stream, "cond.0", q.small == 2 ? (P.storage == 1 ? "cond_stage0_pipe<x1>" : "cond_stage0_pipe<x3>")
-                                                                 : (P.storage == 1 ? "cond_stage0<x1>" : "cond_stage0<x3>"), flops, bytes);
+        hipError_t e = prof->begin(stream, "cond.0", std::string(q.small == 2 ? "cond_stage0_pipe<" : "cond_stage0<") + prod_tag(P.storage) + ">", flops, bytes);
         if (e != hipSuccess) return e;
         e = launch();
         if (e != hipSuccess) return e;
@@ -1968,7 +2025,7 @@ hipError_t run_cond_stage1(const fastsvc_plan& P, const float* blob, const float
     if (!cond_stage_whole(P, 1, F) || g_exact_f32 || (P.storage == 0 && (!amax_in || !amax_hd))) return hipSuccess;
     const DownStage& d = P.down[1];
     const DownStage& d2 = P.down[2];
-    const int prec = P.storage == 1 ? 1 : 0;
+    const int prec = P.storage;             // fragment set = storage
     CondStage1Params q;
     std::memset(&q, 0, sizeof(q));
     q.x = x; q.ldx = (int)T1; q.x_b = (long)d.Cin * T1; q.x_sig = (long)B * q.x_b;
@@ -1994,21 +2051,21 @@ hipError_t run_cond_stage1(const fastsvc_plan& P, const float* blob, const float
     q.hd = hd; q.hd_ld = (int)(T1 / d2.scale); q.hd_s = d2.scale;
     q.hd_b = (long)d.C * q.hd_ld; q.hd_sig = (long)B * q.hd_b;
     // short tiles where the long ones would leave CUs without a workgroup (a batch below one round of them)
-    const long slots_all = P.storage == 1 ? 512 : 256;
+    const long slots_all = P.storage != 0 ? 512 : 256;
     static const int small_env = std::getenv("FASTSVC_COND_SMALL") ? std::atoi(std::getenv("FASTSVC_COND_SMALL")) : -1;
     {
         const int NTb = cond_stage1_tile_columns(0);
         q.small = small_env >= 0 ? small_env : (((T1 + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
     }
-    // the layer pipeline (cond_stage1_pipe_kernel, bfloat16 storage only; q.small = 2, tpw = 32-column chunks per workgroup):
-    // its fill is 11 steps, so only for long runs; "cond.1|B|T1|b" in the launch table forces either (algorithm 4 / 5)
+    // the layer pipeline (cond_stage1_pipe_kernel, 2-byte storage only; q.small = 2, tpw = 32-column chunks per workgroup):
+    // its fill is 11 steps, so only for long runs; "cond.1|B|T1|b" ("|h") in the launch table forces either (algorithm 4 / 5)
     static const int pipe_env = std::getenv("FASTSVC_COND_PIPE") ? std::atoi(std::getenv("FASTSVC_COND_PIPE")) : 1;
-    int pipe_mode = P.storage == 1 ? pipe_env : 0;
-    if (P.storage == 1) {
+    int pipe_mode = P.storage != 0 ? pipe_env : 0;
+    if (P.storage != 0) {
         char key[96];
-        std::snprintf(key, sizeof(key), "cond.1|%d|%ld|b", B, (long)T1);
+        std::snprintf(key, sizeof(key), "cond.1|%d|%ld%s", B, (long)T1, key_suffix(P.storage));
         std::lock_guard<std::mutex> lock(P.tune_mu);
-        auto it = P.tuned.find(key);
+        auto it = tuned_find(P.tuned, key);
         if (it != P.tuned.end() && it->second.algo == 4) pipe_mode = 0;
         if (it != P.tuned.end() && it->second.algo == 5) pipe_mode = 2;
     }
@@ -2029,21 +2086,21 @@ hipError_t run_cond_stage1(const fastsvc_plan& P, const float* blob, const float
     if (q.small == 2) {}
     else if (tpw_env > 0) q.tpw = tpw_env;
     else {
-        const long slots = P.storage == 1 ? 512 : 256, total = ntx * B;
+        const long slots = P.storage != 0 ? 512 : 256, total = ntx * B;
         const long rounds = std::max<long>(1, (total + slots * 32 - 1) / (slots * 32));
         long tpw = std::max<long>(1, (total + slots * rounds - 1) / (slots * rounds));
         while (tpw < ntx && ((ntx + tpw - 1) / tpw) * B > slots * rounds) ++tpw;
         q.tpw = (int)std::min<long>(tpw, ntx);
     }
     done = true;
-    auto launch = [&]() { return P.storage == 1 ? bf16::launch_cond_stage1(q, stream) : launch_cond_stage1(q, stream); };
+    auto launch = [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage1)(q, stream); };
     if (prof) {
         const double C = d.C, Ci = d.Cin, cols = (double)T1 * B;
         const double flops = (2.0 * (2.0 * (3.0 * Ci * C + Ci * C) + 2.0 * 3.0 * 3.0 * C * C) + 2.0 * 3.0 * 4.0 * C * C) * cols;
-        const double ae = P.storage == 1 ? 2.0 : 4.0;
+        const double ae = P.storage != 0 ? 2.0 : 4.0;
         const double bytes = (2.0 * Ci * ae + 2.0 * C * ae + 2.0 * C * ae / d2.scale) * cols +
                              4.0 * (double)(2 * (d.rc1[0].w_floats + d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
-        hipError_t e = prof->begin(stream, "cond.1", q.small == 2 ? "cond_stage1_pipe<x1>" : P.storage == 1 ? "cond_stage1<x1>" : "cond_stage1<x3>", flops, bytes);
+        hipError_t e = prof->begin(stream, "cond.1", std::string(q.small == 2 ? "cond_stage1_pipe<" : "cond_stage1<") + prod_tag(P.storage) + ">", flops, bytes);
         if (e != hipSuccess) return e;
         e = launch();
         if (e != hipSuccess) return e;
@@ -2057,11 +2114,12 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
                     const char* layer) {
     p.CIN = c.cin; p.KC = c.KC; p.nchunks = c.nchunks;
     p.w = blob + c.w_off; p.w_sig = pair_w_stride;
-    const bool act_bf16 = g_tune.plan && g_tune.plan->storage == 1;
+    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
     auto launch = [&](const ConvParams& q, const ConvLaunch& Lq, hipStream_t st) {
-        if (Lq.pipe == 3) return act_bf16 ? bf16::launch_conv_wx(q, Lq, st) : launch_conv_wx(q, Lq, st);
-        if (Lq.pipe == 2) return act_bf16 ? bf16::launch_conv_hx(q, Lq, st) : launch_conv_hx(q, Lq, st);
-        return act_bf16 ? bf16::launch_conv(q, Lq, st) : launch_conv(q, Lq, st);
+        if (Lq.pipe == 3) return FASTSVC_BY_STORAGE(stg, launch_conv_wx)(q, Lq, st);
+        if (Lq.pipe == 2) return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, st);
+        return FASTSVC_BY_STORAGE(stg, launch_conv)(q, Lq, st);
     };
     static const bool no_poly = std::getenv("FASTSVC_NO_POLY") != nullptr;   // A/B switch
     const long T_out = p.T;                                  // output columns (accounting below)
@@ -2161,7 +2219,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         static const int wx_env = std::getenv("FASTSVC_WX") ? std::atoi(std::getenv("FASTSVC_WX")) : 1;
         ConvParams pw = p;
         pw.nch32 = c.nch32;                              // (what geometry() sets for the candidate)
-        const bool wx_ok = hx_ok && wx_env != 0 && act_bf16 && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
+        const bool wx_ok = hx_ok && wx_env != 0 && act_2b && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
                            conv_wx_supported(pw);
         bool wx_have = false;                            // ... and the layer has a shape of it
         if (wx_ok) {
@@ -2198,7 +2256,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         // stride that keeps the component reads conflict-free (planes land 16/D banks apart)
         auto geometry = [&](const Cand& cd, ConvParams& q) {
             if (cd.algo == 3 || cd.algo == 6) {
-                const int prec = act_bf16 ? 1 : 0;
+                const int prec = stg;                   // fragment set = storage
                 q.whx = blob + (p.mode == MODE_POLY ? c.hxp_off[prec] : c.hx_off[prec]); q.whx_sig = c.hx_pair[prec]; q.nch32 = c.nch32;
                 const size_t inv_off = p.mode == MODE_POLY ? c.hxp_inv_off : c.hx_inv_off;
                 q.whx_inv = (prec == 0 && inv_off) ? blob + inv_off : nullptr; q.whx_inv_sig = c.hx_inv_pair;
@@ -2222,13 +2280,13 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
             }
         };
         char key[96];
-        // bfloat16 storage compiles some variants under a different register budget: its own entries ("|b")
-        std::snprintf(key, sizeof(key), act_bf16 ? "%s|%d|%d|b" : "%s|%d|%d", layer, p.B, p.T);
+        // 2-byte storage compiles some variants under a different register budget: its own entries ("|b"; float16: "|h", then "|b")
+        std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
         bool have = false;
         Cand best = cands[0];
         if (g_tune.plan) {
             std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-            auto it = g_tune.plan->tuned.find(key);
+            auto it = tuned_find(g_tune.plan->tuned, key);
             if (it != g_tune.plan->tuned.end()) {
                 // a loaded table may be stale: only shapes this launch is compiled for are taken
                 for (const Cand& cd : cands)
@@ -2293,7 +2351,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
                 auto it = g_tune.plan->priors.find(key);
                 if (it != g_tune.plan->priors.end()) pr = it->second;
                 else {
-                    if (!g_tune.plan->prior_for(layer, p.B, p.T, act_bf16, pr)) pr.algo = -1;
+                    if (!g_tune.plan->prior_for(layer, p.B, p.T, act_2b, pr)) pr.algo = -1;
                     g_tune.plan->priors[key] = pr;
                 }
             }
@@ -2341,12 +2399,12 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
                 const long ntx = (p.T + NT - 1) / NT;
                 const long gy = c.ngroups / cd.WM;
                 const double win = NT + 2.0 * ((halo + 3) & ~3);
-                const double esz = act_bf16 ? 2.0 : 4.0;
+                const double esz = act_2b ? 2.0 : 4.0;
                 const double out_streams = (p.y ? 1 : 0) + ((p.flags & F_AFF_OUT) ? 3 : 0) + (p.res ? 1 : 0);
                 const double bytes_unit = 32.0 * win * esz + 16.0 * c.MW * cd.WM * NT * (poly ? p.s : 1) * esz *
                                           (out_streams + (p.mode == MODE_DEC2 ? 1 : 0)) / c.nch32;
                 const double mem_us = bytes_unit / (4.5e6 / 256.0);
-                const double mfma_us = (poly ? 5.0 : p.mode == MODE_DEC2 ? 4.0 : 3.0) * cd.NW * c.MW * (act_bf16 ? 1 : 3) * 17.0 / 2.0e3;
+                const double mfma_us = (poly ? 5.0 : p.mode == MODE_DEC2 ? 4.0 : 3.0) * cd.NW * c.MW * (act_2b ? 1 : 3) * 17.0 / 2.0e3;
                 const double unit_us = mem_us > mfma_us ? mem_us : mfma_us;
                 for (int tpw = 1; tpw <= 24; ++tpw) {
                     const long wgs = ((ntx + tpw - 1) / tpw) * gy * zb;
@@ -2421,7 +2479,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         if (p.res) el += (double)c.cout * T_out;
         if (p.r1x) el += (double)T_out;
         if (p.flags & (F_STATS | F_AFF_OUT)) el += 2.0 * c.cout * T_out;
-        double bytes = (act_bf16 ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(c.w_floats + c.b_floats) * nsig;
+        double bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(c.w_floats + c.b_floats) * nsig;
         double flops_all = flops;
         if (p.last_w) {                                   // + conv_last: C -> 1, float32 waveform out (the C-channel tensor is not written: p.y is null)
             flops_all += 2.0 * c.cout * cols;
@@ -2430,13 +2488,13 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         char kname[40];
         if (L.pipe == 3) {
             const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
-            std::snprintf(kname, sizeof(kname), "conv_wx<%d,%d,%d,%d,%d,%s>", L.MW, L.NW, L.WM, L.WN, aff ? 4 : p.res ? 2 : 1, act_bf16 ? "x1" : "x3");
+            std::snprintf(kname, sizeof(kname), "conv_wx<%d,%d,%d,%d,%d,%s>", L.MW, L.NW, L.WM, L.WN, aff ? 4 : p.res ? 2 : 1, prod_tag(stg));
         } else if (L.pipe == 2) {
             const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
             const int kind = aff ? 4 : p.r1x ? 3 : p.res ? 2 : 1;
             const bool tail_inst = p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0);      // the row-end (TAILK) instance
             std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,%d,%d,%d,%s%s>", L.MW, L.NW, L.WM, L.WN, p.mode,
-                          p.mode == MODE_DEC2 ? 1 : poly ? (aff ? 4 : 1) : kind, poly ? p.s : 1, act_bf16 ? "x1" : "x3",
+                          p.mode == MODE_DEC2 ? 1 : poly ? (aff ? 4 : 1) : kind, poly ? p.s : 1, prod_tag(stg),
                           tail_inst ? ",tail" : "");
         } else if (L.pipe)
         {
@@ -2458,7 +2516,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         if (e != hipSuccess) return e;
         return prof->end();
     }
-    if (act_bf16 && !L.pipe) return hipErrorNotSupported;   // the scalar kernel exists for float32 storage only
+    if (act_2b && !L.pipe) return hipErrorNotSupported;   // the scalar kernel exists for float32 storage only
 #ifdef FASTSVC_TIMELINE
     if (L.pipe) {
         const int NT = (p.mode == MODE_WINO ? 32 : 16) * L.NW * L.WN;
@@ -2537,12 +2595,13 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         return fail(FASTSVC_E_INVALID, "null argument");
     if (B < 1 || F < 1) return fail(FASTSVC_E_INVALID, "B and F must be >= 1");
     const fastsvc_plan& P = *plan;
-    if (P.storage == 1) {
-        if (F % 4 != 0) return fail(FASTSVC_E_UNSUPPORTED, "bfloat16 storage needs a frame count that is a multiple of 4");
+    if (P.storage != 0) {
+        const std::string mode = P.storage == 2 ? "float16 storage" : "bfloat16 storage";
+        if (F % 4 != 0) return fail(FASTSVC_E_UNSUPPORTED, mode + " needs a frame count that is a multiple of 4");
         for (int k = 0; k < P.n; ++k)
             if (P.down[k].c2[0].KC != 24 || P.up[k].d3.KC != 24 || P.up[k].first.KC != 24)
-                return fail(FASTSVC_E_UNSUPPORTED, "bfloat16 storage needs the pipelined kernels (24-channel K chunks)");
-        if (P.n > 1 && !P.down[1].rc1[0].dec2) return fail(FASTSVC_E_UNSUPPORTED, "bfloat16 storage needs the fused decimating pair");
+                return fail(FASTSVC_E_UNSUPPORTED, mode + " needs the pipelined kernels (24-channel K chunks)");
+        if (P.n > 1 && !P.down[1].rc1[0].dec2) return fail(FASTSVC_E_UNSUPPORTED, mode + " needs the fused decimating pair");
     }
     if (spk_emb && !P.cfg.use_spk_emb)
         return fail(FASTSVC_E_INVALID, "spk_emb given but the generator was built with use_spk_emb=False");
@@ -2689,7 +2748,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             if (k == 0) {
                 if (pr) HIP_TRY(pr->begin(stream, "down.0.c1", "in1_conv", 2.0 * 3 * d.C * (double)Tk * B * 2,
                                               4.0 * (1.0 + d.C) * (double)Tk * B * 2));
-                HIP_TRY((P.storage == 1 ? bf16::launch_in1_conv : launch_in1_conv)(sigbuf, sig_stride, blob + d.c1_raw[0].w_off, blob + d.c1_raw[0].b_off,
+                HIP_TRY(FASTSVC_BY_STORAGE(P.storage, launch_in1_conv)(sigbuf, sig_stride, blob + d.c1_raw[0].w_off, blob + d.c1_raw[0].b_off,
                                         (long)(d.c1_raw[1].w_off - d.c1_raw[0].w_off),
                                         (long)(d.c1_raw[1].b_off - d.c1_raw[0].b_off), c1, 2, B, d.C, (int)Tk,
                                         lengths, (int)(Tk / F), stream, nullptr));     // (c1 is bounded, not measured)
@@ -2884,9 +2943,9 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     // ---- up blocks ----
     if (spk) HIP_TRY(order_after(s_pre, stream));           // speaker biases and zeroed sums are ready
     const float* x = ppg;
-    if (P.storage == 1) {                                          // external float32 input -> workspace bf16
+    if (P.storage != 0) {                                          // external float32 input -> workspace bfloat16 / binary16
         float* pa = buf("ppg_act");
-        HIP_TRY(bf16::launch_act_convert(ppg, pa, (long)B * P.cfg.in_channels * F, stream));
+        HIP_TRY((P.storage == 2 ? f16::launch_act_convert : bf16::launch_act_convert)(ppg, pa, (long)B * P.cfg.in_channels * F, stream));
         x = pa;
     }
     int Cx = P.cfg.in_channels;
@@ -2896,9 +2955,9 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     {
         static const bool no_fuse = std::getenv("FASTSVC_NO_FUSE_LAST") != nullptr;     // A/B switch
         char key[96];
-        std::snprintf(key, sizeof(key), P.storage == 1 ? "conv_last|%d|%ld|b" : "conv_last|%d|%ld", B, (long)T);
+        std::snprintf(key, sizeof(key), "conv_last|%d|%ld%s", B, (long)T, key_suffix(P.storage));
         std::lock_guard<std::mutex> lock(P.tune_mu);
-        auto it = P.tuned.find(key);
+        auto it = tuned_find(P.tuned, key);
         if (no_fuse || (it != P.tuned.end() && it->second.algo != 3)) last_fusable = false;
     }
     for (int i = 0; i < n; ++i) {
@@ -3074,7 +3133,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     if (last_done) return FASTSVC_OK;
     if (prof) HIP_TRY(prof->begin(stream, "conv_last", "pointwise_out", 2.0 * Cx * P.cfg.out_channels * (double)T * B,
                                   4.0 * (Cx + P.cfg.out_channels) * (double)T * B));
-    HIP_TRY((P.storage == 1 ? bf16::launch_pointwise_out : launch_pointwise_out)(x, blob + P.last.w_off, blob + P.last.b_off, out, B, Cx,
+    HIP_TRY(FASTSVC_BY_STORAGE(P.storage, launch_pointwise_out)(x, blob + P.last.w_off, blob + P.last.b_off, out, B, Cx,
                                  P.cfg.out_channels, (int)T, lengths, (int)hop, stream));
     if (prof) HIP_TRY(prof->end());
     return FASTSVC_OK;
@@ -3100,7 +3159,7 @@ int fastsvc_stream_prepare(void* stream) {
 int fastsvc_stream_release(void* stream) { return exec_ctx_release(static_cast<hipStream_t>(stream)); }
 
 int fastsvc_plan_set_storage(fastsvc_plan* plan, int32_t dtype) {
-    if (!plan || (dtype != 0 && dtype != 1)) return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32) or 1 (bfloat16)");
+    if (!plan || (dtype != 0 && dtype != 1 && dtype != 2)) return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
     plan->storage = dtype;
     return FASTSVC_OK;
 }

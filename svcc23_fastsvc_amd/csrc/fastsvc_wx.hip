@@ -39,8 +39,8 @@
 #include "fastsvc_kernels.h"
 
 namespace fastsvc {
-#ifdef FASTSVC_ACT_BF16
-namespace bf16 {
+#ifdef FASTSVC_ACT_2B
+namespace FASTSVC_ACT_NS {
 #endif
 
 #include "fastsvc_device.inc"
@@ -88,7 +88,7 @@ __device__ __forceinline__ void wx_unit(f32x4 (&acc)[NW][MW], const unsigned cha
 
 template <int V> struct WxC { static constexpr int value = V; };        // a compile-time index (register set, role)
 
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
 // Plain / residual epilogue of a wave's 48-channel x 96-column tile (see the file header).  acc: [n][m] result tiles in the
 // MFMA layout (lane (co = lane & 15, q = lane >> 4): channel co, columns 16 n + 4 q ..+3).
 //   v = lrelu?(acc + bias) [+ residual]  ->  bfloat16, 8 bytes per tile into the patch row of the channel;
@@ -161,8 +161,8 @@ __device__ __forceinline__ void wx_epilogue_rows(const ConvParams& p, const EpiR
             if constexpr (EPI == EPI_RES) v += act_unpack4(ops[m % NSET][0][n]);
             acc[n][m] = v;
             u32x2v w;
-            w.x = bf16_pack2(v.x, v.y);
-            w.y = bf16_pack2(v.z, v.w);
+            w.x = a16_pack2(v.x, v.y);
+            w.y = a16_pack2(v.z, v.w);
             *reinterpret_cast<u32x2v*>(wrow + n * 32) = w;
         }
         if (EPI != EPI_AFF || p.y) rows_out(R.y, m);            // (wave-uniform)
@@ -175,8 +175,8 @@ __device__ __forceinline__ void wx_epilogue_rows(const ConvParams& p, const EpiR
                 s1[m] += (u.x + u.y) + (u.z + u.w);
                 s2[m] += (u.x * u.x + u.y * u.y) + (u.z * u.z + u.w * u.w);
                 u32x2v w;
-                w.x = bf16_pack2(u.x, u.y);
-                w.y = bf16_pack2(u.z, u.w);
+                w.x = a16_pack2(u.x, u.y);
+                w.y = a16_pack2(u.z, u.w);
                 *reinterpret_cast<u32x2v*>(wrow + n * 32) = w;
             }
             rows_out(R.y2, m);
@@ -185,7 +185,7 @@ __device__ __forceinline__ void wx_epilogue_rows(const ConvParams& p, const EpiR
 }
 #endif
 
-#ifdef FASTSVC_ACT_BF16           // (bfloat16 storage only: the float32 unit keeps the host queries below)
+#ifdef FASTSVC_ACT_2B           // (2-byte storage only: the float32 unit keeps the host queries below)
 // PRO: staging prologue (0 none, 1 LeakyReLU, 2 InstanceNorm + speaker bias + LeakyReLU); EPI: epilogue kind (fastsvc_device.inc)
 template <int PRO, int EPI>
 __global__ __launch_bounds__(WX_NT, 2)
@@ -351,12 +351,12 @@ void conv_wx_kernel(const ConvParams p0) {
             #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const unsigned w = px[c][j >> 1];
-                float v = __builtin_bit_cast(float, (j & 1) ? (w & 0xffff0000u) : (w << 16));
+                float v = (j & 1) ? a16_hi(w) : a16_lo(w);
                 if constexpr (PRO == 2) v = v * cA[c] + cB[c];
                 e[c] = fmaxf(v, v * slope);
             }
-            o.x = bf16_pack2(e[0], e[1]);
-            o.y = bf16_pack2(e[2], e[3]);
+            o.x = a16_pack2(e[0], e[1]);
+            o.y = a16_pack2(e[2], e[3]);
         }
         if (j >= 4 && row_end) {                                       // (what lies behind the row's end is nobody's data)
             o.x = nvs[SET] > 4 ? o.x : 0u;
@@ -449,7 +449,7 @@ void conv_wx_kernel(const ConvParams p0) {
         const int tcolw = (tile0 + tile) * NT + wave_n * (NW * 16);
         #pragma unroll
         for (int m = 0; m < MW; ++m) { s1[m] = 0.f; s2[m] = 0.f; }
-#ifdef FASTSVC_ACT_BF16
+#ifdef FASTSVC_ACT_2B
         wx_epilogue_rows<EPI>(p, R, acc, k_bias, s1, s2, mg, tcolw, lane, patch);
 #else
         ws_epilogue_kind<MW, NW, EPI, false, 0, -1>(p, R, acc, s1, s2, sig, mg, tcolw, true, lane, K, nullptr);
@@ -531,7 +531,7 @@ static hipError_t wx_launch_instance(dim3 grid, size_t smem, hipStream_t stream,
 }
 
 hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_t stream) {
-#ifndef FASTSVC_ACT_BF16
+#ifndef FASTSVC_ACT_2B
     return hipErrorInvalidValue;                               // (float32 storage: not built)
 #else
     if (!conv_wx_supported(p) || (p.T & 3) || !p.whx || cfg.MW != WX_MW || cfg.NW != WX_NW || cfg.WM != WX_WM || cfg.WN != WX_WN ||
@@ -554,7 +554,7 @@ hipError_t launch_conv_wx(const ConvParams& p, const ConvLaunch& cfg, hipStream_
 #endif
 }
 
-#ifndef FASTSVC_ACT_BF16      // storage-independent host queries: defined once
+#ifndef FASTSVC_ACT_2B      // storage-independent host queries: defined once
 bool conv_wx_shape(int mode, int MW, int NW, int WM, int WN) {
     return mode == MODE_DIRECT && MW == WX_MW && NW == WX_NW && WM == WX_WM && WN == WX_WN;
 }
@@ -575,7 +575,7 @@ bool conv_wx_fits(int nch32, int dil) {
 }
 #endif
 
-#ifdef FASTSVC_ACT_BF16
-}  // namespace bf16
+#ifdef FASTSVC_ACT_2B
+}  // namespace FASTSVC_ACT_NS
 #endif
 }  // namespace fastsvc

@@ -233,6 +233,8 @@ def main(argv=None) -> None:                                  # pragma: no cover
     ap.add_argument("--srcf0stats", default=None)
     ap.add_argument("--trgf0stats", default=None)
     ap.add_argument("--max-batch", type=int, default=32)
+    ap.add_argument("--storage", default="float32", choices=["float32", "bfloat16", "float16"],
+                    help="activation storage of the generator's forward (FastSVCGenerator.activation_storage)")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -240,6 +242,7 @@ def main(argv=None) -> None:                                  # pragma: no cover
     model = FastSVCGenerator(**config["generator_params"])
     model.load_state_dict(torch.load(args.checkpoint, map_location="cpu")["model"]["generator"])
     model.remove_weight_norm()
+    model.activation_storage = args.storage
     model = model.eval().to(device)
     sg_conf = config.get("signal_generator", {})
     sg = SignalGenerator(sample_rate=config["sampling_rate"], hop_size=config["hop_size"],

@@ -24,6 +24,9 @@ _LIB_PATH = os.environ.get("FASTSVC_HIP_LIB") or \
 MAX_STAGES = 8
 # launch shapes measured once on an MI355X by tools/tune_shapes.py (fastsvc_autotune winners for
 # the BASELINE.json workloads); other (B, F) fall back to the static cost model or model.autotune
+# activation storage of a plan: name -> fastsvc_plan_set_storage code / the dtype of the workspace taps
+STORAGE_CODES = {"float32": 0, "bfloat16": 1, "float16": 2}
+STORAGE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
 TUNED_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_mi355x.json")
 
 # every symbol include/fastsvc_hip.h declares (checked by tests/test_boundary.py)
@@ -222,13 +225,15 @@ class Plan:
 
     def __init__(self, cfg: GeneratorConfig, load_shipped_table: bool = True, storage: str = "float32",
                  compact_workspace: bool = False):
-        """``storage``: "float32" (default, the parity path) or "bfloat16" - every workspace tensor is
+        """``storage``: "float32" (default, the parity path), "bfloat16" - every workspace tensor is
         stored as bf16 (half the HBM traffic of the narrow layers, half the workspace; fp32 arithmetic;
-        bf16-activation accuracy, frame counts must be multiples of 4).
+        bf16-activation accuracy, frame counts must be multiples of 4) - or "float16": the same tensors as IEEE
+        binary16 (bfloat16's bytes and kernels' shapes, 11 significand bits instead of 8; unscaled, so every workspace
+        tensor must stay below 65504 in magnitude - see fastsvc_plan_set_storage in include/fastsvc_hip.h).
         ``compact_workspace``: intermediates of different stages share buffers (about 40 % less memory for long
         batches); the ``tap`` of a shared buffer then holds the last stage's tensor only."""
-        if storage not in ("float32", "bfloat16"):
-            raise ValueError("storage must be 'float32' or 'bfloat16'")
+        if storage not in STORAGE_CODES:
+            raise ValueError("storage must be 'float32', 'bfloat16' or 'float16'")
         self.storage = storage
         self.cfg = cfg
         self.lib = load_library()
@@ -246,9 +251,10 @@ class Plan:
         handle = ctypes.c_void_p()
         _check(self.lib, self.lib.fastsvc_plan_create(ctypes.byref(c), ctypes.byref(handle)), "fastsvc_plan_create")
         self._h = handle
-        if storage == "bfloat16":
-            _check(self.lib, self.lib.fastsvc_plan_set_storage(handle, 1), "fastsvc_plan_set_storage")
-            # (bfloat16 launches look their shapes up under "<layer>|<B>|<T>|b": separate entries of the same table)
+        if storage != "float32":
+            _check(self.lib, self.lib.fastsvc_plan_set_storage(handle, STORAGE_CODES[storage]), "fastsvc_plan_set_storage")
+            # (bfloat16 launches look their shapes up under "<layer>|<B>|<T>|b": separate entries of the same table;
+            # float16 launches under "...|h" first, then under "...|b")
         self.compact_workspace = bool(compact_workspace)
         if compact_workspace:
             _check(self.lib, self.lib.fastsvc_plan_set_workspace_mode(handle, 1), "fastsvc_plan_set_workspace_mode")
@@ -288,7 +294,9 @@ class Plan:
         T = F
         for sc in self.cfg.upsampling_scales:
             T *= int(sc)
-        self.load_tuned({f"conv_last|{B}|{T}": [1, 1, 4, 1, 0], f"conv_last|{B}|{T}|b": [1, 1, 4, 1, 0]})
+        # (a float16 plan reads "|h" first and "|b" where there is none: its own entry, in case a tuning run wrote one)
+        self.load_tuned({f"conv_last|{B}|{T}{sfx}": [1, 1, 4, 1, 0]
+                         for sfx in ("", "|b") + (("|h",) if self.storage == "float16" else ())})
 
     def fuse_block_heads(self, B: int, F: int, fused: bool = True) -> None:
         """The head of an up block - ``conv_first`` and the two stretched convs behind it - can run as ONE launch
@@ -317,6 +325,8 @@ class Plan:
             T *= int(sc)
             table[f"up.{i}.d3x|{B}|{T}"] = [2, 1, 4, 1, 0]
             table[f"up.{i}.d3x|{B}|{T}|b"] = [2, 1, 4, 1, 0]
+            if self.storage == "float16":
+                table[f"up.{i}.d3x|{B}|{T}|h"] = [2, 1, 4, 1, 0]
         self.load_tuned(table)
 
     def load_tuned_file(self, path: str, missing_ok: bool = False) -> int:
@@ -346,6 +356,9 @@ class Plan:
                     "accumulation; weights scaled per output channel and activations per tensor and utterance by exact "
                     "powers of two into binary16's range, undone in the epilogue: fp32-class, 4e-6 of the f32-MFMA path, "
                     "held over 2^-20..2^8 input / weight scales by tests/test_dynamic_range_gpu.py)") if hx else "f32"
+        if self.storage == "float16":
+            return ("f16 (binary16 MFMA products, f32 accumulate, binary16 activation storage, unscaled)" if hx
+                    else "f32 arithmetic, binary16 activation storage")
         return ("bf16 (bf16 MFMA products, f32 accumulate, bf16 activation storage)" if hx
                 else "f32 arithmetic, bf16 activation storage")
 
@@ -379,7 +392,7 @@ class Plan:
 
     def padded_frames(self, F: int) -> int:
         """Frame count the library actually runs for an F-frame batch: the next multiple of 4 (the padded batch is run
-        as a ragged one).  bfloat16 storage needs it; float32 storage takes any F, but rows that are not a multiple of
+        as a ragged one).  bfloat16 and float16 storage need it; float32 storage takes any F, but rows that are not a multiple of
         4 long (F-rate and 2F-rate tensors) send their layers to the slower gathered kernels - 64 x 1499 frames took
         27.0 ms against 22.5 ms for 64 x 1500 (tools/ragged_check.py) - so `Plan.forward` pads there too."""
         return F + ((-F) % 4)
@@ -464,8 +477,8 @@ class Plan:
         off, numel, shape = self.tap_info(name, B, F)
         if name.endswith(".stats"):
             return workspace[off: off + numel * 8].view(torch.float64).view(shape)
-        if self.storage == "bfloat16" and name != "sig" and not name.endswith(".spk"):
-            return workspace[off: off + numel * 2].view(torch.bfloat16).view(shape)
+        if self.storage != "float32" and name != "sig" and not name.endswith(".spk"):
+            return workspace[off: off + numel * 2].view(STORAGE_DTYPES[self.storage]).view(shape)
         return workspace[off: off + numel * 4].view(torch.float32).view(shape)
 
     _LENS_SLOTS = 32
@@ -526,8 +539,8 @@ class Plan:
         ppg, sine, lft = (t.to(torch.float32).contiguous() for t in (ppg, sine, lft))
         if spk_emb is not None:
             spk_emb = spk_emb.to(torch.float32).contiguous()
-        if F % 4 != 0 and profile is None and (self.storage == "bfloat16" or self.pad_odd_lengths):
-            # bfloat16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0
+        if F % 4 != 0 and profile is None and (self.storage != "float32" or self.pad_odd_lengths):
+            # bfloat16 / float16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0
             # (three of four real utterances are not); float32 storage runs such rows on its slower kernels.  Pad to
             # the next multiple and run the padded batch as a ragged one - `lengths` makes every utterance exactly
             # what it would be alone at its own length.  The caller's workspace is used when it holds the padded

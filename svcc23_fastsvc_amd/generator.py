@@ -103,8 +103,9 @@ class FastSVCGenerator(nn.Module):
     # of each layer on the device and keeps the fastest (the role cudnn.benchmark plays for the
     # reference, train_fastsvc.py:617).  False: static cost model.
     autotune = False
-    # "float32" (the parity path) or "bfloat16": workspace tensors stored as bf16 (BASELINE config 3:
-    # half the HBM traffic of the narrow layers, bf16-activation accuracy).  Set before the first forward.
+    # "float32" (the parity path), "bfloat16": workspace tensors stored as bf16 (BASELINE config 3:
+    # half the HBM traffic of the narrow layers, bf16-activation accuracy), or "float16": the same tensors as binary16
+    # (bfloat16's traffic, 3 more significand bits, workspace tensors must stay below 65504).  Set before the first forward.
     activation_storage = "float32"
     # True: never build an autograd graph (the plain HIP forward whatever the grad mode says) - for inference code
     # that does not wrap its calls in torch.no_grad()

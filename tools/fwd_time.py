@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Forward time of the shipped-table plan on synthetic workloads (developer tool):
-    python tools/fwd_time.py [cfg1 cfg2 cfg3 cfg3:bf16 ...]      best of 5 x 50 forwards after 10 warm-up ones"""
+    python tools/fwd_time.py [cfg1 cfg2 cfg3 cfg3:bf16 cfg3:f16 ...]      best of 5 x 50 forwards after 10 warm-up ones"""
 import sys, os, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import svcc23_fastsvc_amd as A
@@ -9,7 +9,7 @@ cfg = S.FULL_CONFIG; dev = torch.device("cuda:0")
 plans = {}
 for name in sys.argv[1:] or ["cfg1", "cfg2"]:
     name, _, st = name.partition(":")
-    storage = "bfloat16" if st == "bf16" else "float32"
+    storage = {"bf16": "bfloat16", "f16": "float16"}.get(st, "float32")
     if storage not in plans:
         plan = A.Plan(cfg, storage=storage, compact_workspace=True)
         plans[storage] = (plan, plan.pack(S.synth_state_dict(cfg, 201)).to(dev))

@@ -48,25 +48,26 @@ for k in sorted(fetch, key=lambda k: -fetch[k][0]):
         js[key] = (js.get(key, 0.0) * n0 + hbm * fetch[k][1]) / (n0 + fetch[k][1])
         merged[key] = n0 + fetch[k][1]
     # half-precision MFMA kernels: MW, NW, WM, WN, mode, epilogue kind, S (+ resident weights: merged); x3 = split
-    # binary16 products (float32 storage), x1 = bf16 products (namespace fastsvc::bf16)
+    # binary16 products (float32 storage), x1 = bf16 products (namespace fastsvc::bf16), h1 = binary16 products (fastsvc::f16)
+    tag = "x1" if "bf16::" in k else "h1" if "f16::" in k else "x3"
     # (round 3: a tenth argument marks the row-end instances of ragged batches - same traffic model, merged too)
     m = re.search(r"conv_hx_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+)(?:, (?:true|false)){0,2}>", k)
     if m:
-        key = "conv_hx<%s,%s,%s,%s,%s,%s,%s," % m.groups() + ("x1>" if "bf16::" in k else "x3>")
+        key = "conv_hx<%s,%s,%s,%s,%s,%s,%s," % m.groups() + tag + ">"
         n0 = merged.get(key, 0)
         js[key] = (js.get(key, 0.0) * n0 + hbm * fetch[k][1]) / (n0 + fetch[k][1])
         merged[key] = n0 + fetch[k][1]
     # the wide-layer kernel (csrc/fastsvc_wx.hip): PRO, EPI template arguments; bench.py names it by shape and epilogue kind
     m = re.search(r"conv_wx_kernel<(\d+), (\d+)>", k)
     if m:
-        key = "conv_wx<3,6,4,2,%s,x1>" % m.group(2)
+        key = "conv_wx<3,6,4,2,%s,%s>" % (m.group(2), tag)
         n0 = merged.get(key, 0)
         js[key] = (js.get(key, 0.0) * n0 + hbm * fetch[k][1]) / (n0 + fetch[k][1])
         merged[key] = n0 + fetch[k][1]
     # whole-stage conditioning launches (csrc/fastsvc_cond.hip)
     m = re.search(r"cond_stage(\d)(_pipe)?_kernel", k)
     if m:
-        js["cond_stage%s%s<%s>" % (m.group(1), m.group(2) or "", "x1" if "bf16::" in k else "x3")] = hbm
+        js["cond_stage%s%s<%s>" % (m.group(1), m.group(2) or "", tag)] = hbm
     m = re.search(r"conv_mfma_kernel<(\d+), (\d+), (\d+), (\d+)>", k)
     if m:
         js["conv_mfma<%s,%s,%s,%s>" % m.groups()] = hbm

@@ -41,7 +41,7 @@ def time_forward(plan, blob, ins, ws, n=30):
 
 for name in names:
     name, _, st = name.partition(":")
-    storage = "bfloat16" if st == "bf16" else "float32"
+    storage = {"bf16": "bfloat16", "f16": "float16"}.get(st, "float32")        # (float16 plans write "|h" entries)
     if "x" in name and name.split("x")[0].isdigit():          # "32x1500": any batch size x frame count
         wl = {"B": int(name.split("x")[0]), "F": int(name.split("x")[1]), "seed": 99}
     else:
