@@ -247,6 +247,33 @@ int fastsvc_signal_generate(const float* f0, float* out, void* scratch, int32_t 
 int fastsvc_gather_padded(const float* const* src, const int32_t* lens, const int32_t* pitches, float* dst,
                           int32_t B, int32_t C, int32_t width, void* stream);
 
+/* The two ends of a resident decode session (csrc/fastsvc_decodeio.hip; decode.DecodeSession).  The reference does both
+ * on the host, one utterance at a time (decode_fastsvc.py:150-200).
+ *
+ * Time-major batch assembly: utterance b is a contiguous time-major (lens[b], C) float32 block that starts offsets[b]
+ * ELEMENTS into `packed`, a device buffer of packed_elems floats (the dump layout, audio_feats_dataset.py:30-34, blocks
+ * back to back); dst (B, C, width), device, receives it transposed to channel-major and zero-padded: every column
+ * >= lens[b] is written as 0, whatever dst held.  0 <= lens[b] <= width, 1 <= C <= 65535, no alignment or % 4
+ * requirement on anything (16-byte accesses are used where the addresses allow).  `offsets` and `lens` are HOST arrays
+ * of B entries, read during the call (their values travel in the kernel arguments); a block that does not lie inside
+ * [0, packed_elems) is FASTSVC_E_INVALID, as are null pointers and sizes out of range; a failed launch is
+ * FASTSVC_E_HIP.  One launch per 64 utterances, asynchronous on `stream`. */
+int fastsvc_gather_time_major(const float* packed, int64_t packed_elems, const int64_t* offsets, const int32_t* lens,
+                              float* dst, int32_t B, int32_t C, int32_t width, void* stream);
+
+/* PCM-16 packing: row b of y (B, width), device float32, valid for lens[b] samples, goes to int16 at
+ * dst + offsets[b] (offsets in int16 ELEMENTS; dst a device buffer of dst_elems int16): a packed, unpadded buffer.
+ * Each value is rint of double(y) * 32767.0, computed in float64 (the product is exact there), ties to even,
+ * saturated to [-32768, 32767] - bit for bit what decode.to_pcm16 gives on the host.  +inf / -inf saturate to
+ * 32767 / -32768; NaN becomes 0 (the host's conversion of a NaN is implementation-defined).  Bytes of dst outside
+ * every [offsets[b], offsets[b] + lens[b]) are not touched; rows must not overlap.  Any offsets and lens work; a row
+ * whose destination starts on a 16-byte boundary (every row when lens are multiples of 8) is written with 16-byte
+ * stores.  `lens` and `offsets` are HOST arrays of B entries, read during the call; 0 <= lens[b] <= width; a row that
+ * does not lie inside [0, dst_elems) is FASTSVC_E_INVALID; a failed launch is FASTSVC_E_HIP.  One launch per 64 rows,
+ * asynchronous on `stream`. */
+int fastsvc_pcm16_pack(const float* y, const int32_t* lens, const int64_t* offsets, int16_t* dst, int64_t dst_elems,
+                       int32_t B, int32_t width, void* stream);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

@@ -67,7 +67,12 @@ def to_pcm16(y) -> np.ndarray:
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
-    pcm = to_pcm16(y)
+    """PCM-16 mono wav.  A float waveform goes through ``to_pcm16``; an int16 array (``DecodeSession.convert``) is
+    written as it is."""
+    if isinstance(y, np.ndarray) and y.dtype == np.int16:
+        pcm = np.ascontiguousarray(y).reshape(-1)
+    else:
+        pcm = to_pcm16(y)
     with wave.open(path, "wb") as w:
         w.setnchannels(1)
         w.setsampwidth(2)
@@ -214,6 +219,233 @@ def decode_utterances(model, feats: Sequence[Dict[str, np.ndarray]], signal_gene
     return out  # type: ignore[return-value]
 
 
+def pack_layout(counts: Sequence[int], order: Sequence[int]):
+    """Blocks of ``counts[i]`` elements laid back to back in ``order`` -> (offsets, total): ``offsets[i]`` is where
+    utterance i's block starts (indexed by utterance, not by position)."""
+    offsets = [0] * len(counts)
+    pos = 0
+    for i in order:
+        offsets[i] = pos
+        pos += int(counts[i])
+    return offsets, pos
+
+
+def pack_blocks(arrays: Sequence[np.ndarray], counts: Sequence[int], offsets: Sequence[int], dst: np.ndarray,
+                indices: Optional[Sequence[int]] = None) -> None:
+    """Copy the first ``counts[i]`` elements of every ``arrays[i]`` (flattened in its own C order - a time-major (F, C)
+    array stays time-major: a plain contiguous copy, no transpose) to ``dst[offsets[i]:]``, converting to dst's dtype."""
+    for i in (range(len(arrays)) if indices is None else indices):
+        n = int(counts[i])
+        a = np.asarray(arrays[i]).reshape(-1)
+        if a.size < n:
+            raise ValueError(f"utterance {i}: {a.size} elements, {n} expected")
+        dst[offsets[i]: offsets[i] + n] = a[:n]
+
+
+class DecodeSession:
+    """A data set kept on the device across target speakers: ``ppg`` and ``lft`` (99.7 % of the input bytes, the same for
+    every speaker) cross the bus once, in the dump's own time-major layout and unpadded; every ``convert`` re-runs only
+    what depends on the speaker and brings the waveforms back as unpadded int16.
+
+        with DecodeSession(model, feats, sg, device, src_f0_stats) as s:
+            for emb, stats in speakers:
+                pcm = s.convert(emb, stats)          # list of int16 arrays, one per utterance, in the order of `feats`
+
+    Results are bit-identical to ``decode_utterances`` (same arguments) followed by ``to_pcm16``: the batches are
+    ``bucket_ragged``'s, in the same row order; the F0 shift stays on the host (``F0Statistics.convert``, float64, rounded
+    to float32 by assignment into a float32 buffer, as ``decode_utterances`` does); the batches are assembled on the
+    device by ``gather_time_major`` (ppg) and ``gather_padded`` (lft); ``pcm16_pack`` computes ``to_pcm16``'s value in
+    float64.  F0 is uploaded already padded, (B, 1, Fmax) per batch, and needs no assembly.
+
+    Constructor: packs ppg and lft batch by batch into page-locked memory (contiguous copies, no transposes) and queues
+    each batch's upload on a copy stream as soon as it is packed, so the uploads overlap the packing of the later batches;
+    it returns without waiting for them.  The first ``convert`` makes its compute stream wait per batch for that batch's
+    upload only, so the first batches compute while the last are still in flight; the host packing itself is NOT
+    overlapped with compute (it is finished when the constructor returns).  The page-locked staging is released after the
+    first ``convert``.
+
+    Assembled batches are not kept: every ``convert`` re-assembles them from the packed upload (two memory-bound launches
+    per batch).  Device memory, with F_i frames per utterance, C ppg channels, hop samples per frame:
+        held for the session's life    4 * sum_i F_i * (C + hop) bytes                         (packed ppg + lft)
+        transient, one batch at a time 4 * B_k * Fmax_k * (C + 1 + 3 * hop) bytes              (ppg, f0, lft, sine, y)
+                                       + 2 * hop * sum_{i in batch} F_i (packed int16) + the forward's workspace
+
+    ``uploaded_bytes`` counts the host-to-device copies: ``["init"]`` by the constructor, ``["convert"]`` one entry per
+    ``convert`` (the padded f0 of every batch plus the embedding).  Kernel descriptors (offsets, lengths: 12 - 16 bytes per
+    utterance and launch) travel in kernel arguments and are not copies.
+
+    Not thread-safe; one ``convert`` at a time.  ``out_channels`` must be 1."""
+
+    def __init__(self, model, feats: Sequence[Dict[str, np.ndarray]], signal_generator, device,
+                 src_f0_stats: Optional[Sequence[Sequence[float]]] = None, max_batch: int = 32,
+                 pad_tolerance: float = 0.125):
+        self.model, self.signal_generator = model, signal_generator
+        self.device = torch.device(device)
+        self.hop = int(signal_generator.hop_size)
+        self.src_f0_stats = src_f0_stats
+        self.n = len(feats)
+        self.frames = [int(np.asarray(u["ppg"]).shape[0]) for u in feats]
+        self.batches: List[List[int]] = list(bucket_ragged(range(self.n), self.frames, max_batch, pad_tolerance)) if feats else []
+        self.uploaded_bytes = {"init": 0, "convert": []}
+        self._closed = False
+        self._ready = None
+        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = None
+        if not feats:
+            return
+        if int(getattr(model, "out_channels", 1)) != 1:
+            raise ValueError("DecodeSession supports out_channels == 1 only")
+        if src_f0_stats is not None and len(src_f0_stats) != self.n:
+            raise ValueError("src_f0_stats needs one [mean, std] per utterance")
+        if self.device.type != "cuda":
+            from .engine import FastSVCError
+            raise FastSVCError("DecodeSession needs a GPU device (no CPU fallback); got " + str(self.device))
+        hop, frames = self.hop, self.frames
+        self.channels = C = int(np.asarray(feats[0]["ppg"]).shape[1])
+        for i, u in enumerate(feats):
+            if np.asarray(u["ppg"]).ndim != 2 or int(np.asarray(u["ppg"]).shape[1]) != C:
+                raise ValueError(f"utterance {i}: ppg must be (F, {C}), got {np.asarray(u['ppg']).shape}")
+        order = [i for chunk in self.batches for i in chunk]
+        ppg_counts, lft_counts = [f * C for f in frames], [f * hop for f in frames]
+        self._ppg_off, ppg_total = pack_layout(ppg_counts, order)
+        self._lft_off, lft_total = pack_layout(lft_counts, order)          # (also where utterance i's int16 samples go)
+        self._f0 = [np.asarray(u["f0"], dtype=np.float64).reshape(-1) for u in feats]
+        self._f0_base, pos = [], 0
+        for chunk in self.batches:
+            self._f0_base.append(pos)
+            pos += len(chunk) * frames[chunk[0]]
+        self._h_f0 = torch.empty(max(pos, 1), dtype=torch.float32, pin_memory=True)
+        self._h_ppg = torch.empty(max(ppg_total, 1), dtype=torch.float32, pin_memory=True)
+        self._h_lft = torch.empty(max(lft_total, 1), dtype=torch.float32, pin_memory=True)
+        self._d_ppg = torch.empty(max(ppg_total, 1), dtype=torch.float32, device=self.device)
+        self._d_lft = torch.empty(max(lft_total, 1), dtype=torch.float32, device=self.device)
+        self._copy_stream = torch.cuda.Stream(self.device)
+        self._copy_stream.wait_stream(torch.cuda.current_stream(self.device))    # (the allocator may hand out blocks still in use there)
+        self._d_ppg.record_stream(self._copy_stream)
+        self._d_lft.record_stream(self._copy_stream)
+        hp, hl = self._h_ppg.numpy(), self._h_lft.numpy()
+        ppgs, lfts = [u["ppg"] for u in feats], [u["lft"] for u in feats]
+        self._ready = []
+        for chunk in self.batches:
+            pack_blocks(ppgs, ppg_counts, self._ppg_off, hp, chunk)
+            pack_blocks(lfts, lft_counts, self._lft_off, hl, chunk)
+            with torch.cuda.stream(self._copy_stream):
+                for h, d, off, counts in ((self._h_ppg, self._d_ppg, self._ppg_off, ppg_counts),
+                                          (self._h_lft, self._d_lft, self._lft_off, lft_counts)):
+                    lo, hi = off[chunk[0]], off[chunk[-1]] + counts[chunk[-1]]    # (a batch's blocks are contiguous)
+                    if hi > lo:
+                        d[lo:hi].copy_(h[lo:hi], non_blocking=True)
+                        self.uploaded_bytes["init"] += 4 * (hi - lo)
+                ev = torch.cuda.Event()
+                ev.record(self._copy_stream)
+            self._ready.append(ev)
+        # (C = 1 rows for gather_padded: views of the packed upload, made once)
+        self._lft_rows = [[self._d_lft[self._lft_off[i]: self._lft_off[i] + lft_counts[i]].view(1, -1) for i in chunk]
+                          for chunk in self.batches]
+        self._down = [_PinnedSet(), _PinnedSet()]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        """Wait for the session's device work and release its device and page-locked buffers."""
+        if self._closed:
+            return
+        self._closed = True
+        if self.n and self.device.type == "cuda":
+            self._copy_stream.synchronize()
+            torch.cuda.current_stream(self.device).synchronize()
+        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = None
+        self._lft_rows = self._down = self._ready = None
+
+    @torch.no_grad()
+    def convert(self, trg_emb=None, trg_f0_stats: Optional[Sequence[float]] = None, pcm16: bool = True) -> List[np.ndarray]:
+        """Every utterance converted to one target speaker, in the order of ``feats``.
+
+        pcm16=True   int16 arrays, equal to ``to_pcm16`` of what ``decode_utterances`` returns: views of ONE new array per
+                     call, a copy of the page-locked download buffer (made batch by batch while later batches compute),
+                     so they stay valid after the next ``convert`` and after ``close``.
+        pcm16=False  float32 arrays, copies: exactly what ``decode_utterances`` returns."""
+        if self._closed:
+            raise RuntimeError("DecodeSession is closed")
+        if not self.n:
+            return []
+        from .engine import gather_padded, gather_time_major, pcm16_pack
+        dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
+        stream = torch.cuda.current_stream(dev)
+        up = 0
+        emb_row = None
+        if trg_emb is not None:
+            emb_row = torch.as_tensor(np.asarray(trg_emb), dtype=torch.float32).reshape(1, -1).to(dev)
+            up += 4 * emb_row.numel()
+        shift = self.src_f0_stats is not None and trg_f0_stats is not None
+        hf_all = self._h_f0.numpy()
+        if pcm16 and self._h_pcm is None:
+            self._h_pcm = torch.empty(max(sum(frames) * hop, 1), dtype=torch.int16, pin_memory=True)
+        out: List[Optional[np.ndarray]] = [None] * self.n
+        result = np.empty(sum(frames) * hop, dtype=np.int16) if pcm16 else None
+        pending = {}
+
+        def finish(k: int) -> None:
+            host_y, done = pending.pop(k)
+            done.synchronize()
+            if pcm16:
+                lo, hi = host_y
+                result[lo:hi] = self._h_pcm.numpy()[lo:hi]
+                return
+            y = host_y.numpy()
+            for j, i in enumerate(self.batches[k]):
+                out[i] = y[j].reshape(-1)[: frames[i] * hop].copy()
+
+        for k, chunk in enumerate(self.batches):
+            fmax, B = frames[chunk[0]], len(chunk)
+            lens = [frames[i] for i in chunk]
+            base = self._f0_base[k]
+            hf = hf_all[base: base + B * fmax].reshape(B, 1, fmax)
+            for j, i in enumerate(chunk):
+                f, n = self._f0[i], frames[i]
+                if shift:
+                    f = F0Statistics().convert(f, self.src_f0_stats[i], trg_f0_stats)
+                hf[j, 0, :n] = f
+                hf[j, 0, n:] = 0
+            f0 = self._h_f0[base: base + B * fmax].view(B, 1, fmax).to(dev, non_blocking=True)
+            up += 4 * B * fmax
+            if self._ready is not None:
+                stream.wait_event(self._ready[k])
+            ppg = gather_time_major(self._d_ppg, [self._ppg_off[i] for i in chunk], lens, C, fmax)
+            lft = gather_padded(self._lft_rows[k], fmax * hop)
+            sine = self.signal_generator(f0)
+            emb = None if emb_row is None else emb_row.expand(B, -1).contiguous()
+            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+            if pcm16:
+                lo = self._lft_off[chunk[0]]
+                total = sum(lens) * hop
+                packed = torch.empty(max(total, 1), dtype=torch.int16, device=dev)
+                pcm16_pack(y.view(B, fmax * hop), [n * hop for n in lens], [self._lft_off[i] - lo for i in chunk], out=packed)
+                if total:
+                    self._h_pcm[lo: lo + total].copy_(packed[:total], non_blocking=True)
+                host_y = (lo, lo + total)
+            else:
+                host_y = self._down[k & 1].get("y", tuple(y.shape))
+                host_y.copy_(y, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+            pending[k] = (host_y, done)
+            if k >= 1:
+                finish(k - 1)                        # (while batch k computes; before batch k + 1 reuses that download set)
+        finish(len(self.batches) - 1)
+        stream.synchronize()
+        if pcm16:
+            out = [result[self._lft_off[i]: self._lft_off[i] + frames[i] * hop] for i in range(self.n)]
+        if self._ready is not None:                  # every upload has been waited for: the staging can go
+            self._ready = None
+            self._h_ppg = self._h_lft = None
+        self.uploaded_bytes["convert"].append(up)
+        return out  # type: ignore[return-value]
+
+
 def _read_f0_mean(stats_dir: str, name: str) -> np.ndarray:
     import yaml
     with open(os.path.join(stats_dir, f"{name}.yml")) as f:
@@ -235,6 +467,12 @@ def main(argv=None) -> None:                                  # pragma: no cover
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--storage", default="float32", choices=["float32", "bfloat16", "float16"],
                     help="activation storage of the generator's forward (FastSVCGenerator.activation_storage)")
+    ap.add_argument("--resident", action="store_true",
+                    help="keep the features on the device across target speakers (DecodeSession): ppg / lft are uploaded "
+                         "once per group of dumps, PCM-16 is made on the device; same file names and contents")
+    ap.add_argument("--resident-bytes", type=int, default=4 << 30,
+                    help="device bytes of packed features one resident group may hold (default 4 GiB); a dump directory "
+                         "larger than this is decoded group by group")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -249,6 +487,10 @@ def main(argv=None) -> None:                                  # pragma: no cover
                          sine_amp=sg_conf.get("sine_amp", 0.1), noise_amp=sg_conf.get("noise_amp", 0.003),
                          signal_types=sg_conf.get("signal_types", ["sine"]))
     files = sorted(glob.glob(os.path.join(args.dumpdir, "*.npz")) + glob.glob(os.path.join(args.dumpdir, "*.h5")))
+    if args.resident:
+        os.makedirs(args.outdir, exist_ok=True)
+        _main_resident(args, config, model, sg, device, files)
+        return
     feats = [load_features(p) for p in files]
     utt_ids = [os.path.splitext(os.path.basename(p))[0] for p in files]
     os.makedirs(args.outdir, exist_ok=True)
@@ -267,6 +509,55 @@ def main(argv=None) -> None:                                  # pragma: no cover
         for utt, y in zip(utt_ids, ys):
             write_wav(os.path.join(args.outdir, f"{utt}_{trgspk}_gen.wav"), y, config["sampling_rate"])
         print(f"{len(ys)} utterances -> {trgspk}: RTF = {dt / (total / config['sampling_rate']):.5f}")
+
+
+def resident_groups(files: Sequence[str], budget_bytes: int, hop: int, load=load_features):
+    """Consecutive runs of ``files`` whose packed features (4 * F * (C + hop) bytes per utterance, what a DecodeSession
+    holds) fit ``budget_bytes``; a single utterance above the budget is a group of its own.  Yields (paths, feats),
+    loading one group at a time."""
+    paths, feats, used = [], [], 0
+    for p in files:
+        u = load(p)
+        ppg = np.asarray(u["ppg"])
+        need = 4 * int(ppg.shape[0]) * (int(ppg.shape[1]) + hop)
+        if paths and used + need > budget_bytes:
+            yield paths, feats
+            paths, feats, used = [], [], 0
+        paths.append(p)
+        feats.append(u)
+        used += need
+    if paths:
+        yield paths, feats
+
+
+def _main_resident(args, config, model, sg, device, files) -> None:      # pragma: no cover - exercised on a GPU box
+    """The CLI's speaker loop with the features resident: one session per group of dumps, every target speaker inside it.
+    A dump directory that fits one group runs the same batches as the default path, so the files are the same byte for
+    byte; split into several groups the batches differ, and the waveforms agree to the harness's batching invariance
+    (2e-5 in float, tests/test_parity_gpu.py) before the PCM rounding."""
+    embs = dict(np.load(args.spk_emb)) if args.spk_emb else {}
+    speakers = config.get("convert_to_speakers", [None])
+    spent, samples = {s: 0.0 for s in speakers}, {s: 0 for s in speakers}
+    for paths, feats in resident_groups(files, args.resident_bytes, int(config["hop_size"])):
+        utt_ids = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+        src_stats = None
+        if args.srcf0stats and args.trgf0stats:
+            src_stats = [_read_f0_mean(args.srcf0stats, u.split("_")[0]) for u in utt_ids]
+        with DecodeSession(model, feats, sg, device, src_stats, args.max_batch) as session:
+            for trgspk in speakers:
+                trg_emb = embs.get(trgspk) if config["generator_params"].get("use_spk_emb") else None
+                trg_stats = None
+                if src_stats is not None and trgspk is not None:
+                    trg_stats = _read_f0_mean(args.trgf0stats, trgspk)
+                t0 = time.time()
+                pcm = session.convert(trg_emb, trg_stats)
+                spent[trgspk] += time.time() - t0
+                samples[trgspk] += sum(len(p) for p in pcm)
+                for utt, p in zip(utt_ids, pcm):
+                    write_wav(os.path.join(args.outdir, f"{utt}_{trgspk}_gen.wav"), p, config["sampling_rate"])
+    for trgspk in speakers:
+        if samples[trgspk]:
+            print(f"{len(files)} utterances -> {trgspk}: RTF = {spent[trgspk] / (samples[trgspk] / config['sampling_rate']):.5f}")
 
 
 if __name__ == "__main__":                                    # pragma: no cover

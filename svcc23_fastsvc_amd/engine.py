@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "fastsvc_flops_per_sample", "fastsvc_signal_scratch_bytes", "fastsvc_signal_generate",
     "fastsvc_stream_prepare", "fastsvc_stream_release", "fastsvc_split_half", "fastsvc_plan_set_workspace_mode",
     "fastsvc_loudness_frames", "fastsvc_loudness_scratch_bytes", "fastsvc_loudness_extract",
-    "fastsvc_gather_padded",
+    "fastsvc_gather_padded", "fastsvc_gather_time_major", "fastsvc_pcm16_pack",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -150,6 +150,10 @@ def load_library():
     lib.fastsvc_stream_release.restype = ctypes.c_int
     lib.fastsvc_gather_padded.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32), vp, i32, i32, i32, vp]
     lib.fastsvc_gather_padded.restype = ctypes.c_int
+    lib.fastsvc_gather_time_major.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32), vp, i32, i32, i32, vp]
+    lib.fastsvc_gather_time_major.restype = ctypes.c_int
+    lib.fastsvc_pcm16_pack.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), vp, i64, i32, i32, vp]
+    lib.fastsvc_pcm16_pack.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -209,6 +213,72 @@ def gather_padded(rows: Sequence[torch.Tensor], width: int, out: Optional[torch.
         stream = torch.cuda.current_stream(first.device).cuda_stream
         _check(lib, lib.fastsvc_gather_padded(src, lens, pitches, ctypes.c_void_p(out.data_ptr()), B, C, width,
                                               ctypes.c_void_p(stream)), "fastsvc_gather_padded")
+    return out
+
+
+def gather_time_major(packed: torch.Tensor, offsets: Sequence[int], lens: Sequence[int], C: int, width: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Assemble a zero-padded channel-major batch from time-major blocks: utterance b is the contiguous (lens[b], C)
+    float32 block that starts ``offsets[b]`` elements into ``packed`` (a 1-D device tensor - the dump layout, blocks back to
+    back) -> (B, C, width), transposed, every column >= lens[b] zero.  No alignment or % 4 requirement.  One HIP launch per
+    64 utterances on the current stream (fastsvc_gather_time_major, csrc/fastsvc_decodeio.hip); fails loudly off the GPU."""
+    lib = load_library()
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise FastSVCError("gather_time_major needs a GPU tensor (no CPU fallback); got " +
+                           str(getattr(packed, "device", type(packed))))
+    B, C, width = len(lens), int(C), int(width)
+    if B == 0 or len(offsets) != B:
+        raise ValueError("gather_time_major needs at least one utterance and one offset per length")
+    if packed.dim() != 1 or packed.dtype != torch.float32 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous 1-D float32 tensor")
+    if out is None:
+        out = torch.empty((B, C, width), dtype=torch.float32, device=packed.device)
+    elif tuple(out.shape) != (B, C, width) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != packed.device:
+        raise ValueError(f"out must be a contiguous float32 {(B, C, width)} tensor on {packed.device}")
+    offs = (ctypes.c_int64 * B)(*[int(v) for v in offsets])
+    ls = (ctypes.c_int32 * B)(*[int(v) for v in lens])
+    with torch.cuda.device(packed.device):
+        stream = torch.cuda.current_stream(packed.device).cuda_stream
+        _check(lib, lib.fastsvc_gather_time_major(ctypes.c_void_p(packed.data_ptr()), packed.numel(), offs, ls,
+                                                  ctypes.c_void_p(out.data_ptr()), B, C, width, ctypes.c_void_p(stream)),
+               "fastsvc_gather_time_major")
+    return out
+
+
+def pcm16_pack(y: torch.Tensor, lens: Sequence[int], offsets: Optional[Sequence[int]] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PCM-16 of a batch of waveforms, packed: row b of ``y`` (B, width) or (B, 1, width), float32 on the device, valid for
+    ``lens[b]`` samples, goes to ``out[offsets[b]: offsets[b] + lens[b]]`` (1-D int16; default offsets: the rows back to
+    back, default out: a new tensor of sum(lens) samples).  The values are ``decode.to_pcm16``'s bit for bit (float64
+    product, round half to even, saturated; NaN -> 0); samples of ``out`` outside the rows are left as they are.  One HIP
+    launch per 64 rows on the current stream (fastsvc_pcm16_pack, csrc/fastsvc_decodeio.hip); fails loudly off the GPU."""
+    lib = load_library()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise FastSVCError("pcm16_pack needs a GPU tensor (no CPU fallback); got " + str(getattr(y, "device", type(y))))
+    if y.dim() == 3 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous() or y.shape[0] != len(lens) or y.shape[0] == 0:
+        raise ValueError(f"y must be a contiguous float32 (B, width) tensor with one length per row; got {tuple(y.shape)} {y.dtype}")
+    B, width = int(y.shape[0]), int(y.shape[1])
+    lens = [int(v) for v in lens]
+    if offsets is None:
+        offsets = [0] * B
+        for b in range(1, B):
+            offsets[b] = offsets[b - 1] + lens[b - 1]
+    elif len(offsets) != B:
+        raise ValueError("pcm16_pack needs one offset per row")
+    if out is None:
+        out = torch.empty(max(int(o) + n for o, n in zip(offsets, lens)), dtype=torch.int16, device=y.device)
+    elif out.dim() != 1 or out.dtype != torch.int16 or not out.is_contiguous() or out.device != y.device:
+        raise ValueError(f"out must be a contiguous 1-D int16 tensor on {y.device}")
+    if out.numel() == 0:
+        return out
+    offs = (ctypes.c_int64 * B)(*[int(v) for v in offsets])
+    ls = (ctypes.c_int32 * B)(*lens)
+    with torch.cuda.device(y.device):
+        stream = torch.cuda.current_stream(y.device).cuda_stream
+        _check(lib, lib.fastsvc_pcm16_pack(ctypes.c_void_p(y.data_ptr()), ls, offs, ctypes.c_void_p(out.data_ptr()),
+                                           out.numel(), B, width, ctypes.c_void_p(stream)), "fastsvc_pcm16_pack")
     return out
 
 

@@ -1,6 +1,16 @@
-"""Throughput of the decode harness (svcc23_fastsvc_amd.decode.decode_utterances) from HOST-resident features - what
-`python -m svcc23_fastsvc_amd.decode` does after reading the dumps: 512 utterances of 2 - 10 s (SURVEY 8d's variant of
-cfg4), time-major numpy features, F0 shift on, waveforms back as numpy arrays.   python tools/decode_throughput.py"""
+"""Throughput of the decode harness from HOST-resident features - what `python -m svcc23_fastsvc_amd.decode` does after
+reading the dumps: 512 utterances of 2 - 10 s (SURVEY 8d's variant of cfg4), time-major numpy features, F0 shift on.
+
+Four legs, for activation storage float32 and bfloat16, alternated within the one run and repeated (DECODE_REPS, default
+5; spread printed), every timed region ending in a device synchronise:
+
+    floats      decode_utterances: float32 waveforms back as numpy arrays (the leg this tool has always had)
+    (a) pcm     the same followed by to_pcm16 of every utterance - what the CLI does per target speaker
+    (b) first   DecodeSession(...) + its first convert(): packing, the one upload, int16 back
+    (c) next    the same session's second convert(), for another speaker: F0 shift + f0 upload only
+
+Before timing, (b) and (c) are checked to equal (a) sample for sample.  The figures go to profiles/decode_session.txt.
+    python tools/decode_throughput.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,10 +18,12 @@ import torch
 import svcc23_fastsvc_amd as A
 from svcc23_fastsvc_amd import synth as S, decode as Dc
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dev = torch.device("cuda:0")
 cfg = S.FULL_CONFIG
 frames = S.workload_frames("cfg4var")
 n = int(os.environ.get("DECODE_UTTS", "512"))
+reps = max(int(os.environ.get("DECODE_REPS", "5")), 1)
 frames = frames[:n]
 rng = np.random.default_rng(3)
 feats = []
@@ -19,28 +31,74 @@ for f in frames:
     f0 = np.where(rng.random((f, 1)) < 0.3, 0.0, rng.uniform(80, 400, (f, 1)))
     feats.append({"ppg": rng.standard_normal((f, cfg.in_channels), dtype=np.float32), "f0": f0,
                   "lft": rng.uniform(-9, 1, (f * cfg.hop, 1)).astype(np.float32)})
-m = A.FastSVCGenerator(in_channels=cfg.in_channels, mid_channels=list(cfg.mid_channels), upsampling_scales=list(cfg.upsampling_scales),
-                       out_channels=cfg.out_channels, spk_emb_size=cfg.spk_emb_size, use_spk_emb=True)
-m.load_state_dict({k: torch.from_numpy(v) for k, v in S.synth_state_dict(cfg, 1).items()})
-m.remove_weight_norm()
-m = m.eval().to(dev)
 sg = A.SignalGenerator(sample_rate=24000, hop_size=cfg.hop, noise_amp=0.0, signal_types=["sine"])
 emb = rng.standard_normal(cfg.spk_emb_size).astype(np.float32)
+emb2 = rng.standard_normal(cfg.spk_emb_size).astype(np.float32)
 src = [[5.0, 1.0]] * len(feats)
-fns = {"decode_utterances": Dc.decode_utterances}
-try:
-    from svcc23_fastsvc_amd import _decode_old
-    fns["one batch at a time (before)"] = _decode_old.decode_utterances
-except ImportError:
-    pass
+trg, trg2 = [5.3, 1.0], [4.8, 1.0]
 samples = sum(frames) * cfg.hop
-for name, fn in fns.items():
-    ys = fn(m, feats, sg, dev, trg_emb=emb, src_f0_stats=src, trg_f0_stats=[5.3, 1.0], max_batch=64)   # warm (packs, loads)
+MB = 64
+lines = [f"decode_throughput: {len(feats)} utterances (cfg4var), {samples} samples = {samples / 24000:.0f} s of audio, "
+         f"max_batch {MB}, {reps} repetitions, legs alternated; {torch.cuda.get_device_name(0)}",
+         f"feature bytes (ppg + lft, unpadded): {4 * sum(frames) * (cfg.in_channels + cfg.hop) / 1e6:.1f} MB; "
+         f"int16 waveforms: {2 * samples / 1e6:.1f} MB; float32 waveforms: {4 * samples / 1e6:.1f} MB"]
+print("\n".join(lines), flush=True)
+
+
+def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(3):
-        ys = fn(m, feats, sg, dev, trg_emb=emb, src_f0_stats=src, trg_f0_stats=[5.3, 1.0], max_batch=64)
-    dt = (time.perf_counter() - t0) / 3
-    assert all(y.shape == (f * cfg.hop,) and np.isfinite(y).all() for y, f in zip(ys, frames))
-    print(f"{name}: {dt * 1e3:.1f} ms per pass over {len(feats)} utterances = {samples / dt / 1e6:.1f} M samples/s "
-          f"({samples / 24000 / dt:.0f} x real time)")
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+for storage in ("float32", "bfloat16"):
+    m = A.FastSVCGenerator(in_channels=cfg.in_channels, mid_channels=list(cfg.mid_channels), upsampling_scales=list(cfg.upsampling_scales),
+                           out_channels=cfg.out_channels, spk_emb_size=cfg.spk_emb_size, use_spk_emb=True)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in S.synth_state_dict(cfg, 1).items()})
+    m.remove_weight_norm()
+    m.activation_storage = storage
+    m = m.eval().to(dev)
+
+    def floats(e=emb, t=trg):
+        return Dc.decode_utterances(m, feats, sg, dev, trg_emb=e, src_f0_stats=src, trg_f0_stats=t, max_batch=MB)
+
+    def with_pcm(e=emb, t=trg):
+        return [Dc.to_pcm16(y) for y in floats(e, t)]
+
+    # warm every shape (packs, code objects, page-locked pools) and check the session against the existing path
+    want, want2 = with_pcm(), with_pcm(emb2, trg2)
+    assert all(y.shape == (f * cfg.hop,) for y, f in zip(want, frames))
+    with Dc.DecodeSession(m, feats, sg, dev, src, max_batch=MB) as s:
+        got, got2 = s.convert(emb, trg), s.convert(emb2, trg2)
+        same = all(np.array_equal(a, b) for a, b in zip(got, want)) and all(np.array_equal(a, b) for a, b in zip(got2, want2))
+        up = dict(s.uploaded_bytes)
+    del want, want2, got, got2
+    t = {"floats": [], "a": [], "b": [], "c": []}
+    for _ in range(reps):
+        t["floats"].append(timed(floats)[0])
+        t["a"].append(timed(with_pcm)[0])
+        box = {}
+
+        def first():
+            box["s"] = Dc.DecodeSession(m, feats, sg, dev, src, max_batch=MB)
+            return box["s"].convert(emb, trg)
+        t["b"].append(timed(first)[0])
+        t["c"].append(timed(lambda: box["s"].convert(emb2, trg2))[0])
+        box["s"].close()
+    names = {"floats": "decode_utterances (float32 waveforms)", "a": "(a) decode_utterances + to_pcm16",
+             "b": "(b) DecodeSession + first convert", "c": "(c) second convert, another speaker"}
+    out = [f"--- activation storage {storage}: session output equals (a) sample for sample: {same}; uploaded by the "
+           f"constructor {up['init'] / 1e6:.1f} MB, by each convert {up['convert'][0] / 1e6:.2f} MB"]
+    for key, name in names.items():
+        v = np.array(t[key]) * 1e3
+        med = float(np.median(v))
+        out.append(f"{name:42s} median {med:8.1f} ms  (min {v.min():8.1f}, max {v.max():8.1f})  "
+                   f"{samples / med / 1e3:7.1f} M samples/s  {samples / 24000 / med * 1e3:6.0f} x real time")
+    print("\n".join(out), flush=True)
+    lines += out
+    assert same, "DecodeSession differs from decode_utterances + to_pcm16"
+os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+with open(os.path.join(ROOT, "profiles", "decode_session.txt"), "w") as f:
+    f.write("\n".join(lines) + "\n")
