@@ -119,6 +119,22 @@ size_t fastsvc_weight_blob_bytes(const fastsvc_plan* plan);
 int fastsvc_pack_weights(const fastsvc_plan* plan, const fastsvc_tensor* tensors, int32_t n_tensors,
                          void* host_blob);
 
+/* Device twin of fastsvc_pack_weights (csrc/fastsvc_pack.hip): `tensors[i].data` are DEVICE pointers (float32, contiguous)
+ * on the current device; dev_blob receives fastsvc_weight_blob_bytes(plan) bytes, bit for bit what fastsvc_pack_weights
+ * writes for the same values (one exception, unreachable from finite parameters: a NaN that the packing arithmetic itself
+ * generates - an infinite folded weight, an all-zero weight_v row - has x86's sign bit on the host and none here);
+ * scratch >= fastsvc_pack_device_scratch_bytes(plan), device memory, contents irrelevant (FASTSVC_E_WORKSPACE if smaller).
+ * Names and element counts are checked on the host before anything is launched (FASTSVC_E_MISSING with the host packer's
+ * messages; null arguments FASTSVC_E_INVALID).  Asynchronous on `stream`: no synchronisation and no device allocation;
+ * the first call on a plan page-locks a copy of the plan's job table (host memory, freed with the plan), every call
+ * copies it into the scratch.  dev_blob may be the blob that earlier forwards on `stream` read (stream order protects
+ * them).  The number of launches (kernels, one copy, one memset) is fastsvc_pack_device_launch_count(plan): it depends
+ * on the configuration only through ceil(layers / 160), a dozen for every generator that exists. */
+size_t fastsvc_pack_device_scratch_bytes(const fastsvc_plan* plan);
+int fastsvc_pack_device_launch_count(const fastsvc_plan* plan);
+int fastsvc_pack_weights_device(const fastsvc_plan* plan, const fastsvc_tensor* tensors, int32_t n_tensors,
+                                void* dev_blob, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Workspace layout of the plan's later fastsvc_workspace_bytes / fastsvc_forward calls: 0 (default) = every
  * intermediate has its own buffer (all fastsvc_workspace_tap tensors stay readable after a forward); 1 = compact,
  * intermediates of different stages whose lifetimes cannot overlap share buffers (about 40 % less at 64 x 10 s;

@@ -28,6 +28,7 @@
 
 #include "fastsvc_hip.h"
 #include "fastsvc_kernels.h"
+#include "fastsvc_pack.h"
 
 using namespace fastsvc;
 
@@ -191,6 +192,17 @@ int choose_mw(int cout) {
     return 3;
 }
 
+// The device packer's view of the plan (fastsvc_pack.h): the job table as the kernels read it, the state-dict layers in
+// table order and the scratch it needs.  Built once, with the plan.
+struct PackTable {
+    fastsvc_pack::PkHeader h{};
+    std::vector<unsigned char> bytes;
+    struct Layer { std::string name; int cout; size_t per; };
+    std::vector<Layer> layers;
+    size_t scratch_bytes = 0;
+    int n_launches = 0;
+};
+
 }  // namespace
 
 struct fastsvc_plan {
@@ -223,6 +235,10 @@ struct fastsvc_plan {
     // nearest (cached per key; algo < 0 = the table has nothing for the layer); cleared whenever `tuned` changes.
     mutable std::map<std::string, Choice> priors;
     mutable std::vector<double> pack_cost;      // per pack job: what the last fastsvc_pack_weights measured (longest first next time)
+    PackTable pk;                               // device packer (fastsvc_pack_weights_device)
+    mutable std::once_flag pk_once;             // the first device pack page-locks a copy of pk.bytes: the source of every
+    mutable void* pk_pinned = nullptr;          // pack's table copy, which therefore never waits for the stream
+    ~fastsvc_plan() { if (pk_pinned) (void)hipHostFree(pk_pinned); }
 
     // |ln work ratio| + a quarter of |ln row-length ratio|: what a launch shape trades off (workgroups against tiles
     // per workgroup against columns per tile) depends on B * T first and on the row length second
@@ -544,6 +560,266 @@ int build_plan(fastsvc_plan& P) {
 }
 
 // ------------------------------------------------------------------------------------------
+// device packer: the job lists above as a table (fastsvc_pack.h).  Mirrors fastsvc_pack_weights job by job; the
+// kernels of fastsvc_pack.hip compute what its lambdas compute.
+// ------------------------------------------------------------------------------------------
+int build_pack_table(fastsvc_plan& P) {
+    using namespace fastsvc_pack;
+    PackTable& T = P.pk;
+    std::vector<PkLayer> layers;
+    std::vector<PkVirt> virts;
+    std::vector<PkFrag> frags;
+    std::vector<PkHx> hxs;
+    std::vector<PkHxUnit> units;
+    std::vector<PkCopy> copies;
+    std::vector<PkBound> bounds;
+    std::vector<PkCond> conds;
+    std::map<std::string, int> layer_index;
+    std::map<std::string, uint32_t> virt_index;             // piece names -> s_dst
+    size_t s_floats = 0;                                    // scratch arena, in floats; the table sits behind it
+    uint32_t virt_work = 0, frag_work = 0, hx_work = 0, hx_rows = 0, copy_work = 0;
+    bool ok = true;
+    auto salloc = [&](size_t n) { const size_t off = s_floats; s_floats += align_up(n, 64); return (uint32_t)off; };
+    auto work = [](uint32_t& counter, size_t n) { const uint32_t w0 = counter; counter += (uint32_t)align_up(n, PK_BLOCK); return w0; };
+    auto layer = [&](const std::string& name, int cout, size_t per) -> PkLayer {
+        auto it = layer_index.find(name);
+        if (it != layer_index.end()) {
+            if (T.layers[it->second].cout != cout || T.layers[it->second].per != per) ok = false;
+            return layers[it->second];
+        }
+        PkLayer L;
+        L.cout = (uint32_t)cout; L.per = (uint32_t)per;
+        L.s_bias = salloc(cout); L.s_sc = salloc(cout); L.s_w = salloc((size_t)cout * per);
+        layer_index[name] = (int)layers.size();
+        layers.push_back(L);
+        T.layers.push_back({name, cout, per});
+        return L;
+    };
+    auto copy = [&](size_t d_dst, size_t n, uint32_t s_a, uint32_t s_b, uint32_t mode) {
+        copies.push_back(PkCopy{work(copy_work, n), (uint32_t)d_dst, (uint32_t)n, s_a, s_b, mode});
+    };
+    auto bound1 = [&](size_t d_dst, uint32_t s_w, int rows, size_t per, uint32_t s_bias) {
+        bounds.push_back(PkBound{(uint32_t)d_dst, s_w, (uint32_t)rows, (uint32_t)per, (uint32_t)rows, {s_bias, s_bias}, {PK_NONE, PK_NONE}});
+    };
+    auto frag = [&](size_t d_dst, uint32_t s_src, uint32_t s_src1, const PackedConv& c, int ntaps, int MW, int Q, int ngroups, uint32_t kind) {
+        frags.push_back(PkFrag{work(frag_work, (size_t)ngroups * Q * 64 * MW), (uint32_t)d_dst, s_src, s_src1, (uint32_t)c.cout, (uint32_t)c.cin,
+                               (uint32_t)ntaps, (uint32_t)c.KC, (uint32_t)MW, (uint32_t)Q, (uint32_t)ngroups, kind});
+    };
+    // pack_hx(c with `nch` units, off, nslots, ..., inv_off, ntables, ...): the units are pushed by the caller first
+    auto hx = [&](const PackedConv& c, const size_t (&off)[3], int nslots, size_t inv_off, int ntables, int nch, uint32_t unit0) {
+        PkHx J;
+        const size_t n16 = (size_t)c.ngroups * 16 * c.MW;
+        J.work0 = work(hx_work, (size_t)c.ngroups * nch * nslots * c.MW * 64);
+        J.row0 = work(hx_rows, (size_t)ntables * n16);
+        for (int p = 0; p < 3; ++p) J.d_off[p] = (uint32_t)off[p];
+        J.d_inv = (uint32_t)inv_off;
+        J.s_ex = salloc((size_t)ntables * n16);
+        J.ntables = (uint32_t)ntables; J.nslots = (uint32_t)nslots; J.MW = (uint32_t)c.MW; J.ngroups = (uint32_t)c.ngroups;
+        J.nch = (uint32_t)nch; J.cout = (uint32_t)c.cout; J.unit0 = unit0;
+        hxs.push_back(J);
+    };
+    auto unit = [&](uint32_t s_src, uint32_t s_src1, int ld, int cj0, int lim, uint32_t kind, uint32_t table) {
+        units.push_back(PkHxUnit{s_src, s_src1, (uint32_t)ld, (uint32_t)cj0, (uint32_t)lim, kind, table});
+    };
+    // the virtual dense weight of a multi-piece source (pieces of (rows / 2) x (cin / 2)) - shared by the heads' own
+    // job and the fused FiLM net's
+    auto virt_of = [&](const PackSource& src, int rows, int cin, int ntaps, PkLayer (&pl)[4]) -> uint32_t {
+        std::string key;
+        for (const auto& pc : src.pieces) key += pc.layer + "|";
+        const int np = (int)src.pieces.size();
+        for (int i = 0; i < np && i < 4; ++i) pl[i] = layer(src.pieces[i].layer, rows / 2, (size_t)(cin / 2) * ntaps);
+        auto it = virt_index.find(key);
+        if (it != virt_index.end()) return it->second;
+        PkVirt V{};
+        V.work0 = work(virt_work, (size_t)rows * cin * ntaps);
+        V.s_dst = salloc((size_t)rows * cin * ntaps);
+        V.rows = (uint32_t)rows; V.cin = (uint32_t)cin; V.ntaps = (uint32_t)ntaps; V.npieces = (uint32_t)np;
+        for (int i = 0; i < np && i < 4; ++i)
+            V.piece[i] = {pl[i].s_w, (uint32_t)src.pieces[i].co_off, (uint32_t)src.pieces[i].ci_off, (uint32_t)(rows / 2), (uint32_t)(cin / 2)};
+        virts.push_back(V);
+        virt_index[key] = V.s_dst;
+        return V.s_dst;
+    };
+
+    for (const auto& job : P.pack_jobs) {
+        const PackedConv& c = *job.first;
+        const PackSource& src = job.second;
+        if (src.dec2) {
+            const PkLayer L3 = layer(src.pieces[0].layer, c.cout, (size_t)c.cin * 3);
+            const PkLayer L1 = layer(src.pieces[1].layer, c.cout, (size_t)c.cin);
+            frag(c.w_off, L3.s_w, L1.s_w, c, 3, c.MW, c.Q, c.ngroups, PK_FRAG_DEC2);
+            copy(c.b_off, c.cout, L3.s_bias, PK_NONE, 0);
+            copy(c.b2_off, c.cout, L1.s_bias, PK_NONE, 0);
+            if (c.hx) {
+                const uint32_t u0 = (uint32_t)units.size();
+                for (int u = 0; u < c.nch32; ++u) unit(L3.s_w, L1.s_w, c.cin, 32 * u, c.cin, PK_HX_DEC2, 0);
+                hx(c, c.hx_off, 4, c.hx_inv_off, 2, c.nch32, u0);
+            }
+            continue;
+        }
+        const int np = (int)src.pieces.size();
+        uint32_t s_W;
+        if (np == 1) {
+            const PkLayer L = layer(src.pieces[0].layer, c.cout, (size_t)c.cin * c.ntaps);
+            s_W = L.s_w;
+            copy(c.b_off, c.cout, L.s_bias, PK_NONE, 1);
+            bound1(c.bnd_off, s_W, c.cout, (size_t)c.cin * c.ntaps, L.s_bias);
+        } else {
+            // FiLM heads: [scale_lft | scale_sine] over [shift_lft | shift_sine]; the biases of a row's two pieces add
+            const int h = c.cout / 2;
+            if (np != 4 || src.pieces[0].co_off != 0 || src.pieces[1].co_off != 0 || src.pieces[2].co_off != h || src.pieces[3].co_off != h) return FASTSVC_E_UNSUPPORTED;
+            PkLayer pl[4];
+            s_W = virt_of(src, c.cout, c.cin, c.ntaps, pl);
+            copy(c.b_off, h, pl[0].s_bias, pl[1].s_bias, 2);
+            copy(c.b_off + h, h, pl[2].s_bias, pl[3].s_bias, 2);
+            bounds.push_back(PkBound{(uint32_t)c.bnd_off, s_W, (uint32_t)c.cout, (uint32_t)(c.cin * c.ntaps), (uint32_t)h,
+                                     {pl[0].s_bias, pl[2].s_bias}, {pl[1].s_bias, pl[3].s_bias}});
+        }
+        frag(c.w_off, s_W, PK_NONE, c, c.ntaps, c.MW, c.Q, c.ngroups, PK_FRAG_PLAIN);
+        if (c.hx) {
+            const uint32_t u0 = (uint32_t)units.size();
+            for (int u = 0; u < c.nch32; ++u) unit(s_W, PK_NONE, c.cin, 32 * u, c.cin, PK_HX_PLAIN, 0);
+            hx(c, c.hx_off, 3, c.hx_inv_off, 1, c.nch32, u0);
+        }
+        if (c.wino) {
+            frag(c.ww_off, s_W, PK_NONE, c, 3, c.MW, c.Qw, (c.cout + 16 * c.MW - 1) / (16 * c.MW), PK_FRAG_WINO);
+            if (c.wino2) frag(c.ww2_off, s_W, PK_NONE, c, 3, 2, c.Qw, (c.cout + 31) / 32, PK_FRAG_WINO);
+        }
+        if (c.poly) {
+            frag(c.wp_off, s_W, PK_NONE, c, c.ntaps, c.MW, c.Q, c.ngroups, PK_FRAG_POLY);
+            if (c.hx) {
+                const uint32_t u0 = (uint32_t)units.size();
+                for (int u = 0; u < c.nch32; ++u) unit(s_W, PK_NONE, c.cin, 32 * u, c.cin, PK_HX_POLY, 0);
+                hx(c, c.hxp_off, 3, c.hxp_inv_off, 1, c.nch32, u0);
+            }
+        }
+    }
+    for (const auto& job : P.chain_jobs) {
+        const PackedConv& c = *job.c;
+        const PkLayer LA = layer(job.first, c.cin, (size_t)c.cout * 3);
+        const PkLayer LB = layer(job.second, c.cout, (size_t)c.cin * 3);
+        const int nch = c.nch32;
+        const uint32_t u0 = (uint32_t)units.size();
+        for (int u = 0; u < 2 * nch; ++u) unit(u < nch ? LA.s_w : LB.s_w, PK_NONE, c.cin, 32 * (u < nch ? u : u - nch), c.cin, PK_HX_PLAIN, u < nch ? 0 : 1);
+        hx(c, c.hxc_off, 3, c.hxc_inv_off, 2, 2 * nch, u0);
+        const size_t cst = c.hxc_inv_off + 2 * (size_t)c.ngroups * 16 * c.MW;
+        bound1(cst, LA.s_w, c.cin, (size_t)c.cout * 3, LA.s_bias);
+        if (!job.in1.empty()) {
+            const PkLayer L1 = layer(job.in1, c.cout, 3);
+            bound1(cst + 2, L1.s_w, c.cout, 3, L1.s_bias);
+        } else {
+            bound1(cst + 2, 0, 0, 0, 0);
+        }
+    }
+    for (const auto& job : P.xr_jobs) {
+        const PackedConv& c = *job.c;
+        const PkLayer LA = layer(job.conv, c.cout, (size_t)c.cin * 3);
+        const PkLayer LB = layer(job.res, c.cout, (size_t)c.cin * 3);
+        const uint32_t u0 = (uint32_t)units.size();
+        for (int u = 0; u < 2 * c.nch32; ++u) unit((u & 1) ? LB.s_w : LA.s_w, PK_NONE, c.cin, 32 * (u >> 1), c.cin, PK_HX_PLAIN, u & 1);
+        hx(c, c.hxc_off, 3, c.hxc_inv_off, 2, 2 * c.nch32, u0);
+    }
+    for (const auto& job : P.film_chain_jobs) {
+        const PackedConv& c = *job.c;
+        const int C = job.C, C2 = 2 * C;
+        PackSource diag;                                    // block-diagonal first conv
+        diag.pieces = {{job.conv[0], 0, 0}, {job.conv[1], C, C}};
+        PkLayer pa[4], pb[4];
+        const uint32_t s_WA = virt_of(diag, C2, C2, 3, pa);
+        for (int sgn = 0; sgn < 2; ++sgn) copy(c.bmid_off + (size_t)sgn * C, C, pa[sgn].s_bias, PK_NONE, 0);
+        const uint32_t s_WB = virt_of(job.heads, C2, C2, 3, pb);
+        const int nch = c.nch32;
+        const uint32_t u0 = (uint32_t)units.size();
+        for (int u = 0; u < 2 * nch; ++u) unit(u < nch ? s_WA : s_WB, PK_NONE, C2, 32 * (u < nch ? u : u - nch), C2, PK_HX_PLAIN, u < nch ? 0 : 1);
+        hx(c, c.hxc_off, 3, c.hxc_inv_off, 2, 2 * nch, u0);
+        const size_t cst = c.hxc_inv_off + 2 * (size_t)c.ngroups * 16 * c.MW;
+        bounds.push_back(PkBound{(uint32_t)cst, s_WA, (uint32_t)C2, (uint32_t)(C2 * 3), (uint32_t)C, {pa[0].s_bias, pa[1].s_bias}, {PK_NONE, PK_NONE}});
+        bound1(cst + 2, 0, 0, 0, 0);
+    }
+    for (const auto& job : P.up_head_jobs) {
+        const PackedConv& c = *job.c;
+        const int cin = job.cin, C = job.C;
+        const PkLayer LF = layer(job.first, C, (size_t)cin * 3);
+        const PkLayer LR = layer(job.res, C, (size_t)C * 3);
+        const PkLayer LU = layer(job.up, C, (size_t)C * 3);
+        const int nchA = c.nch32, nchB = (C + 31) / 32;
+        const uint32_t u0 = (uint32_t)units.size();
+        for (int u = 0; u < nchA; ++u) unit(LF.s_w, PK_NONE, cin, 32 * u, cin, PK_HX_PLAIN, 0);
+        for (int u = 0; u < nchB; ++u) unit(LR.s_w, PK_NONE, C, 32 * u, C, PK_HX_POLY, 1);
+        for (int u = 0; u < nchB; ++u) unit(LU.s_w, PK_NONE, C, 32 * u, C, PK_HX_POLY, 2);
+        hx(c, c.hxc_off, 3, c.hxc_inv_off, 3, nchA + 2 * nchB, u0);
+        const size_t cst = c.hxc_inv_off + 3 * (size_t)c.ngroups * 16 * c.MW;
+        bound1(cst, LF.s_w, C, (size_t)cin * 3, LF.s_bias);
+        bound1(cst + 2, 0, 0, 0, 0);
+    }
+    for (int k : P.cond_bound_jobs) {
+        const DownStage& d = P.down[k];
+        const int C = d.C, Cin = d.Cin;
+        for (int sgn = 0; sgn < 2; ++sgn) {
+            const std::string pre = std::string("downsampling_") + (sgn ? "sine." : "lft.") + std::to_string(k);
+            const std::string fpre = std::string("film_") + (sgn ? "sine." : "lft.") + std::to_string(k);
+            const PkLayer L[5] = {layer(pre + ".downsample_block.2", C, (size_t)Cin * 3), layer(pre + ".residual_block.0", C, (size_t)Cin),
+                                  layer(pre + ".downsample_block.4", C, (size_t)C * 3), layer(pre + ".downsample_block.6", C, (size_t)C * 3),
+                                  layer(fpre + ".conv", C, (size_t)C * 3)};
+            PkCond J;
+            J.d_dst = (uint32_t)d.cbnd_off[sgn]; J.C = (uint32_t)C; J.Cin = (uint32_t)Cin;
+            J.s_tmp = salloc((size_t)8 * C);
+            for (int i = 0; i < 5; ++i) { J.s_w[i] = L[i].s_w; J.s_b[i] = L[i].s_bias; }
+            conds.push_back(J);
+        }
+    }
+    for (const RawParam* r : P.raw_jobs) {
+        const int cout = (int)r->b_floats;
+        const size_t per = r->w_floats / cout;
+        const PkLayer L = layer(r->layer, cout, per);
+        copy(r->w_off, r->w_floats, L.s_w, PK_NONE, 0);
+        copy(r->b_off, r->b_floats, L.s_bias, PK_NONE, 0);
+        bound1(r->bnd_off, L.s_w, cout, per, L.s_bias);
+    }
+    if (!ok || s_floats >= 0xffffffffu || P.blob_floats >= 0xffffffffu) return FASTSVC_E_UNSUPPORTED;
+
+    // the table image, every array on a 16-byte boundary
+    PkHeader& h = T.h;
+    auto put = [&](const void* data, size_t bytes) {
+        const size_t off = align_up(T.bytes.size(), 16);
+        T.bytes.resize(off + bytes);
+        if (bytes) std::memcpy(T.bytes.data() + off, data, bytes);
+        return (uint32_t)off;
+    };
+    const uint32_t base = (uint32_t)(s_floats * sizeof(float));
+    h.n_layers = (uint32_t)layers.size(); h.layers = base + put(layers.data(), layers.size() * sizeof(PkLayer));
+    h.n_virt = (uint32_t)virts.size(); h.virts = base + put(virts.data(), virts.size() * sizeof(PkVirt)); h.virt_work = virt_work;
+    h.n_frag = (uint32_t)frags.size(); h.frags = base + put(frags.data(), frags.size() * sizeof(PkFrag)); h.frag_work = frag_work;
+    h.n_hx = (uint32_t)hxs.size(); h.hxs = base + put(hxs.data(), hxs.size() * sizeof(PkHx));
+    h.hx_units = base + put(units.data(), units.size() * sizeof(PkHxUnit)); h.hx_work = hx_work; h.hx_rows = hx_rows;
+    h.n_copy = (uint32_t)copies.size(); h.copies = base + put(copies.data(), copies.size() * sizeof(PkCopy)); h.copy_work = copy_work;
+    h.n_bound = (uint32_t)bounds.size(); h.bounds = base + put(bounds.data(), bounds.size() * sizeof(PkBound));
+    h.n_cond = (uint32_t)conds.size(); h.conds = base + put(conds.data(), conds.size() * sizeof(PkCond));
+    h.max_rows = 0; h.max_w = 0;
+    for (const PkLayer& L : layers) { h.max_rows = std::max(h.max_rows, L.cout); h.max_w = std::max(h.max_w, L.cout * L.per); }
+    h.table_off = base;
+    h.table_bytes = (uint32_t)T.bytes.size();
+    T.scratch_bytes = (size_t)base + align_up(T.bytes.size(), 256);
+    T.n_launches = 2 + 2 * (int)((layers.size() + PK_PTR_LAYERS - 1) / PK_PTR_LAYERS) + (h.n_virt ? 1 : 0) + (h.n_frag ? 1 : 0) +
+                   (h.n_hx ? 2 : 0) + (h.n_copy ? 1 : 0) + (h.n_bound ? 1 : 0) + (h.n_cond ? 1 : 0);
+
+    // every destination inside the blob (a table that is wrong must fail here, not write out of bounds on a GPU)
+    const size_t nb = P.blob_floats;
+    for (const PkFrag& J : frags) if ((size_t)J.d_dst + (size_t)J.ngroups * J.Q * 64 * J.MW > nb) ok = false;
+    for (const PkHx& J : hxs) {
+        const size_t frags_n = (size_t)J.ngroups * J.nch * J.nslots * J.MW;
+        if (J.d_off[0] && J.d_off[0] + frags_n * 512 > nb) ok = false;
+        for (int p = 1; p < 3; ++p) if (J.d_off[p] && J.d_off[p] + frags_n * 256 > nb) ok = false;
+        if (J.d_inv && (size_t)J.d_inv + (size_t)J.ntables * J.ngroups * 16 * J.MW > nb) ok = false;
+        if (J.unit0 + J.nch > units.size()) ok = false;
+    }
+    for (const PkCopy& J : copies) if ((size_t)J.d_dst + J.n > nb) ok = false;
+    for (const PkBound& J : bounds) if ((size_t)J.d_dst + 2 > nb) ok = false;
+    for (const PkCond& J : conds) if ((size_t)J.d_dst + (size_t)8 * J.C > nb) ok = false;
+    return ok ? FASTSVC_OK : FASTSVC_E_UNSUPPORTED;
+}
+
+// ------------------------------------------------------------------------------------------
 // weight lookup / fold
 // ------------------------------------------------------------------------------------------
 struct HostLayer { std::vector<float> w; std::vector<float> b; };
@@ -602,8 +878,9 @@ int fastsvc_plan_create(const fastsvc_config* cfg, fastsvc_plan** out_plan) {
     if (cfg->use_spk_emb && cfg->spk_emb_size < 1) return fail(FASTSVC_E_INVALID, "spk_emb_size must be positive");
     fastsvc_plan* P = new fastsvc_plan();
     P->cfg = *cfg;
-    const int rc = build_plan(*P);
-    if (rc != FASTSVC_OK) { delete P; return rc; }
+    int rc = build_plan(*P);
+    if (rc == FASTSVC_OK) rc = build_pack_table(*P);
+    if (rc != FASTSVC_OK) { delete P; return fail(rc, "cannot build the plan"); }
     *out_plan = P;
     return FASTSVC_OK;
 }
@@ -1133,6 +1410,65 @@ int fastsvc_pack_weights(const fastsvc_plan* plan, const fastsvc_tensor* tensors
         std::fprintf(stderr, "\n");
     }
     if (first_rc.load() != FASTSVC_OK) return fail(first_rc.load(), err_msg);
+    return FASTSVC_OK;
+}
+
+}  // extern "C"
+
+// ==========================================================================================
+// device packer (kernels: fastsvc_pack.hip)
+// ==========================================================================================
+extern "C" {
+
+size_t fastsvc_pack_device_scratch_bytes(const fastsvc_plan* plan) { return plan ? plan->pk.scratch_bytes : 0; }
+
+int fastsvc_pack_device_launch_count(const fastsvc_plan* plan) { return plan ? plan->pk.n_launches : 0; }
+
+int fastsvc_pack_weights_device(const fastsvc_plan* plan, const fastsvc_tensor* tensors, int32_t n_tensors,
+                                void* dev_blob, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!plan || !tensors || !dev_blob || !scratch) return fail(FASTSVC_E_INVALID, "null argument");
+    std::unordered_map<std::string, const fastsvc_tensor*> sd;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!tensors[i].name || !tensors[i].data) return fail(FASTSVC_E_INVALID, "tensor entry with null name/data");
+        sd[tensors[i].name] = &tensors[i];
+    }
+    // fetch_layer's checks and messages, before anything is launched
+    const PackTable& T = plan->pk;
+    std::vector<const float*> ptrs(3 * T.layers.size(), nullptr);
+    for (size_t l = 0; l < T.layers.size(); ++l) {
+        const std::string& layer = T.layers[l].name;
+        const int cout = T.layers[l].cout;
+        auto bi = sd.find(layer + ".bias");
+        if (bi == sd.end() || bi->second->numel != cout)
+            return fail(FASTSVC_E_MISSING, "missing or mis-sized tensor: " + layer + ".bias");
+        ptrs[3 * l] = bi->second->data;
+        const int64_t wn = (int64_t)cout * (int64_t)T.layers[l].per;
+        auto wi = sd.find(layer + ".weight");
+        if (wi != sd.end()) {
+            if (wi->second->numel != wn) return fail(FASTSVC_E_MISSING, "mis-sized tensor: " + layer + ".weight");
+            ptrs[3 * l + 1] = wi->second->data;
+            continue;
+        }
+        auto gi = sd.find(layer + ".weight_g");
+        auto vi = sd.find(layer + ".weight_v");
+        if (gi == sd.end() || vi == sd.end())
+            return fail(FASTSVC_E_MISSING, "missing tensor: " + layer + ".weight (or .weight_g/.weight_v)");
+        if (gi->second->numel != cout || vi->second->numel != wn)
+            return fail(FASTSVC_E_MISSING, "mis-sized tensor: " + layer + ".weight_g/.weight_v");
+        ptrs[3 * l + 1] = vi->second->data;
+        ptrs[3 * l + 2] = gi->second->data;
+    }
+    if (scratch_bytes < T.scratch_bytes) return fail(FASTSVC_E_WORKSPACE, "pack scratch too small");
+    std::call_once(plan->pk_once, [&]() {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, T.bytes.size(), hipHostMallocPortable) != hipSuccess) return;
+        std::memcpy(p, T.bytes.data(), T.bytes.size());
+        plan->pk_pinned = p;
+    });
+    if (!plan->pk_pinned) return fail(FASTSVC_E_HIP, "cannot page-lock the pack table");
+    const int rc = fastsvc_pack::launch_pack(T.h, plan->pk_pinned, ptrs.data(), dev_blob, plan->blob_floats * sizeof(float), scratch,
+                                             stream, nullptr);
+    if (rc != 0) return fail(FASTSVC_E_HIP, std::string("device pack: ") + hipGetErrorString((hipError_t)rc));
     return FASTSVC_OK;
 }
 

@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "fastsvc_abi_version", "fastsvc_last_error", "fastsvc_plan_create", "fastsvc_plan_destroy",
     "fastsvc_plan_set_storage", "fastsvc_plan_get_storage",
     "fastsvc_weight_blob_bytes", "fastsvc_pack_weights", "fastsvc_workspace_bytes",
+    "fastsvc_pack_device_scratch_bytes", "fastsvc_pack_device_launch_count", "fastsvc_pack_weights_device",
     "fastsvc_forward", "fastsvc_autotune", "fastsvc_tuned_count", "fastsvc_tuned_get", "fastsvc_tuned_set",
     "fastsvc_forward_profile", "fastsvc_workspace_tap", "fastsvc_forward_launch_count",
     "fastsvc_flops_per_sample", "fastsvc_signal_scratch_bytes", "fastsvc_signal_generate",
@@ -102,6 +103,12 @@ def load_library():
     lib.fastsvc_weight_blob_bytes.restype = sz
     lib.fastsvc_pack_weights.argtypes = [vp, ctypes.POINTER(_Tensor), i32, vp]
     lib.fastsvc_pack_weights.restype = ctypes.c_int
+    lib.fastsvc_pack_device_scratch_bytes.argtypes = [vp]
+    lib.fastsvc_pack_device_scratch_bytes.restype = sz
+    lib.fastsvc_pack_device_launch_count.argtypes = [vp]
+    lib.fastsvc_pack_device_launch_count.restype = ctypes.c_int
+    lib.fastsvc_pack_weights_device.argtypes = [vp, ctypes.POINTER(_Tensor), i32, vp, vp, sz, vp]
+    lib.fastsvc_pack_weights_device.restype = ctypes.c_int
     lib.fastsvc_workspace_bytes.argtypes = [vp, i32, i32]
     lib.fastsvc_workspace_bytes.restype = sz
     lib.fastsvc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
@@ -532,6 +539,78 @@ class Plan:
             raise KeyError(self.lib.fastsvc_last_error().decode())
         _check(self.lib, rc, "fastsvc_pack_weights")
         return blob
+
+    @property
+    def pack_device_scratch_bytes(self) -> int:
+        return int(self.lib.fastsvc_pack_device_scratch_bytes(self._h))
+
+    @property
+    def pack_device_launches(self) -> int:
+        """Launches one ``pack_device`` enqueues (kernels + one table copy + one memset)."""
+        return int(self.lib.fastsvc_pack_device_launch_count(self._h))
+
+    def pack_device(self, state_dict: Mapping[str, torch.Tensor], out: Optional[torch.Tensor] = None,
+                    scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``pack`` for parameters that are already on the GPU: the same bytes, written by HIP kernels
+        (csrc/fastsvc_pack.hip) into a device blob, asynchronously on the current stream - no weight crosses the host
+        link in either direction.  Every value must be a float32 CUDA tensor on one device (non-contiguous ones are made
+        contiguous); anything else raises ``FastSVCError`` - there is no fallback to the host packer.  ``out``: a
+        contiguous device tensor of ``blob_bytes`` bytes to write into (the blob of earlier forwards on the stream is
+        fine); returned as it is.  ``scratch``: a uint8 device tensor of at least ``pack_device_scratch_bytes`` bytes, any
+        contents (default: one per device and stream, kept by the plan).  ``KeyError`` for a missing or mis-sized tensor,
+        like ``pack``."""
+        items = list(state_dict.items())
+        if not items:
+            raise KeyError("empty state dict")
+        dev = None
+        for k, v in items:
+            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32:
+                raise FastSVCError(f"pack_device needs float32 GPU tensors (no CPU fallback: use pack); {k} is "
+                                   f"{getattr(v, 'dtype', type(v))} on {getattr(v, 'device', 'the host')}")
+            if dev is None:
+                dev = v.device
+            elif v.device != dev:
+                raise FastSVCError(f"pack_device: {k} is on {v.device}, expected {dev}")
+        nbytes = self.blob_bytes
+        if out is None:
+            out = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.device != dev or not out.is_contiguous() or \
+                out.numel() * out.element_size() != nbytes:
+            raise ValueError(f"out must be a contiguous tensor of {nbytes} bytes on {dev}")
+        tensors = [v.detach() if v.is_contiguous() else v.detach().contiguous() for _, v in items]
+        # the ctypes table is rebuilt only when a tensor moved (a training loop packs the same parameters every step)
+        key = tuple((t.data_ptr(), t.numel()) for t in tensors)
+        cached = getattr(self, "_pack_device_args", None)
+        if cached is None or cached[0] != key or cached[1] != [k for k, _ in items]:
+            arr = (_Tensor * len(items))()
+            names = [k.encode("utf-8") for k, _ in items]
+            for i, t in enumerate(tensors):
+                arr[i].name = names[i]
+                arr[i].data = ctypes.cast(ctypes.c_void_p(t.data_ptr()), ctypes.POINTER(ctypes.c_float))
+                arr[i].numel = t.numel()
+            cached = self._pack_device_args = (key, [k for k, _ in items], arr, names)
+        arr = cached[2]
+        need = self.pack_device_scratch_bytes
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if scratch is None:
+                # one per (device, stream): packs of one plan on different streams must not share it
+                pool = self.__dict__.setdefault("_pack_device_scratch", {})
+                skey = (str(dev), int(stream))
+                if skey not in pool:
+                    if len(pool) >= 4:
+                        pool.pop(next(iter(pool)))
+                    pool[skey] = torch.empty(need, dtype=torch.uint8, device=dev)
+                scratch = pool[skey]
+            elif scratch.device != dev or scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+                raise ValueError(f"scratch must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+            rc = self.lib.fastsvc_pack_weights_device(self._h, arr, len(items), ctypes.c_void_p(out.data_ptr()),
+                                                      ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.c_void_p(stream))
+        if rc == -2:
+            raise KeyError(self.lib.fastsvc_last_error().decode())
+        _check(self.lib, rc, "fastsvc_pack_weights_device")
+        self._pack_device_keep = tensors             # (contiguous copies: alive until the next pack on this plan)
+        return out
 
     def tap_info(self, name: str, B: int, F: int) -> Tuple[int, int, Tuple[int, int, int]]:
         off = ctypes.c_size_t()

@@ -178,12 +178,17 @@ class FastSVCGenerator(nn.Module):
     # `FastSVCGenerator.checksum_weights = True` to fingerprint the parameter storage on every
     # forward (one device reduction per parameter: safe, slower).
     checksum_weights = False
+    # True: parameters that live on the GPU are packed THERE (Plan.pack_device: HIP kernels, the same bytes as the host
+    # packer's, nothing crosses the host link, the blob buffer is rewritten in place).  Off by default - inference packs
+    # once, on the host; TrainStep switches it on for its generator, whose every optimizer update invalidates the blob.
+    pack_on_device = False
 
     def invalidate_packed_weights(self):
         """Forget the packed device blob; the next forward folds and packs the parameters again."""
         self._blob = None
         self._blob_key = None
         self._prefetch = None
+        self._device_blob = None         # (the buffer pack_on_device rewrites in place)
 
     def _weights_key(self, device):
         key = (str(device),) + tuple((id(p), p._version) for p in self.parameters())
@@ -209,6 +214,7 @@ class FastSVCGenerator(nn.Module):
         state = self.__dict__.copy()
         state["_plan"] = None
         state["_blob"] = None
+        state["_device_blob"] = None
         state["_blob_key"] = None
         state["_prefetch"] = None
         state["_tuned_shapes"] = set()
@@ -237,13 +243,27 @@ class FastSVCGenerator(nn.Module):
         key = self._weights_key(device)
         if self._blob is None or self._blob_key != key:
             on_gpu = torch.device(device).type != "cpu"
-            pre = getattr(self, "_prefetch", None)
-            pre = pre[1] if (pre is not None and pre[0] == key) else None
-            host = self._plan.pack(self.state_dict(), reuse_pinned=on_gpu, prefetched=pre)   # staging buffer: uploaded right here
-            self._blob = host.to(device)
+            if self.pack_on_device and on_gpu and self._params_on(device):
+                # the parameters themselves (no state_dict() copies); the buffer of the stale blob is reused - forwards
+                # already enqueued on the stream read it before the pack's kernels overwrite it
+                old = getattr(self, "_device_blob", None)
+                if old is not None and (old.device != torch.device(device) or old.numel() * 4 != self._plan.blob_bytes):
+                    old = None
+                self._blob = self._device_blob = self._plan.pack_device(dict(self.named_parameters()), out=old)
+            else:
+                pre = getattr(self, "_prefetch", None)
+                pre = pre[1] if (pre is not None and pre[0] == key) else None
+                host = self._plan.pack(self.state_dict(), reuse_pinned=on_gpu, prefetched=pre)   # staging buffer: uploaded right here
+                self._blob = host.to(device)
             self._blob_key = key
         self._prefetch = None
         return self._blob
+
+    def _params_on(self, device) -> bool:
+        dev = torch.device(device)
+        if dev.index is None and dev.type == "cuda":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return all(p.device == dev and p.dtype == torch.float32 for p in self.parameters())
 
     def prefetch_packed_weights(self):
         """Call right after an optimizer update: starts the asynchronous device-to-host copy of the parameters that the next
@@ -251,7 +271,7 @@ class FastSVCGenerator(nn.Module):
         enqueued in between (the train step puts the discriminator's real-batch forward there) instead of draining the
         stream at the next forward."""
         p = next(self.parameters())
-        if not p.is_cuda:
+        if not p.is_cuda or self.pack_on_device:         # (packed on the device: nothing goes to the host)
             return
         if self._plan is None:
             self._plan = Plan(self._cfg, storage=self.activation_storage, compact_workspace=True)

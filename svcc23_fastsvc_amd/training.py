@@ -528,6 +528,10 @@ class TrainStep:
         # MelGAN and HiFiGAN families as the reference builds them); a BatchNorm or spectral-norm discriminator gets the
         # reference's two calls in its order (train_fastsvc.py:207-211)
         self._stateless_d = discriminator_is_per_sample_stateless(discriminator)
+        # the optimizer invalidates the generator's packed weights every step: re-pack them on the GPU (HIP kernels, the
+        # host packer's bytes - so no loss or parameter changes with this key) instead of download, host pack, upload
+        if dev.type == "cuda" and hasattr(type(generator), "pack_on_device"):
+            generator.pack_on_device = bool(cfg.get("pack_on_device", True))
 
     def _autocast(self, discriminator: bool = False):
         dev = next(self.generator.parameters()).device
