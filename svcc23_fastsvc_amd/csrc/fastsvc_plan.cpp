@@ -43,6 +43,51 @@ int fail(int code, const std::string& msg) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Every environment switch of the library, read ONCE (first use): name, default, meaning.  INTEGRATION.md section 4 lists
+// the same names (tests/test_env_switches.py keeps the two in step).  FASTSVC_TIMELINE_LAYER / FASTSVC_TIMELINE_OUT of the
+// diagnostic build are read per call (timeline_launch: tools/timeline.py changes them between forwards).
+struct Switches {
+    static int num(const char* name, int dflt) { const char* v = std::getenv(name); return v ? std::atoi(v) : dflt; }
+    static double real(const char* name, double dflt) { const char* v = std::getenv(name); return v ? std::atof(v) : dflt; }
+    static bool given(const char* name) { return std::getenv(name) != nullptr; }
+    // kernel families and fused routes (A/B)
+    const int hx = num("FASTSVC_HX", 1);                  // half-precision MFMA kernels: 0 off, 2 on even where a loaded table says otherwise
+    const int wx = num("FASTSVC_WX", 1);                  // the wide layers' kernel: 0 off, 2 wherever it exists (A/B, tests), else by table / tuning
+    const int wino = num("FASTSVC_WINO", -1);             // 0 / 1 / 2: direct / Winograd in the layer's grouping / in 32-channel groups
+    const int chain = num("FASTSVC_CHAIN", 1);            // fused two-conv launches: 0 off, 2 fused regardless of the table
+    const int uphead = num("FASTSVC_UPHEAD", 1);          // fused block heads: 0 off, 2 wherever the variant exists
+    const int d3x = num("FASTSVC_D3X", 1);                // residual conv inside the d = 3 launch: 0 never, 2 wherever it exists
+    const bool no_poly = given("FASTSVC_NO_POLY");        // the plain stretched launches
+    const bool no_dec2 = given("FASTSVC_NO_DEC2");        // the plain decimating launches
+    const bool no_fuse_last = given("FASTSVC_NO_FUSE_LAST");   // conv_last as its own launch
+    const int prior = num("FASTSVC_PRIOR", 1);            // 0: off-table launches from the cost model alone
+    const double startup_us = real("FASTSVC_STARTUP_US", 4.0);     // the cost models' fixed cost of a workgroup
+    const int stagger = num("FASTSVC_STAGGER", 2);        // conv_wx: start delay between the workgroups of an XCD, in 64-cycle steps per K chunk - an eighth of a unit
+    const int dbg = num("FASTSVC_DBG", 0);                // ablation bits (kernels of the `build --timeline` library only)
+    // whole-stage conditioning launches
+    const int cond = num("FASTSVC_COND", 1);              // 0 none, 1 all, 4 stage 0 only
+    const int cond_pipe = num("FASTSVC_COND_PIPE", 1);    // the layer pipelines: 0 never, 2 always (tests, A/B)
+    const int cond_small = num("FASTSVC_COND_SMALL", -1); // >= 0: that tile variant
+    const int cond_tpw = num("FASTSVC_COND_TPW", 0);      // > 0: tiles (chunks) per workgroup of stage 0 ...
+    const int cond1_tpw = num("FASTSVC_COND1_TPW", 0);    // ... of stage 1
+    const int cond_dbg = num("FASTSVC_COND_DBG", 0);      // ablation bits of stage 0 (results then invalid)
+    const bool cond_trace = given("FASTSVC_COND_TRACE");  // cycle stamps (a library built with -DFASTSVC_COND_TRACE only)
+    const bool no_amax_scan = given("FASTSVC_NO_AMAX_SCAN");   // A/B timing only: inputs then count as unit-scale
+    // schedule
+    const bool serial = given("FASTSVC_SERIAL");          // one stream
+    const int streams = num("FASTSVC_STREAMS", -1);       // >= 0: helper-stream mask (0: one stream)
+    const double fork_join_limit_us = real("FASTSVC_FORK_JOIN_LIMIT_US", 40.0);   // measured: 24-27 us where the streams are independent, 52 us where they are not
+    const bool stream_debug = given("FASTSVC_STREAM_DEBUG");   // print the fork + join measurement
+    // weight packer, diagnostics
+    const int pack_threads = num("FASTSVC_PACK_THREADS", 0);   // > 0: the packer's pool size
+    const bool pack_debug = given("FASTSVC_PACK_DEBUG");       // per-job timings
+    const bool verbose_shapes = given("FASTSVC_VERBOSE_SHAPES");   // what every launch of a profiled forward chose (tuning aid)
+};
+const Switches& env() {
+    static const Switches s;
+    return s;
+}
+
 // A convolution whose weights live in the blob in MFMA fragment order.
 struct PackedConv {
     int cin = 0, cout = 0, ntaps = 3, dil = 1;
@@ -1358,14 +1403,14 @@ int fastsvc_pack_weights(const fastsvc_plan* plan, const fastsvc_tensor* tensors
         }
         return FASTSVC_OK;
     });
-    static const int env_threads = std::getenv("FASTSVC_PACK_THREADS") ? std::atoi(std::getenv("FASTSVC_PACK_THREADS")) : 0;
+    const int env_threads = env().pack_threads;
     unsigned nthreads = env_threads > 0 ? (unsigned)env_threads : std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
     nthreads = (unsigned)std::min<size_t>(nthreads, tasks.size());
     std::atomic<size_t> next{0};
     std::atomic<int> first_rc{FASTSVC_OK};
     std::mutex err_mu;
     std::string err_msg;
-    static const bool pack_debug = std::getenv("FASTSVC_PACK_DEBUG") != nullptr;
+    const bool pack_debug = env().pack_debug;
     // Longest job first: the jobs differ 20:1 (the 2C -> 2C FiLM heads and block-diagonal chains of the C = 192 stage
     // against a 1 x 1 conv), the queue is dynamic, and a long job that starts last IS the makespan.  The order comes
     // from the durations the previous pack of this plan measured (a training step packs after every optimizer
@@ -1504,18 +1549,10 @@ struct Workspace {
 // Which conditioning stages run as ONE launch each (run_cond_stage0 / run_cond_stage1) - a function of the plan and
 // the frame count alone, so that the compact layout can leave out what those launches never write (h_k, r_k, c1 / c2,
 // film_u of the stage) and the forward can insist on the launch instead of falling back into missing buffers.
-int cond_env_mode() {
-    static const int v = std::getenv("FASTSVC_COND") ? std::atoi(std::getenv("FASTSVC_COND")) : 1;     // 0 none, 1 all, 4 stage 0 only
-    return v;
-}
-bool amax_scan_disabled() {
-    static const bool v = std::getenv("FASTSVC_NO_AMAX_SCAN") != nullptr;    // A/B timing only: inputs then count as unit-scale
-    return v;
-}
 bool cond_stage_whole(const fastsvc_plan& P, int k, int F) {
-    const int mode = cond_env_mode();
+    const int mode = env().cond;
     if (!P.compact || !mode || P.n < k + 2) return false;
-    if (P.storage == 0 && (F <= 4 || amax_scan_disabled())) return false;    // exact-f32 mode / no measured maxima
+    if (P.storage == 0 && (F <= 4 || env().no_amax_scan)) return false;    // exact-f32 mode / no measured maxima
     int64_t hop = 1;
     for (int i = 0; i < P.n; ++i) hop *= P.cfg.upsampling_scales[i];
     const int64_t T = hop * F;
@@ -1725,9 +1762,9 @@ bool measure_fork_join(hipStream_t stream, ExecCtx* c) {
     for (hipEvent_t e : t) (void)hipEventDestroy(e);
     if (!ok) return false;
     c->fork_join_us = (best_forked - best_alone) * 1e3f / R;
-    static const double limit_us = std::getenv("FASTSVC_FORK_JOIN_LIMIT_US") ? std::atof(std::getenv("FASTSVC_FORK_JOIN_LIMIT_US")) : 40.0;   // measured: 24-27 us where the streams are independent, 52 us where they are not
+    const double limit_us = env().fork_join_limit_us;
     c->pays = c->fork_join_us < limit_us;
-    if (std::getenv("FASTSVC_STREAM_DEBUG"))
+    if (env().stream_debug)
         std::fprintf(stderr, "[fastsvc] fork + join through a helper stream: %.1f us (limit %.0f): helper streams %s\n",
                      c->fork_join_us, limit_us, c->pays ? "on" : "off");
     return true;
@@ -1800,29 +1837,26 @@ int exec_ctx_release(hipStream_t stream) {
     return 1;
 }
 
-// Autotuning state of one forward call (fastsvc_autotune): when `tuning` every pipelined conv
-// times all its candidate launch shapes on the device before the real launch.
-struct TuneCtx {
+// What one forward call carries to its launch routes: the entry point creates it, forward_impl fills in the plan's part.
+struct CallCtx {
     const fastsvc_plan* plan = nullptr;
+    int storage = 0;                   // the plan's activation storage (0 float32, 1 bfloat16, 2 float16)
+    // fastsvc_autotune: every route times all its candidate launch shapes on the device before the real launch ...
     bool tuning = false;
-    int trials = 0;
+    int trials = 0;                    // ... and counts them
+    // Batches of at most 4 frames (40 ms of audio) run on the f32-input-MFMA kernels throughout: an InstanceNorm over the
+    // 2 - 8 samples such an utterance has at the first blocks is ill-conditioned (1 / sqrt(var + 1e-5) up to 316), and the
+    // split-binary16 products' error - 2^-22 of the TENSOR's maximum rather than of each value - then shows: a 1-frame
+    // utterance sat at 3.4e-3 of the output's range where the float32 reference is 4e-5 from float64
+    // (tools/stress_parity.py, seed 75).  Float32 storage only.  (fastsvc_kernels.hip speaks of it as g_exact_f32.)
+    bool exact_f32 = false;
 };
-thread_local TuneCtx g_tune;
-// set by run_conv when the launch it made also computed conv_last (ConvParams::last_w accepted)
-thread_local bool g_last_fused = false;
-// Batches of at most 4 frames (40 ms of audio) run on the f32-input-MFMA kernels throughout: an InstanceNorm over the
-// 2 - 8 samples such an utterance has at the first blocks is ill-conditioned (1 / sqrt(var + 1e-5) up to 316), and the
-// split-binary16 products' error - 2^-22 of the TENSOR's maximum rather than of each value - then shows: a 1-frame
-// utterance sat at 3.4e-3 of the output's range where the float32 reference is 4e-5 from float64
-// (tools/stress_parity.py, seed 75).  Set by forward_impl for the duration of the call; float32 storage only.
-thread_local bool g_exact_f32 = false;
-
 
 #ifdef FASTSVC_TIMELINE
 // diagnostic build (python -m svcc23_fastsvc_amd.build --timeline; tools/timeline.py): per-wave cycle stamps
 // of the launch named by FASTSVC_TIMELINE_LAYER, dumped to FASTSVC_TIMELINE_OUT.  True when this launch was it.
 template <class LaunchFn>
-bool timeline_launch(const char* layer, ConvParams p, long wgs, int nchunks, const ConvLaunch& L, hipStream_t stream,
+bool timeline_launch(const char* layer, ConvParams& p, long wgs, int nchunks, const ConvLaunch& L, hipStream_t stream,
                      LaunchFn&& fn, hipError_t& err) {
     const char* want = std::getenv("FASTSVC_TIMELINE_LAYER");
     const char* out = std::getenv("FASTSVC_TIMELINE_OUT");
@@ -1832,8 +1866,8 @@ bool timeline_launch(const char* layer, ConvParams p, long wgs, int nchunks, con
     const size_t bytes = (size_t)cap * 8 * 64 * sizeof(unsigned long long);
     if (hipMalloc(&dbuf, bytes) != hipSuccess) { err = hipErrorOutOfMemory; return true; }
     hipMemsetAsync(dbuf, 0, bytes, stream);
-    p.tl = dbuf; p.tl_wgs = (int)cap;
-    err = fn(p);
+    p.tl = dbuf; p.tl_wgs = (int)cap;                     // (fn launches with the caller's p)
+    err = fn();
     if (err != hipSuccess) return true;
     hipStreamSynchronize(stream);
     std::vector<unsigned long long> host((size_t)cap * 8 * 64);
@@ -1848,13 +1882,6 @@ bool timeline_launch(const char* layer, ConvParams p, long wgs, int nchunks, con
     return true;
 }
 #endif
-
-// The c2 -> c3 pair of a down stage as ONE launch (fastsvc_hx.hip, MODE_CHAIN): p describes the SECOND conv's
-// launch (x = the first conv's input, y / res / r1x as for c3).  `done` = false when the pair has no fused
-// variant for this call (the caller then runs the two launches); with a tuning pass the fused launch is
-// also timed against the two separate ones and the table remembers which won (algo 3 fused, 0 separate).
-hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int nsig, long pair_w_stride,
-                    long pair_b_stride, hipStream_t stream, Profiler* prof, const char* layer);
 
 // Launch-table keys end in nothing (float32 storage), "|b" (bfloat16) or "|h" (float16).  The float16 objects have
 // bfloat16's instance set and register budgets, so a float16 plan that has no "|h" entry runs on the "|b" one.
@@ -1874,21 +1901,156 @@ inline auto tuned_find(Map& tuned, const char* key) -> decltype(tuned.find(key))
 inline const char* prod_tag(int storage) { return storage == 2 ? "h1" : storage == 1 ? "x1" : "x3"; }
 // a launcher of the plan's activation storage
 #define FASTSVC_BY_STORAGE(storage, fn) ((storage) == 2 ? f16::fn : (storage) == 1 ? bf16::fn : fn)
+// FASTSVC_VERBOSE_SHAPES (tuning aid; tools/dump_routes.py reads it back): what every launch of a PROFILED forward chose,
+// one line each - the kernel as in the profile record; `small` for the whole-stage conditioning launches only
+void print_choice(const char* layer, const char* kernel, int tpw, int small = -1) {
+    if (!env().verbose_shapes) return;
+    if (small >= 0) std::fprintf(stderr, "[fastsvc] %s %s tpw %d small %d\n", layer, kernel, tpw, small);
+    else std::fprintf(stderr, "[fastsvc] %s %s tpw %d\n", layer, kernel, tpw);
+}
 
-hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob, ConvParams p, int nsig,
+// ---- what the launch routes below share: table lookup, tuning trials, the no-entry fill rules, the launch itself ----
+
+// The launch-table entry under `key` (a float16 key falls back to its "|b" twin: tuned_find), or nothing.  What an entry
+// MEANS is each route's own rule - which fields count, whether the shape must be one the launch is compiled for.
+bool table_entry(const fastsvc_plan& P, const char* key, fastsvc_plan::Choice& out) {
+    std::lock_guard<std::mutex> lock(P.tune_mu);
+    auto it = tuned_find(P.tuned, key);
+    if (it == P.tuned.end()) return false;
+    out = it->second;
+    return true;
+}
+void table_record(const fastsvc_plan& P, const char* key, const fastsvc_plan::Choice& ch) {
+    std::lock_guard<std::mutex> lock(P.tune_mu);
+    P.tuned[key] = ch;
+    P.priors.clear();
+}
+
+// A launch shape a route may take.  algo (run_conv; the fused routes' shapes are all 3): 0 as launched, 1 Winograd (MW of
+// the layer), 2 Winograd MW = 2, 3 half-precision MFMA (fastsvc_hx.hip), 6 the wide layers' kernel (fastsvc_wx.hip)
+struct Cand { int NW, WM, WN, algo; };
+
+struct EventPair {                                     // (destroyed on every way out of a timing loop: ADVICE r5)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+    bool create() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
+};
+
+// A tuning pass times every (shape, tiles-per-workgroup) on the device: one warm launch, then 3 timed ones.
+// `prepare(cd)` sets the candidate up and returns its tile count per row (a larger tpw changes nothing), `launch(tpw)`
+// launches it.  The first candidate wins a tie; best / best_tpw keep what they held when nothing was timed.
+// (fine steps matter: the winner is often the count that fills the last round of workgroups best)
+template <class PrepareFn, class LaunchFn>
+hipError_t time_candidates(const std::vector<Cand>& cands, hipStream_t stream, int& trials, PrepareFn&& prepare, LaunchFn&& launch,
+                           Cand& best, int& best_tpw, float& best_ms) {
+    static const int tpws[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 20, 24};
+    EventPair ev;
+    if (!ev.create()) return hipErrorUnknown;
+    best_ms = 1e30f;
+    for (const Cand& cd : cands) {
+        const long ntx = prepare(cd);
+        for (int tpw : tpws) {
+            hipError_t e = launch(tpw);                           // warm
+            if (e != hipSuccess && cd.algo == 6) break;           // (this conv_wx shape does not fit the layer's LDS budget)
+            if (e != hipSuccess) return e;
+            hipEventRecord(ev.e0, stream);
+            for (int r = 0; r < 3; ++r) { e = launch(tpw); if (e != hipSuccess) return e; }
+            hipEventRecord(ev.e1, stream);
+            if (hipEventSynchronize(ev.e1) != hipSuccess) return hipErrorUnknown;
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, ev.e0, ev.e1);
+            ++trials;
+            if (ms < best_ms) { best_ms = ms; best = cd; best_tpw = tpw; }
+            if (tpw >= ntx) break;
+        }
+    }
+    return hipSuccess;
+}
+
+// A tuning pass times the launches a fused route would replace: `run()` (a FASTSVC_* status) 3 times back to back on
+// `on`, milliseconds per run - the fused launch is then timed against it.  warm: once more in front, untimed (that run
+// tunes the separate launches' own shapes).
+template <class RunFn>
+int time_separate(hipStream_t on, bool warm, RunFn&& run, double& ms_each) {
+    int rc = warm ? run() : FASTSVC_OK;
+    if (rc != FASTSVC_OK) return rc;
+    EventPair ev;
+    if (!ev.create()) return fail(FASTSVC_E_HIP, "hipEventCreate");
+    hipEventRecord(ev.e0, on);
+    for (int r = 0; r < 3 && rc == FASTSVC_OK; ++r) rc = run();
+    hipEventRecord(ev.e1, on);
+    float ms = 0.f;
+    if (rc == FASTSVC_OK && hipEventSynchronize(ev.e1) == hipSuccess) hipEventElapsedTime(&ms, ev.e0, ev.e1);
+    ms_each = ms / 3.0;
+    return rc;
+}
+
+// A fused route has no table entry: tiles per workgroup such that the grid - ceil(ntx / tpw) * rows workgroups, in rounds
+// of 256 - fills the CUs about evenly (a workgroup costs a start of 4 plus 2 per tile and 32-channel chunk)
+int fill_tpw(long ntx, long rows, int nch32, int tpw_max) {
+    int best = 1;
+    double best_t = 1e30;
+    for (int tpw = 1; tpw <= tpw_max; ++tpw) {
+        const long wgs = ((ntx + tpw - 1) / tpw) * rows;
+        const double t = (double)((wgs + 255) / 256) * (4.0 + tpw * nch32 * 2.0);
+        if (t < best_t * 0.999) { best_t = t; best = tpw; }
+    }
+    return best;
+}
+
+// Tiles per workgroup of a whole-stage conditioning launch (phase kernels): the grid runs in whole rounds of the `slots`
+// resident workgroups, at most ~32 tiles each (a workgroup's start - 24 KB of weight fragments per wave, zeroed tiles -
+// costs about two tiles)
+int cond_tpw(long ntx, int B, long slots) {
+    const long total = ntx * B;
+    const long rounds = std::max<long>(1, (total + slots * 32 - 1) / (slots * 32));
+    long tpw = std::max<long>(1, (total + slots * rounds - 1) / (slots * rounds));
+    // (per-utterance rounding: ceil(ntx / tpw) * B workgroups must not spill into one more round)
+    while (tpw < ntx && ((ntx + tpw - 1) / tpw) * B > slots * rounds) ++tpw;
+    return (int)std::min<long>(tpw, ntx);
+}
+
+// The end of every route: the launch - bracketed by the profiler where the forward has one (kernel / flops / bytes are only
+// filled in then), which is also where FASTSVC_VERBOSE_SHAPES prints the choice.  tl_p (the convolution routes that have
+// per-wave stamps in the diagnostic build): the ConvParams `launch` launches with, tl_wgs its grid, tl_chunks its K chunks.
+template <class LaunchFn>
+hipError_t launch_tail(Profiler* prof, hipStream_t stream, const char* layer, const char* kernel, int tpw, int small,
+                       double flops, double bytes, LaunchFn&& launch, ConvParams* tl_p = nullptr, const ConvLaunch* tl_L = nullptr,
+                       long tl_wgs = 0, int tl_chunks = 0) {
+    if (prof) {
+        print_choice(layer, kernel, tpw, small);
+        hipError_t e = prof->begin(stream, layer, kernel, flops, bytes);
+        if (e != hipSuccess) return e;
+        e = launch();
+        if (e != hipSuccess) return e;
+        return prof->end();
+    }
+#ifdef FASTSVC_TIMELINE
+    if (tl_p) {
+        hipError_t e = hipSuccess;
+        if (timeline_launch(layer, *tl_p, tl_wgs, tl_chunks, *tl_L, stream, launch, e)) return e;
+    }
+#endif
+    (void)tl_p; (void)tl_L; (void)tl_wgs; (void)tl_chunks;
+    return launch();
+}
+
+// The c2 -> c3 pair of a down stage as ONE launch (fastsvc_hx.hip, MODE_CHAIN): p describes the SECOND conv's
+// launch (x = the first conv's input, y / res / r1x as for c3).  `done` = false when the pair has no fused
+// variant for this call (the caller then runs the two launches); with a tuning pass the fused launch is
+// also timed against the two separate ones and the table remembers which won (algo 3 fused, 0 separate).
+hipError_t run_chain(CallCtx& cc, const PackedConv& a, const PackedConv& c, const float* blob, ConvParams p, int nsig,
                      long pair_b_stride, hipStream_t stream, Profiler* prof, const char* layer, double sep_ms, bool& done,
                      const RawParam* in1 = nullptr) {
     // in1: the stage's 1 -> C first conv (lft / sine twins) computed by the launch itself from the raw signal p.x
     // (MODE_CHAIN1)
     done = false;
-    static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
-    static const int chain_env = std::getenv("FASTSVC_CHAIN") ? std::atoi(std::getenv("FASTSVC_CHAIN")) : 1;
-    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const int stg = cc.storage;
     const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
     const int prec = stg;                   // fragment set = storage
     p.ldx = p.x_T; p.ldy = p.T;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; }
-    if (!hx_env || !chain_env || g_exact_f32 || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T ||
+    if (!env().hx || !env().chain || cc.exact_f32 || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T ||
         (p.lens && ((p.len_mul & 3) || (p.xlen_mul & 3))))
         return hipSuccess;
     p.mode = in1 ? MODE_CHAIN1 : MODE_CHAIN;
@@ -1903,14 +2065,10 @@ hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob
     p.bias = blob + c.b_off; p.bias_sig = pair_b_stride;
     p.bias_mid = blob + c.bmid_off; p.bias_mid_sig = c.bmid_pair;
     p.vec = 1; p.tpw = 1;
-    {
-        static const int dbg = std::getenv("FASTSVC_DBG") ? std::atoi(std::getenv("FASTSVC_DBG")) : 0;
-        p.dbg = dbg;
-    }
+    p.dbg = env().dbg;
     auto launch = [&](const ConvParams& q, const ConvLaunch& Lq) {
         return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, stream);
     };
-    struct Cand { int NW, WM, WN; };
     std::vector<Cand> cands;
     static const int shapes[][3] = {{6, 2, 2}, {4, 2, 2}, {3, 1, 4}, {2, 1, 4}};
     const int np = act_2b ? 1 : 2;
@@ -1918,111 +2076,67 @@ hipError_t run_chain(const PackedConv& a, const PackedConv& c, const float* blob
         if (!conv_hx_shape(p.mode, c.MW, sh[0], sh[1], sh[2]) || c.ngroups != sh[1]) continue;
         const int NT = 16 * sh[0] * sh[2];
         const size_t lds = (size_t)2 * np * (NT + 16 + 8 + 4) * 64 + (size_t)c.nch32 * np * (NT + 16) * 64 + 4096;
-        if (lds <= 160 * 1024) cands.push_back(Cand{sh[0], sh[1], sh[2]});
+        if (lds <= 160 * 1024) cands.push_back(Cand{sh[0], sh[1], sh[2], 3});
     }
     if (cands.empty()) return hipSuccess;
     char key[96];
     std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
     bool have = false, fused = true;
     Cand best = cands[0];
-    if (g_tune.plan) {
-        std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        auto it = tuned_find(g_tune.plan->tuned, key);
-        if (it != g_tune.plan->tuned.end()) {
-            if (it->second.algo != 3 && chain_env != 2) { have = true; fused = false; }      // FASTSVC_CHAIN=2: fused regardless (A/B)
-            for (const Cand& cd : cands)
-                if (it->second.algo == 3 && cd.NW == it->second.NW && cd.WM == it->second.WM && cd.WN == it->second.WN &&
-                    it->second.tpw >= 1 && it->second.tpw <= 64) { best = cd; p.tpw = it->second.tpw; have = true; }
-        }
-    }
-    if (!have && g_tune.tuning && g_tune.plan) {
-        static const int tpws[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 20, 24};
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return hipErrorUnknown;
-        float best_ms = 1e30f;
-        ConvParams q = p;
-        for (const Cand& cd : cands) {
-            const long ntx = (p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN);
-            for (int tpw : tpws) {
-                q.tpw = tpw;
-                ConvLaunch Lq{c.MW, cd.NW, cd.WM, cd.WN, nsig, 2};
-                hipError_t e = launch(q, Lq);
-                if (e != hipSuccess) return e;
-                hipEventRecord(e0, stream);
-                for (int r = 0; r < 3; ++r) { e = launch(q, Lq); if (e != hipSuccess) return e; }
-                hipEventRecord(e1, stream);
-                if (hipEventSynchronize(e1) != hipSuccess) return hipErrorUnknown;
-                float ms = 0.f;
-                hipEventElapsedTime(&ms, e0, e1);
-                ++g_tune.trials;
-                if (ms < best_ms) { best_ms = ms; best = cd; p.tpw = tpw; }
-                if (tpw >= ntx) break;
+    fastsvc_plan::Choice ch;
+    if (table_entry(*cc.plan, key, ch)) {
+        // (a shape only from an algorithm-3 entry)
+        if (ch.algo != 3 && env().chain != 2) { have = true; fused = false; }      // FASTSVC_CHAIN=2: fused regardless (A/B)
+        for (const Cand& cd : cands)
+            if (ch.algo == 3 && cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && ch.tpw >= 1 && ch.tpw <= 64) {
+                best = cd; p.tpw = ch.tpw; have = true;
             }
-        }
-        hipEventDestroy(e0); hipEventDestroy(e1);
+    }
+    auto ntx_of = [&](const Cand& cd) { return (long)(p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN); };
+    if (!have && cc.tuning) {
+        float best_ms = 1e30f;
+        ConvParams q = p;                                  // (these trials run with the launch's own flags)
+        ConvLaunch Lq{c.MW, 0, 0, 0, nsig, 2};
+        hipError_t e = time_candidates(cands, stream, cc.trials,
+                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; return ntx_of(cd); },
+                                       [&](int tpw) { q.tpw = tpw; return launch(q, Lq); }, best, p.tpw, best_ms);
+        if (e != hipSuccess) return e;
         fused = sep_ms <= 0.0 || best_ms / 3.0 < sep_ms;
-        std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        g_tune.plan->tuned[key] = fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, fused ? 3 : 0};
-        g_tune.plan->priors.clear();
+        table_record(*cc.plan, key, fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, fused ? 3 : 0});
         have = true;
     }
-    if (!have) {
-        // no table entry: the widest tile that exists, workgroups sized so that the grid fills the CUs about evenly
-        const int NT = 16 * best.NW * best.WN;
-        const long ntx = (p.T + NT - 1) / NT;
-        const long zb = (long)nsig * p.B;
-        double best_t = 1e30;
-        for (int tpw = 1; tpw <= 16; ++tpw) {
-            const long wgs = ((ntx + tpw - 1) / tpw) * zb;
-            const double t = (double)((wgs + 255) / 256) * (4.0 + tpw * c.nch32 * 2.0);
-            if (t < best_t * 0.999) { best_t = t; p.tpw = tpw; }
-        }
-    }
+    // no table entry: the widest tile that exists, workgroups sized so that the grid fills the CUs about evenly
+    if (!have) p.tpw = fill_tpw(ntx_of(best), (long)nsig * p.B, c.nch32, 16);
     if (!fused) return hipSuccess;
     ConvLaunch L{c.MW, best.NW, best.WM, best.WN, nsig, 2};
     done = true;
+    double flops = 0.0, bytes = 0.0;
+    char kname[48] = "";
     if (prof) {
         const double cols = (double)p.T * p.B * nsig;
         // (split input = the FiLM net: its first conv is block-diagonal over the two signals, half the dense count)
-        const double flops = 2.0 * 3.0 * ((p.xsplit ? 0.5 : 1.0) * a.cin * a.cout + (double)c.cin * c.cout + (in1 ? (double)a.cin : 0.0)) * cols;
+        flops = 2.0 * 3.0 * ((p.xsplit ? 0.5 : 1.0) * a.cin * a.cout + (double)c.cin * c.cout + (in1 ? (double)a.cin : 0.0)) * cols;
         double el = (in1 ? 1.0 : (double)a.cin) * p.T + (double)c.cout * p.T;
         if (p.res) el += (double)c.cout * p.T;
         if (p.r1x) el += (double)p.T;
-        const double bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig +
-                             4.0 * (double)(a.w_floats + a.b_floats + c.w_floats + c.b_floats) * nsig;
-        char kname[48];
+        bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(a.w_floats + a.b_floats + c.w_floats + c.b_floats) * nsig;
         std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,%d,%d,1,%s>", L.MW, L.NW, L.WM, L.WN, p.mode,
                       p.r1x ? 3 : p.res ? 2 : 1, prod_tag(stg));
-        hipError_t e = prof->begin(stream, layer, kname, flops, bytes);
-        if (e != hipSuccess) return e;
-        e = launch(p, L);
-        if (e != hipSuccess) return e;
-        return prof->end();
     }
-#ifdef FASTSVC_TIMELINE
-    {
-        const int NT = 16 * L.NW * L.WN;
-        const long ntx = (p.T + NT - 1) / NT;
-        const long wgs = ((ntx + p.tpw - 1) / p.tpw) * (long)nsig * p.B;
-        hipError_t e = hipSuccess;
-        if (timeline_launch(layer, p, wgs, p.nch32, L, stream, [&](const ConvParams& q) { return launch(q, L); }, e)) return e;
-    }
-#endif
-    return launch(p, L);
+    const long wgs = ((ntx_of(best) + p.tpw - 1) / p.tpw) * (long)nsig * p.B;
+    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() { return launch(p, L); }, &p, &L, wgs, p.nch32);
 }
 
 // The head of an up block as ONE launch (fastsvc_hx.hip, MODE_UPHEAD): p describes the input x (T = x_T = input
 // columns), y = xr, y2 = u1 with ss_out / st_out; `done` = false when this call has no fused variant (float32 storage,
 // rows a multiple of 4 long, table entry "<layer>|B|T" not 0).
-hipError_t run_uphead(const UpStage& u, const float* blob, ConvParams p, hipStream_t stream, Profiler* prof, const char* layer,
+hipError_t run_uphead(const CallCtx& cc, const UpStage& u, const float* blob, ConvParams p, hipStream_t stream, Profiler* prof, const char* layer,
                       bool& done) {
     done = false;
-    static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
-    static const int head_env = std::getenv("FASTSVC_UPHEAD") ? std::atoi(std::getenv("FASTSVC_UPHEAD")) : 1;
     const PackedConv& c = u.head;
-    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const int stg = cc.storage;
     const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
-    if (!hx_env || !head_env || g_exact_f32 || act_2b || !c.hxc_off[0] || (p.x_T & 3) || g_tune.tuning) return hipSuccess;
+    if (!env().hx || !env().uphead || cc.exact_f32 || act_2b || !c.hxc_off[0] || (p.x_T & 3) || cc.tuning) return hipSuccess;
     p.T = p.x_T;
     p.ldx = p.x_T; p.ldy = p.x_T * u.scale;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; if ((p.len_mul & 3) != 0) return hipSuccess; }
@@ -2048,32 +2162,25 @@ hipError_t run_uphead(const UpStage& u, const float* blob, ConvParams p, hipStre
     // run conv_first, two polyphase convs and two epilogues back to back while the separate launches spread over more
     // workgroups), so it only runs where the launch table says it won for this (B, T): algorithm 3; FASTSVC_UPHEAD=2
     // forces it (A/B).
-    bool fused = head_env == 2;
-    if (g_tune.plan) {
-        std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        auto it = tuned_find(g_tune.plan->tuned, key);
-        if (it != g_tune.plan->tuned.end()) {
-            fused = it->second.algo == 3 || (head_env == 2 && it->second.algo != 0);
-            if (it->second.algo == 0) fused = false;                     // table says: separate launches
-            if (it->second.tpw >= 1 && it->second.tpw <= 64) p.tpw = it->second.tpw;
-        }
+    bool fused = env().uphead == 2;
+    fastsvc_plan::Choice ch;
+    if (table_entry(*cc.plan, key, ch)) {                            // (only algorithm and tpw count)
+        fused = ch.algo == 3 || (env().uphead == 2 && ch.algo != 0);
+        if (ch.algo == 0) fused = false;                                 // table says: separate launches
+        if (ch.tpw >= 1 && ch.tpw <= 64) p.tpw = ch.tpw;
     }
     if (!fused) return hipSuccess;
     done = true;
+    double flops = 0.0, bytes = 0.0;
+    char kname[48] = "";
     if (prof) {
         const double cin = u.Cin, C = u.C, Ti = (double)p.x_T, To = Ti * u.scale;
-        const double flops = (2.0 * 3.0 * cin * C * Ti + 2.0 * 2.0 * 3.0 * C * C * To) * p.B;
-        const double bytes = 4.0 * (cin * Ti + 4.0 * C * To) * p.B +
-                             4.0 * (double)(u.first.w_floats + u.res.w_floats + u.up.w_floats + 3 * u.res.b_floats);
-        char kname[48];
+        flops = (2.0 * 3.0 * cin * C * Ti + 2.0 * 2.0 * 3.0 * C * C * To) * p.B;
+        bytes = 4.0 * (cin * Ti + 4.0 * C * To) * p.B +
+                4.0 * (double)(u.first.w_floats + u.res.w_floats + u.up.w_floats + 3 * u.res.b_floats);
         std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,8,4,%d,x3>", L.MW, L.NW, L.WM, L.WN, u.scale);
-        hipError_t e = prof->begin(stream, layer, kname, flops, bytes);
-        if (e != hipSuccess) return e;
-        e = launch_conv_hx(p, L, stream);
-        if (e != hipSuccess) return e;
-        return prof->end();
     }
-    return launch_conv_hx(p, L, stream);
+    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() { return launch_conv_hx(p, L, stream); });
 }
 
 // The middle conv of an up block (d = 3) with the block's stretched residual conv folded into its accumulator
@@ -2082,18 +2189,16 @@ hipError_t run_uphead(const UpStage& u, const float* blob, ConvParams p, hipStre
 // d = 3 conv's launch WITHOUT its residual operand, plus x2 / x2_b / x2_T / s2 / amax_x2 / bnd_x2.
 // what: 0 = only answer whether this call would run fused (`done`), 1 = launch, 2 = tuning pass: time the fused shapes
 // against `sep_ms` (the two separate launches) and record the winner under "<layer>|B|T" (algorithm 3 fused, 0 separate).
-hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_t stream, Profiler* prof, const char* layer,
+hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams p, hipStream_t stream, Profiler* prof, const char* layer,
                    int what, double sep_ms, bool& done) {
     done = false;
-    static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
-    static const int x_env = std::getenv("FASTSVC_D3X") ? std::atoi(std::getenv("FASTSVC_D3X")) : 1;     // 0: never, 2: wherever it exists (A/B)
     const PackedConv& c = u.d3;
-    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const int stg = cc.storage;
     const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
     const int prec = stg;                   // fragment set = storage
     p.ldx = p.x_T; p.ldy = p.T; p.ldx2 = p.x2_T;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; p.x2len_mul = p.x2_T / p.frames_ld; }
-    if (!hx_env || !x_env || g_exact_f32 || p.no_hx || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T || (long)p.x2_T * p.s2 != p.T ||
+    if (!env().hx || !env().d3x || cc.exact_f32 || p.no_hx || !c.hxc_off[prec] || (p.T & 3) || p.x_T != p.T || (long)p.x2_T * p.s2 != p.T ||
         (p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)) || !conv_hx_x2_ok(c.MW, c.nch32, p.s2) || c.dil > 28 ||
         (act_2b && !conv_hx_x2_rows_ok(p)))
         return hipSuccess;
@@ -2105,134 +2210,85 @@ hipError_t run_d3x(const UpStage& u, const float* blob, ConvParams p, hipStream_
     p.bias = blob + c.b_off; p.bias_sig = 0; p.bias2 = blob + c.b2_off; p.bias2_sig = 0;
     p.res = nullptr;
     p.vec = 1; p.tpw = 1; p.xs = 0; p.ps = 0;
-    {
-        static const int stagger = std::getenv("FASTSVC_STAGGER") ? std::atoi(std::getenv("FASTSVC_STAGGER")) : 2;
-        p.stagger = stagger;
-        static const int dbg = std::getenv("FASTSVC_DBG") ? std::atoi(std::getenv("FASTSVC_DBG")) : 0;
-        p.dbg = dbg;
-    }
+    p.stagger = env().stagger; p.dbg = env().dbg;
     auto launch = [&](const ConvParams& q, const ConvLaunch& Lq) {
         return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, stream);
     };
-    struct Cand { int NW, WM, WN; };
     std::vector<Cand> cands;
     static const int shapes[][3] = {{4, 2, 2}, {2, 1, 4}, {3, 1, 4}, {2, 2, 2}};      // (FiLM-affine epilogue: MW * NW <= 12)
     for (const auto& sh : shapes)
         if (conv_hx_shape(MODE_DIRECT, c.MW, sh[0], sh[1], sh[2]) && c.ngroups % sh[1] == 0 && sh[0] * c.MW <= 12)
-            cands.push_back(Cand{sh[0], sh[1], sh[2]});
+            cands.push_back(Cand{sh[0], sh[1], sh[2], 3});
     if (cands.empty()) return hipSuccess;
     char key[96];
     std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
     bool have = false, fused = true;
     Cand best = cands[0];
-    if (g_tune.plan) {
-        std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        auto it = tuned_find(g_tune.plan->tuned, key);
-        if (it != g_tune.plan->tuned.end()) {
-            if (it->second.algo != 3 && x_env != 2) { have = true; fused = false; }
-            for (const Cand& cd : cands)
-                if (cd.NW == it->second.NW && cd.WM == it->second.WM && cd.WN == it->second.WN &&
-                    it->second.tpw >= 1 && it->second.tpw <= 64) { best = cd; p.tpw = it->second.tpw; have = true; }
-        }
+    fastsvc_plan::Choice ch;
+    if (table_entry(*cc.plan, key, ch)) {
+        // (the shape whatever the entry's algorithm says)
+        if (ch.algo != 3 && env().d3x != 2) { have = true; fused = false; }
+        for (const Cand& cd : cands)
+            if (cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && ch.tpw >= 1 && ch.tpw <= 64) { best = cd; p.tpw = ch.tpw; have = true; }
     }
+    auto ntx_of = [&](const Cand& cd) { return (long)(p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN); };
     if (what == 2) {
-        if (have || !g_tune.tuning || !g_tune.plan) return hipSuccess;
-        static const int tpws[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 20, 24};
-        struct EventPair {                                 // (destroyed on every way out of the timing loop: ADVICE r5)
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
-        } ev;
-        if (hipEventCreate(&ev.e0) != hipSuccess || hipEventCreate(&ev.e1) != hipSuccess) return hipErrorUnknown;
+        if (have || !cc.tuning) return hipSuccess;
         float best_ms = 1e30f;
         ConvParams q = p;
         q.flags &= ~F_STATS;                               // (the trial launches do not accumulate InstanceNorm sums)
-        for (const Cand& cd : cands) {
-            const long ntx = (p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN);
-            for (int tpw : tpws) {
-                q.tpw = tpw;
-                ConvLaunch Lq{c.MW, cd.NW, cd.WM, cd.WN, 1, 2};
-                hipError_t e = launch(q, Lq);
-                if (e != hipSuccess) return e;
-                hipEventRecord(ev.e0, stream);
-                for (int r = 0; r < 3; ++r) { e = launch(q, Lq); if (e != hipSuccess) return e; }
-                hipEventRecord(ev.e1, stream);
-                if (hipEventSynchronize(ev.e1) != hipSuccess) return hipErrorUnknown;
-                float ms = 0.f;
-                hipEventElapsedTime(&ms, ev.e0, ev.e1);
-                ++g_tune.trials;
-                if (ms < best_ms) { best_ms = ms; best = cd; p.tpw = tpw; }
-                if (tpw >= ntx) break;
-            }
-        }
+        ConvLaunch Lq{c.MW, 0, 0, 0, 1, 2};
+        hipError_t e = time_candidates(cands, stream, cc.trials,
+                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; return ntx_of(cd); },
+                                       [&](int tpw) { q.tpw = tpw; return launch(q, Lq); }, best, p.tpw, best_ms);
+        if (e != hipSuccess) return e;
         // (sep_ms times the two separate launches back to back on ONE stream; in production the residual conv runs on the side
         // stream under up_stretch, so this comparison favours the fused launch by at most the residual conv's own time - the
         // fused launch also saves that tensor's write and read, which the whole-forward timing of tools/tune_shapes.py sees)
         fused = sep_ms <= 0.0 || best_ms / 3.0 < sep_ms;
-        std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-        g_tune.plan->tuned[key] = fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, fused ? 3 : 0};
-        g_tune.plan->priors.clear();
+        table_record(*cc.plan, key, fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, fused ? 3 : 0});
         return hipSuccess;
     }
     if (!have) {
-        if (g_tune.tuning) return hipSuccess;              // (a tuning pass runs the separate launches, then times this one)
+        if (cc.tuning) return hipSuccess;              // (a tuning pass runs the separate launches, then times this one)
         // no table entry: the nearest entry of this layer, else the first shape; workgroups sized so that the grid
         // fills the CUs about evenly
-        if (g_tune.plan) {
+        {
             fastsvc_plan::Choice pr{0, 0, 0, 0, -1};
-            std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-            if (g_tune.plan->prior_for(layer, p.B, p.T, act_2b, pr)) {
-                if (pr.algo != 3 && x_env != 2) fused = false;
+            std::lock_guard<std::mutex> lock(cc.plan->tune_mu);
+            if (cc.plan->prior_for(layer, p.B, p.T, act_2b, pr)) {
+                if (pr.algo != 3 && env().d3x != 2) fused = false;
                 for (const Cand& cd : cands) if (cd.NW == pr.NW && cd.WM == pr.WM && cd.WN == pr.WN) best = cd;
             }
         }
-        const int NT = 16 * best.NW * best.WN;
-        const long ntx = (p.T + NT - 1) / NT;
-        const long gy = c.ngroups / best.WM;
-        double best_t = 1e30;
-        for (int tpw = 1; tpw <= 24; ++tpw) {
-            const long wgs = ((ntx + tpw - 1) / tpw) * gy * p.B;
-            const double t = (double)((wgs + 255) / 256) * (4.0 + tpw * c.nch32 * 2.0);
-            if (t < best_t * 0.999) { best_t = t; p.tpw = tpw; }
-        }
+        p.tpw = fill_tpw(ntx_of(best), (long)(c.ngroups / best.WM) * p.B, c.nch32, 24);
     }
     if (!fused) return hipSuccess;
     done = true;
     if (what == 0) return hipSuccess;
     ConvLaunch L{c.MW, best.NW, best.WM, best.WN, 1, 2};
+    double flops = 0.0, bytes = 0.0;
+    char kname[48] = "";
     if (prof) {
         const double cols = (double)p.T * p.B;
-        const double flops = 2.0 * 2.0 * 3.0 * c.cin * c.cout * cols;      // both convs at the OUTPUT rate, as the reference runs them
+        flops = 2.0 * 2.0 * 3.0 * c.cin * c.cout * cols;      // both convs at the OUTPUT rate, as the reference runs them
         const double el = (double)c.cin * p.T + (double)c.cin * p.x2_T + 4.0 * c.cout * p.T;   // u1, a | xmid, u2, scale, shift
-        const double bytes = (act_2b ? 2.0 : 4.0) * el * p.B + 4.0 * 2.0 * (double)(c.w_floats + c.b_floats);
-        char kname[48];
+        bytes = (act_2b ? 2.0 : 4.0) * el * p.B + 4.0 * 2.0 * (double)(c.w_floats + c.b_floats);
         std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,0,4,%d,%s>", L.MW, L.NW, L.WM, L.WN, p.s2, prod_tag(stg));
-        hipError_t e = prof->begin(stream, layer, kname, flops, bytes);
-        if (e != hipSuccess) return e;
-        e = launch(p, L);
-        if (e != hipSuccess) return e;
-        return prof->end();
     }
-#ifdef FASTSVC_TIMELINE
-    {
-        const int NT = 16 * L.NW * L.WN;
-        const long ntx = (p.T + NT - 1) / NT;
-        const long wgs = ((ntx + p.tpw - 1) / p.tpw) * (long)(c.ngroups / L.WM) * p.B;
-        hipError_t e = hipSuccess;
-        if (timeline_launch(layer, p, wgs, 2 * p.nch32, L, stream, [&](const ConvParams& q) { return launch(q, L); }, e)) return e;
-    }
-#endif
-    return launch(p, L);
+    const long wgs = ((ntx_of(best) + p.tpw - 1) / p.tpw) * (long)(c.ngroups / L.WM) * p.B;
+    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() { return launch(p, L); }, &p, &L, wgs, 2 * p.nch32);
 }
 
 // Stage 0 of the conditioning nets as ONE launch (fastsvc_cond.hip): raw signals -> ss.0 and the compact h_0[..., ::s_1].
 // `done` = false when this call has no such variant (the caller runs the separate launches).
-hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float* sig, long sig_stride, int B, long T, int F,
+hipError_t run_cond_stage0(const CallCtx& cc, const float* blob, const float* sig, long sig_stride, int B, long T, int F,
                            const int* lengths, float* ss, float* hd, const float* amax_in, float* amax_hd, hipStream_t stream,
                            Profiler* prof, bool& done) {
     done = false;
-    static const int tpw_env = std::getenv("FASTSVC_COND_TPW") ? std::atoi(std::getenv("FASTSVC_COND_TPW")) : 0;
+    const fastsvc_plan& P = *cc.plan;
     // (float32 storage needs the measured maxima of the raw signals: not with FASTSVC_NO_AMAX_SCAN)
-    if (!cond_stage_whole(P, 0, F) || g_exact_f32 || (P.storage == 0 && (!amax_in || !amax_hd))) return hipSuccess;
+    if (!cond_stage_whole(P, 0, F) || cc.exact_f32 || (P.storage == 0 && (!amax_in || !amax_hd))) return hipSuccess;
     const DownStage& d = P.down[0];
     const DownStage& d1 = P.down[1];
     const int prec = P.storage;             // fragment set = storage
@@ -2260,30 +2316,24 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
     q.ss = ss; q.ss_b = 2L * d.C * T;
     q.hd = hd; q.hd_ld = (int)(T / d1.scale); q.hd_s = d1.scale;
     q.hd_b = (long)d.C * q.hd_ld; q.hd_sig = (long)B * q.hd_b;
-    // tiles per workgroup: the grid runs in whole rounds of the 2 x 256 resident workgroups, at most ~32 tiles each
-    // (a workgroup's start - 24 KB of weight fragments per wave, zeroed tiles - costs about two tiles)
     // short tiles where the long ones would leave CUs without a workgroup (a batch below one round of them)
-    const long slots_all = P.storage != 0 ? 512 : 256;
-    static const int small_env = std::getenv("FASTSVC_COND_SMALL") ? std::atoi(std::getenv("FASTSVC_COND_SMALL")) : -1;
+    const long slots_all = P.storage != 0 ? 512 : 256;     // workgroups resident at a time (LDS: two per CU in 2-byte storage, one in float32)
     {
         const int NTb = cond_stage0_tile_columns(0);
-        q.small = small_env >= 0 ? small_env : (((T + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
+        q.small = env().cond_small >= 0 ? env().cond_small : (((T + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
     }
     // The layer pipeline (cond_stage0_pipe_kernel; q.small = 2, tpw = chunks per workgroup) where a workgroup gets a long
     // run of chunks - its fill costs 5 + 8 / N steps -: one or two rounds of the 256 resident workgroups (one per CU).
     // FASTSVC_COND_PIPE = 0: never, 2: always (tests, A/B); a launch-table entry "cond.0|B|T[|b]" with algorithm 4
     // (phase kernel) / 5 (pipeline) decides for one batch shape.
-    static const int pipe_env = std::getenv("FASTSVC_COND_PIPE") ? std::atoi(std::getenv("FASTSVC_COND_PIPE")) : 1;
-    int pipe_mode = pipe_env;
+    int pipe_mode = env().cond_pipe;
     {
         char key[96];
         std::snprintf(key, sizeof(key), "cond.0|%d|%ld%s", B, (long)T, key_suffix(P.storage));
-        std::lock_guard<std::mutex> lock(P.tune_mu);
-        auto it = tuned_find(P.tuned, key);
-        if (it != P.tuned.end() && it->second.algo == 4) pipe_mode = 0;
-        if (it != P.tuned.end() && it->second.algo == 5) pipe_mode = 2;
+        fastsvc_plan::Choice ch;
+        if (table_entry(P, key, ch)) pipe_mode = ch.algo == 4 ? 0 : ch.algo == 5 ? 2 : pipe_mode;
     }
-    if (pipe_mode && small_env < 0) {
+    if (pipe_mode && env().cond_small < 0) {
         const int NTp = cond_stage0_tile_columns(P.storage != 0 ? 3 : 2);
         const long nchunks = (T + NTp - 1) / NTp;
         long kc = 0;
@@ -2294,25 +2344,15 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
         }
         // (the pipeline addresses both signals' hd rows of an utterance through ONE 32-bit-offset descriptor)
         const bool hd_fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * (P.storage != 0 ? 2L : 4L) < (1L << 31);
-        if (kc && hd_fits) { q.small = 2; q.tpw = (int)std::min<long>(tpw_env > 0 ? tpw_env : kc, 0xffff); }
+        if (kc && hd_fits) { q.small = 2; q.tpw = (int)std::min<long>(env().cond_tpw > 0 ? env().cond_tpw : kc, 0xffff); }
     }
     const int NT = q.small == 2 ? 0 : cond_stage0_tile_columns(q.small);
     const long ntx = q.small == 2 ? 0 : (T + NT - 1) / NT;
-    if (q.small == 2) {}
-    else if (tpw_env > 0) q.tpw = tpw_env;
-    else {
-        const long slots = P.storage != 0 ? 512 : 256, total = ntx * B;     // workgroups resident at a time (LDS: two per CU in 2-byte storage, one in float32)
-        const long rounds = std::max<long>(1, (total + slots * 32 - 1) / (slots * 32));
-        long tpw = std::max<long>(1, (total + slots * rounds - 1) / (slots * rounds));
-        // (per-utterance rounding: ceil(ntx / tpw) * B workgroups must not spill into one more round)
-        while (tpw < ntx && ((ntx + tpw - 1) / tpw) * B > slots * rounds) ++tpw;
-        q.tpw = (int)std::min<long>(tpw, ntx);
-    }
-    static const int dbg_env = std::getenv("FASTSVC_COND_DBG") ? std::atoi(std::getenv("FASTSVC_COND_DBG")) : 0;
-    q.tpw |= dbg_env << 16;
+    if (q.small != 2) q.tpw = env().cond_tpw > 0 ? env().cond_tpw : cond_tpw(ntx, B, slots_all);
+    q.tpw |= env().cond_dbg << 16;
     static unsigned long long* trace_buf = nullptr;
 #ifdef FASTSVC_COND_TRACE
-    static const bool trace_env = std::getenv("FASTSVC_COND_TRACE") != nullptr;
+    const bool trace_env = env().cond_trace;
 #else
     // (only a library whose kernels were built with -DFASTSVC_COND_TRACE writes stamps through amax_hd: in the product build the
     // kernel's atomicMax into that 4 KB buffer would run out of bounds for B >= 3)
@@ -2324,41 +2364,39 @@ hipError_t run_cond_stage0(const fastsvc_plan& P, const float* blob, const float
         q.amax_hd = reinterpret_cast<float*>(trace_buf);
     }
     done = true;
-    auto launch = [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage0)(q, stream); };
+    double flops = 0.0, bytes = 0.0;
+    std::string kname;
     if (prof) {
         const double C = d.C, cols = (double)T * B;
-        const double flops = (2.0 * (2.0 * (3.0 * C + C) + 2.0 * 3.0 * 3.0 * C * C) + 2.0 * 3.0 * 4.0 * C * C) * cols;
+        flops = (2.0 * (2.0 * (3.0 * C + C) + 2.0 * 3.0 * 3.0 * C * C) + 2.0 * 3.0 * 4.0 * C * C) * cols;
         const double ae = P.storage != 0 ? 2.0 : 4.0;
-        const double bytes = (2.0 * 4.0 + 2.0 * C * ae + 2.0 * C * ae / d1.scale) * cols +
-                             4.0 * (double)(2 * (d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
-        hipError_t e = prof->begin(stream, "cond.0", std::string(q.small == 2 ? "cond_stage0_pipe<" : "cond_stage0<") + prod_tag(P.storage) + ">", flops, bytes);
-        if (e != hipSuccess) return e;
-        e = launch();
-        if (e != hipSuccess) return e;
-        e = prof->end();
-        if (trace_env && trace_buf) {
-            unsigned long long h[4 * 64];
-            (void)hipStreamSynchronize(stream);
-            (void)hipMemcpy(h, trace_buf, sizeof(h), hipMemcpyDeviceToHost);
-            for (int w = 0; w < 4; ++w) {
-                std::fprintf(stderr, "[cond trace] wave %d:", w);
-                for (int i = 1; i < 64 && h[w * 64 + i]; ++i) std::fprintf(stderr, " %llu", h[w * 64 + i] - h[w * 64 + i - 1]);
-                std::fprintf(stderr, "\n");
-            }
-        }
-        return e;
+        bytes = (2.0 * 4.0 + 2.0 * C * ae + 2.0 * C * ae / d1.scale) * cols +
+                4.0 * (double)(2 * (d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
+        kname = std::string(q.small == 2 ? "cond_stage0_pipe<" : "cond_stage0<") + prod_tag(P.storage) + ">";
     }
-    return launch();
+    const hipError_t e = launch_tail(prof, stream, "cond.0", kname.c_str(), q.tpw & 0xffff, q.small, flops, bytes,
+                                     [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage0)(q, stream); });
+    if (e == hipSuccess && prof && trace_env && trace_buf) {
+        unsigned long long h[4 * 64];
+        (void)hipStreamSynchronize(stream);
+        (void)hipMemcpy(h, trace_buf, sizeof(h), hipMemcpyDeviceToHost);
+        for (int w = 0; w < 4; ++w) {
+            std::fprintf(stderr, "[cond trace] wave %d:", w);
+            for (int i = 1; i < 64 && h[w * 64 + i]; ++i) std::fprintf(stderr, " %llu", h[w * 64 + i] - h[w * 64 + i - 1]);
+            std::fprintf(stderr, "\n");
+        }
+    }
+    return e;
 }
 
 // Stage 1 of the conditioning nets (C = 48) as ONE launch (fastsvc_cond.hip): the compact decimated output of stage 0 ->
 // ss.1 and the compact h_1[..., ::s_2].  `done` = false when this call has no such variant.
-hipError_t run_cond_stage1(const fastsvc_plan& P, const float* blob, const float* x, int B, long T1, int F, const int* lengths,
+hipError_t run_cond_stage1(const CallCtx& cc, const float* blob, const float* x, int B, long T1, int F, const int* lengths,
                            float* ss, float* hd, const float* amax_in, float* amax_hd, hipStream_t stream, Profiler* prof,
                            bool& done) {
     done = false;
-    static const int tpw_env = std::getenv("FASTSVC_COND1_TPW") ? std::atoi(std::getenv("FASTSVC_COND1_TPW")) : 0;
-    if (!cond_stage_whole(P, 1, F) || g_exact_f32 || (P.storage == 0 && (!amax_in || !amax_hd))) return hipSuccess;
+    const fastsvc_plan& P = *cc.plan;
+    if (!cond_stage_whole(P, 1, F) || cc.exact_f32 || (P.storage == 0 && (!amax_in || !amax_hd))) return hipSuccess;
     const DownStage& d = P.down[1];
     const DownStage& d2 = P.down[2];
     const int prec = P.storage;             // fragment set = storage
@@ -2388,24 +2426,20 @@ hipError_t run_cond_stage1(const fastsvc_plan& P, const float* blob, const float
     q.hd_b = (long)d.C * q.hd_ld; q.hd_sig = (long)B * q.hd_b;
     // short tiles where the long ones would leave CUs without a workgroup (a batch below one round of them)
     const long slots_all = P.storage != 0 ? 512 : 256;
-    static const int small_env = std::getenv("FASTSVC_COND_SMALL") ? std::atoi(std::getenv("FASTSVC_COND_SMALL")) : -1;
     {
         const int NTb = cond_stage1_tile_columns(0);
-        q.small = small_env >= 0 ? small_env : (((T1 + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
+        q.small = env().cond_small >= 0 ? env().cond_small : (((T1 + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
     }
     // the layer pipeline (cond_stage1_pipe_kernel, 2-byte storage only; q.small = 2, tpw = 32-column chunks per workgroup):
     // its fill is 11 steps, so only for long runs; "cond.1|B|T1|b" ("|h") in the launch table forces either (algorithm 4 / 5)
-    static const int pipe_env = std::getenv("FASTSVC_COND_PIPE") ? std::atoi(std::getenv("FASTSVC_COND_PIPE")) : 1;
-    int pipe_mode = P.storage != 0 ? pipe_env : 0;
+    int pipe_mode = P.storage != 0 ? env().cond_pipe : 0;
     if (P.storage != 0) {
         char key[96];
         std::snprintf(key, sizeof(key), "cond.1|%d|%ld%s", B, (long)T1, key_suffix(P.storage));
-        std::lock_guard<std::mutex> lock(P.tune_mu);
-        auto it = tuned_find(P.tuned, key);
-        if (it != P.tuned.end() && it->second.algo == 4) pipe_mode = 0;
-        if (it != P.tuned.end() && it->second.algo == 5) pipe_mode = 2;
+        fastsvc_plan::Choice ch;
+        if (table_entry(P, key, ch)) pipe_mode = ch.algo == 4 ? 0 : ch.algo == 5 ? 2 : pipe_mode;
     }
-    if (pipe_mode && small_env < 0) {
+    if (pipe_mode && env().cond_small < 0) {
         const int NTp = cond_stage1_tile_columns(2);
         const long nchunks = (T1 + NTp - 1) / NTp;
         long kc = 0;
@@ -2415,51 +2449,40 @@ hipError_t run_cond_stage1(const fastsvc_plan& P, const float* blob, const float
             if (k >= 16 || pipe_mode == 2) kc = k;          // (8 x 600 frames, 19 chunks each: 58 vs 94 us for the phase kernel)
         }
         const bool fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * 2L < (1L << 31) && (long)d.Cin * T1 * 2L < (1L << 31);
-        if (kc && fits) { q.small = 2; q.tpw = (int)std::min<long>(tpw_env > 0 ? tpw_env : kc, 0xffff); }
+        if (kc && fits) { q.small = 2; q.tpw = (int)std::min<long>(env().cond1_tpw > 0 ? env().cond1_tpw : kc, 0xffff); }
     }
     const int NT = q.small == 2 ? 0 : cond_stage1_tile_columns(q.small);
     const long ntx = q.small == 2 ? 0 : (T1 + NT - 1) / NT;
-    if (q.small == 2) {}
-    else if (tpw_env > 0) q.tpw = tpw_env;
-    else {
-        const long slots = P.storage != 0 ? 512 : 256, total = ntx * B;
-        const long rounds = std::max<long>(1, (total + slots * 32 - 1) / (slots * 32));
-        long tpw = std::max<long>(1, (total + slots * rounds - 1) / (slots * rounds));
-        while (tpw < ntx && ((ntx + tpw - 1) / tpw) * B > slots * rounds) ++tpw;
-        q.tpw = (int)std::min<long>(tpw, ntx);
-    }
+    if (q.small != 2) q.tpw = env().cond1_tpw > 0 ? env().cond1_tpw : cond_tpw(ntx, B, slots_all);
     done = true;
-    auto launch = [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage1)(q, stream); };
+    double flops = 0.0, bytes = 0.0;
+    std::string kname;
     if (prof) {
         const double C = d.C, Ci = d.Cin, cols = (double)T1 * B;
-        const double flops = (2.0 * (2.0 * (3.0 * Ci * C + Ci * C) + 2.0 * 3.0 * 3.0 * C * C) + 2.0 * 3.0 * 4.0 * C * C) * cols;
+        flops = (2.0 * (2.0 * (3.0 * Ci * C + Ci * C) + 2.0 * 3.0 * 3.0 * C * C) + 2.0 * 3.0 * 4.0 * C * C) * cols;
         const double ae = P.storage != 0 ? 2.0 : 4.0;
-        const double bytes = (2.0 * Ci * ae + 2.0 * C * ae + 2.0 * C * ae / d2.scale) * cols +
-                             4.0 * (double)(2 * (d.rc1[0].w_floats + d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
-        hipError_t e = prof->begin(stream, "cond.1", std::string(q.small == 2 ? "cond_stage1_pipe<" : "cond_stage1<") + prod_tag(P.storage) + ">", flops, bytes);
-        if (e != hipSuccess) return e;
-        e = launch();
-        if (e != hipSuccess) return e;
-        return prof->end();
+        bytes = (2.0 * Ci * ae + 2.0 * C * ae + 2.0 * C * ae / d2.scale) * cols +
+                4.0 * (double)(2 * (d.rc1[0].w_floats + d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
+        kname = std::string(q.small == 2 ? "cond_stage1_pipe<" : "cond_stage1<") + prod_tag(P.storage) + ">";
     }
-    return launch();
+    return launch_tail(prof, stream, "cond.1", kname.c_str(), q.tpw & 0xffff, q.small, flops, bytes,
+                       [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage1)(q, stream); });
 }
 
-hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int nsig, long pair_w_stride,
-                    long pair_b_stride, hipStream_t stream, Profiler* prof,
-                    const char* layer) {
+// last_fused: whether the launch also computed conv_last (ConvParams::last_w accepted)
+hipError_t run_conv(CallCtx& cc, const PackedConv& c, const float* blob, ConvParams p, int nsig, long pair_w_stride,
+                    long pair_b_stride, hipStream_t stream, Profiler* prof, const char* layer, bool* last_fused = nullptr) {
     p.CIN = c.cin; p.KC = c.KC; p.nchunks = c.nchunks;
     p.w = blob + c.w_off; p.w_sig = pair_w_stride;
-    const int stg = g_tune.plan ? g_tune.plan->storage : 0;
+    const int stg = cc.storage;
     const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
     auto launch = [&](const ConvParams& q, const ConvLaunch& Lq, hipStream_t st) {
         if (Lq.pipe == 3) return FASTSVC_BY_STORAGE(stg, launch_conv_wx)(q, Lq, st);
         if (Lq.pipe == 2) return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, st);
         return FASTSVC_BY_STORAGE(stg, launch_conv)(q, Lq, st);
     };
-    static const bool no_poly = std::getenv("FASTSVC_NO_POLY") != nullptr;   // A/B switch
     const long T_out = p.T;                                  // output columns (accounting below)
-    if (p.mode == MODE_STRETCH && c.poly && !no_poly && c.dil == 1 && (long)p.x_T * p.s == p.T) {
+    if (p.mode == MODE_STRETCH && c.poly && !env().no_poly && c.dil == 1 && (long)p.x_T * p.s == p.T) {
         // Stretch2d + conv at the INPUT rate (polyphase): tiles walk the input columns
         ConvParams q = p;
         q.mode = MODE_POLY; q.T = p.x_T; q.w = blob + c.wp_off;
@@ -2478,10 +2501,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
     p.Q = c.Q; p.ngroups = c.ngroups; p.COUT = c.cout;
     p.ntaps = c.ntaps; p.dil = c.dil;
     p.vec = (p.T % 4 == 0) ? 1 : 0;
-    {
-        static const int dbg = std::getenv("FASTSVC_DBG") ? std::atoi(std::getenv("FASTSVC_DBG")) : 0;
-        p.dbg = dbg;
-    }
+    p.dbg = env().dbg;
     const int halo = c.ntaps == 3 ? c.dil : 0;
     const long zb = (long)nsig * p.B;
     ConvLaunch L{c.MW, 4, 1, 4, nsig, 0};
@@ -2497,8 +2517,6 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
             const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
             epi_kind = aff ? 4 : ((p.mode == MODE_STRETCH || poly) ? 1 : p.r1x ? 3 : p.res ? 2 : 1);
         }
-        // algo 0: as launched, 1: Winograd (MW of the layer), 2: Winograd MW = 2, 3: half-precision MFMA (fastsvc_hx.hip)
-        struct Cand { int NW, WM, WN, algo; };
         auto is_wino = [](int algo) { return algo == 1 || algo == 2; };
         std::vector<Cand> cands;
         if (poly) {
@@ -2515,8 +2533,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
             cands.swap(keep);
         }
         // Winograd F(2,3) variants of the same launch (fastsvc_kernels.h, MODE_WINO)
-        static const int wino_env = std::getenv("FASTSVC_WINO") ? std::atoi(std::getenv("FASTSVC_WINO")) : -1;
-        const bool wino_ok = c.wino && wino_env != 0 && p.mode == MODE_DIRECT && (!p.r1x || c.MW == 2) &&
+        const bool wino_ok = c.wino && env().wino != 0 && p.mode == MODE_DIRECT && (!p.r1x || c.MW == 2) &&
                              !(p.flags & (F_STATS | F_AFF_OUT | F_PRE_AFFINE));
         if (wino_ok) {
             const size_t nd = cands.size();
@@ -2531,7 +2548,6 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         }
         // Half-precision MFMA variants (split-half f16 products in float32 storage, bf16 products in bfloat16
         // storage): FASTSVC_HX=0 switches them off (A/B), they need rows that are a multiple of 4 long
-        static const int hx_env = std::getenv("FASTSVC_HX") ? std::atoi(std::getenv("FASTSVC_HX")) : 1;
         const bool hx_mode = (p.mode == MODE_DIRECT && p.x_T == p.T) || (p.mode == MODE_POLY && c.hxp_off[0]) ||
                              (p.mode == MODE_DEC2 && (p.x_T & 3) == 0);
         // ragged batch whose rows run at the frame rate or twice it (len_mul 1 or 2): an utterance's own row length
@@ -2540,7 +2556,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         const bool ragged_tail = p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0);
         const bool hx_tail_ok = !ragged_tail || ((p.ldx & 3) == 0 && (p.ldy & 3) == 0 &&
                                                  conv_hx_tail_ok(p.mode, c.MW, epi_kind, poly ? p.s : 1));
-        const bool hx_ok = hx_env != 0 && !p.no_hx && !g_exact_f32 && c.hx && hx_mode && c.ntaps == 3 && (p.T & 3) == 0 &&
+        const bool hx_ok = env().hx != 0 && !p.no_hx && !cc.exact_f32 && c.hx && hx_mode && c.ntaps == 3 && (p.T & 3) == 0 &&
                            c.dil <= 28 && !(p.flags & F_PRE_AFFINE) && hx_tail_ok;
         if (hx_ok) {
             static const int shapes[][3] = {{8, 4, 1}, {4, 4, 1}, {6, 2, 2}, {4, 2, 2}, {2, 2, 2}, {3, 1, 4}, {2, 1, 4}};
@@ -2552,10 +2568,9 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         // The wide-layer kernel (fastsvc_wx.hip, algorithm 6): every wave multiplies, weights through LDS.  Direct launches of
         // the 48-channel-group layers (C >= 96) in bfloat16 storage with a plain / residual / FiLM-affine epilogue.
         // FASTSVC_WX = 0: off, 2: wherever it exists (A/B, tests), else by the launch table / tuning
-        static const int wx_env = std::getenv("FASTSVC_WX") ? std::atoi(std::getenv("FASTSVC_WX")) : 1;
         ConvParams pw = p;
         pw.nch32 = c.nch32;                              // (what geometry() sets for the candidate)
-        const bool wx_ok = hx_ok && wx_env != 0 && act_2b && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
+        const bool wx_ok = hx_ok && env().wx != 0 && act_2b && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
                            conv_wx_supported(pw);
         bool wx_have = false;                            // ... and the layer has a shape of it
         if (wx_ok) {
@@ -2566,7 +2581,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
                     wx_have = true;
                 }
         }
-        const bool wx_force = wx_env == 2 && wx_have;
+        const bool wx_force = env().wx == 2 && wx_have;
         if (p.last_w) {
             // conv_last rides on the half-precision instances with one workgroup row of channel groups; it saves a
             // launch and a write + read of the block's output, more than any shape of the other family wins back:
@@ -2596,9 +2611,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
                 q.whx = blob + (p.mode == MODE_POLY ? c.hxp_off[prec] : c.hx_off[prec]); q.whx_sig = c.hx_pair[prec]; q.nch32 = c.nch32;
                 const size_t inv_off = p.mode == MODE_POLY ? c.hxp_inv_off : c.hx_inv_off;
                 q.whx_inv = (prec == 0 && inv_off) ? blob + inv_off : nullptr; q.whx_inv_sig = c.hx_inv_pair;
-                static const int stagger = std::getenv("FASTSVC_STAGGER") ? std::atoi(std::getenv("FASTSVC_STAGGER")) : 2;
-                // (conv_wx: start delay between the workgroups of an XCD, in 64-cycle steps per K chunk - an eighth of a unit)
-                q.stagger = stagger;
+                q.stagger = env().stagger;
                 q.xs = 0; q.ps = 0;
             } else if (cd.algo >= 1) {
                 const int NTo = 32 * cd.NW * cd.WN, D = c.dil;
@@ -2620,58 +2633,37 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
         bool have = false;
         Cand best = cands[0];
-        if (g_tune.plan) {
-            std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-            auto it = tuned_find(g_tune.plan->tuned, key);
-            if (it != g_tune.plan->tuned.end()) {
-                // a loaded table may be stale: only shapes this launch is compiled for are taken
-                for (const Cand& cd : cands)
-                    if (cd.NW == it->second.NW && cd.WM == it->second.WM && cd.WN == it->second.WN &&
-                        cd.algo == it->second.algo && it->second.tpw >= 1 && it->second.tpw <= 64 &&
-                        !(hx_env == 2 && hx_ok && cd.algo != 3 && cd.algo != 6) &&   // FASTSVC_HX=2: older tables do not hold it back
-                        !(wx_force && cd.algo != 6)) {
-                        best = cd; p.tpw = it->second.tpw;
-                        have = true;
-                    }
-            }
+        fastsvc_plan::Choice ch;
+        if (table_entry(*cc.plan, key, ch)) {
+            // a loaded table may be stale: only shapes this launch is compiled for are taken, algorithm included
+            for (const Cand& cd : cands)
+                if (cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && cd.algo == ch.algo && ch.tpw >= 1 && ch.tpw <= 64 &&
+                    !(env().hx == 2 && hx_ok && cd.algo != 3 && cd.algo != 6) &&   // FASTSVC_HX=2: older tables do not hold it back
+                    !(wx_force && cd.algo != 6)) {
+                    best = cd; p.tpw = ch.tpw;
+                    have = true;
+                }
         }
-        if (!have && g_tune.tuning && g_tune.plan) {
+        if (!have && cc.tuning) {
             // time every (shape, tiles-per-workgroup) on the device; InstanceNorm sums are not
             // accumulated by the trial launches (the real launch below does that once)
-            // (fine steps matter: the winner is often the count that fills the last round of workgroups best)
-            static const int tpws[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 20, 24};
-            hipEvent_t e0, e1;
-            if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return hipErrorUnknown;
+            std::vector<Cand> trial;
+            for (const Cand& cd : cands)
+                if (!(wx_force && cd.algo != 6)) trial.push_back(cd);     // FASTSVC_WX=2: only the wide-layer kernel's shapes
             float best_ms = 1e30f;
             ConvParams q = p;
-            q.flags &= ~F_STATS;
-            for (const Cand& cd : cands) {
-                const int NT = (is_wino(cd.algo) ? 32 : 16) * cd.NW * cd.WN;
-                const long ntx = (p.T + NT - 1) / NT;
-                if (wx_force && cd.algo != 6) continue;                   // FASTSVC_WX=2: only the wide-layer kernel's shapes
-                q = p; q.flags &= ~F_STATS;
-                geometry(cd, q);
-                for (int tpw : tpws) {
-                    q.tpw = tpw;
-                    ConvLaunch Lq{cd.algo == 2 ? 2 : c.MW, cd.NW, cd.WM, cd.WN, nsig, cd.algo == 6 ? 3 : cd.algo == 3 ? 2 : 1};
-                    hipError_t e = launch(q, Lq, stream);                 // warm
-                    if (e != hipSuccess && cd.algo == 6) break;           // (this shape does not fit the layer's LDS budget)
-                    if (e != hipSuccess) return e;
-                    hipEventRecord(e0, stream);
-                    for (int r = 0; r < 3; ++r) { e = launch(q, Lq, stream); if (e != hipSuccess) return e; }
-                    hipEventRecord(e1, stream);
-                    if (hipEventSynchronize(e1) != hipSuccess) return hipErrorUnknown;
-                    float ms = 0.f;
-                    hipEventElapsedTime(&ms, e0, e1);
-                    ++g_tune.trials;
-                    if (ms < best_ms) { best_ms = ms; best = cd; p.tpw = tpw; }
-                    if (tpw >= ntx) break;                                // larger tpw changes nothing
-                }
-            }
-            hipEventDestroy(e0); hipEventDestroy(e1);
-            std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-            g_tune.plan->tuned[key] = fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, best.algo};
-            g_tune.plan->priors.clear();
+            ConvLaunch Lq = L;
+            hipError_t e = time_candidates(trial, stream, cc.trials,
+                [&](const Cand& cd) {
+                    q = p; q.flags &= ~F_STATS;
+                    geometry(cd, q);
+                    Lq = ConvLaunch{cd.algo == 2 ? 2 : c.MW, cd.NW, cd.WM, cd.WN, nsig, cd.algo == 6 ? 3 : cd.algo == 3 ? 2 : 1};
+                    const int NT = (is_wino(cd.algo) ? 32 : 16) * cd.NW * cd.WN;
+                    return (long)(p.T + NT - 1) / NT;
+                },
+                [&](int tpw) { q.tpw = tpw; return launch(q, Lq, stream); }, best, p.tpw, best_ms);
+            if (e != hipSuccess) return e;
+            table_record(*cc.plan, key, fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, best.algo});
             have = true;
         }
         // No entry for this (B, T): the tile shape and algorithm of the table entry of this layer with the nearest
@@ -2679,16 +2671,15 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         // the size (the tuned tables agree on it across batch shapes far more often than the model below finds it:
         // tools/costmodel_gap.py) - and only the tiles per workgroup from the model.
         bool prior_pick = false;
-        static const int prior_env = std::getenv("FASTSVC_PRIOR") ? std::atoi(std::getenv("FASTSVC_PRIOR")) : 1;
-        if (!have && g_tune.plan && prior_env && !wx_force) {
+        if (!have && env().prior && !wx_force) {
             fastsvc_plan::Choice pr{0, 0, 0, 0, -1};
             {
-                std::lock_guard<std::mutex> lock(g_tune.plan->tune_mu);
-                auto it = g_tune.plan->priors.find(key);
-                if (it != g_tune.plan->priors.end()) pr = it->second;
+                std::lock_guard<std::mutex> lock(cc.plan->tune_mu);
+                auto it = cc.plan->priors.find(key);
+                if (it != cc.plan->priors.end()) pr = it->second;
                 else {
-                    if (!g_tune.plan->prior_for(layer, p.B, p.T, act_2b, pr)) pr.algo = -1;
-                    g_tune.plan->priors[key] = pr;
+                    if (!cc.plan->prior_for(layer, p.B, p.T, act_2b, pr)) pr.algo = -1;
+                    cc.plan->priors[key] = pr;
                 }
             }
             if (pr.algo >= 0)
@@ -2705,7 +2696,6 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         // start-up (launch, slot set-up, first window in flight) plus tpw * nchunks units, a unit
         // being bounded by the consumer wave's MFMA stream or by the producers' window traffic;
         // the grid runs in ceil(workgroups / resident slots) rounds.
-        static const double startup_us = std::getenv("FASTSVC_STARTUP_US") ? std::atof(std::getenv("FASTSVC_STARTUP_US")) : 4.0;
         double best_t = 1e30;
         for (const Cand& cd : cands) {
             // Without a table entry the model takes Winograd wherever the layer has it, the 32-channel
@@ -2713,7 +2703,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
             // and cfg2 (0.56 vs 0.62 ms, 2.24 vs 2.32 ms).  C = 24 layers (MW == 2) stay direct: their
             // Winograd variant loses to the scalar phase-plane staging.  FASTSVC_WINO = 0 / 1 / 2
             // forces direct / layer grouping / 32-channel grouping.
-            const int wino_pref = wino_env >= 0 ? wino_env : (c.MW == 2 ? 0 : 2);
+            const int wino_pref = env().wino >= 0 ? env().wino : (c.MW == 2 ? 0 : 2);
             if (cd.algo == 6) {
                 // no model of its own: taken by table / prior, or wherever it exists with FASTSVC_WX=2 (first shape that fits,
                 // one round of workgroups where the batch allows)
@@ -2745,7 +2735,7 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
                 for (int tpw = 1; tpw <= 24; ++tpw) {
                     const long wgs = ((ntx + tpw - 1) / tpw) * gy * zb;
                     const long rounds = (wgs + 255) / 256;
-                    const double t = rounds * (startup_us + tpw * c.nch32 * unit_us);
+                    const double t = rounds * (env().startup_us + tpw * c.nch32 * unit_us);
                     if (t < best_t * 0.999) { best_t = t; best = cd; p.tpw = tpw; }
                 }
                 continue;
@@ -2776,22 +2766,15 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
             for (int tpw = 1; tpw <= 16; ++tpw) {
                 const long wgs = ((ntx + tpw - 1) / tpw) * gy * zb;
                 const long rounds = (wgs + slots - 1) / slots;
-                const double t = rounds * (startup_us + tpw * c.nchunks * unit_us);
+                const double t = rounds * (env().startup_us + tpw * c.nchunks * unit_us);
                 if (t < best_t * 0.999) { best_t = t; best = cd; p.tpw = tpw; }
             }
         }
         }
         L.pipe = best.algo == 6 ? 3 : best.algo == 3 ? 2 : 1;
         L.NW = best.NW; L.WM = best.WM; L.WN = best.WN;
-        if (p.last_w) g_last_fused = true;                  // (the candidates were restricted to the instances that have it)
         if (best.algo == 2) L.MW = 2;
         geometry(best, p);
-        {
-            static const bool verbose = std::getenv("FASTSVC_VERBOSE_SHAPES") != nullptr;   // tuning aid
-            if (verbose && prof)
-                std::fprintf(stderr, "[fastsvc] %-20s mode %d  MW %d NW %d WM %d WN %d tpw %d\n", layer, p.mode,
-                             L.MW, L.NW, L.WM, L.WN, p.tpw);
-        }
     } else {
         p.last_w = nullptr;
         int NW = 4;
@@ -2800,11 +2783,14 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         const int W = 64 * NW + 2 * halo;
         p.xs = (W + 15) / 32 * 32 + 16;
     }
+    if (last_fused) *last_fused = p.last_w != nullptr;      // (the candidates were restricted to the instances that have it)
+    double flops_all = 0.0, bytes = 0.0;
+    char kname[48] = "";
     if (prof) {
         // algorithmic work of the layer as the reference defines it (3 taps at the OUTPUT rate for
         // the stretched convs, whichever way they are computed)
         const double cols = (double)T_out * p.B * nsig;
-        const double flops = 2.0 * (c.dec2 ? 4 : c.ntaps) * c.cin * c.cout * cols;    // DEC2: k=3 conv + 1x1
+        flops_all = 2.0 * (c.dec2 ? 4 : c.ntaps) * c.cin * c.cout * cols;    // DEC2: k=3 conv + 1x1
         double in_cols = (double)T_out;                     // source columns actually needed
         if (p.mode == MODE_STRETCH || poly) in_cols = (double)p.x_T;
         double el = (double)c.cin * in_cols;
@@ -2815,13 +2801,11 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         if (p.res) el += (double)c.cout * T_out;
         if (p.r1x) el += (double)T_out;
         if (p.flags & (F_STATS | F_AFF_OUT)) el += 2.0 * c.cout * T_out;
-        double bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(c.w_floats + c.b_floats) * nsig;
-        double flops_all = flops;
+        bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(c.w_floats + c.b_floats) * nsig;
         if (p.last_w) {                                   // + conv_last: C -> 1, float32 waveform out (the C-channel tensor is not written: p.y is null)
             flops_all += 2.0 * c.cout * cols;
             bytes += 4.0 * cols;
         }
-        char kname[40];
         if (L.pipe == 3) {
             const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
             std::snprintf(kname, sizeof(kname), "conv_wx<%d,%d,%d,%d,%d,%s>", L.MW, L.NW, L.WM, L.WN, aff ? 4 : p.res ? 2 : 1, prod_tag(stg));
@@ -2846,23 +2830,13 @@ hipError_t run_conv(const PackedConv& c, const float* blob, ConvParams p, int ns
         }
         else
             std::snprintf(kname, sizeof(kname), "conv_mfma<%d,%d,1,4>", L.MW, L.NW);
-        hipError_t e = prof->begin(stream, layer, kname, flops_all, bytes);
-        if (e != hipSuccess) return e;
-        e = launch(p, L, stream);
-        if (e != hipSuccess) return e;
-        return prof->end();
     }
-    if (act_2b && !L.pipe) return hipErrorNotSupported;   // the scalar kernel exists for float32 storage only
-#ifdef FASTSVC_TIMELINE
-    if (L.pipe) {
-        const int NT = (p.mode == MODE_WINO ? 32 : 16) * L.NW * L.WN;
-        const long ntx = (p.T + NT - 1) / NT;
-        const long wgs = ((ntx + p.tpw - 1) / p.tpw) * ((p.ngroups + L.WM - 1) / L.WM) * zb;
-        hipError_t e = hipSuccess;
-        if (timeline_launch(layer, p, wgs, p.nchunks, L, stream, [&](const ConvParams& q) { return launch(q, L, stream); }, e)) return e;
-    }
-#endif
-    return launch(p, L, stream);
+    else if (act_2b && !L.pipe) return hipErrorNotSupported;   // the scalar kernel exists for float32 storage only
+    // (per-wave stamps of the diagnostic build: the pipelined launches only)
+    const int NT = (p.mode == MODE_WINO ? 32 : 16) * L.NW * L.WN;
+    const long wgs = (((p.T + NT - 1) / NT + p.tpw - 1) / p.tpw) * ((p.ngroups + L.WM - 1) / L.WM) * zb;
+    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops_all, bytes, [&]() { return launch(p, L, stream); },
+                       L.pipe ? &p : nullptr, &L, wgs, p.nchunks);
 }
 
 }  // namespace
@@ -2910,9 +2884,8 @@ int fastsvc_forward_launch_count(const fastsvc_plan* plan, int32_t with_spk_emb)
     // c1 + 1x1 launch, else 4) + FiLM (2 per stage) + up blocks (6 each) + conv_last.
     // An upper bound: where a call's shapes and the launch table allow it, a down stage's c2 -> c3 pair is one
     // launch (MODE_CHAIN) and stage 0 is one launch altogether (MODE_CHAIN1).
-    static const bool no_dec2 = std::getenv("FASTSVC_NO_DEC2") != nullptr;
     int down = 3;
-    for (int k = 1; k < n; ++k) down += (plan->down[k].rc1[0].dec2 && !no_dec2) ? 3 : 4;
+    for (int k = 1; k < n; ++k) down += (plan->down[k].rc1[0].dec2 && !env().no_dec2) ? 3 : 4;
     return (with_spk_emb ? 1 : 0) + (plan->storage == 0 ? 1 : 0) + down + 2 * n + 6 * n + 1;     // (+ the input scan of float32 storage)
 }
 
@@ -2923,7 +2896,7 @@ int fastsvc_forward_launch_count(const fastsvc_plan* plan, int32_t with_spk_emb)
             return fail(FASTSVC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));    \
     } while (0)
 
-static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
+static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_blob,
                     const float* ppg, const float* sine, const float* lft, const float* spk_emb,
                     float* out, int32_t B, int32_t F, const int32_t* lengths,
                     void* workspace, size_t workspace_bytes, void* stream_, Profiler* prof) {
@@ -2944,8 +2917,9 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     const Workspace ws = layout_workspace(P, B, F);
     if (workspace_bytes < ws.bytes) return fail(FASTSVC_E_WORKSPACE, "workspace too small");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    g_tune.plan = plan;
-    g_exact_f32 = plan->storage == 0 && F <= 4;
+    cc.plan = plan;
+    cc.storage = plan->storage;
+    cc.exact_f32 = plan->storage == 0 && F <= 4;
     // Scheduling: the FiLM nets of stages 0..n-2 + the speaker projections can run on a lowest-priority
     // helper stream (mask bit 1; bit 0: the 1x1 / stretch residual convs, an experiment that never paid).  With the
     // fused launches that is worth ~2 % at cfg2 and nothing at cfg3 / cfg1 - and only where a fork + join through the
@@ -2953,18 +2927,16 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     // created after an RCCL communicator the same schedule ran cfg2 in 2.54 ms instead of 1.43.  Default: bit 1 from
     // ~1.5e5 samples per call where the context says it pays, one stream otherwise; FASTSVC_STREAMS=<mask> forces a
     // mask (0: one stream), FASTSVC_SERIAL one stream.
-    static const bool serial = std::getenv("FASTSVC_SERIAL") != nullptr;
-    static const int streams_env = std::getenv("FASTSVC_STREAMS") ? std::atoi(std::getenv("FASTSVC_STREAMS")) : -1;
     int64_t hop_all = 1;
     for (int i = 0; i < plan->n; ++i) hop_all *= plan->cfg.upsampling_scales[i];
-    int streams_mask = serial ? 0 : streams_env >= 0 ? (streams_env & 3) : ((int64_t)B * F * hop_all >= 150000 ? 2 : 0);
+    int streams_mask = env().serial ? 0 : env().streams >= 0 ? (env().streams & 3) : ((int64_t)B * F * hop_all >= 150000 ? 2 : 0);
     // per-launch profiling and autotuning run on ONE stream so that every kernel is timed alone
-    ExecCtx* ctx = (streams_mask == 0 || g_tune.tuning || prof) ? nullptr : exec_ctx_for(stream);
+    ExecCtx* ctx = (streams_mask == 0 || cc.tuning || prof) ? nullptr : exec_ctx_for(stream);
     std::unique_lock<std::mutex> ctx_lock;
     if (ctx) {
         ctx_lock = std::unique_lock<std::mutex>(ctx->busy);
         ensure_measured(stream, ctx);
-        if (streams_env < 0 && !ctx->pays) { ctx_lock.unlock(); ctx_lock = std::unique_lock<std::mutex>(); ctx = nullptr; streams_mask = 0; }
+        if (env().streams < 0 && !ctx->pays) { ctx_lock.unlock(); ctx_lock = std::unique_lock<std::mutex>(); ctx = nullptr; streams_mask = 0; }
     }
     hipStream_t s_film = (ctx && (streams_mask & 2)) ? ctx->aux[0] : stream;      // FiLM nets of stages 0..n-2
     hipStream_t s_side = (ctx && (streams_mask & 1)) ? ctx->aux[1] : stream;      // 1x1 / stretch residual convs
@@ -3015,7 +2987,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     const std::ptrdiff_t sig_bytes = reinterpret_cast<const char*>(sine) - reinterpret_cast<const char*>(lft);
     if (sig_bytes % (std::ptrdiff_t)sizeof(float) != 0) return fail(FASTSVC_E_INVALID, "sine / lft must be 4-byte aligned");
     const long sig_stride = (long)(sig_bytes / (std::ptrdiff_t)sizeof(float));
-    const bool no_scan = amax_scan_disabled();                     // A/B timing only: inputs then count as unit-scale
+    const bool no_scan = env().no_amax_scan;                     // A/B timing only: inputs then count as unit-scale
     if (P.storage == 0 && !no_scan) {
         // float32 storage: largest magnitudes of the inputs (scales of the split-binary16 staging) and zeroed amax
         // rows of the intermediates - ONE small launch, first thing on the caller's stream (everything else is
@@ -3095,21 +3067,20 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
                 p.x = hprev; p.x_sig = (long)B * Cprev * Tprev; p.x_b = (long)Cprev * Tprev; p.x_T = (int)Tprev;
                 p.mode = MODE_DECIMATE; p.s = hprev_compact ? 1 : d.scale;
                 p.amax_in = am_prev;
-                static const bool no_dec2 = std::getenv("FASTSVC_NO_DEC2") != nullptr;      // A/B switch
-                if (d.rc1[0].dec2 && !no_dec2) {
+                if (d.rc1[0].dec2 && !env().no_dec2) {
                     // both convs of the decimated input in one launch: c1 -> y, r -> y2
                     p.mode = MODE_DEC2;
                     p.y = c1; p.y_sig = tsig; p.y_b = tb;
                     p.y2 = r; p.y2_sig = tsig; p.y2_b = tb;
-                    HIP_TRY(run_conv(d.rc1[0], blob, p, 2, (long)(d.rc1[1].w_off - d.rc1[0].w_off),
+                    HIP_TRY(run_conv(cc, d.rc1[0], blob, p, 2, (long)(d.rc1[1].w_off - d.rc1[0].w_off),
                                      (long)(d.rc1[1].b_off - d.rc1[0].b_off), stream, pr, ("down." + s + ".c1_res1x1").c_str()));
                 } else {
                 p.y = r; p.y_sig = tsig; p.y_b = tb;
                 HIP_TRY(order_after(stream, s_side));                  // h_{k-1} is ready
-                HIP_TRY(run_conv(d.r[0], blob, p, 2, (long)(d.r[1].w_off - d.r[0].w_off), (long)(d.r[1].b_off - d.r[0].b_off), s_side, pr, ("down." + s + ".res1x1").c_str()));
+                HIP_TRY(run_conv(cc, d.r[0], blob, p, 2, (long)(d.r[1].w_off - d.r[0].w_off), (long)(d.r[1].b_off - d.r[0].b_off), s_side, pr, ("down." + s + ".res1x1").c_str()));
                 p.flags = F_PRE_LRELU;                                 // c1 = conv3_d1(lrelu(h_{k-1}[::s]))
                 p.y = c1;
-                HIP_TRY(run_conv(d.c1[0], blob, p, 2, (long)(d.c1[1].w_off - d.c1[0].w_off), (long)(d.c1[1].b_off - d.c1[0].b_off), stream, pr, ("down." + s + ".c1").c_str()));
+                HIP_TRY(run_conv(cc, d.c1[0], blob, p, 2, (long)(d.c1[1].w_off - d.c1[0].w_off), (long)(d.c1[1].b_off - d.c1[0].b_off), stream, pr, ("down." + s + ".c1").c_str()));
                 }
             }
             {
@@ -3133,31 +3104,21 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
                 const long b3 = (long)(d.c3[1].b_off - d.c3[0].b_off);
                 auto separate = [&](Profiler* pr) -> int {
                     p.y = c2; p.y_sig = tsig; p.y_b = tb;
-                    HIP_TRY(run_conv(d.c2[0], blob, p, 2, (long)(d.c2[1].w_off - d.c2[0].w_off), (long)(d.c2[1].b_off - d.c2[0].b_off), stream, pr, n2.c_str()));
+                    HIP_TRY(run_conv(cc, d.c2[0], blob, p, 2, (long)(d.c2[1].w_off - d.c2[0].w_off), (long)(d.c2[1].b_off - d.c2[0].b_off), stream, pr, n2.c_str()));
                     ConvParams q = p3;
                     q.x = c2; q.bnd_path[1] = blob + d.c2[0].bnd_off; q.bnd_sig[1] = d.c2[0].bnd_pair;   // ... and c2 behind it
-                    HIP_TRY(run_conv(d.c3[0], blob, q, 2, (long)(d.c3[1].w_off - d.c3[0].w_off), b3, stream, pr, n3.c_str()));
+                    HIP_TRY(run_conv(cc, d.c3[0], blob, q, 2, (long)(d.c3[1].w_off - d.c3[0].w_off), b3, stream, pr, n3.c_str()));
                     return FASTSVC_OK;
                 };
                 // one launch for the pair where the stage has the fused variant (c2 then never reaches memory);
                 // a tuning pass times it against the two launches and the table keeps the winner
                 double sep_ms = 0.0;
-                if (g_tune.tuning && !pr && d.c3[0].hxc_off[0]) {
-                    int rc = separate(nullptr);                        // tunes the two launches' own shapes
+                if (cc.tuning && !pr && d.c3[0].hxc_off[0]) {
+                    const int rc = time_separate(stream, true, [&]() { return separate(nullptr); }, sep_ms);
                     if (rc != FASTSVC_OK) return rc;
-                    hipEvent_t e0, e1;
-                    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(FASTSVC_E_HIP, "hipEventCreate");
-                    hipEventRecord(e0, stream);
-                    for (int r = 0; r < 3 && rc == FASTSVC_OK; ++r) rc = separate(nullptr);
-                    hipEventRecord(e1, stream);
-                    float ms = 0.f;
-                    if (rc == FASTSVC_OK && hipEventSynchronize(e1) == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
-                    hipEventDestroy(e0); hipEventDestroy(e1);
-                    if (rc != FASTSVC_OK) return rc;
-                    sep_ms = ms / 3.0;
                 }
                 bool fused = false;
-                HIP_TRY(run_chain(d.c2[0], d.c3[0], blob, p3, 2, b3, stream, pr, n23.c_str(), sep_ms, fused));
+                HIP_TRY(run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, b3, stream, pr, n23.c_str(), sep_ms, fused));
                 if (!fused) { const int rc = separate(pr); if (rc != FASTSVC_OK) return rc; }
             }
             return FASTSVC_OK;
@@ -3166,7 +3127,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         // workspace: h_0 itself is then not materialised, stage 1 reads the compact decimated copy)
         if (k == 0 && P.compact) {
             bool whole = false;
-            HIP_TRY(run_cond_stage0(P, blob, sigbuf, sig_stride, B, T, F, lengths, buf("ss.0"), buf("down_hd.1"),
+            HIP_TRY(run_cond_stage0(cc, blob, sigbuf, sig_stride, B, T, F, lengths, buf("ss.0"), buf("down_hd.1"),
                                     (P.storage == 0 && !no_scan) ? amax_inb : nullptr, am("down_h.0"), stream, prof, whole));
             if (whole) {
                 hprev = buf("down_hd.1"); Cprev = d.C; Tprev = Tk / P.down[1].scale; hprev_compact = true;
@@ -3177,7 +3138,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         }
         if (k == 1 && P.compact && hprev_compact && n > 2) {
             bool whole = false;
-            HIP_TRY(run_cond_stage1(P, blob, hprev, B, Tk, F, lengths, buf("ss.1"), buf("down_hd.2"),
+            HIP_TRY(run_cond_stage1(cc, blob, hprev, B, Tk, F, lengths, buf("ss.1"), buf("down_hd.2"),
                                     P.storage == 0 ? am("down_h.0") : nullptr, am("down_h.1"), stream, prof, whole));
             if (whole) {
                 hprev = buf("down_hd.2"); Cprev = d.C; Tprev = Tk / P.down[2].scale; hprev_compact = true;
@@ -3200,21 +3161,11 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             if ((d.r_raw[1].b_off - d.r_raw[0].b_off) != (d.r_raw[1].w_off - d.r_raw[0].w_off))
                 return fail(FASTSVC_E_INVALID, "internal: rank-1 pair strides");
             double sep_ms = 0.0;
-            if (g_tune.tuning && !prof) {
-                int rc = stage_unfused(nullptr);                   // tunes that path's own launches
+            if (cc.tuning && !prof) {
+                const int rc = time_separate(stream, true, [&]() { return stage_unfused(nullptr); }, sep_ms);
                 if (rc != FASTSVC_OK) return rc;
-                hipEvent_t e0, e1;
-                if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(FASTSVC_E_HIP, "hipEventCreate");
-                hipEventRecord(e0, stream);
-                for (int r = 0; r < 3 && rc == FASTSVC_OK; ++r) rc = stage_unfused(nullptr);
-                hipEventRecord(e1, stream);
-                float ms = 0.f;
-                if (rc == FASTSVC_OK && hipEventSynchronize(e1) == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
-                hipEventDestroy(e0); hipEventDestroy(e1);
-                if (rc != FASTSVC_OK) return rc;
-                sep_ms = ms / 3.0;
             }
-            HIP_TRY(run_chain(d.c2[0], d.c3[0], blob, p3, 2, (long)(d.c3[1].b_off - d.c3[0].b_off), stream, prof,
+            HIP_TRY(run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, (long)(d.c3[1].b_off - d.c3[0].b_off), stream, prof,
                               "down.0.c123", sep_ms, stage_fused, d.c1_raw));
         }
         if (!stage_fused) { const int rc = stage_unfused(prof); if (rc != FASTSVC_OK) return rc; }
@@ -3232,14 +3183,14 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
                 p.flags = F_POST_LRELU;
                 p.y = u; p.y_sig = tb; p.y_b = 2 * tb;
                 p.amax_in = am_h;
-                HIP_TRY(run_conv(d.film[0], blob, p, 2, (long)(d.film[1].w_off - d.film[0].w_off), (long)(d.film[1].b_off - d.film[0].b_off), sf, pr, nconv.c_str()));
+                HIP_TRY(run_conv(cc, d.film[0], blob, p, 2, (long)(d.film[1].w_off - d.film[0].w_off), (long)(d.film[1].b_off - d.film[0].b_off), sf, pr, nconv.c_str()));
                 ConvParams q = base;                               // [scale ; shift] summed over both signals
                 q.x = u; q.x_sig = 0; q.x_b = 2 * tb; q.x_T = (int)Tk;
                 q.y = ssb; q.y_sig = 0; q.y_b = 2 * tb;
                 // u = [lrelu(conv_lft(h_lft)) ; lrelu(conv_sine(h_sine))]: the larger of the two halves' bounds
                 q.amax_in = am_h; q.amax_in_sig = 0; q.amax_in2 = B;
                 q.bnd_path[0] = blob + d.film[0].bnd_off; q.bnd_sig[0] = d.film[0].bnd_pair;
-                HIP_TRY(run_conv(d.heads, blob, q, 1, 0, 0, sf, pr, nheads.c_str()));
+                HIP_TRY(run_conv(cc, d.heads, blob, q, 1, 0, 0, sf, pr, nheads.c_str()));
                 return FASTSVC_OK;
             };
             // the whole FiLM net of the stage in one launch where it has the variant: the 2C-channel intermediate
@@ -3247,25 +3198,15 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             bool film_fused = false;
             if (d.filmc.hxc_off[0] && ((long)tsig + (long)d.C * Tk) * 4 < (1L << 31)) {
                 double sep_ms = 0.0;
-                if (g_tune.tuning && !prof) {
-                    int rc = film_separate(nullptr);
+                if (cc.tuning && !prof) {
+                    const int rc = time_separate(sf, true, [&]() { return film_separate(nullptr); }, sep_ms);
                     if (rc != FASTSVC_OK) return rc;
-                    hipEvent_t e0, e1;
-                    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(FASTSVC_E_HIP, "hipEventCreate");
-                    hipEventRecord(e0, sf);
-                    for (int r = 0; r < 3 && rc == FASTSVC_OK; ++r) rc = film_separate(nullptr);
-                    hipEventRecord(e1, sf);
-                    float ms = 0.f;
-                    if (rc == FASTSVC_OK && hipEventSynchronize(e1) == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
-                    hipEventDestroy(e0); hipEventDestroy(e1);
-                    if (rc != FASTSVC_OK) return rc;
-                    sep_ms = ms / 3.0;
                 }
                 ConvParams p3 = base;
                 p3.x = h; p3.x_sig = tsig; p3.x_b = tb; p3.x_T = (int)Tk; p3.xsplit = d.C;
                 p3.y = ssb; p3.y_sig = 0; p3.y_b = 2 * tb;
                 p3.amax_in = am_h; p3.amax_in2 = B;                 // channels [lft ; sine]: the larger of the two chains' maxima
-                HIP_TRY(run_chain(d.filmc, d.filmc, blob, p3, 1, 0, sf, prof, nchain.c_str(), sep_ms, film_fused));
+                HIP_TRY(run_chain(cc, d.filmc, d.filmc, blob, p3, 1, 0, sf, prof, nchain.c_str(), sep_ms, film_fused));
             }
             if (!film_fused) { const int rc = film_separate(prof); if (rc != FASTSVC_OK) return rc; }
             if (sf != stream && ctx) {
@@ -3289,12 +3230,10 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
     bool last_done = false;
     bool last_fusable = true;
     {
-        static const bool no_fuse = std::getenv("FASTSVC_NO_FUSE_LAST") != nullptr;     // A/B switch
         char key[96];
         std::snprintf(key, sizeof(key), "conv_last|%d|%ld%s", B, (long)T, key_suffix(P.storage));
-        std::lock_guard<std::mutex> lock(P.tune_mu);
-        auto it = tuned_find(P.tuned, key);
-        if (no_fuse || (it != P.tuned.end() && it->second.algo != 3)) last_fusable = false;
+        fastsvc_plan::Choice ch;
+        if (env().no_fuse_last || (table_entry(P, key, ch) && ch.algo != 3)) last_fusable = false;
     }
     for (int i = 0; i < n; ++i) {
         const UpStage& u = P.up[i];
@@ -3337,7 +3276,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             ph.flags = F_POST_LRELU | aff_out;
             ph.ss_out = ss; ph.ss_out_b = 2 * cb; ph.st_out = st;
             ph.amax_in = am_x;
-            HIP_TRY(run_uphead(u, blob, ph, stream, prof, ("up." + s + ".head").c_str(), head_fused));
+            HIP_TRY(run_uphead(cc, u, blob, ph, stream, prof, ("up." + s + ".head").c_str(), head_fused));
         }
         // xmid = conv_d3(lrelu(norm(u1))) + xr with xr computed INSIDE that launch from `a` (run_d3x) where the variant
         // exists and the launch table does not say otherwise: the residual conv's launch and the tensor xr then go
@@ -3352,14 +3291,14 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         pd3.amax_x2 = am_x; pd3.bnd_x2 = blob + u.first.bnd_off;   // |a| <= l1 |x| + bmax
         const std::string nd3x = "up." + s + ".d3x";
         bool d3_fused = false;
-        if (!head_fused) HIP_TRY(run_d3x(u, blob, pd3, stream, nullptr, nd3x.c_str(), 0, 0.0, d3_fused));
+        if (!head_fused) HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 0, 0.0, d3_fused));
         ConvParams p = base;
         if (!head_fused) {
         p = base;                                                  // a = conv_first(x)
         p.x = x; p.x_b = (long)Cx * Tin; p.x_T = (int)Tin;
         p.y = a; p.y_b = (long)u.C * Tin; p.T = (int)Tin;
         p.amax_in = am_x;
-        HIP_TRY(run_conv(u.first, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".conv_first").c_str()));
+        HIP_TRY(run_conv(cc, u.first, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".conv_first").c_str()));
 
         p = base;                                                  // xr = conv_res(stretch(a))
         p.x = a; p.x_b = (long)u.C * Tin; p.x_T = (int)Tin;
@@ -3368,13 +3307,13 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         p.amax_in = am_x; p.bnd_path[0] = blob + u.first.bnd_off;  // |a| <= l1 |x| + bmax  (xr is only ever a residual: not tracked)
         if (!d3_fused) {
         HIP_TRY(order_after(stream, s_side));                      // a is ready
-        HIP_TRY(run_conv(u.res, blob, p, 1, 0, 0, s_side, prof, ("up." + s + ".res_stretch").c_str()));
+        HIP_TRY(run_conv(cc, u.res, blob, p, 1, 0, 0, s_side, prof, ("up." + s + ".res_stretch").c_str()));
         }
 
         p.flags = F_PRE_LRELU | F_POST_LRELU | aff_out;            // u1 = aff(lrelu(conv_up(stretch(lrelu(a)))))
         p.y = nullptr; p.y2 = u1; p.y2_b = cb;
         p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st;
-        HIP_TRY(run_conv(u.up, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".up_stretch").c_str()));
+        HIP_TRY(run_conv(cc, u.up, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".up_stretch").c_str()));
         }
 
         // tiny batches: the sums the epilogue accumulated are replaced by exact ones (see stats_exact_kernel)
@@ -3383,7 +3322,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             // B x C one-wave workgroups that leave at once for the longer ones: not worth it on big batches, where a
             // decode harness's length buckets never put a 1-frame utterance anyway)
             const bool small_ragged = lengths && P.storage == 0 && F <= 64;
-            if (!spk || !(g_exact_f32 || small_ragged)) return hipSuccess;
+            if (!spk || !(cc.exact_f32 || small_ragged)) return hipSuccess;
             return launch_stats_exact(ut, stp, B, u.C, (int)Tout, lengths, (int)(Tout / F), 4, stream);
         };
         HIP_TRY(exact_stats(u1, st));
@@ -3401,15 +3340,15 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st + stn;
         if (d3_fused) {
             bool ran = false;
-            HIP_TRY(run_d3x(u, blob, pd3, stream, prof, nd3x.c_str(), 1, 0.0, ran));
+            HIP_TRY(run_d3x(cc, u, blob, pd3, stream, prof, nd3x.c_str(), 1, 0.0, ran));
             // (the route was decided by the query call in front of conv_first - the separate residual launch was skipped on its
             // word; a launch table that changed in between - another thread's load_tuned on this plan - must not leave xmid / u2
             // unwritten: ADVICE r5)
             if (!ran) return fail(FASTSVC_E_INVALID, "up." + s + ".d3x: the launch table changed between the route decision and the launch");
         } else {
         HIP_TRY(order_after(s_side, stream));                      // xr is ready
-        HIP_TRY(run_conv(u.d3, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d3").c_str()));
-        if (g_tune.tuning && !prof && !head_fused) {
+        HIP_TRY(run_conv(cc, u.d3, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d3").c_str()));
+        if (cc.tuning && !prof && !head_fused) {
             // tuning pass: the two separate launches again, timed, then the fused shapes against them
             ConvParams pr = base;
             pr.x = a; pr.x_b = (long)u.C * Tin; pr.x_T = (int)Tin;
@@ -3418,22 +3357,16 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             pr.amax_in = am_x; pr.bnd_path[0] = blob + u.first.bnd_off;
             ConvParams pq = p;
             pq.flags &= ~F_STATS;                                  // (the InstanceNorm sums are accumulated once)
-            hipEvent_t e0, e1;
-            if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(FASTSVC_E_HIP, "hipEventCreate");
-            hipEventRecord(e0, stream);
-            int rc = FASTSVC_OK;
-            for (int r = 0; r < 3 && rc == FASTSVC_OK; ++r) {
-                if (run_conv(u.res, blob, pr, 1, 0, 0, stream, nullptr, ("up." + s + ".res_stretch").c_str()) != hipSuccess ||
-                    run_conv(u.d3, blob, pq, 1, 0, 0, stream, nullptr, ("up." + s + ".d3").c_str()) != hipSuccess)
-                    rc = fail(FASTSVC_E_HIP, "timing the separate residual / d3 launches");
-            }
-            hipEventRecord(e1, stream);
-            float ms = 0.f;
-            if (rc == FASTSVC_OK && hipEventSynchronize(e1) == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
-            hipEventDestroy(e0); hipEventDestroy(e1);
+            double sep_ms = 0.0;
+            const int rc = time_separate(stream, false, [&]() {
+                if (run_conv(cc, u.res, blob, pr, 1, 0, 0, stream, nullptr, ("up." + s + ".res_stretch").c_str()) != hipSuccess ||
+                    run_conv(cc, u.d3, blob, pq, 1, 0, 0, stream, nullptr, ("up." + s + ".d3").c_str()) != hipSuccess)
+                    return fail(FASTSVC_E_HIP, "timing the separate residual / d3 launches");
+                return (int)FASTSVC_OK;
+            }, sep_ms);
             if (rc != FASTSVC_OK) return rc;
             bool dummy = false;
-            HIP_TRY(run_d3x(u, blob, pd3, stream, nullptr, nd3x.c_str(), 2, ms / 3.0, dummy));
+            HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 2, sep_ms, dummy));
         }
         }
         HIP_TRY(exact_stats(u2, st + stn));
@@ -3442,7 +3375,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
         p.y = nullptr; p.y2 = u3;
         p.st_out = st + 2 * stn;
         
-        HIP_TRY(run_conv(u.d9, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d9").c_str()));
+        HIP_TRY(run_conv(cc, u.d9, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d9").c_str()));
         HIP_TRY(exact_stats(u3, st + 2 * stn));
 
         p.x = u3; p.st_in = st + 2 * stn;                          // out = conv_d27(lrelu(norm(u3))) + xmid
@@ -3458,9 +3391,7 @@ static int forward_impl(const fastsvc_plan* plan, const void* dev_blob,
             p.last_y = out; p.last_y_b = (long)P.cfg.out_channels * T;
             if (lengths) HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * T, stream));   // ragged batch: zero padding of the waveform
         }
-        g_last_fused = false;
-        HIP_TRY(run_conv(u.d27, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d27").c_str()));
-        if (i == n - 1) last_done = g_last_fused;
+        HIP_TRY(run_conv(cc, u.d27, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d27").c_str(), &last_done));
 
         x = xo; Cx = u.C; Tin = Tout;
     }
@@ -3523,9 +3454,7 @@ int fastsvc_tuned_get(const fastsvc_plan* plan, int32_t index, char* key_out, in
 int fastsvc_tuned_set(const fastsvc_plan* plan, const char* key, const int32_t shape[5]) {
     if (!plan || !key || !shape) return fail(FASTSVC_E_INVALID, "null argument");
     if (std::strlen(key) >= 96) return fail(FASTSVC_E_INVALID, "key too long");
-    std::lock_guard<std::mutex> lock(plan->tune_mu);
-    plan->tuned[key] = fastsvc_plan::Choice{shape[0], shape[1], shape[2], shape[3], shape[4]};
-    plan->priors.clear();
+    table_record(*plan, key, fastsvc_plan::Choice{shape[0], shape[1], shape[2], shape[3], shape[4]});
     return FASTSVC_OK;
 }
 
@@ -3533,7 +3462,8 @@ int fastsvc_forward(const fastsvc_plan* plan, const void* dev_blob,
                     const float* ppg, const float* sine, const float* lft, const float* spk_emb,
                     float* out, int32_t B, int32_t F, const int32_t* lengths,
                     void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_impl(plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
+    CallCtx cc;
+    return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
                         workspace_bytes, stream, nullptr);
 }
 
@@ -3541,12 +3471,11 @@ int fastsvc_autotune(const fastsvc_plan* plan, const void* dev_blob,
                      const float* ppg, const float* sine, const float* lft, const float* spk_emb,
                      float* out, int32_t B, int32_t F,
                      void* workspace, size_t workspace_bytes, void* stream, int32_t* n_trials) {
-    g_tune.tuning = true;
-    g_tune.trials = 0;
-    const int rc = forward_impl(plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, nullptr, workspace,
+    CallCtx cc;
+    cc.tuning = true;
+    const int rc = forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, nullptr, workspace,
                                 workspace_bytes, stream, nullptr);
-    g_tune.tuning = false;
-    if (n_trials) *n_trials = g_tune.trials;
+    if (n_trials) *n_trials = cc.trials;
     if (rc != FASTSVC_OK) return rc;
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return FASTSVC_OK;
@@ -3560,7 +3489,8 @@ int fastsvc_forward_profile(const fastsvc_plan* plan, const void* dev_blob,
     if (!records || !n_records || max_records < 1) return fail(FASTSVC_E_INVALID, "null argument");
     Profiler prof;
     prof.stream = static_cast<hipStream_t>(stream);
-    const int rc = forward_impl(plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
+    CallCtx cc;
+    const int rc = forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
                                 workspace_bytes, stream, &prof);
     if (rc != FASTSVC_OK) return rc;
     HIP_TRY(prof.finish());
