@@ -290,6 +290,37 @@ int fastsvc_gather_time_major(const float* packed, int64_t packed_elems, const i
 int fastsvc_pcm16_pack(const float* y, const int32_t* lens, const int64_t* offsets, int16_t* dst, int64_t dst_elems,
                        int32_t B, int32_t width, void* stream);
 
+/* Training-batch assembly from a resident corpus (csrc/fastsvc_collate.hip) - what the reference's Collater.__call__
+ * (harana/bin/train_fastsvc.py:500-543) slices on the host, cut out of five packed float32 DEVICE buffers by one launch.
+ * Stored utterance u has n_frames[u] frames and starts at frame frame_off[u] of the store:
+ *   f0          elements [frame_off[u], + n_frames[u])                      (f0_elems floats)
+ *   ppg         time-major (n_frames[u], D) at element frame_off[u] * D     (ppg_elems floats; the dump's own layout)
+ *   wave, lft   n_frames[u] * hop samples at frame_off[u] * hop             (wave_elems floats each)
+ *   emb         (n_utts, S), or NULL (use_spk_emb False: emb_out is then not touched and may be NULL)
+ * Batch row b is the crop of utterance utt[b] that starts at frame start[b], ctx <= start[b] <= n_frames - frames - ctx
+ * (the closed end; the reference's np.random.randint draws from the half-open range).  With T = frames * hop:
+ *   y       (B, 1, T)                 wave[(frame_off + start) * hop, + T)
+ *   lft_out (B, 1, T)                 lft, the same samples
+ *   f0_out  (B, 1, frames)            f0[frame_off + start, + frames)
+ *   ppg_out (B, D, frames + 2 ctx)    ppg frames [start - ctx, start + frames + ctx), transposed to channel-major
+ *   emb_out (B, S)                    emb[utt[b], :]
+ * all device float32, contiguous; every value is copied bit for bit.  No alignment or % 4 requirement on anything:
+ * 16-byte requests are used where source and destination addresses allow (hop % 4 == 0, D % 4 == 0, T % 4 == 0 and
+ * blocks that start on 16-byte boundaries make that every request), 4-byte ones elsewhere.  No load touches a byte
+ * outside the crop's own source range - a crop may end at the last element of the store - and no store a byte outside
+ * the five outputs.  `frame_off`, `n_frames` (n_utts entries) and `utt`, `start` (B entries) are HOST arrays, read during
+ * the call (the rows' values travel in the kernel arguments).  Everything is checked on the host BEFORE anything is
+ * launched: null pointers, sizes out of range, utt[b] outside [0, n_utts), start[b] outside [ctx, n_frames - frames - ctx],
+ * an utterance whose block does not lie inside its buffers - FASTSVC_E_INVALID, with the row and the reason in
+ * fastsvc_last_error(); a failed launch is FASTSVC_E_HIP.  One launch per 64 rows (fastsvc_collate_launch_count(B)),
+ * asynchronous on `stream`. */
+int fastsvc_collate_launch_count(int32_t B);
+int fastsvc_collate_crops(const float* wave, const float* lft, int64_t wave_elems, const float* ppg, int64_t ppg_elems,
+                          const float* f0, int64_t f0_elems, const float* emb, int32_t n_utts,
+                          const int64_t* frame_off, const int32_t* n_frames, const int32_t* utt, const int32_t* start,
+                          float* y, float* lft_out, float* ppg_out, float* f0_out, float* emb_out,
+                          int32_t B, int32_t D, int32_t S, int32_t hop, int32_t frames, int32_t ctx, void* stream);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

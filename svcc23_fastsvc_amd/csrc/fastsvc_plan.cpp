@@ -903,6 +903,11 @@ int fetch_layer(const std::unordered_map<std::string, const fastsvc_tensor*>& sd
 
 }  // namespace
 
+// the other translation units' way to the text fastsvc_last_error() returns (fastsvc_collate.hip)
+namespace fastsvc {
+int set_last_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
+}
+
 // ==========================================================================================
 // C ABI
 // ==========================================================================================

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "fastsvc_stream_prepare", "fastsvc_stream_release", "fastsvc_split_half", "fastsvc_plan_set_workspace_mode",
     "fastsvc_loudness_frames", "fastsvc_loudness_scratch_bytes", "fastsvc_loudness_extract",
     "fastsvc_gather_padded", "fastsvc_gather_time_major", "fastsvc_pcm16_pack",
+    "fastsvc_collate_launch_count", "fastsvc_collate_crops",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -161,6 +162,11 @@ def load_library():
     lib.fastsvc_gather_time_major.restype = ctypes.c_int
     lib.fastsvc_pcm16_pack.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), vp, i64, i32, i32, vp]
     lib.fastsvc_pcm16_pack.restype = ctypes.c_int
+    lib.fastsvc_collate_launch_count.argtypes = [i32]
+    lib.fastsvc_collate_launch_count.restype = ctypes.c_int
+    lib.fastsvc_collate_crops.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                          ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp, vp] + [i32] * 6 + [vp]
+    lib.fastsvc_collate_crops.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -287,6 +293,70 @@ def pcm16_pack(y: torch.Tensor, lens: Sequence[int], offsets: Optional[Sequence[
         _check(lib, lib.fastsvc_pcm16_pack(ctypes.c_void_p(y.data_ptr()), ls, offs, ctypes.c_void_p(out.data_ptr()),
                                            out.numel(), B, width, ctypes.c_void_p(stream)), "fastsvc_pcm16_pack")
     return out
+
+
+def collate_launch_count(B: int) -> int:
+    """Launches one ``collate_crops`` of B rows enqueues: one per 64 rows."""
+    return int(load_library().fastsvc_collate_launch_count(int(B)))
+
+
+def collate_crops(wave: torch.Tensor, lft: torch.Tensor, ppg: torch.Tensor, f0: torch.Tensor, emb: Optional[torch.Tensor],
+                  frame_off: Sequence[int], n_frames: Sequence[int], utt: Sequence[int], start: Sequence[int],
+                  D: int, hop: int, frames: int, ctx: int = 0, out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """Cut a training batch out of a resident corpus: the reference Collater's slices (train_fastsvc.py:500-543), bit for
+    bit, by ONE HIP launch per 64 rows on the current stream (fastsvc_collate_crops, csrc/fastsvc_collate.hip).
+
+    ``wave``, ``lft``, ``ppg``, ``f0`` are the packed 1-D float32 device buffers of the store (utterance u: ``n_frames[u]``
+    frames from frame ``frame_off[u]``; ppg time-major (n, D), wave / lft ``hop`` samples per frame), ``emb`` (U, S) or None.
+    Row b is utterance ``utt[b]`` from frame ``start[b]``, ``ctx <= start[b] <= n_frames - frames - ctx``.  Returns
+    ``(y (B, 1, T), lft (B, 1, T), ppg (B, D, frames + 2 ctx), f0 (B, 1, frames), emb (B, S) or None)``; ``out``: the same
+    five, contiguous float32 tensors to write into (views of larger buffers are fine).  Anything out of range raises
+    ``ValueError`` before a launch; fails loudly off the GPU."""
+    lib = load_library()
+    for name, t in (("wave", wave), ("lft", lft), ("ppg", ppg), ("f0", f0)) + ((("emb", emb),) if emb is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"collate_crops needs GPU tensors (no CPU fallback); {name} is on " +
+                               str(getattr(t, "device", type(t))))
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != wave.device or t.dim() != (2 if name == "emb" else 1):
+            raise ValueError(f"{name} must be a contiguous float32 {'(U, S)' if name == 'emb' else '1-D'} tensor on {wave.device}")
+    if lft.numel() != wave.numel():
+        raise ValueError("wave and lft must hold the same number of samples")
+    B, U = len(utt), len(n_frames)
+    D, hop, frames, ctx = int(D), int(hop), int(frames), int(ctx)
+    if B == 0 or len(start) != B or U == 0 or len(frame_off) != U:
+        raise ValueError("collate_crops needs at least one row, one start per row and one offset per stored utterance")
+    if emb is not None and emb.shape[0] != U:
+        raise ValueError(f"emb must hold one row per stored utterance ({U}), got {tuple(emb.shape)}")
+    S = int(emb.shape[1]) if emb is not None else 0
+    T, W = frames * hop, frames + 2 * ctx
+    shapes = [(B, 1, T), (B, 1, T), (B, D, W), (B, 1, frames), (B, S)]
+    if out is None:
+        out = [None] * 5
+    outs = []
+    for i, shp in enumerate(shapes):
+        t = out[i] if i < len(out) else None
+        if i == 4 and emb is None:
+            outs.append(None)
+        elif t is None:
+            outs.append(torch.empty(shp, dtype=torch.float32, device=wave.device))
+        elif not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError("collate_crops needs GPU tensors (no CPU fallback) for out")
+        elif tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != wave.device:
+            raise ValueError(f"out[{i}] must be a contiguous float32 {shp} tensor on {wave.device}")
+        else:
+            outs.append(t)
+    # (a session hands in the ctypes arrays it made once: a corpus has thousands of entries, a batch a few dozen)
+    offs = frame_off if isinstance(frame_off, ctypes.Array) else (ctypes.c_int64 * U)(*[int(v) for v in frame_off])
+    nfr = n_frames if isinstance(n_frames, ctypes.Array) else (ctypes.c_int32 * U)(*[int(v) for v in n_frames])
+    us = (ctypes.c_int32 * B)(*[int(v) for v in utt])
+    st = (ctypes.c_int32 * B)(*[int(v) for v in start])
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    with torch.cuda.device(wave.device):
+        stream = torch.cuda.current_stream(wave.device).cuda_stream
+        _check(lib, lib.fastsvc_collate_crops(ptr(wave), ptr(lft), wave.numel(), ptr(ppg), ppg.numel(), ptr(f0), f0.numel(),
+                                              ptr(emb), U, offs, nfr, us, st, *[ptr(t) for t in outs],
+                                              B, D, S, hop, frames, ctx, ctypes.c_void_p(stream)), "fastsvc_collate_crops")
+    return tuple(outs)
 
 
 def _check(lib, rc: int, what: str):

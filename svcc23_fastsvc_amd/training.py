@@ -619,3 +619,32 @@ class TrainStep:
             self.sched_d.step()
         self.steps += 1
         return {k: float(v) for k, v in logd.items()} if log else {}
+
+    @torch.no_grad()
+    def eval_step(self, batch) -> Dict[str, float]:
+        """The reference trainer's `_eval_step` (train_fastsvc.py:266-311) on one batch of the `step` layout: both modules in
+        `.eval()` for the call (their previous modes are restored), no gradient, and - as in the reference - every term
+        whatever `discriminator_train_start_steps` says: `y_ = G(*x)`, the STFT loss, `adv = gen_adv(D(y_))`,
+        `gen = lambda_aux * (sc + mag) + lambda_adv * adv`, `real, fake = dis_adv(D(y_), D(y))`.  Returns the seven values
+        under `step`'s key names (the reference logs them as `eval/<name>`).  Parameters, gradients, optimizer and
+        scheduler state and `steps` are left as they are."""
+        x, y = batch
+        cfg = self.config
+        modes = [(m, m.training) for m in (self.generator, self.discriminator)]
+        try:
+            for m, _ in modes:
+                m.eval()
+            with self._autocast():
+                y_ = self.generator(*x)
+            sc, mag = self.stft(y_.float(), y.float())
+            with self._autocast(discriminator=True):
+                p_ = self.discriminator(y_)
+                adv = generator_adversarial_loss(p_)
+                real, fake = discriminator_adversarial_loss(p_, self.discriminator(y))
+            gen = (sc + mag) * cfg.get("lambda_aux", 1.0) + cfg["lambda_adv"] * adv.float()
+            logd = {"spectral_convergence_loss": sc, "log_stft_magnitude_loss": mag, "adversarial_loss": adv,
+                    "generator_loss": gen, "real_loss": real, "fake_loss": fake, "discriminator_loss": real.float() + fake.float()}
+            return {k: float(v) for k, v in logd.items()}
+        finally:
+            for m, was_training in modes:
+                m.train(was_training)
