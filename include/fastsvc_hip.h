@@ -290,6 +290,37 @@ int fastsvc_gather_time_major(const float* packed, int64_t packed_elems, const i
 int fastsvc_pcm16_pack(const float* y, const int32_t* lens, const int64_t* offsets, int16_t* dst, int64_t dst_elems,
                        int32_t B, int32_t width, void* stream);
 
+/* What the PCM-16 conversion hides, per row: the conversion writes a NaN as 0 and saturates everything beyond the int16
+ * range, so a packed buffer looks like audio whatever the waveform held.  One entry per row, 16 bytes. */
+typedef struct fastsvc_row_report {
+    int32_t nonfinite;   /* NaN / +-inf among the row's first lens[b] samples */
+    int32_t clipped;     /* finite samples whose PCM-16 value saturates: rint(double(y) * 32767.0) outside [-32768, 32767] */
+    float   max_abs;     /* largest |y| over the row's finite samples, 0 when there is none (exact: a maximum, not a sum) */
+    int32_t reserved;    /* written as 0 */
+} fastsvc_row_report;
+
+/* Checked PCM-16 packing: writes into dst exactly the bytes the unchecked packing writes, and touches exactly the same
+ * bytes, in the same single pass over y (the eight samples a lane converts are the eight it reports on), and fills
+ * report[b] for every row.  `report` is a DEVICE array of B entries that every call OVERWRITES: one memset on `stream`,
+ * then the launches; calls never accumulate.  Samples at or beyond lens[b] are never read into the report.  Blocks reduce
+ * in registers and LDS and issue integer atomics only (count sums, a maximum over the bit pattern of |y|), so the report
+ * is bit-reproducible.  Arguments, checks and error codes are those of the unchecked packing, and a null `report` is
+ * FASTSVC_E_INVALID; on an argument error nothing is enqueued.  One launch per 64 rows (row b's report at report + b),
+ * asynchronous on `stream`.
+ *
+ * What a report tells about float16 activation storage (the RANGE CONTRACT above): an overflow that REACHES the waveform
+ * is seen - an infinity survives LeakyReLU, turns a convolution's sum into inf / NaN even through a zero weight and
+ * poisons InstanceNorm's mean, so it arrives as inf / NaN samples and `nonfinite` counts them.  Not seen: precision lost
+ * below 2^-14, and a tensor past the ceiling whose infinity is never read.  The contract itself is unchanged; this
+ * detects its observable violations (decode.DecodeSession(checked=True) acts on them). */
+int fastsvc_pcm16_pack_checked(const float* y, const int32_t* lens, const int64_t* offsets, int16_t* dst, int64_t dst_elems,
+                               fastsvc_row_report* report, int32_t B, int32_t width, void* stream);
+
+/* The same reduction without a destination (for waveforms that stay float32): report[b] of row b of y (B, width) over its
+ * first lens[b] samples.  `lens` a HOST array, `report` a DEVICE array of B entries, overwritten as above. */
+int fastsvc_output_check(const float* y, const int32_t* lens, fastsvc_row_report* report,
+                         int32_t B, int32_t width, void* stream);
+
 /* Training-batch assembly from a resident corpus (csrc/fastsvc_collate.hip) - what the reference's Collater.__call__
  * (harana/bin/train_fastsvc.py:500-543) slices on the host, cut out of five packed float32 DEVICE buffers by one launch.
  * Stored utterance u has n_frames[u] frames and starts at frame frame_off[u] of the store:

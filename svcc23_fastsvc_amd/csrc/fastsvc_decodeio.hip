@@ -3,7 +3,9 @@
 //   gather_time_major   the dump's own layout, utterance b a contiguous time-major (len_b, C) float32 block of ONE packed
 //                       device buffer, into the zero-padded channel-major (B, C, width) batch the forward reads;
 //   pcm16_pack          the forward's (B, width) float32 waveforms into ONE packed, unpadded int16 buffer - exactly
-//                       decode.to_pcm16's values, so that 2 bytes per valid sample cross the bus instead of 4 per padded one.
+//                       decode.to_pcm16's values, so that 2 bytes per valid sample cross the bus instead of 4 per padded one;
+//   pcm16_check         the same pass with a per-row report of what the conversion hides (non-finite and saturating
+//                       samples, the largest magnitude), with or without the int16 destination.
 //
 // The reference decodes one utterance at a time on the host (decode_fastsvc.py:150-200: numpy transpose, sf.write's
 // PCM_16 conversion) and has no counterpart.  Both kernels are pure data movement, priced like fastsvc_stage.hip:
@@ -151,6 +153,130 @@ void pcm16_pack_kernel(PcmArgs a, const float* __restrict__ y, short* __restrict
     }
 }
 
+// What pcm16_of hides, for one sample: counts in one word (non-finite in the low half, saturating in the high half: a block
+// sees at most 2048 of either) and the largest finite magnitude as the bit pattern of |y| (non-negative floats order like
+// their bits).  No float64 here: double(y) * 32767.0 is exact and rint is monotonic, so "rint(...) outside [-32768, 32767]"
+// is a comparison of y itself with two float32 constants - the product reaches 32767.5 (the tie rounds to the even 32768)
+// from the smallest float32 >= 32767.5 / 32767 on, and falls below -32768.5 (that tie rounds to -32768, a value) from the
+// largest float32 < -32768.5 / 32767 down.  (A second rint next to pcm16_of's is not merged by the compiler: each sinks
+// into its own branch.)
+constexpr float PCM16_CLIPS_FROM = 0x1.000102p+0f;             // bits 0x3f800081
+constexpr float PCM16_CLIPS_DOWN_FROM = -0x1.000302p+0f;       // bits 0xbf800181
+
+__device__ __forceinline__ void pcm16_tally(float y, unsigned& counts, unsigned& maxbits) {
+    const unsigned mag = __float_as_uint(y) & 0x7fffffffu;
+    const bool finite = mag < 0x7f800000u;
+    const bool clips = y >= PCM16_CLIPS_FROM || y <= PCM16_CLIPS_DOWN_FROM;        // (false for a NaN)
+    counts += finite ? (clips ? 0x10000u : 0u) : 1u;
+    maxbits = (finite && mag > maxbits) ? mag : maxbits;
+}
+
+// pcm16_pack_kernel's geometry and ownership (PACK: the same pieces, the same stores; otherwise no destination and no
+// alignment shift), plus the report: every lane tallies the samples it converts - the clipped head and tail pieces sample by
+// sample, like their stores, so each valid sample is counted by exactly one lane - then the block reduces in registers
+// (wave64 shuffles), through 32 bytes of LDS (one slot per wave), and its first lane issues at most one integer atomic per
+// field into report[b]: sums of counts and a maximum of bit patterns do not depend on the order the blocks arrive in.
+// Only whole blocks past the row leave before the barrier (a block-uniform test); a lane whose piece starts past `len` in a
+// block that still holds valid samples carries zeros through the reduction.
+template <bool PACK>
+__global__ __launch_bounds__(256)
+void pcm16_check_kernel(PcmArgs a, const float* __restrict__ y, short* __restrict__ dst,
+                        fastsvc_row_report* __restrict__ report, int width) {
+    __shared__ unsigned red[2][4];
+    const int b = blockIdx.y;
+    const int len = a.len[b];
+    short* d = PACK ? dst + a.off[b] : nullptr;
+    const int s = PACK ? (int)((reinterpret_cast<uintptr_t>(d) >> 1) & 7) : 0;
+    if ((long)blockIdx.x * 2048 - s >= len) return;                 // (uniform: the block's first piece starts past the row)
+    const long k0 = ((long)blockIdx.x * 256 + threadIdx.x) * 8 - s;
+    unsigned counts = 0, maxbits = 0;
+    if (k0 < len) {
+        const float* src = y + (long)b * width;
+        if (k0 >= 0 && k0 + 8 <= len) {
+            float v[8];
+            if ((reinterpret_cast<uintptr_t>(src + k0) & 15) == 0) {
+                const float4 lo = *reinterpret_cast<const float4*>(src + k0), hi = *reinterpret_cast<const float4*>(src + k0 + 4);
+                v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+            } else {
+                #pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = src[k0 + e];
+            }
+            #pragma unroll
+            for (int e = 0; e < 8; ++e) pcm16_tally(v[e], counts, maxbits);
+            if (PACK) {
+                short8 o;
+                #pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = pcm16_of(v[e]);
+                *reinterpret_cast<short8*>(d + k0) = o;
+            }
+        } else {
+            #pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const long k = k0 + e;
+                if (k >= 0 && k < len) {
+                    const float v = src[k];
+                    pcm16_tally(v, counts, maxbits);
+                    if (PACK) d[k] = pcm16_of(v);
+                }
+            }
+        }
+    }
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        counts += __shfl_down(counts, o);
+        const unsigned m = __shfl_down(maxbits, o);
+        maxbits = m > maxbits ? m : maxbits;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = counts;
+        red[1][threadIdx.x >> 6] = maxbits;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned c = 0, m = 0;
+        #pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            c += red[0][w];
+            m = red[1][w] > m ? red[1][w] : m;
+        }
+        fastsvc_row_report* r = report + b;
+        if (c & 0xffffu) atomicAdd(&r->nonfinite, (int)(c & 0xffffu));
+        if (c >> 16) atomicAdd(&r->clipped, (int)(c >> 16));
+        if (m) atomicMax(reinterpret_cast<unsigned*>(&r->max_abs), m);
+    }
+}
+
+// Host side of both checked entry points: the arguments of fastsvc_pcm16_pack checked the same way (nothing is enqueued
+// when one is bad), the report cleared by one memset on the stream, then one launch per 64 rows with its reports at
+// report + b0.
+template <bool PACK>
+int pcm16_check_launch(const float* y, const int32_t* lens, const int64_t* offsets, int16_t* dst, int64_t dst_elems,
+                       fastsvc_row_report* report, int32_t B, int32_t width, void* stream_) {
+    if (!y || !lens || !report || B < 1 || width < 1) return FASTSVC_E_INVALID;
+    if (PACK && (!offsets || !dst || dst_elems < 0 || (reinterpret_cast<uintptr_t>(dst) & 1))) return FASTSVC_E_INVALID;
+    int maxlen = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 0 || lens[b] > width) return FASTSVC_E_INVALID;
+        if (PACK && (offsets[b] < 0 || offsets[b] + (int64_t)lens[b] > dst_elems)) return FASTSVC_E_INVALID;
+        maxlen = lens[b] > maxlen ? lens[b] : maxlen;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (hipMemsetAsync(report, 0, sizeof(fastsvc_row_report) * (size_t)B, stream) != hipSuccess) return FASTSVC_E_HIP;
+    if (maxlen == 0) return FASTSVC_OK;
+    const unsigned gx = (unsigned)(((long)maxlen + 7 + 2047) / 2048);      // (up to 7 samples of alignment shift per row)
+    for (int b0 = 0; b0 < B; b0 += IO_MAX) {
+        const int nb = B - b0 < IO_MAX ? B - b0 : IO_MAX;
+        PcmArgs a;
+        for (int i = 0; i < IO_MAX; ++i) {
+            a.off[i] = (PACK && i < nb) ? (long)offsets[b0 + i] : 0;
+            a.len[i] = i < nb ? lens[b0 + i] : 0;
+        }
+        hipLaunchKernelGGL(pcm16_check_kernel<PACK>, dim3(gx, (unsigned)nb), dim3(256), 0, stream,
+                           a, y + (long)b0 * width, reinterpret_cast<short*>(dst), report + b0, width);
+    }
+    return hipGetLastError() == hipSuccess ? FASTSVC_OK : FASTSVC_E_HIP;
+}
+
 }  // namespace
 
 extern "C" {
@@ -201,6 +327,16 @@ int fastsvc_pcm16_pack(const float* y, const int32_t* lens, const int64_t* offse
                            a, y + (long)b0 * width, reinterpret_cast<short*>(dst), width);
     }
     return hipGetLastError() == hipSuccess ? FASTSVC_OK : FASTSVC_E_HIP;
+}
+
+int fastsvc_output_check(const float* y, const int32_t* lens, fastsvc_row_report* report, int32_t B, int32_t width,
+                         void* stream) {
+    return pcm16_check_launch<false>(y, lens, nullptr, nullptr, 0, report, B, width, stream);
+}
+
+int fastsvc_pcm16_pack_checked(const float* y, const int32_t* lens, const int64_t* offsets, int16_t* dst, int64_t dst_elems,
+                               fastsvc_row_report* report, int32_t B, int32_t width, void* stream) {
+    return pcm16_check_launch<true>(y, lens, offsets, dst, dst_elems, report, B, width, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,10 @@ are read here (``.h5`` as well when h5py is importable - it is not a dependency)
 
     python -m svcc23_fastsvc_amd.decode --dumpdir feats/ --checkpoint ckpt.pkl --config conf.yaml \\
         --outdir wav/ --spk-emb embs.npz --srcf0stats src_stats/ --trgf0stats trg_stats/
+
+``--resident`` keeps the features on the device across target speakers (``DecodeSession``); with it, ``--checked
+[--fallback bfloat16,float32]`` reports per utterance what the PCM-16 conversion hides and re-runs in a fallback storage the
+batches whose output is not finite, and ``--storage auto`` is float16 storage with ``--checked --fallback bfloat16``.
 """
 from __future__ import annotations
 
@@ -64,6 +68,49 @@ def to_pcm16(y) -> np.ndarray:
     if isinstance(y, torch.Tensor):
         y = y.detach().to("cpu", torch.float32).numpy()
     return np.clip(np.rint(np.asarray(y, dtype=np.float64).reshape(-1) * 32767.0), -32768, 32767).astype(np.int16)
+
+
+def output_report(y, lens: Optional[Sequence[int]] = None):
+    """What ``to_pcm16`` hides, per row: ``(nonfinite, clipped, max_abs)``, int32, int32 and float32 arrays with one entry
+    per row of ``y`` - a (B, width) / (B, 1, width) array or tensor, or a sequence of 1-D waveforms (what
+    ``decode_utterances`` returns) - over each row's first ``lens[b]`` samples (default: the whole row):
+
+        nonfinite  NaN / +-inf samples (``to_pcm16`` saturates the infinities; a NaN has no defined int16 value);
+        clipped    finite samples whose PCM-16 value saturates: rint(float64(y) * 32767.0) outside [-32768, 32767], with
+                   ``to_pcm16``'s own float64 arithmetic (so -32768 itself, reached from -1 - 2^-15, is a value, not a clip);
+        max_abs    the largest |y| over the finite samples, 0 when there is none.
+
+    The host reference of ``engine.output_check`` / ``pcm16_pack(report=)``, which give the same numbers bit for bit."""
+    if isinstance(y, torch.Tensor):
+        y = y.detach().to("cpu", torch.float32).numpy()
+    rows = [np.asarray(r, dtype=np.float32).reshape(-1) for r in y]
+    B = len(rows)
+    if lens is None:
+        lens = [r.size for r in rows]
+    elif len(lens) != B:
+        raise ValueError("output_report needs one length per row")
+    nonfinite, clipped, max_abs = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
+    for b, row in enumerate(rows):
+        n = int(lens[b])
+        if n < 0 or n > row.size:
+            raise ValueError(f"row {b}: length {n} outside [0, {row.size}]")
+        v = row[:n]
+        finite = np.isfinite(v)
+        v = v[finite]
+        r = np.rint(v.astype(np.float64) * 32767.0)
+        nonfinite[b] = n - int(finite.sum())
+        clipped[b] = int(((r < -32768.0) | (r > 32767.0)).sum())
+        max_abs[b] = np.abs(v).max() if v.size else 0.0
+    return nonfinite, clipped, max_abs
+
+
+def flagged_batches(batches: Sequence[Sequence[int]], flagged, among: Optional[Sequence[int]] = None) -> List[int]:
+    """Indices, ascending, of the batches that hold at least one utterance of ``flagged`` - the batches a checked
+    ``DecodeSession`` runs again, each as a whole.  ``among``: look at these batch indices only (a later round looks at the
+    batches of the round before, with the utterances that are still flagged)."""
+    flagged = set(int(i) for i in flagged)
+    ks = range(len(batches)) if among is None else sorted(set(int(k) for k in among))
+    return [k for k in ks if any(int(i) in flagged for i in batches[k])]
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
@@ -274,11 +321,42 @@ class DecodeSession:
     ``convert`` (the padded f0 of every batch plus the embedding).  Kernel descriptors (offsets, lengths: 12 - 16 bytes per
     utterance and launch) travel in kernel arguments and are not copies.
 
+    ``checked=True`` (default False: nothing changes - launches, uploads, ``uploaded_bytes``, results): every batch is packed
+    by the checked entry point (``pcm16_pack(report=)``; with ``pcm16=False`` the forward is followed by ``output_check``),
+    and its reports, 16 bytes a row, come down on the same stream into page-locked memory next to the samples - no extra
+    synchronisation per batch.  After the pass, every batch that holds a row with non-finite samples is run again AS A
+    WHOLE - same rows, same order, same padded width and ``lengths`` - with the model switched
+    (``use_activation_storage``) to the next entry of ``fallback``; only the flagged rows' samples and reports are
+    replaced, and batches still flagged go on to the next entry.  The model's storage is restored afterwards, also when
+    a forward raises.  So a float16-storage session returns, for exactly the utterances that left float16's range, what
+    the fallback storage computes: a row that was never flagged has the bits of an unchecked session in the model's
+    storage, a replaced row the bits of an unchecked session in the storage that replaced it (a ragged batch computes every
+    row as if alone, and the forward is bit-reproducible).
+    ``last_report``: after a checked ``convert``, one dict per utterance in the order of ``feats`` - ``storage`` (what
+    produced the returned samples), ``nonfinite`` / ``clipped`` / ``max_abs`` (``output_report`` of those samples) and
+    ``tried`` (the storages that gave non-finite samples before it).  ``forwards``: the forwards of the last ``convert``.
+    ``strict=True`` raises ``FastSVCError`` naming the utterances still non-finite after the last fallback; otherwise
+    their last result is returned and the report says so.
+    What the check sees: an overflow of float16 storage that reaches the waveform - an infinity survives LeakyReLU, turns a
+    convolution's sum into inf / NaN even through a zero weight and poisons InstanceNorm's mean, so it arrives as inf / NaN
+    samples.  What it does not see: precision lost below 2^-14, and a tensor past the ceiling whose infinity is never
+    read.  The range contract of float16 storage is unchanged; this detects its observable violations.
+
     Not thread-safe; one ``convert`` at a time.  ``out_channels`` must be 1."""
 
     def __init__(self, model, feats: Sequence[Dict[str, np.ndarray]], signal_generator, device,
                  src_f0_stats: Optional[Sequence[Sequence[float]]] = None, max_batch: int = 32,
-                 pad_tolerance: float = 0.125):
+                 pad_tolerance: float = 0.125, checked: bool = False, fallback: Sequence[str] = ("bfloat16",),
+                 strict: bool = False):
+        from .engine import STORAGE_CODES
+        fallback = (fallback,) if isinstance(fallback, str) else tuple(fallback)
+        for name in fallback:
+            if name not in STORAGE_CODES:
+                raise ValueError(f"fallback storage must be one of {sorted(STORAGE_CODES)}, got {name!r}")
+        self.checked, self.fallback, self.strict = bool(checked), fallback, bool(strict)
+        self.last_report: List[Dict[str, object]] = []
+        self.forwards = 0
+        self._h_rep = None
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
         self.hop = int(signal_generator.hop_size)
@@ -299,6 +377,9 @@ class DecodeSession:
         if self.device.type != "cuda":
             from .engine import FastSVCError
             raise FastSVCError("DecodeSession needs a GPU device (no CPU fallback); got " + str(self.device))
+        if checked and fallback and not hasattr(model, "use_activation_storage"):
+            raise ValueError("a checked session with fallback storages needs a model with use_activation_storage() "
+                             "(FastSVCGenerator); pass fallback=() to report only")
         hop, frames = self.hop, self.frames
         self.channels = C = int(np.asarray(feats[0]["ppg"]).shape[1])
         for i, u in enumerate(feats):
@@ -342,6 +423,10 @@ class DecodeSession:
         self._lft_rows = [[self._d_lft[self._lft_off[i]: self._lft_off[i] + lft_counts[i]].view(1, -1) for i in chunk]
                           for chunk in self.batches]
         self._down = [_PinnedSet(), _PinnedSet()]
+        self._row_base, pos = [], 0                  # (a batch's reports: rows [_row_base[k], + len(batch)) of _h_rep)
+        for chunk in self.batches:
+            self._row_base.append(pos)
+            pos += len(chunk)
 
     def __enter__(self):
         return self
@@ -357,7 +442,7 @@ class DecodeSession:
         if self.n and self.device.type == "cuda":
             self._copy_stream.synchronize()
             torch.cuda.current_stream(self.device).synchronize()
-        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = None
+        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = self._h_rep = None
         self._lft_rows = self._down = self._ready = None
 
     @torch.no_grad()
@@ -372,10 +457,12 @@ class DecodeSession:
             raise RuntimeError("DecodeSession is closed")
         if not self.n:
             return []
-        from .engine import gather_padded, gather_time_major, pcm16_pack
+        from .engine import FastSVCError, gather_padded, gather_time_major, output_check, pcm16_pack, report_arrays
         dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
+        checked = self.checked
         stream = torch.cuda.current_stream(dev)
         up = 0
+        self.forwards = 0
         emb_row = None
         if trg_emb is not None:
             emb_row = torch.as_tensor(np.asarray(trg_emb), dtype=torch.float32).reshape(1, -1).to(dev)
@@ -384,34 +471,48 @@ class DecodeSession:
         hf_all = self._h_f0.numpy()
         if pcm16 and self._h_pcm is None:
             self._h_pcm = torch.empty(max(sum(frames) * hop, 1), dtype=torch.int16, pin_memory=True)
+        if checked and self._h_rep is None:
+            self._h_rep = torch.empty((self.n, 4), dtype=torch.int32, pin_memory=True)
         out: List[Optional[np.ndarray]] = [None] * self.n
         result = np.empty(sum(frames) * hop, dtype=np.int16) if pcm16 else None
         pending = {}
 
-        def finish(k: int) -> None:
+        def finish(k: int, rows: Optional[Sequence[int]] = None) -> None:
+            """Take batch k's samples out of the page-locked buffers (``rows``: those rows of it only)."""
             host_y, done = pending.pop(k)
             done.synchronize()
+            chunk = self.batches[k]
             if pcm16:
-                lo, hi = host_y
-                result[lo:hi] = self._h_pcm.numpy()[lo:hi]
+                if rows is None:
+                    lo, hi = host_y
+                    result[lo:hi] = self._h_pcm.numpy()[lo:hi]
+                else:
+                    for j in rows:
+                        lo, hi = self._lft_off[chunk[j]], self._lft_off[chunk[j]] + frames[chunk[j]] * hop
+                        result[lo:hi] = self._h_pcm.numpy()[lo:hi]
                 return
             y = host_y.numpy()
-            for j, i in enumerate(self.batches[k]):
+            for j in (range(len(chunk)) if rows is None else rows):
+                i = chunk[j]
                 out[i] = y[j].reshape(-1)[: frames[i] * hop].copy()
 
-        for k, chunk in enumerate(self.batches):
+        def enqueue(k: int, rows: Optional[Sequence[int]] = None) -> int:
+            """Batch k on the stream, whole: f0 up, assembly, forward, packing, downloads.  ``rows`` (a fallback run): the
+            padded f0 is still in its page-locked slot from the first pass, and only those rows' samples and reports come
+            down.  Returns the bytes uploaded."""
+            chunk = self.batches[k]
             fmax, B = frames[chunk[0]], len(chunk)
             lens = [frames[i] for i in chunk]
             base = self._f0_base[k]
-            hf = hf_all[base: base + B * fmax].reshape(B, 1, fmax)
-            for j, i in enumerate(chunk):
-                f, n = self._f0[i], frames[i]
-                if shift:
-                    f = F0Statistics().convert(f, self.src_f0_stats[i], trg_f0_stats)
-                hf[j, 0, :n] = f
-                hf[j, 0, n:] = 0
+            if rows is None:
+                hf = hf_all[base: base + B * fmax].reshape(B, 1, fmax)
+                for j, i in enumerate(chunk):
+                    f, n = self._f0[i], frames[i]
+                    if shift:
+                        f = F0Statistics().convert(f, self.src_f0_stats[i], trg_f0_stats)
+                    hf[j, 0, :n] = f
+                    hf[j, 0, n:] = 0
             f0 = self._h_f0[base: base + B * fmax].view(B, 1, fmax).to(dev, non_blocking=True)
-            up += 4 * B * fmax
             if self._ready is not None:
                 stream.wait_event(self._ready[k])
             ppg = gather_time_major(self._d_ppg, [self._ppg_off[i] for i in chunk], lens, C, fmax)
@@ -419,30 +520,85 @@ class DecodeSession:
             sine = self.signal_generator(f0)
             emb = None if emb_row is None else emb_row.expand(B, -1).contiguous()
             y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+            self.forwards += 1
+            report = torch.empty((B, 4), dtype=torch.int32, device=dev) if checked else None
             if pcm16:
                 lo = self._lft_off[chunk[0]]
                 total = sum(lens) * hop
                 packed = torch.empty(max(total, 1), dtype=torch.int16, device=dev)
-                pcm16_pack(y.view(B, fmax * hop), [n * hop for n in lens], [self._lft_off[i] - lo for i in chunk], out=packed)
-                if total:
-                    self._h_pcm[lo: lo + total].copy_(packed[:total], non_blocking=True)
+                pcm16_pack(y.view(B, fmax * hop), [n * hop for n in lens], [self._lft_off[i] - lo for i in chunk], out=packed,
+                           report=report)
+                if rows is None:
+                    if total:
+                        self._h_pcm[lo: lo + total].copy_(packed[:total], non_blocking=True)
+                else:
+                    for j in rows:
+                        a, n = self._lft_off[chunk[j]], lens[j] * hop
+                        if n:
+                            self._h_pcm[a: a + n].copy_(packed[a - lo: a - lo + n], non_blocking=True)
                 host_y = (lo, lo + total)
             else:
                 host_y = self._down[k & 1].get("y", tuple(y.shape))
                 host_y.copy_(y, non_blocking=True)
+                if checked:
+                    output_check(y.view(B, fmax * hop), [n * hop for n in lens], out=report)
+            if checked:
+                r0 = self._row_base[k]
+                if rows is None:
+                    self._h_rep[r0: r0 + B].copy_(report, non_blocking=True)
+                else:
+                    for j in rows:
+                        self._h_rep[r0 + j].copy_(report[j], non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
             pending[k] = (host_y, done)
+            return 4 * B * fmax
+
+        for k in range(len(self.batches)):
+            up += enqueue(k)
             if k >= 1:
                 finish(k - 1)                        # (while batch k computes; before batch k + 1 reuses that download set)
         finish(len(self.batches) - 1)
         stream.synchronize()
-        if pcm16:
-            out = [result[self._lft_off[i]: self._lft_off[i] + frames[i] * hop] for i in range(self.n)]
         if self._ready is not None:                  # every upload has been waited for: the staging can go
             self._ready = None
             self._h_ppg = self._h_lft = None
+        still = []
+        if checked:
+            row_of = {i: self._row_base[k] + j for k, chunk in enumerate(self.batches) for j, i in enumerate(chunk)}
+            rep = self._h_rep.numpy()
+            first = getattr(self.model, "activation_storage", "float32")
+            storage, tried = [first] * self.n, [[] for _ in range(self.n)]
+            flagged = [i for i in range(self.n) if rep[row_of[i], 0] > 0]
+            again = None
+            try:
+                for name in self.fallback:
+                    again = flagged_batches(self.batches, flagged, again)
+                    if not again:
+                        break
+                    self.model.use_activation_storage(name)
+                    for k in again:                  # (the rare path: one batch at a time)
+                        rows = [j for j, i in enumerate(self.batches[k]) if i in flagged]
+                        up += enqueue(k, rows)
+                        finish(k, rows)
+                        for j in rows:
+                            i = self.batches[k][j]
+                            tried[i].append(storage[i])
+                            storage[i] = name
+                    flagged = [i for i in flagged if rep[row_of[i], 0] > 0]
+            finally:
+                if getattr(self.model, "activation_storage", first) != first:
+                    self.model.use_activation_storage(first)
+            nonfinite, clipped, max_abs = report_arrays(rep)
+            self.last_report = [dict(storage=storage[i], nonfinite=int(nonfinite[row_of[i]]), clipped=int(clipped[row_of[i]]),
+                                     max_abs=float(max_abs[row_of[i]]), tried=tried[i]) for i in range(self.n)]
+            still = flagged
+        if pcm16:
+            out = [result[self._lft_off[i]: self._lft_off[i] + frames[i] * hop] for i in range(self.n)]
         self.uploaded_bytes["convert"].append(up)
+        if still and self.strict:
+            raise FastSVCError(f"utterances {still} still have non-finite samples after storages "
+                               f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
         return out  # type: ignore[return-value]
 
 
@@ -465,8 +621,14 @@ def main(argv=None) -> None:                                  # pragma: no cover
     ap.add_argument("--srcf0stats", default=None)
     ap.add_argument("--trgf0stats", default=None)
     ap.add_argument("--max-batch", type=int, default=32)
-    ap.add_argument("--storage", default="float32", choices=["float32", "bfloat16", "float16"],
-                    help="activation storage of the generator's forward (FastSVCGenerator.activation_storage)")
+    ap.add_argument("--storage", default="float32", choices=["float32", "bfloat16", "float16", "auto"],
+                    help="activation storage of the generator's forward (FastSVCGenerator.activation_storage); auto: float16 "
+                         "with --checked --fallback bfloat16 (needs --resident)")
+    ap.add_argument("--checked", action="store_true",
+                    help="with --resident: report non-finite and clipped samples per utterance and run the batches that "
+                         "hold a non-finite utterance again in the --fallback storages (DecodeSession(checked=True))")
+    ap.add_argument("--fallback", default=None,
+                    help="comma-separated storages to fall back to, in order (default with --checked: bfloat16)")
     ap.add_argument("--resident", action="store_true",
                     help="keep the features on the device across target speakers (DecodeSession): ppg / lft are uploaded "
                          "once per group of dumps, PCM-16 is made on the device; same file names and contents")
@@ -474,6 +636,16 @@ def main(argv=None) -> None:                                  # pragma: no cover
                     help="device bytes of packed features one resident group may hold (default 4 GiB); a dump directory "
                          "larger than this is decoded group by group")
     args = ap.parse_args(argv)
+    if args.storage == "auto":
+        args.storage, args.checked = "float16", True
+    if (args.checked or args.fallback is not None) and not args.resident:
+        ap.error("--checked / --fallback / --storage auto work on the --resident route")
+    if args.fallback is not None and not args.checked:
+        ap.error("--fallback needs --checked")
+    args.fallback = tuple(v for v in (args.fallback if args.fallback is not None else "bfloat16").split(",") if v)
+    for name in args.fallback:
+        if name not in ("float32", "bfloat16", "float16"):
+            ap.error(f"--fallback: unknown storage {name!r}")
     with open(args.config) as f:
         config = yaml.safe_load(f)
     device = torch.device("cuda")
@@ -538,12 +710,14 @@ def _main_resident(args, config, model, sg, device, files) -> None:      # pragm
     embs = dict(np.load(args.spk_emb)) if args.spk_emb else {}
     speakers = config.get("convert_to_speakers", [None])
     spent, samples = {s: 0.0 for s in speakers}, {s: 0 for s in speakers}
+    reports = {s: [] for s in speakers}
     for paths, feats in resident_groups(files, args.resident_bytes, int(config["hop_size"])):
         utt_ids = [os.path.splitext(os.path.basename(p))[0] for p in paths]
         src_stats = None
         if args.srcf0stats and args.trgf0stats:
             src_stats = [_read_f0_mean(args.srcf0stats, u.split("_")[0]) for u in utt_ids]
-        with DecodeSession(model, feats, sg, device, src_stats, args.max_batch) as session:
+        with DecodeSession(model, feats, sg, device, src_stats, args.max_batch, checked=args.checked,
+                           fallback=args.fallback) as session:
             for trgspk in speakers:
                 trg_emb = embs.get(trgspk) if config["generator_params"].get("use_spk_emb") else None
                 trg_stats = None
@@ -553,11 +727,30 @@ def _main_resident(args, config, model, sg, device, files) -> None:      # pragm
                 pcm = session.convert(trg_emb, trg_stats)
                 spent[trgspk] += time.time() - t0
                 samples[trgspk] += sum(len(p) for p in pcm)
+                reports[trgspk] += session.last_report if args.checked else []
                 for utt, p in zip(utt_ids, pcm):
                     write_wav(os.path.join(args.outdir, f"{utt}_{trgspk}_gen.wav"), p, config["sampling_rate"])
     for trgspk in speakers:
         if samples[trgspk]:
             print(f"{len(files)} utterances -> {trgspk}: RTF = {spent[trgspk] / (samples[trgspk] / config['sampling_rate']):.5f}")
+        if args.checked:
+            print(f"{trgspk}: " + summarize_reports(reports[trgspk], args.storage))
+
+
+def summarize_reports(reports: Sequence[Dict[str, object]], storage: str) -> str:
+    """The CLI's closing line for one target speaker, from the ``last_report`` entries of its converts."""
+    fell: Dict[str, int] = {}
+    for r in reports:
+        if r["tried"]:
+            fell[str(r["storage"])] = fell.get(str(r["storage"]), 0) + 1
+    bad = sum(1 for r in reports if r["nonfinite"])
+    text = f"{len(reports)} utterances checked in {storage} storage; {sum(fell.values())} fell back"
+    if fell:
+        text += " (" + ", ".join(f"{n} to {name}" for name, n in sorted(fell.items())) + ")"
+    if bad:
+        text += f"; {bad} STILL NON-FINITE after the last fallback"
+    text += f"; {sum(1 for r in reports if r['clipped'])} have clipped samples"
+    return text + f"; largest max_abs {max((float(r['max_abs']) for r in reports), default=0.0):.4g}"
 
 
 if __name__ == "__main__":                                    # pragma: no cover

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "fastsvc_stream_prepare", "fastsvc_stream_release", "fastsvc_split_half", "fastsvc_plan_set_workspace_mode",
     "fastsvc_loudness_frames", "fastsvc_loudness_scratch_bytes", "fastsvc_loudness_extract",
     "fastsvc_gather_padded", "fastsvc_gather_time_major", "fastsvc_pcm16_pack",
+    "fastsvc_pcm16_pack_checked", "fastsvc_output_check",
     "fastsvc_collate_launch_count", "fastsvc_collate_crops",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
@@ -162,6 +163,10 @@ def load_library():
     lib.fastsvc_gather_time_major.restype = ctypes.c_int
     lib.fastsvc_pcm16_pack.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), vp, i64, i32, i32, vp]
     lib.fastsvc_pcm16_pack.restype = ctypes.c_int
+    lib.fastsvc_pcm16_pack_checked.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), vp, i64, vp, i32, i32, vp]
+    lib.fastsvc_pcm16_pack_checked.restype = ctypes.c_int
+    lib.fastsvc_output_check.argtypes = [vp, ctypes.POINTER(i32), vp, i32, i32, vp]
+    lib.fastsvc_output_check.restype = ctypes.c_int
     lib.fastsvc_collate_launch_count.argtypes = [i32]
     lib.fastsvc_collate_launch_count.restype = ctypes.c_int
     lib.fastsvc_collate_crops.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i32),
@@ -258,13 +263,58 @@ def gather_time_major(packed: torch.Tensor, offsets: Sequence[int], lens: Sequen
     return out
 
 
+def _report_tensor(report, B: int, device) -> torch.Tensor:
+    if not isinstance(report, torch.Tensor) or not report.is_cuda:
+        raise FastSVCError("the report must be a GPU tensor (no CPU fallback); got " + str(getattr(report, "device", type(report))))
+    if tuple(report.shape) != (B, 4) or report.dtype != torch.int32 or not report.is_contiguous() or report.device != device:
+        raise ValueError(f"report must be a contiguous int32 {(B, 4)} tensor on {device}")
+    return report
+
+
+def output_check(y: torch.Tensor, lens: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What a PCM-16 conversion of ``y`` would hide, per row: -> (B, 4) int32 on the device, row b the
+    ``fastsvc_row_report`` of ``y[b, :lens[b]]`` - non-finite samples, finite samples whose PCM-16 value saturates, the
+    bit pattern of the largest finite ``|y|`` (float32), 0.  ``report_arrays`` decodes a downloaded one;
+    ``decode.output_report`` is the host's version.  ``y`` as for ``pcm16_pack``; ``out``: a (B, 4) int32 tensor to
+    overwrite.  One memset and one HIP launch per 64 rows on the current stream (fastsvc_output_check); fails loudly
+    off the GPU."""
+    lib = load_library()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise FastSVCError("output_check needs a GPU tensor (no CPU fallback); got " + str(getattr(y, "device", type(y))))
+    if y.dim() == 3 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous() or y.shape[0] != len(lens) or y.shape[0] == 0:
+        raise ValueError(f"y must be a contiguous float32 (B, width) tensor with one length per row; got {tuple(y.shape)} {y.dtype}")
+    B, width = int(y.shape[0]), int(y.shape[1])
+    report = torch.empty((B, 4), dtype=torch.int32, device=y.device) if out is None else _report_tensor(out, B, y.device)
+    ls = (ctypes.c_int32 * B)(*[int(v) for v in lens])
+    with torch.cuda.device(y.device):
+        stream = torch.cuda.current_stream(y.device).cuda_stream
+        _check(lib, lib.fastsvc_output_check(ctypes.c_void_p(y.data_ptr()), ls, ctypes.c_void_p(report.data_ptr()),
+                                             B, width, ctypes.c_void_p(stream)), "fastsvc_output_check")
+    return report
+
+
+def report_arrays(report) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """A downloaded (B, 4) int32 report (``output_check``, ``pcm16_pack(report=)``; tensor or array) ->
+    ``(nonfinite, clipped, max_abs)``: int32, int32 and - column 2 reinterpreted - float32 arrays of B entries."""
+    if isinstance(report, torch.Tensor):
+        report = report.detach().cpu().numpy()
+    r = np.ascontiguousarray(report, dtype=np.int32).reshape(-1, 4)
+    return r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy().view(np.float32)
+
+
 def pcm16_pack(y: torch.Tensor, lens: Sequence[int], offsets: Optional[Sequence[int]] = None,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, report: Optional[torch.Tensor] = None) -> torch.Tensor:
     """PCM-16 of a batch of waveforms, packed: row b of ``y`` (B, width) or (B, 1, width), float32 on the device, valid for
     ``lens[b]`` samples, goes to ``out[offsets[b]: offsets[b] + lens[b]]`` (1-D int16; default offsets: the rows back to
     back, default out: a new tensor of sum(lens) samples).  The values are ``decode.to_pcm16``'s bit for bit (float64
     product, round half to even, saturated; NaN -> 0); samples of ``out`` outside the rows are left as they are.  One HIP
-    launch per 64 rows on the current stream (fastsvc_pcm16_pack, csrc/fastsvc_decodeio.hip); fails loudly off the GPU."""
+    launch per 64 rows on the current stream (fastsvc_pcm16_pack, csrc/fastsvc_decodeio.hip); fails loudly off the GPU.
+
+    ``report``: a (B, 4) int32 device tensor; when given, the checked entry point runs instead
+    (fastsvc_pcm16_pack_checked: the same bytes into ``out`` from the same pass, plus one memset) and overwrites it with
+    the rows' ``fastsvc_row_report`` (see ``output_check``)."""
     lib = load_library()
     if not isinstance(y, torch.Tensor) or not y.is_cuda:
         raise FastSVCError("pcm16_pack needs a GPU tensor (no CPU fallback); got " + str(getattr(y, "device", type(y))))
@@ -284,12 +334,21 @@ def pcm16_pack(y: torch.Tensor, lens: Sequence[int], offsets: Optional[Sequence[
         out = torch.empty(max(int(o) + n for o, n in zip(offsets, lens)), dtype=torch.int16, device=y.device)
     elif out.dim() != 1 or out.dtype != torch.int16 or not out.is_contiguous() or out.device != y.device:
         raise ValueError(f"out must be a contiguous 1-D int16 tensor on {y.device}")
+    if report is not None:
+        _report_tensor(report, B, y.device)
     if out.numel() == 0:
+        if report is not None:
+            report.zero_()
         return out
     offs = (ctypes.c_int64 * B)(*[int(v) for v in offsets])
     ls = (ctypes.c_int32 * B)(*lens)
     with torch.cuda.device(y.device):
         stream = torch.cuda.current_stream(y.device).cuda_stream
+        if report is not None:
+            _check(lib, lib.fastsvc_pcm16_pack_checked(ctypes.c_void_p(y.data_ptr()), ls, offs, ctypes.c_void_p(out.data_ptr()),
+                                                       out.numel(), ctypes.c_void_p(report.data_ptr()), B, width,
+                                                       ctypes.c_void_p(stream)), "fastsvc_pcm16_pack_checked")
+            return out
         _check(lib, lib.fastsvc_pcm16_pack(ctypes.c_void_p(y.data_ptr()), ls, offs, ctypes.c_void_p(out.data_ptr()),
                                            out.numel(), B, width, ctypes.c_void_p(stream)), "fastsvc_pcm16_pack")
     return out

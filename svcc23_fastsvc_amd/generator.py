@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
-from .engine import FastSVCError, Plan
+from .engine import STORAGE_CODES, FastSVCError, Plan
 from .synth import GeneratorConfig
 
 
@@ -105,7 +105,8 @@ class FastSVCGenerator(nn.Module):
     autotune = False
     # "float32" (the parity path), "bfloat16": workspace tensors stored as bf16 (BASELINE config 3:
     # half the HBM traffic of the narrow layers, bf16-activation accuracy), or "float16": the same tensors as binary16
-    # (bfloat16's traffic, 3 more significand bits, workspace tensors must stay below 65504).  Set before the first forward.
+    # (bfloat16's traffic, 3 more significand bits, workspace tensors must stay below 65504).  Set before the first forward;
+    # afterwards switch with use_activation_storage().
     activation_storage = "float32"
     # True: never build an autograd graph (the plain HIP forward whatever the grad mode says) - for inference code
     # that does not wrap its calls in torch.no_grad()
@@ -213,6 +214,7 @@ class FastSVCGenerator(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_plan"] = None
+        state.pop("_storage_plans", None)
         state["_blob"] = None
         state["_device_blob"] = None
         state["_blob_key"] = None
@@ -294,6 +296,23 @@ class FastSVCGenerator(nn.Module):
         if self._plan is None:
             self._plan = Plan(self._cfg, storage=self.activation_storage, compact_workspace=True)
         return self._plan
+
+    def use_activation_storage(self, storage: str) -> None:
+        """Switch ``activation_storage`` on a generator that may already have run (the attribute alone is read when the
+        plan is first built).  Every storage gets the plan a fresh generator would build for it, kept for the next
+        switch; the packed weights stay, as one blob serves the three storages of a configuration."""
+        if storage not in STORAGE_CODES:
+            raise ValueError("storage must be 'float32', 'bfloat16' or 'float16'")
+        if storage == self.activation_storage:
+            return
+        plans = self.__dict__.setdefault("_storage_plans", {})
+        if self._plan is not None:
+            plans[self.activation_storage] = self._plan
+        self.activation_storage = storage
+        self._plan = plans.get(storage)
+        self._tuned_shapes = set()
+        if self._blob is not None and self.plan.blob_bytes != self._blob.numel() * self._blob.element_size():
+            self.invalidate_packed_weights()         # (never for today's plans: the packer ignores the storage)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, s, l, spk_emb=None, *, lengths=None, out=None):

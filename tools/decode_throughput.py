@@ -10,7 +10,15 @@ Four legs, for activation storage float32 and bfloat16, alternated within the on
     (c) next    the same session's second convert(), for another speaker: F0 shift + f0 upload only
 
 Before timing, (b) and (c) are checked to equal (a) sample for sample.  The figures go to profiles/decode_session.txt.
-    python tools/decode_throughput.py"""
+
+The checked legs (profiles/decode_checked.txt), in float16 activation storage on the same utterances:
+
+    unchecked   a resident session's convert()                      } two sessions alive side by side, their converts
+    checked     DecodeSession(checked=True)'s convert()             } alternated, DECODE_REPS each
+    pack alone  pcm16_pack and pcm16_pack(report=) on 32 rows of 160000 samples, alternated, device time per call
+
+The checked median is compared with the min - max spread of the unchecked repetitions of the same run; no threshold.
+    python tools/decode_throughput.py                  (DECODE_LEGS=session or =checked: one of the two parts only)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -53,13 +61,84 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
-for storage in ("float32", "bfloat16"):
+def build_model(storage):
     m = A.FastSVCGenerator(in_channels=cfg.in_channels, mid_channels=list(cfg.mid_channels), upsampling_scales=list(cfg.upsampling_scales),
                            out_channels=cfg.out_channels, spk_emb_size=cfg.spk_emb_size, use_spk_emb=True)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in S.synth_state_dict(cfg, 1).items()})
     m.remove_weight_norm()
     m.activation_storage = storage
-    m = m.eval().to(dev)
+    return m.eval().to(dev)
+
+
+def spread(name, seconds, unit_samples=None):
+    v = np.array(seconds) * 1e3
+    med = float(np.median(v))
+    tail = "" if unit_samples is None else f"  {unit_samples / med / 1e3:7.1f} M samples/s"
+    return med, f"{name:42s} median {med:9.3f} ms  (min {v.min():9.3f}, max {v.max():9.3f}){tail}"
+
+
+def checked_legs():
+    """float16 storage: unchecked against checked resident sessions, and the two pack entry points alone."""
+    out = [lines[0], "--- activation storage float16, resident sessions: convert() of an unchecked and of a checked session, alternated"]
+    m = build_model("float16")
+    with Dc.DecodeSession(m, feats, sg, dev, src, max_batch=MB) as plain, \
+            Dc.DecodeSession(m, feats, sg, dev, src, max_batch=MB, checked=True) as chk:
+        want, got = plain.convert(emb, trg), chk.convert(emb, trg)               # (warm: first converts wait for the uploads)
+        same = all(np.array_equal(a, b) for a, b in zip(got, want))
+        fell = sum(1 for r in chk.last_report if r["tried"])
+        clipped = sum(1 for r in chk.last_report if r["clipped"])
+        out.append(f"checked output equals unchecked sample for sample: {same}; forwards {chk.forwards} for {len(chk.batches)} batches; "
+                   f"{fell} utterances fell back, {clipped} have clipped samples, largest max_abs "
+                   f"{max(r['max_abs'] for r in chk.last_report):.3f}; report download {16 * len(feats)} bytes per convert")
+        del want, got
+        t = {"u": [], "c": []}
+        for _ in range(reps):
+            t["u"].append(timed(lambda: plain.convert(emb2, trg2))[0])
+            t["c"].append(timed(lambda: chk.convert(emb2, trg2))[0])
+    mu, line_u = spread("unchecked convert, per speaker", t["u"], samples)
+    mc, line_c = spread("checked convert, per speaker", t["c"], samples)
+    inside = min(t["u"]) * 1e3 <= mc <= max(t["u"]) * 1e3
+    out += [line_u, line_c, f"checked median - unchecked median: {mc - mu:+.3f} ms ({(mc / mu - 1) * 100:+.2f} %); checked median "
+            f"{'inside' if inside else 'OUTSIDE'} the unchecked min - max spread"]
+    # the two entry points alone
+    B, W, calls = 32, 160000, 50
+    y = (torch.randn(B, W, device=dev) * 0.35).contiguous()
+    lens = [W] * B
+    dst = torch.empty(B * W, dtype=torch.int16, device=dev)
+    report = torch.empty((B, 4), dtype=torch.int32, device=dev)
+
+    def device_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) / calls * 1e-3
+
+    legs = {"p": lambda: A.pcm16_pack(y, lens, out=dst), "c": lambda: A.pcm16_pack(y, lens, out=dst, report=report)}
+    for fn in legs.values():
+        device_ms(fn)
+    tp = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, fn in legs.items():
+            tp[k].append(device_ms(fn))
+    out.append(f"--- pack entry points alone: {B} rows of {W} samples ({6 * B * W / 1e6:.1f} MB read + written by the packs), "
+               f"{calls} calls per repetition, device time per call")
+    mp, line_p = spread("pcm16_pack", tp["p"])
+    mk, line_k = spread("pcm16_pack(report=)  [memset + launch]", tp["c"])
+    out += [line_p + f"  {6 * B * W / mp / 1e6:7.1f} GB/s", line_k + f"  {6 * B * W / mk / 1e6:7.1f} GB/s",
+            f"checked pack - unchecked pack: {(mk - mp) * 1e3:+.1f} us per call ({(mk / mp - 1) * 100:+.1f} %)"]
+    print("\n".join(out[1:]), flush=True)
+    assert same, "the checked session differs from the unchecked one"
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_checked.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
+LEGS = os.environ.get("DECODE_LEGS", "all")
+for storage in (("float32", "bfloat16") if LEGS in ("all", "session") else ()):
+    m = build_model(storage)
 
     def floats(e=emb, t=trg):
         return Dc.decode_utterances(m, feats, sg, dev, trg_emb=e, src_f0_stats=src, trg_f0_stats=t, max_batch=MB)
@@ -99,6 +178,9 @@ for storage in ("float32", "bfloat16"):
     print("\n".join(out), flush=True)
     lines += out
     assert same, "DecodeSession differs from decode_utterances + to_pcm16"
-os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-with open(os.path.join(ROOT, "profiles", "decode_session.txt"), "w") as f:
-    f.write("\n".join(lines) + "\n")
+if LEGS in ("all", "session"):
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_session.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+if LEGS in ("all", "checked"):
+    checked_legs()
