@@ -352,6 +352,44 @@ int fastsvc_collate_crops(const float* wave, const float* lft, int64_t wave_elem
                           float* y, float* lft_out, float* ppg_out, float* f0_out, float* emb_out,
                           int32_t B, int32_t D, int32_t S, int32_t hop, int32_t frames, int32_t ctx, void* stream);
 
+/* Speaker fan-out batch assembly for a resident decode session (csrc/fastsvc_fanout.hip;
+ * decode.DecodeSession.convert_many) - a decode batch whose rows are (utterance, target speaker) pairs, so that a small
+ * source set fills its batches across the speaker axis.  The reference converts one utterance to one speaker at a time on
+ * the host (decode_fastsvc.py:150-200).  Three packed float32 DEVICE buffers hold the utterances; utterance u has
+ * n_frames[u] frames and
+ *   ppg   its time-major (n_frames[u], C) block at element ppg_off[u]           (ppg_elems floats; the dump's own layout)
+ *   lft   n_frames[u] * hop samples at element lft_off[u]                       (lft_elems floats)
+ *   f0    n_frames[u] values at element f0_off[u]                               (f0_elems floats; the dump's values)
+ * and batch row r = (utt[r], spk[r]) becomes, all device float32, contiguous:
+ *   ppg_out (R, C, width)        the block transposed to channel-major, every column >= n_frames written as 0 - the bits
+ *                                of fastsvc_gather_time_major
+ *   lft_out (R, 1, width * hop)  the samples copied bit for bit, the tail written as 0 - the bits of fastsvc_gather_padded
+ *   f0_out  (R, 1, width)        voiced frames (f > 0): (float) exp((s1 / s0) * (log((double) f) - m0) + m1) with
+ *                                (m0, s0) = src_stats[utt[r]] and (m1, s1) = spk_stats[spk[r]] - F0Statistics.convert
+ *                                (features.py:88-108), every operation a separately rounded IEEE double operation in that
+ *                                order (no fused multiply-add; log and exp are the device library's double-precision ones,
+ *                                so the float32 result is within one ulp of the host's); unvoiced frames and the padding
+ *                                are exactly 0.  src_stats (n_utts, 2) and spk_stats (n_spk, 2) are DEVICE tables of
+ *                                doubles, [mean, std] of log F0 per row; when either is NULL f0 is copied bit for bit
+ *   emb_out (R, E)               row spk[r] of spk_emb (n_spk, E), a DEVICE float32 table; a NULL spk_emb leaves emb_out
+ *                                untouched (it may be NULL then)
+ * 0 <= n_frames[u] <= width.  No alignment or % 4 requirement on anything (16-byte requests where source and destination
+ * addresses agree mod 16, element requests elsewhere); no load touches a byte outside the row's own source block and no
+ * store a byte outside the four outputs.  `ppg_off`, `lft_off`, `f0_off`, `n_frames` (n_utts entries) and `utt`, `spk`
+ * (R entries) are HOST arrays, read during the call (the rows' values travel in the kernel arguments).  Everything is
+ * checked on the host BEFORE anything is enqueued: null pointers, sizes out of range, utt[r] outside [0, n_utts), spk[r]
+ * outside [0, n_spk), n_frames > width, a block that does not lie inside its buffer - FASTSVC_E_INVALID, with the row and
+ * the reason in fastsvc_last_error(); a failed launch is FASTSVC_E_HIP.  One launch per 64 rows
+ * (fastsvc_fanout_launch_count(R)), asynchronous on `stream`. */
+int fastsvc_fanout_launch_count(int32_t R);
+int fastsvc_fanout_assemble(const float* ppg, int64_t ppg_elems, const float* lft, int64_t lft_elems,
+                            const float* f0, int64_t f0_elems, int32_t n_utts,
+                            const int64_t* ppg_off, const int64_t* lft_off, const int64_t* f0_off, const int32_t* n_frames,
+                            const double* src_stats, const double* spk_stats, const float* spk_emb, int32_t n_spk,
+                            const int32_t* utt, const int32_t* spk,
+                            float* ppg_out, float* lft_out, float* f0_out, float* emb_out,
+                            int32_t R, int32_t C, int32_t E, int32_t hop, int32_t width, void* stream);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libfastsvc_hip.so")
 # the stamped diagnostic build (--timeline) is a separate file: loaded only when FASTSVC_HIP_LIB names it
 TIMELINE_LIB_PATH = os.path.join(PKG_DIR, "libfastsvc_hip_timeline.so")
-SOURCES = ["fastsvc_kernels.hip", "fastsvc_hx.hip", "fastsvc_wx.hip", "fastsvc_cond.hip", "fastsvc_plan.cpp", "fastsvc_signal.hip", "fastsvc_loudness.hip", "fastsvc_stftloss.hip", "fastsvc_convgrad.hip", "fastsvc_filmnorm.hip", "fastsvc_gconv.hip", "fastsvc_decodeio.hip", "fastsvc_pack.hip", "fastsvc_collate.hip"]
+SOURCES = ["fastsvc_kernels.hip", "fastsvc_hx.hip", "fastsvc_wx.hip", "fastsvc_cond.hip", "fastsvc_plan.cpp", "fastsvc_signal.hip", "fastsvc_loudness.hip", "fastsvc_stftloss.hip", "fastsvc_convgrad.hip", "fastsvc_filmnorm.hip", "fastsvc_gconv.hip", "fastsvc_decodeio.hip", "fastsvc_pack.hip", "fastsvc_collate.hip", "fastsvc_fanout.hip"]
 HEADERS = [os.path.join(CSRC, "fastsvc_kernels.h"), os.path.join(ROOT, "include", "fastsvc_hip.h")]
 ARCH = "gfx950"
 
@@ -63,6 +63,8 @@ UNITS = [
     ("fastsvc_gconv.hip", [], "gconv.o"),
     ("fastsvc_decodeio.hip", [], "decodeio.o"),
     ("fastsvc_collate.hip", [], "collate.o"),
+    # (the F0 transform rounds after every double operation, as numpy does on the host: no fused multiply-add)
+    ("fastsvc_fanout.hip", ["-ffp-contract=off"], "fanout.o"),
     # (the device packer must round where the host packer rounds - x86-64 code without a fused multiply-add, IEEE sqrt and
     # division: no contraction, and the correctly rounded float32 `/` and sqrtf spelled out rather than left to a default)
     ("fastsvc_pack.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"], "pack.o"),

@@ -14,7 +14,8 @@ are read here (``.h5`` as well when h5py is importable - it is not a dependency)
     python -m svcc23_fastsvc_amd.decode --dumpdir feats/ --checkpoint ckpt.pkl --config conf.yaml \\
         --outdir wav/ --spk-emb embs.npz --srcf0stats src_stats/ --trgf0stats trg_stats/
 
-``--resident`` keeps the features on the device across target speakers (``DecodeSession``); with it, ``--checked
+``--resident`` keeps the features on the device across target speakers (``DecodeSession``); with it, ``--fanout N`` converts
+the speakers in groups of N whose batches hold (utterance, speaker) rows (``convert_many``: for small source sets), ``--checked
 [--fallback bfloat16,float32]`` reports per utterance what the PCM-16 conversion hides and re-runs in a fallback storage the
 batches whose output is not finite, and ``--storage auto`` is float16 storage with ``--checked --fallback bfloat16``.
 """
@@ -25,7 +26,7 @@ import glob
 import os
 import time
 import wave
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -111,6 +112,41 @@ def flagged_batches(batches: Sequence[Sequence[int]], flagged, among: Optional[S
     flagged = set(int(i) for i in flagged)
     ks = range(len(batches)) if among is None else sorted(set(int(k) for k in among))
     return [k for k in ks if any(int(i) in flagged for i in batches[k])]
+
+
+def fanout_batches(frames: Sequence[int], n_speakers: int, max_batch: int = 32,
+                   pad_tolerance: float = 0.125) -> List[List[Tuple[int, int]]]:
+    """Batches of ``(utterance, speaker)`` rows for ``DecodeSession.convert_many``: ``bucket_ragged`` over the expanded row
+    list ``r = utterance * n_speakers + speaker`` with ``n_frames[r] = frames[utterance]``, mapped back to pairs.  Longest
+    first; the rows of one utterance are adjacent, speaker ascending - they share a length and pad nothing - and the
+    utterances follow each other in ``bucket_ragged``'s own order, so with ``n_speakers == 1`` the batches are exactly
+    ``bucket_ragged(range(len(frames)), frames, ...)``'s."""
+    S = int(n_speakers)
+    if S < 1:
+        raise ValueError("fanout_batches needs at least one speaker")
+    n = len(frames) * S
+    rows = bucket_ragged(range(n), [int(frames[r // S]) for r in range(n)], max_batch, pad_tolerance)
+    return [[(r // S, r % S) for r in chunk] for chunk in rows]
+
+
+def fanout_layout(chunk: Sequence[Tuple[int, int]], counts: Sequence[int], offsets: Sequence[int]):
+    """Where the rows of one fan-out batch go: ``(row_offsets, runs, total)``.  The batch's packed buffer is laid
+    ``[speaker][utterance]``: ``row_offsets[j]`` is where row j's ``counts[utterance]`` elements start in it.  A
+    speaker's utterances of one batch follow each other in the session's packing order (``offsets``: ``pack_layout`` in
+    ``bucket_ragged``'s order, which is the order of ``fanout_batches``' utterances, and only a batch's first and last
+    utterance can lack speakers), so each speaker is one contiguous run both there and in its own packed result:
+    ``runs`` holds ``(speaker, first element in the speaker's result, start in the batch's buffer, count)``."""
+    by_spk: Dict[int, List[int]] = {}
+    for j, (_, sp) in enumerate(chunk):
+        by_spk.setdefault(sp, []).append(j)
+    row_offsets, runs, pos = [0] * len(chunk), [], 0
+    for sp in sorted(by_spk):
+        start = pos
+        for j in by_spk[sp]:
+            row_offsets[j] = pos
+            pos += int(counts[chunk[j][0]])
+        runs.append((sp, int(offsets[chunk[by_spk[sp][0]][0]]), start, pos - start))
+    return row_offsets, runs, pos
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
@@ -365,6 +401,8 @@ class DecodeSession:
         self.frames = [int(np.asarray(u["ppg"]).shape[0]) for u in feats]
         self.batches: List[List[int]] = list(bucket_ragged(range(self.n), self.frames, max_batch, pad_tolerance)) if feats else []
         self.uploaded_bytes = {"init": 0, "convert": []}
+        self.max_batch, self.pad_tolerance = int(max_batch), float(pad_tolerance)
+        self._fan = None                             # (convert_many's resident extras, made by its first call)
         self._closed = False
         self._ready = None
         self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = None
@@ -443,7 +481,7 @@ class DecodeSession:
             self._copy_stream.synchronize()
             torch.cuda.current_stream(self.device).synchronize()
         self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = self._h_rep = None
-        self._lft_rows = self._down = self._ready = None
+        self._lft_rows = self._down = self._ready = self._fan = None
 
     @torch.no_grad()
     def convert(self, trg_emb=None, trg_f0_stats: Optional[Sequence[float]] = None, pcm16: bool = True) -> List[np.ndarray]:
@@ -602,6 +640,222 @@ class DecodeSession:
         return out  # type: ignore[return-value]
 
 
+    def _fanout_init(self) -> None:
+        """convert_many's resident extras, made once: f0 packed like lft (utterance i's frames at ``_lft_off[i] / hop``),
+        float32, the values ``convert`` uploads batch by batch; the (n, 2) float64 table of source statistics; and the
+        layout as the ctypes arrays every ``fanout_assemble`` reads."""
+        import ctypes
+        hop, frames, C = self.hop, self.frames, self.channels
+        f0_off = [o // hop for o in self._lft_off]
+        h = np.empty(max(sum(frames), 1), dtype=np.float32)
+        for i, f in enumerate(self._f0):
+            if f.size < frames[i]:
+                raise ValueError(f"utterance {i}: {f.size} f0 values, {frames[i]} expected")
+            h[f0_off[i]: f0_off[i] + frames[i]] = f[: frames[i]]
+        fan = {"f0": torch.from_numpy(h).to(self.device), "src": None, "stage": [None, None]}
+        up = 4 * sum(frames)
+        if self.src_f0_stats is not None:
+            table = np.ascontiguousarray(np.asarray(self.src_f0_stats, dtype=np.float64).reshape(self.n, 2))
+            fan["src"] = torch.from_numpy(table).to(self.device)
+            up += table.nbytes
+        fan["ppg_off"] = (ctypes.c_int64 * self.n)(*self._ppg_off)
+        fan["lft_off"] = (ctypes.c_int64 * self.n)(*self._lft_off)
+        fan["f0_off"] = (ctypes.c_int64 * self.n)(*f0_off)
+        fan["frames"] = (ctypes.c_int32 * self.n)(*frames)
+        self._fan = fan
+        self.uploaded_bytes["fanout_init"] = up
+        self.uploaded_bytes["convert_many"] = []
+
+    @torch.no_grad()
+    def convert_many(self, speakers: Sequence[Tuple[object, Optional[Sequence[float]]]], pcm16: bool = True):
+        """Every utterance converted to every speaker of ``speakers``, a sequence of ``(trg_emb | None, trg_f0_stats |
+        None)`` (all with an embedding or none, all with statistics or none): ``result[s][i]`` is utterance i (the order of
+        ``feats``) for speaker s, the array kinds ``convert`` returns - int16 views of one new array per call
+        (``pcm16=True``) or float32 copies.
+
+        The batches are ``fanout_batches``': their rows are (utterance, speaker) pairs, so a source set smaller than
+        ``max_batch`` still fills its batches, across the speaker axis (the forward couples no rows; it takes a per-row
+        embedding and ``lengths``).  Each batch is one ``fanout_assemble`` launch per 64 rows - ppg, lft, the F0 shift in
+        double precision on the device and the embedding rows, from the resident buffers - one ``signal_generator`` call
+        (batches in order), one forward, and one ``pcm16_pack`` into the batch's ``[speaker][utterance]`` layout (or
+        ``output_check`` with ``pcm16=False``); downloads run one batch behind.  The first call uploads the packed f0 (4
+        bytes a frame) and the table of source statistics, counted once under ``uploaded_bytes["fanout_init"]``; after
+        that a call uploads its speaker tables only (embeddings and statistics; one entry per call in
+        ``uploaded_bytes["convert_many"]``) - no f0 crosses the bus again.  ``convert`` and its accounting do not change.
+
+        Against ``convert``: with one speaker the batches are ``self.batches`` and, without an F0 shift, the result is
+        ``convert``'s bit for bit.  With a shift the device's F0 is within one float32 ulp of the host's
+        (``fastsvc_fanout_assemble``); with several speakers the batches differ, and the waveforms agree to the harness's
+        batching invariance (2e-5 in float32 storage, tests/test_parity_gpu.py).  The excitation noise is seeded per
+        ``signal_generator`` call and row, so with ``noise_amp > 0`` a fan-out pass draws other noise than sequential
+        converts do - as two sequential converts of the same speaker already differ from each other.
+
+        A checked session keeps ``convert``'s semantics per row: a fan-out batch that holds a row with non-finite samples
+        is run again whole in the next fallback storage and only the flagged rows are replaced; ``last_report`` becomes
+        a list per speaker of the per-utterance dicts; ``strict`` names the ``(utterance, speaker)`` pairs; the model's
+        storage is restored also when a forward raises."""
+        if self._closed:
+            raise RuntimeError("DecodeSession is closed")
+        speakers = list(speakers)
+        S = len(speakers)
+        if not self.n or not S:
+            return [[] for _ in speakers]
+        from .engine import FastSVCError, fanout_assemble, output_check, pcm16_pack, report_arrays
+        dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
+        checked = self.checked
+        stream = torch.cuda.current_stream(dev)
+        embs, stats = [e for e, _ in speakers], [t for _, t in speakers]
+        for name, vals in (("an embedding", embs), ("F0 statistics", stats)):
+            if any(v is None for v in vals) and not all(v is None for v in vals):
+                raise ValueError(f"convert_many: every speaker of one call needs {name}, or none does")
+        if self._fan is None:
+            self._fanout_init()
+        fan = self._fan
+        up = 0
+        self.forwards = 0
+        emb_table = stats_table = None
+        if embs[0] is not None:
+            emb_table = torch.from_numpy(np.ascontiguousarray(
+                np.stack([np.asarray(e, dtype=np.float32).reshape(-1) for e in embs]))).to(dev)
+            up += 4 * emb_table.numel()
+        shift = self.src_f0_stats is not None and stats[0] is not None
+        if shift:
+            stats_table = torch.from_numpy(np.ascontiguousarray(
+                np.stack([np.asarray(t, dtype=np.float64).reshape(-1)[:2] for t in stats]))).to(dev)
+            up += 8 * stats_table.numel()
+        batches = fanout_batches(frames, S, self.max_batch, self.pad_tolerance)
+        row_base, pos = [], 0                        # (batch k's rows are rows [row_base[k], + len(batch)) of the pass)
+        for chunk in batches:
+            row_base.append(pos)
+            pos += len(chunk)
+        total = sum(frames) * hop                    # (one speaker's samples: speaker s starts at s * total)
+        h_rep = torch.empty((self.n * S, 4), dtype=torch.int32, pin_memory=True) if checked else None
+        out: List[List[Optional[np.ndarray]]] = [[None] * self.n for _ in range(S)]
+        result = np.empty(S * total, dtype=np.int16) if pcm16 else None
+        if self._ready is not None:                  # (the constructor's uploads, when no convert has waited for them yet)
+            for ev in self._ready:
+                stream.wait_event(ev)
+        plans, pending = {}, {}
+
+        def plan(k: int):
+            if k not in plans:
+                plans[k] = fanout_layout(batches[k], [f * hop for f in frames], self._lft_off)
+            return plans[k]
+
+        def finish(k: int, rows: Optional[Sequence[int]] = None) -> None:
+            """Take batch k's samples out of the page-locked buffers (``rows``: those rows of it only)."""
+            host_y, done = pending.pop(k)
+            done.synchronize()
+            chunk = batches[k]
+            if pcm16:
+                offs, runs, _ = plan(k)
+                h = host_y.numpy()
+                if rows is None:
+                    for sp, first, start, count in runs:
+                        result[sp * total + first: sp * total + first + count] = h[start: start + count]
+                else:
+                    for j in rows:
+                        u, sp = chunk[j]
+                        a, n = sp * total + self._lft_off[u], frames[u] * hop
+                        result[a: a + n] = h[offs[j]: offs[j] + n]
+                return
+            y = host_y.numpy()
+            for j in (range(len(chunk)) if rows is None else rows):
+                u, sp = chunk[j]
+                out[sp][u] = y[j].reshape(-1)[: frames[u] * hop].copy()
+
+        def enqueue(k: int, rows: Optional[Sequence[int]] = None) -> None:
+            """Batch k on the stream, whole: assembly, excitation, forward, packing, downloads.  ``rows`` (a fallback
+            run): only those rows' reports replace the first pass's."""
+            chunk = batches[k]
+            R, fmax = len(chunk), frames[chunk[0][0]]
+            lens = [frames[u] for u, _ in chunk]
+            ppg, lft, f0, emb = fanout_assemble(self._d_ppg, self._d_lft, fan["f0"], fan["ppg_off"], fan["lft_off"],
+                                                fan["f0_off"], fan["frames"], [u for u, _ in chunk], [sp for _, sp in chunk],
+                                                C, hop, fmax, src_stats=fan["src"] if shift else None,
+                                                spk_stats=stats_table, spk_emb=emb_table, n_spk=S)
+            sine = self.signal_generator(f0)
+            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+            self.forwards += 1
+            report = torch.empty((R, 4), dtype=torch.int32, device=dev) if checked else None
+            if pcm16:
+                offs, _, count = plan(k)
+                packed = torch.empty(max(count, 1), dtype=torch.int16, device=dev)
+                pcm16_pack(y.view(R, fmax * hop), [n * hop for n in lens], offs, out=packed, report=report)
+                host_y = fan["stage"][k & 1]
+                if host_y is None or host_y.numel() < packed.numel():
+                    host_y = fan["stage"][k & 1] = torch.empty(packed.numel(), dtype=torch.int16, pin_memory=True)
+                host_y = host_y[: packed.numel()]
+                host_y.copy_(packed, non_blocking=True)
+            else:
+                host_y = self._down[k & 1].get("y", tuple(y.shape))
+                host_y.copy_(y, non_blocking=True)
+                if checked:
+                    output_check(y.view(R, fmax * hop), [n * hop for n in lens], out=report)
+            if checked:
+                r0 = row_base[k]
+                if rows is None:
+                    h_rep[r0: r0 + R].copy_(report, non_blocking=True)
+                else:
+                    for j in rows:
+                        h_rep[r0 + j].copy_(report[j], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+            pending[k] = (host_y, done)
+
+        for k in range(len(batches)):
+            enqueue(k)
+            if k >= 1:
+                finish(k - 1)                        # (while batch k computes; before batch k + 1 reuses that download set)
+        finish(len(batches) - 1)
+        stream.synchronize()
+        if self._ready is not None:                  # every upload has been waited for: the staging can go
+            self._ready = None
+            self._h_ppg = self._h_lft = None
+        still: List[Tuple[int, int]] = []
+        if checked:
+            pairs = [pair for chunk in batches for pair in chunk]            # (row of the pass -> (utterance, speaker))
+            row_batches = [list(range(row_base[k], row_base[k] + len(chunk))) for k, chunk in enumerate(batches)]
+            rep = h_rep.numpy()
+            first = getattr(self.model, "activation_storage", "float32")
+            storage, tried = [first] * len(pairs), [[] for _ in pairs]
+            flagged = [r for r in range(len(pairs)) if rep[r, 0] > 0]
+            again = None
+            try:
+                for name in self.fallback:
+                    again = flagged_batches(row_batches, flagged, again)
+                    if not again:
+                        break
+                    self.model.use_activation_storage(name)
+                    for k in again:                  # (the rare path: one batch at a time)
+                        rows = [j for j, r in enumerate(row_batches[k]) if r in flagged]
+                        enqueue(k, rows)
+                        finish(k, rows)
+                        for j in rows:
+                            r = row_batches[k][j]
+                            tried[r].append(storage[r])
+                            storage[r] = name
+                    flagged = [r for r in flagged if rep[r, 0] > 0]
+            finally:
+                if getattr(self.model, "activation_storage", first) != first:
+                    self.model.use_activation_storage(first)
+            nonfinite, clipped, max_abs = report_arrays(rep)
+            report_of: List[List[Optional[Dict[str, object]]]] = [[None] * self.n for _ in range(S)]
+            for r, (u, sp) in enumerate(pairs):
+                report_of[sp][u] = dict(storage=storage[r], nonfinite=int(nonfinite[r]), clipped=int(clipped[r]),
+                                        max_abs=float(max_abs[r]), tried=tried[r])
+            self.last_report = report_of
+            still = [pairs[r] for r in flagged]
+        if pcm16:
+            out = [[result[sp * total + self._lft_off[i]: sp * total + self._lft_off[i] + frames[i] * hop]
+                    for i in range(self.n)] for sp in range(S)]
+        self.uploaded_bytes["convert_many"].append(up)
+        if still and self.strict:
+            raise FastSVCError(f"(utterance, speaker) pairs {still} still have non-finite samples after storages "
+                               f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
+        return out
+
+
 def _read_f0_mean(stats_dir: str, name: str) -> np.ndarray:
     import yaml
     with open(os.path.join(stats_dir, f"{name}.yml")) as f:
@@ -635,7 +889,15 @@ def main(argv=None) -> None:                                  # pragma: no cover
     ap.add_argument("--resident-bytes", type=int, default=4 << 30,
                     help="device bytes of packed features one resident group may hold (default 4 GiB); a dump directory "
                          "larger than this is decoded group by group")
+    ap.add_argument("--fanout", type=int, default=1,
+                    help="with --resident: convert the target speakers in groups of N by DecodeSession.convert_many, whose "
+                         "batches hold (utterance, speaker) rows - for source sets smaller than --max-batch; same file "
+                         "names (default 1: one convert per speaker)")
     args = ap.parse_args(argv)
+    if args.fanout < 1:
+        ap.error("--fanout needs a group size of at least 1")
+    if args.fanout > 1 and not args.resident:
+        ap.error("--fanout works on the --resident route")
     if args.storage == "auto":
         args.storage, args.checked = "float16", True
     if (args.checked or args.fallback is not None) and not args.resident:
@@ -702,6 +964,18 @@ def resident_groups(files: Sequence[str], budget_bytes: int, hop: int, load=load
         yield paths, feats
 
 
+def speaker_groups(speakers: Sequence, size: int, kind=lambda s: None) -> List[list]:
+    """Consecutive runs of at most ``size`` speakers that share ``kind(speaker)`` - one ``convert_many`` call each (a call
+    takes speakers that all have an embedding and statistics, or all have none)."""
+    groups: List[list] = []
+    for s in speakers:
+        if groups and len(groups[-1]) < size and kind(groups[-1][0]) == kind(s):
+            groups[-1].append(s)
+        else:
+            groups.append([s])
+    return groups
+
+
 def _main_resident(args, config, model, sg, device, files) -> None:      # pragma: no cover - exercised on a GPU box
     """The CLI's speaker loop with the features resident: one session per group of dumps, every target speaker inside it.
     A dump directory that fits one group runs the same batches as the default path, so the files are the same byte for
@@ -718,7 +992,22 @@ def _main_resident(args, config, model, sg, device, files) -> None:      # pragm
             src_stats = [_read_f0_mean(args.srcf0stats, u.split("_")[0]) for u in utt_ids]
         with DecodeSession(model, feats, sg, device, src_stats, args.max_batch, checked=args.checked,
                            fallback=args.fallback) as session:
-            for trgspk in speakers:
+            for group in (speaker_groups(speakers, args.fanout, lambda s: (embs.get(s) is None, s is None))
+                          if args.fanout > 1 else []):
+                trg = []
+                for trgspk in group:
+                    trg_emb = embs.get(trgspk) if config["generator_params"].get("use_spk_emb") else None
+                    trg.append((trg_emb, _read_f0_mean(args.trgf0stats, trgspk) if src_stats is not None and trgspk is not None else None))
+                t0 = time.time()
+                pcms = session.convert_many(trg)
+                dt = (time.time() - t0) / len(group)
+                for k, (trgspk, pcm) in enumerate(zip(group, pcms)):
+                    spent[trgspk] += dt
+                    samples[trgspk] += sum(len(p) for p in pcm)
+                    reports[trgspk] += session.last_report[k] if args.checked else []
+                    for utt, p in zip(utt_ids, pcm):
+                        write_wav(os.path.join(args.outdir, f"{utt}_{trgspk}_gen.wav"), p, config["sampling_rate"])
+            for trgspk in (speakers if args.fanout == 1 else []):
                 trg_emb = embs.get(trgspk) if config["generator_params"].get("use_spk_emb") else None
                 trg_stats = None
                 if src_stats is not None and trgspk is not None:

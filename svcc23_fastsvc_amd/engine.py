@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "fastsvc_gather_padded", "fastsvc_gather_time_major", "fastsvc_pcm16_pack",
     "fastsvc_pcm16_pack_checked", "fastsvc_output_check",
     "fastsvc_collate_launch_count", "fastsvc_collate_crops",
+    "fastsvc_fanout_launch_count", "fastsvc_fanout_assemble",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -172,6 +173,11 @@ def load_library():
     lib.fastsvc_collate_crops.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i32),
                                           ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp, vp] + [i32] * 6 + [vp]
     lib.fastsvc_collate_crops.restype = ctypes.c_int
+    lib.fastsvc_fanout_launch_count.argtypes = [i32]
+    lib.fastsvc_fanout_launch_count.restype = ctypes.c_int
+    lib.fastsvc_fanout_assemble.argtypes = [vp, i64, vp, i64, vp, i64, i32] + [ctypes.POINTER(i64)] * 3 + [ctypes.POINTER(i32)] + \
+        [vp, vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp] + [i32] * 5 + [vp]
+    lib.fastsvc_fanout_assemble.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -415,6 +421,87 @@ def collate_crops(wave: torch.Tensor, lft: torch.Tensor, ppg: torch.Tensor, f0: 
         _check(lib, lib.fastsvc_collate_crops(ptr(wave), ptr(lft), wave.numel(), ptr(ppg), ppg.numel(), ptr(f0), f0.numel(),
                                               ptr(emb), U, offs, nfr, us, st, *[ptr(t) for t in outs],
                                               B, D, S, hop, frames, ctx, ctypes.c_void_p(stream)), "fastsvc_collate_crops")
+    return tuple(outs)
+
+
+def fanout_launch_count(R: int) -> int:
+    """Launches one ``fanout_assemble`` of R rows enqueues: one per 64 rows."""
+    return int(load_library().fastsvc_fanout_launch_count(int(R)))
+
+
+def fanout_assemble(ppg: torch.Tensor, lft: torch.Tensor, f0: torch.Tensor, ppg_off: Sequence[int], lft_off: Sequence[int],
+                    f0_off: Sequence[int], n_frames: Sequence[int], utt: Sequence[int], spk: Sequence[int],
+                    C: int, hop: int, width: int, src_stats: Optional[torch.Tensor] = None,
+                    spk_stats: Optional[torch.Tensor] = None, spk_emb: Optional[torch.Tensor] = None, n_spk: Optional[int] = None,
+                    out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """Assemble a decode batch whose rows are (utterance, target speaker) pairs out of a resident session's packed
+    buffers, by ONE HIP launch per 64 rows on the current stream (fastsvc_fanout_assemble, csrc/fastsvc_fanout.hip).
+
+    ``ppg``, ``lft``, ``f0`` are packed 1-D float32 device buffers; utterance u has ``n_frames[u]`` frames, its time-major
+    (n, C) ppg block at element ``ppg_off[u]``, its n * hop lft samples at ``lft_off[u]`` and its n f0 values at
+    ``f0_off[u]``.  Row r is utterance ``utt[r]`` for speaker ``spk[r]``.  Returns ``(ppg (R, C, width), lft (R, 1, width *
+    hop), f0 (R, 1, width), emb (R, E) or None)``: ppg with ``gather_time_major``'s bits, lft with ``gather_padded``'s, f0
+    moved from ``src_stats[utt]`` to ``spk_stats[spk]`` (device float64 tables (U, 2) and (S, 2) of [mean, std];
+    ``decode.F0Statistics.convert`` in double precision, within one float32 ulp; unvoiced and padded frames exactly 0;
+    copied bit for bit when either table is None) and row ``spk`` of ``spk_emb`` (S, E) (None: no embedding is returned).
+    ``n_spk``: the number of speakers when neither table is given (default: 1 + max(spk)).  ``out``: the same four,
+    contiguous float32 tensors to write into.  Anything out of range raises ``ValueError`` before a launch; fails loudly
+    off the GPU."""
+    lib = load_library()
+    named = [("ppg", ppg, torch.float32, 1), ("lft", lft, torch.float32, 1), ("f0", f0, torch.float32, 1)]
+    named += [(n, t, torch.float64, 2) for n, t in (("src_stats", src_stats), ("spk_stats", spk_stats)) if t is not None]
+    if spk_emb is not None:
+        named.append(("spk_emb", spk_emb, torch.float32, 2))
+    for name, t, dtype, dim in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"fanout_assemble needs GPU tensors (no CPU fallback); {name} is on " +
+                               str(getattr(t, "device", type(t))))
+        if t.dtype != dtype or not t.is_contiguous() or t.device != ppg.device or t.dim() != dim:
+            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {ppg.device}")
+    R, U = len(utt), len(n_frames)
+    C, hop, width = int(C), int(hop), int(width)
+    if R == 0 or len(spk) != R or U == 0 or len(ppg_off) != U or len(lft_off) != U or len(f0_off) != U:
+        raise ValueError("fanout_assemble needs at least one row, one speaker per row and three offsets per stored utterance")
+    if src_stats is not None and tuple(src_stats.shape) != (U, 2):
+        raise ValueError(f"src_stats must be ({U}, 2), got {tuple(src_stats.shape)}")
+    tables = [int(t.shape[0]) for t in (spk_stats, spk_emb) if t is not None]
+    if spk_stats is not None and spk_stats.shape[1] != 2:
+        raise ValueError(f"spk_stats must be (S, 2), got {tuple(spk_stats.shape)}")
+    if n_spk is None:
+        n_spk = tables[0] if tables else 1 + max(int(v) for v in spk)
+    n_spk = int(n_spk)
+    if any(n != n_spk for n in tables):
+        raise ValueError(f"spk_stats and spk_emb must hold one row per speaker ({n_spk})")
+    E = int(spk_emb.shape[1]) if spk_emb is not None else 0
+    shapes = [(R, C, width), (R, 1, width * hop), (R, 1, width), (R, E)]
+    if out is None:
+        out = [None] * 4
+    outs = []
+    for i, shp in enumerate(shapes):
+        t = out[i] if i < len(out) else None
+        if i == 3 and spk_emb is None:
+            outs.append(None)
+        elif t is None:
+            outs.append(torch.empty(shp, dtype=torch.float32, device=ppg.device))
+        elif not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError("fanout_assemble needs GPU tensors (no CPU fallback) for out")
+        elif tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ppg.device:
+            raise ValueError(f"out[{i}] must be a contiguous float32 {shp} tensor on {ppg.device}")
+        else:
+            outs.append(t)
+    # (a session hands in the ctypes arrays it made once)
+    i64s = lambda v: v if isinstance(v, ctypes.Array) else (ctypes.c_int64 * U)(*[int(x) for x in v])      # noqa: E731
+    po, lo, fo = i64s(ppg_off), i64s(lft_off), i64s(f0_off)
+    nfr = n_frames if isinstance(n_frames, ctypes.Array) else (ctypes.c_int32 * U)(*[int(v) for v in n_frames])
+    us = (ctypes.c_int32 * R)(*[int(v) for v in utt])
+    ss = (ctypes.c_int32 * R)(*[int(v) for v in spk])
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    with torch.cuda.device(ppg.device):
+        stream = torch.cuda.current_stream(ppg.device).cuda_stream
+        _check(lib, lib.fastsvc_fanout_assemble(ptr(ppg), ppg.numel(), ptr(lft), lft.numel(), ptr(f0), f0.numel(), U,
+                                                po, lo, fo, nfr, ptr(src_stats), ptr(spk_stats), ptr(spk_emb), n_spk, us, ss,
+                                                *[ptr(t) for t in outs], R, C, E, hop, width, ctypes.c_void_p(stream)),
+               "fastsvc_fanout_assemble")
     return tuple(outs)
 
 

@@ -18,7 +18,15 @@ The checked legs (profiles/decode_checked.txt), in float16 activation storage on
     pack alone  pcm16_pack and pcm16_pack(report=) on 32 rows of 160000 samples, alternated, device time per call
 
 The checked median is compared with the min - max spread of the unchecked repetitions of the same run; no threshold.
-    python tools/decode_throughput.py                  (DECODE_LEGS=session or =checked: one of the two parts only)"""
+
+The fan-out leg (DECODE_LEGS=fanout only; profiles/decode_fanout.txt), float32 and bfloat16 storage, one resident session:
+
+    sequential  S convert() calls, one per target speaker           } alternated, DECODE_REPS each, median
+    fan-out     one convert_many() of the S speakers                }
+
+for the first U in {1, 8, 64} utterances with S = 16 speakers, and for U = 512 with S = 2 (the large-corpus case).
+    python tools/decode_throughput.py                  (DECODE_LEGS=session or =checked: one of the two parts only;
+                                                        DECODE_LEGS=fanout: the fan-out leg)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -136,6 +144,45 @@ def checked_legs():
         f.write("\n".join(out) + "\n")
 
 
+def fanout_legs():
+    """Sequential converts against one convert_many, same session, same process."""
+    out = [f"decode fan-out: S sequential DecodeSession.convert() calls against one convert_many() of the same S speakers; "
+           f"utterances of 2 - 10 s (cfg4var), max_batch {MB}, F0 shift on, int16 out, {reps} repetitions, legs alternated, "
+           f"median (min, max); {torch.cuda.get_device_name(0)}"]
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for U, n_spk in ((1, 16), (8, 16), (64, 16), (512, 2)):
+            if U > len(feats):
+                continue
+            sub, fr = feats[:U], frames[:U]
+            r = np.random.default_rng(100 + U)
+            speakers = [(r.standard_normal(cfg.spk_emb_size).astype(np.float32), [4.6 + 0.05 * k, 1.0]) for k in range(n_spk)]
+            unit = sum(fr) * cfg.hop * n_spk
+            with Dc.DecodeSession(m, sub, sg, dev, src[:U], max_batch=MB) as s:
+                seq = lambda: [s.convert(e, t) for e, t in speakers]                         # noqa: E731
+                fan = lambda: s.convert_many(speakers)                                       # noqa: E731
+                want, got = seq(), fan()                                                     # (warm both; compare)
+                diff = max(int(np.abs(a.astype(np.int32) - b.astype(np.int32)).max()) for ws, gs in zip(want, got) for a, b in zip(ws, gs))
+                n_seq, n_fan = len(s.batches) * n_spk, len(Dc.fanout_batches(fr, n_spk, MB, s.pad_tolerance))
+                up = s.uploaded_bytes
+                up_seq, up_fan, up_init = sum(up["convert"]) / n_spk, up["convert_many"][0], up["fanout_init"]
+                del want, got
+                t = {"seq": [], "fan": []}
+                for _ in range(reps):
+                    t["seq"].append(timed(seq)[0])
+                    t["fan"].append(timed(fan)[0])
+            ms, line_s = spread(f"U {U:3d} S {n_spk:2d} sequential ({n_seq} forwards)", t["seq"], unit)
+            mf, line_f = spread(f"U {U:3d} S {n_spk:2d} fan-out    ({n_fan} forwards)", t["fan"], unit)
+            out += [line_s, line_f,
+                    f"    fan-out / sequential time {mf / ms:.3f} (speed-up {ms / mf:.2f} x); largest PCM-16 difference {diff}; "
+                    f"uploads: {up_seq:.0f} B per convert, {up_fan} B per convert_many, {up_init} B once"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_fanout.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 LEGS = os.environ.get("DECODE_LEGS", "all")
 for storage in (("float32", "bfloat16") if LEGS in ("all", "session") else ()):
     m = build_model(storage)
@@ -184,3 +231,5 @@ if LEGS in ("all", "session"):
         f.write("\n".join(lines) + "\n")
 if LEGS in ("all", "checked"):
     checked_legs()
+if LEGS == "fanout":
+    fanout_legs()
