@@ -60,9 +60,12 @@ namespace FASTSVC_ACT_NS {
 // tile's MFMAs only (two whole copies of the unit under an if/else made hipcc spill).
 // NS / SOFF / ADV: the ring holds NS fragments per unit of which this conv's start at slot SOFF; the last conv of the
 // unit advances the ring (a launch with a second operand runs two convs per unit, ConvParams::x2).
-template <int MW, int NW, bool RELOAD, bool OPT_LAST = false, int NS = 3 * MW * HX_NP, int SOFF = 0, bool ADV = true>
+// HOLD (two-per-CU instances, hx_two_cu): when `hold` (wave-uniform: the unit that ends a tile) the ring is neither
+// re-requested nor advanced here - the caller does both behind the tile's epilogue (HxWeightStream::refill), so that the
+// ring's registers are free while the epilogue runs.
+template <int MW, int NW, bool RELOAD, bool OPT_LAST = false, int NS = 3 * MW * HX_NP, int SOFF = 0, bool ADV = true, bool HOLD = false>
 __device__ __forceinline__ void hx_unit_direct(f32x4 (&acc)[NW][MW], const unsigned char* tile, const int (&aoff)[3],
-                                               int lo_off, HxWeightStream<NS>& ws, bool do_last = true) {
+                                               int lo_off, HxWeightStream<NS>& ws, bool do_last = true, bool hold = false) {
     constexpr int NSTEP = 3 * NW;
     // The A fragments are read PF steps ahead.  bfloat16 storage: a step is MW products = 16 MW cycles of the matrix
     // pipe, less than an LDS round trip - one step ahead the consumer stalled at every step (film.3.heads: 2.0k cycles
@@ -79,13 +82,13 @@ __device__ __forceinline__ void hx_unit_direct(f32x4 (&acc)[NW][MW], const unsig
             __builtin_amdgcn_sched_barrier(0);                 // reads stay ahead of the MFMAs
         }
         if (!OPT_LAST || n + 1 < NW || do_last) hx_step<MW, OPT_LAST>(acc[n], a[s % (PF + 1)], &ws.wr[SOFF + tap * MW * HX_NP]);
-        if (RELOAD && n + 1 == NW) {                            // last use of this tap's fragments
+        if (RELOAD && n + 1 == NW && !(HOLD && hold)) {         // last use of this tap's fragments
             #pragma unroll
             for (int q = 0; q < MW * HX_NP; ++q) ws.request(SOFF + tap * MW * HX_NP + q);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (RELOAD && ADV) ws.advance();
+    if (RELOAD && ADV && !(HOLD && hold)) ws.advance();
 }
 
 // DIRECT unit whose weight fragments are read from LDS (`wl`: this unit's [tap][m][piece] KB-sized fragments,
@@ -534,8 +537,26 @@ constexpr bool hx_estage() {
 template <int MW, int NW, int MODE, int EPI>
 constexpr bool hx_est2() { return hx_estage<MW, NW, MODE, EPI>() && MW * NW <= 4; }
 
-template <int MW, int NW, int MODE, int EPI, int S = 1>
+// 2-byte storages, the C = 48 FiLM-affine convs (up.2.d9, up.2.d3x: MW 3, NW 2): re-budgeted to 128 VGPRs so that a CU
+// holds two workgroups, like their C = 24 twins.  What the budget took: the weight ring is empty while a tile's epilogue
+// runs (hx_unit_direct HOLD: the next tile's first fragments are requested behind the epilogue instead of under the
+// tile's last products - the consumers then wait for them at the unit barrier, where they wait for the staging waves
+// anyway), and the lanes' float64 InstanceNorm sums live in LDS between tiles, one private slot per lane (the same
+// additions in the same order as the register-held sums: bit-identical).  The row-end instances (TAILK) keep their budget.
+template <int MW, int NW, int MODE, int EPI, bool TAILK = false>
+constexpr bool hx_two_cu() {
+#ifdef FASTSVC_ACT_2B
+    return MODE == MODE_DIRECT && MW == 3 && NW == 2 && EPI == EPI_AFF && !TAILK;
+#else
+    return false;
+#endif
+}
+// the lanes' InstanceNorm sums of such an instance: [wave][m][sum, sum of squares][lane] float64
+template <int MW> constexpr int hx_gsum_bytes() { return 4 * MW * 2 * 64 * (int)sizeof(double); }
+
+template <int MW, int NW, int MODE, int EPI, int S = 1, bool TAILK = false>
 constexpr int hx_min_waves() {
+    if (hx_two_cu<MW, NW, MODE, EPI, TAILK>()) return 4;        // (no spill, no scratch: tests/test_hx_budget.py)
 #ifdef FASTSVC_ACT_2B
     // ... and the C = 24 middle conv with its second operand (bfloat16 storage): it sits at the edge of the budget, and
     // past it the CU holds one workgroup instead of two (measured 948 -> 1147 us at 64 x 240000)
@@ -603,7 +624,7 @@ constexpr bool hx_w8(int MODE, bool tailk, int S) {      // (the decimating pair
 }
 
 template <int MW, int NW, int WM, int WN, int MODE, int EPI, int S, bool WSTATIC, bool TAILK = false>
-__global__ __launch_bounds__(512, (hx_min_waves<MW, NW, MODE, EPI, S>()))
+__global__ __launch_bounds__(512, (hx_min_waves<MW, NW, MODE, EPI, S, TAILK>()))
 void conv_hx_kernel(const ConvParams p0) {
     constexpr bool UPH = MODE == MODE_UPHEAD;                          // conv_first -> {stretched residual conv, stretched up conv + FiLM affine}
     constexpr bool POLY = MODE == MODE_POLY, DEC2 = MODE == MODE_DEC2, CHAIN = MODE == MODE_CHAIN || MODE == MODE_CHAIN1 || UPH;
@@ -682,7 +703,7 @@ void conv_hx_kernel(const ConvParams p0) {
     // Two workgroups share a CU in the 128-VGPR variants.  Dispatched together they would run their phases
     // in lockstep (both load, both multiply, both store): the second one of a CU (workgroup ids 256 apart
     // in dispatch order) starts about half a unit late, so one stores while the other multiplies.
-    if constexpr (hx_min_waves<MW, NW, MODE, EPI, S>() >= 4) {
+    if constexpr (hx_min_waves<MW, NW, MODE, EPI, S, TAILK>() >= 4) {
         const int wg_id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
         if ((wg_id >> 8) & 1) {
             for (int k = 0; k < p.stagger; ++k) __builtin_amdgcn_s_sleep(16);      // 16 x 64 cycles per step
@@ -1309,7 +1330,8 @@ void conv_hx_kernel(const ConvParams p0) {
         float s1[MW], s2[MW];
         // small tiles: the lane's InstanceNorm sums of ALL tiles stay in registers and the rows are joined once, after the
         // loop (larger tiles have no registers to spare: per tile, through LDS atomics)
-        constexpr bool GSTAT = MODE == MODE_DIRECT && (MW * NW <= 6 || (MW == 3 && NW == 4));   // (3 x 4: 202 -> 214 registers of 256)
+        constexpr bool TWO = hx_two_cu<MW, NW, MODE, EPI, TAILK>();       // two workgroups per CU: see hx_two_cu
+        constexpr bool GSTAT = !TWO && MODE == MODE_DIRECT && (MW * NW <= 6 || (MW == 3 && NW == 4));   // (3 x 4: 202 -> 214 registers of 256)
         double g1[GSTAT ? MW : 1], g2[GSTAT ? MW : 1];
         #pragma unroll
         for (int m = 0; m < (GSTAT ? MW : 1); ++m) g1[m] = g2[m] = 0.0;
@@ -1400,6 +1422,16 @@ void conv_hx_kernel(const ConvParams p0) {
         float* Xw = const_cast<float*>(reinterpret_cast<const float*>(tiles + 2 * bufsz)) + (EST2 ? 2 : 1) * est_set +
                     cw * (16 * 36);
         (void)Xw;
+        // TWO: this lane's float64 InstanceNorm sums of all its tiles, behind the patches ([m][sum, squares][lane]: only
+        // this lane ever touches its slots - no fence, no barrier; the same additions in the same order as g1 / g2)
+        double* Gw = nullptr;
+        if constexpr (TWO) {
+            Gw = reinterpret_cast<double*>(const_cast<unsigned char*>(tiles) + 2 * bufsz + sizeof(float) * (est_set + 4 * 16 * 36)) +
+                 cw * (MW * 2 * 64) + lane;
+            #pragma unroll
+            for (int q = 0; q < MW * 2; ++q) Gw[q * 64] = 0.0;
+        }
+        (void)Gw;
         stamp(2);
         setup_shared();
         if constexpr (HX_NP == 2) {
@@ -1599,6 +1631,7 @@ void conv_hx_kernel(const ConvParams p0) {
                     ++u;
                     if (active) {
                         if constexpr (XSPLIT) hx_unit_direct<MW, NW, !WSTATIC>(accX, tiles + bufsz, aoffX, lo_off, wstX);
+                        else if constexpr (TWO) hx_unit_direct<MW, NW, !WSTATIC, false, NSLOT, 0, true, true>(acc, tiles + bufsz, aoffX, lo_off, wstX, true, ch + 1 == nch);
                         else hx_unit_direct<MW, NW, !WSTATIC>(acc, tiles + bufsz, aoffX, lo_off, wstX);
                     }
                     stamp(7);
@@ -1611,16 +1644,19 @@ void conv_hx_kernel(const ConvParams p0) {
                         }
                         #pragma unroll
                         for (int m = 0; m < MW; ++m) { s1[m] = 0.f; s2[m] = 0.f; }
-                        if constexpr (EST) { if (active) ws_epilogue_stage_wait<NSLOT>(!WSTATIC); }
+                        // (TWO: the held unit left nothing younger than the staged pieces in flight)
+                        if constexpr (EST) { if (active) ws_epilogue_stage_wait<NSLOT>(!WSTATIC && !TWO); }
 #ifdef FASTSVC_ACT_2B
                         if constexpr (PAIRS) hx_epilogue8<MW, NW / 2, EPI, EST, false, false>(p, R, acc, s1, s2, sig, mg, tcolw, active, lane, K, Ew, Xw);
                         else
 #endif
                         ws_epilogue_kind<MW, NW, EPI, EST, 0, -1>(p, R, acc, s1, s2, sig, mg, tcolw, active, lane, K, Ew);
+                        if constexpr (TWO && !WSTATIC) { if (active) wstX.refill(); }      // the next tile's first fragments
                         if (flags & F_STATS) {
                             #pragma unroll
                             for (int m = 0; m < MW; ++m) {
-                                if constexpr (GSTAT) { g1[m] += (double)s1[m]; g2[m] += (double)s2[m]; }
+                                if constexpr (TWO) { Gw[(2 * m) * 64] += (double)s1[m]; Gw[(2 * m + 1) * 64] += (double)s2[m]; }
+                                else if constexpr (GSTAT) { g1[m] += (double)s1[m]; g2[m] += (double)s2[m]; }
                                 else {
                                     float a1 = s1[m], a2 = s2[m];
                                     a1 = row_xsum(a1); a2 = row_xsum(a2);
@@ -1672,6 +1708,7 @@ void conv_hx_kernel(const ConvParams p0) {
                 if (active && !(FASTSVC_DBG_ON(p, DBG_NO_MFMA))) {
                     if constexpr (POLY) hx_unit_poly<MW, NW, !WSTATIC>(acc3, tiles + (u & 1) * bufsz, aoff, lo_off, wst);
                     else if constexpr (DEC2) hx_unit_dec2<MW, NW, !WSTATIC>(acc2, tiles + (u & 1) * bufsz, aoff, lo_off, raw_off, wst);
+                    else if constexpr (TWO) hx_unit_direct<MW, NW, !WSTATIC, false, NSLOT, 0, true, true>(acc, tiles + (u & 1) * bufsz, aoff, lo_off, wst, true, ch + 1 == nch);
                     else hx_unit_direct<MW, NW, !WSTATIC>(acc, tiles + (u & 1) * bufsz, aoff, lo_off, wst);
                 }
                 stamp(7);
@@ -1697,7 +1734,8 @@ void conv_hx_kernel(const ConvParams p0) {
                             hx_wait_vmcnt(ndma + nst);
                         }
                     } else
-                    if constexpr (EST) { if (active) ws_epilogue_stage_wait<NSLOT>(!WSTATIC && !(FASTSVC_DBG_ON(p, DBG_NO_MFMA))); }
+                    // (TWO: the held unit left nothing younger than the staged pieces in flight)
+                    if constexpr (EST) { if (active) ws_epilogue_stage_wait<NSLOT>(!WSTATIC && !TWO && !(FASTSVC_DBG_ON(p, DBG_NO_MFMA))); }
                     stamp(10);                         // (timeline build: the staged operands have landed)
                     if constexpr (POLY) {
 #ifdef FASTSVC_ACT_2B
@@ -1743,12 +1781,16 @@ void conv_hx_kernel(const ConvParams p0) {
                                 hx_last_reduce<MW, NW, PAIRS>(p, acc, k_last, b_last, b, (tile0 + tl) * NT + wave_n * (NW * 16), lane);
                         }
                     }
+                    if constexpr (TWO && !WSTATIC) {       // the next tile's first fragments (the held unit's re-requests)
+                        if (active && !(FASTSVC_DBG_ON(p, DBG_NO_MFMA))) wst.refill();
+                    }
                     stamp(11);                         // (timeline build: tile epilogue issued)
                     if constexpr (TRACKS) { if (p.amax_out) amax_tile_flush(R); }
                     if ((flags & F_STATS) && !(FASTSVC_DBG_ON(p, DBG_NO_EPILOGUE))) {
                         #pragma unroll
                         for (int m = 0; m < MW; ++m) {
-                            if constexpr (GSTAT) { g1[m] += (double)s1[m]; g2[m] += (double)s2[m]; }
+                            if constexpr (TWO) { Gw[(2 * m) * 64] += (double)s1[m]; Gw[(2 * m + 1) * 64] += (double)s2[m]; }
+                            else if constexpr (GSTAT) { g1[m] += (double)s1[m]; g2[m] += (double)s2[m]; }
                             else {
                                 float a1 = s1[m], a2 = s2[m];
                                 a1 = row_xsum(a1); a2 = row_xsum(a2);
@@ -1767,13 +1809,14 @@ void conv_hx_kernel(const ConvParams p0) {
             }
         }
         if constexpr (TRACKS) amax_flush(p, R, &s_amax, &s_cnt, 4, sig, b, lane, blockIdx.x);   // (float32 storage: the next conv's split-binary16 scale)
-        if constexpr (GSTAT) {
+        if constexpr (GSTAT || TWO) {
             // the lanes' InstanceNorm partial sums of all tiles: rows joined once per workgroup (per tile that was two
             // cross-row exchanges and two LDS atomics per channel tile inside a divergent region)
             if ((flags & F_STATS) && !(FASTSVC_DBG_ON(p, DBG_NO_EPILOGUE))) {
                 #pragma unroll
                 for (int m = 0; m < MW; ++m) {
-                    double a1 = g1[m], a2 = g2[m];
+                    double a1 = g1[GSTAT ? m : 0], a2 = g2[GSTAT ? m : 0];
+                    if constexpr (TWO) { a1 = Gw[(2 * m) * 64]; a2 = Gw[(2 * m + 1) * 64]; }
                     a1 += __shfl_xor(a1, 16); a2 += __shfl_xor(a2, 16);
                     a1 += __shfl_xor(a1, 32); a2 += __shfl_xor(a2, 32);
                     if (active && lane < 16) {
@@ -1893,6 +1936,8 @@ static hipError_t hx_launch_shape(const ConvParams& p, int nsig, hipStream_t str
             ((kind == EPI_AFF && hx_est2<MW, NW, MODE_DIRECT, EPI_AFF>()) || (kind == EPI_RES && hx_est2<MW, NW, MODE_DIRECT, EPI_RES>())))
             est *= 2;                                                              // one K chunk: two slot sets (EST2, the next tile's operands)
         if (PAIRS) est += sizeof(float) * 4 * 16 * 36;                             // the waves' re-layout patches
+        if (kind == EPI_AFF && hx_two_cu<MW, NW, MODE_DIRECT, EPI_AFF>() && !(p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0)))
+            est += hx_gsum_bytes<MW>();                                            // the lanes' InstanceNorm sums (two-per-CU instances)
         if (p.x2) {
             // second operand (ConvParams::x2): FiLM-affine epilogue, no residual tensor, rows a multiple of 4 long; the
             // stretch factors of the recipe's blocks per channel-tile count (C = 24: x5, one K chunk; C >= 48: x2 / x4)

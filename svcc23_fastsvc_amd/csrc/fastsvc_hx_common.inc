@@ -74,6 +74,12 @@ struct HxWeightStream {
     }
     __device__ __forceinline__ void request(int s) { wr[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, next + s * HX_FRAG, 0); }
     __device__ __forceinline__ void advance() { next += NSLOT * HX_FRAG; if (next >= total) next = 0; }
+    // every slot at once: the re-requests a held unit left out (hx_unit_direct HOLD)
+    __device__ __forceinline__ void refill() {
+        #pragma unroll
+        for (int s = 0; s < NSLOT; ++s) request(s);
+        advance();
+    }
 };
 
 struct HxFrag { hx8 p[HX_NP]; };
