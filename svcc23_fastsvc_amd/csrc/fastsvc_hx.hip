@@ -622,6 +622,22 @@ __device__ __forceinline__ void hx_last_reduce(const ConvParams& p, const f32x4 
 constexpr bool hx_w8(int MODE, bool tailk, int S) {      // (the decimating pair: its compact-input instance, S = 2)
     return FASTSVC_HX_W8 != 0 && HX_NP == 1 && !tailk && (MODE == MODE_DIRECT || MODE == MODE_POLY || (MODE == MODE_DEC2 && S == 2));
 }
+// Halo carry (direct convs without a second operand, 16-byte windows, 128-column tiles): consecutive tiles of a workgroup
+// share 2 halo_al window rows - the last ones of tile t are the first ones of tile t + 1, the same tensor through the same
+// per-(b, c) coefficients, i.e. the same bits, and they are in LDS already.  From a workgroup's second tile on the staging
+// waves request, transform and write only the NT = 128 fresh rows [2 halo_al, W) - 16 row octets x 16 channel PAIRS = one
+// (2 channels, 8 rows) item per thread: two 16-byte requests and half the prologue arithmetic of a window item - and
+// copy rows [NT, NT + 2 halo_al) of the previous tile's window of the same K chunk to rows [0, 2 halo_al): NT is a
+// multiple of 8, so hx_lds_off(r, s) - hx_lds_off(r - NT, s) = NT * HX_ROW for every row and slot, and the copy is ONE
+// 16-byte LDS read and write per thread over a contiguous range.  What the consumer waves read does not change.
+// Run-time conditions (wave-uniform, see the staging waves): tpw > 1, at most two K chunks (with three the chunk's
+// buffer has been overwritten in between), 2 halo_al <= NT.  -DFASTSVC_HX_CARRY=0: every tile stages its whole window.
+#ifndef FASTSVC_HX_CARRY
+#define FASTSVC_HX_CARRY 1
+#endif
+constexpr bool hx_carry(int MODE, bool tailk, int S, int NT) {
+    return FASTSVC_HX_CARRY != 0 && hx_w8(MODE, tailk, S) && MODE == MODE_DIRECT && S == 1 && NT == 128;
+}
 
 template <int MW, int NW, int WM, int WN, int MODE, int EPI, int S, bool WSTATIC, bool TAILK = false>
 __global__ __launch_bounds__(512, (hx_min_waves<MW, NW, MODE, EPI, S, TAILK>()))
@@ -1277,6 +1293,152 @@ void conv_hx_kernel(const ConvParams p0) {
         };
         pwin_t pa[ITEMS][8], pb[ITEMS][8];
         unsigned oka = 0, okb = 0;                       // per-item "rows inside the utterance" bits
+        bool carried = false;
+#ifdef FASTSVC_ACT_2B
+        if constexpr (hx_carry(MODE, TAILK, S, NT)) {
+            // ---- halo carry (see hx_carry): whole windows for the workgroup's first tile, fresh rows + an LDS copy behind it.
+            // ONE wave-uniform branch around the whole staging loop; inside, requests and commits are straight-line as below.
+            carried = p.tpw > 1 && nch <= 2 && 2 * halo_al <= NT && 8 * halo_al <= NPROD_T;
+            if (carried) {
+                // fresh item = (channels 2 f_pair, 2 f_pair + 1; window rows 2 halo_al + 8 f_oct .. + 8): 16 x 16 items
+                const int f_pair = ptid & 15, f_oct = ptid >> 4;
+                const int f_row = 2 * halo_al + 8 * f_oct;
+                auto ploadF = [&](int un, act4_t (&px)[4], unsigned& nv) {
+                    const int tl = l_tl, ch = l_ch;
+                    pos_next(l_tl, l_ch);
+                    const int t = (tile0 + tl) * NT - halo_al + f_row;            // a multiple of 8, like a window item's
+                    const int soff = ch * HX_KC * p.ldx * 4;
+                    const int rows_left = p.CIN - ch * HX_KC;
+                    const bool live = ((unsigned)t < (unsigned)p.T) & (un < nunits) & !(FASTSVC_DBG_ON(p, DBG_NO_LOAD));
+                    nv = live ? (unsigned)min(8, p.T - t) : 0u;                   // 8, or 4 at the row's end
+                    #pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const int r = f_pair * 2 + c;
+                        typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
+                        const u32x4w w = __builtin_amdgcn_raw_buffer_load_b128(xr, (live & (r < rows_left)) ? (r * p.ldx + t) * 2 : OOB_OFF, soff >> 1, FASTSVC_LD_AUX);
+                        px[2 * c] = act4_t{w.x, w.y};
+                        px[2 * c + 1] = act4_t{w.z, w.w};
+                    }
+                };
+                // the same FMA, LeakyReLU and rounding per value as pcommit's 16-byte-window branch: 4 bytes per row
+                auto pcommitF = [&](const act4_t (&pw)[4], unsigned nvi, unsigned char* tile) {
+                    if (FASTSVC_DBG_ON(p, DBG_NO_COMMIT)) return;
+                    const int ch = c_ch;
+                    { int dummy = 0; pos_next(dummy, c_ch); }
+                    const bool row_end = (p.T & 7) != 0;       // (wave-uniform) the last item of a row holds 4 rows of it
+                    const f32x4 cf = *reinterpret_cast<const f32x4*>(ncoef + (nvi != 0 ? ch * HX_KC + f_pair * 2 : CINp));
+                    const float A[2] = {cf.x, cf.z};
+                    const float Bc[2] = {cf.y, cf.w};
+                    f32x4 px[4];
+                    #pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        act4_t w = pw[c];
+                        asm volatile("" : "+v"(w));            // (the conversion stays behind the unit barrier, see pcommit)
+                        px[c] = act_unpack4(w);
+                    }
+                    #pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        float e[2];
+                        #pragma unroll
+                        for (int c = 0; c < 2; ++c) e[c] = px[2 * c + (j >> 2)][j & 3] * A[c] + Bc[c];
+                        if (j >= 4 && row_end) {
+                            #pragma unroll
+                            for (int c = 0; c < 2; ++c) e[c] = nvi > 4 ? e[c] : 0.f;
+                        }
+                        #pragma unroll
+                        for (int c = 0; c < 2; ++c) e[c] = fmaxf(e[c], e[c] * slope);
+                        *reinterpret_cast<unsigned*>(tile + hx_lds_off(f_row + j, f_pair >> 2) + (f_pair & 3) * 4) = a16_pack2(e[0], e[1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+                // carry piece `ptid`: 16 bytes of the 2 halo_al shared rows (64 halo_al bytes, contiguous: see hx_carry);
+                // threads without a piece re-read piece 0 and park what they read in the spare rows behind the window
+                const bool c_live = ptid < 8 * halo_al;
+                const int c_src = NT * HX_ROW + (c_live ? ptid : 0) * 16;
+                const int c_dst = c_live ? ptid * 16 : W * HX_ROW + (ptid & 31) * 16;
+                auto cread = [&](const unsigned char* buf) -> u32x4 { return *reinterpret_cast<const u32x4*>(buf + c_src); };
+                auto cwrite = [&](unsigned char* buf, const u32x4& v) { *reinterpret_cast<u32x4*>(buf + c_dst) = v; };
+                act4_t fa[4], fb[4];
+                unsigned na = 0, nb = 0;
+                if (nch == 1) {
+                    // buffers alternate by tile: tile t + 1's shared rows come out of the buffer the consumers multiply tile t
+                    // from - read-only in that half -, read and written in the half that commits tile t + 1
+                    pload(0, pa, oka);
+                    ploadF(1, fb, nb);
+                    stamp(2);
+                    setup_shared();
+                    pcommit(0, pa, oka, tiles);
+                    stamp(3);
+                    __syncthreads();                           // unit 0 staged
+                    stamp(4);
+                    for (int u = 0; u < nunits; u += 2) {      // (pairs of units, phantom unit and all: as in the loop below)
+                        const u32x4 ca = cread(tiles);
+                        ploadF(u + 2, fa, na);
+                        stamp(9);
+                        cwrite(tiles + bufsz, ca);
+                        pcommitF(fb, nb, tiles + bufsz);
+                        stamp(5);
+                        __syncthreads();                       // end of unit u
+                        stamp(6);
+                        const u32x4 cb = cread(tiles + bufsz);
+                        ploadF(u + 3, fb, nb);
+                        stamp(9);
+                        cwrite(tiles, cb);
+                        pcommitF(fa, na, tiles);
+                        stamp(5);
+                        __syncthreads();                       // end of unit u + 1 (or the phantom one)
+                        stamp(6);
+                    }
+                } else {
+                    // two chunks: a buffer always holds the same chunk, the copy is in place.  Its source rows are fresh rows
+                    // that OTHER threads overwrite in the half that commits the unit, so they are read one half earlier -
+                    // while the consumers multiply from that buffer - and held in registers over the unit barrier
+                    pload(0, pa, oka);
+                    pload(1, pb, okb);
+                    stamp(2);
+                    setup_shared();
+                    pcommit(0, pa, oka, tiles);
+                    stamp(3);
+                    __syncthreads();                           // unit 0 staged
+                    stamp(4);
+                    u32x4 ca = cread(tiles), cb;               // tile 0's units: whole windows
+                    ploadF(2, fa, na);
+                    stamp(9);
+                    pcommit(1, pb, okb, tiles + bufsz);
+                    stamp(5);
+                    __syncthreads();                           // end of unit 0
+                    stamp(6);
+                    cb = cread(tiles + bufsz);
+                    ploadF(3, fb, nb);
+                    stamp(9);
+                    cwrite(tiles, ca);
+                    pcommitF(fa, na, tiles);
+                    stamp(5);
+                    __syncthreads();                           // end of unit 1
+                    stamp(6);
+                    for (int u = 2; u < nunits; u += 2) {      // (nunits is even)
+                        ca = cread(tiles);
+                        ploadF(u + 2, fa, na);
+                        stamp(9);
+                        cwrite(tiles + bufsz, cb);
+                        pcommitF(fb, nb, tiles + bufsz);
+                        stamp(5);
+                        __syncthreads();                       // end of unit u
+                        stamp(6);
+                        cb = cread(tiles + bufsz);
+                        ploadF(u + 3, fb, nb);
+                        stamp(9);
+                        cwrite(tiles, ca);
+                        pcommitF(fa, na, tiles);
+                        stamp(5);
+                        __syncthreads();                       // end of unit u + 1
+                        stamp(6);
+                    }
+                }
+            }
+        }
+#endif
+        if (!carried) {
         // No branch may sit between a load and its use (hipcc then counts vmcnt for the path WITHOUT the
         // newer loads and so waits for them too - a full memory latency per unit): loads and commits are
         // unconditional; past the last unit they fetch nothing (offsets out of range) and stage zeros into the
@@ -1318,6 +1480,7 @@ void conv_hx_kernel(const ConvParams p0) {
             __syncthreads();                           // end of unit u+1 (or the phantom one)
             if (CHAIN && u + 1 < nunits && ((u + 1) % nch) == nch - 1) __syncthreads();
             stamp(6);
+        }
         }
         }
     } else {
