@@ -390,6 +390,64 @@ int fastsvc_fanout_assemble(const float* ppg, int64_t ppg_elems, const float* lf
                             float* ppg_out, float* lft_out, float* f0_out, float* emb_out,
                             int32_t R, int32_t C, int32_t E, int32_t hop, int32_t width, void* stream);
 
+/* Windowed decode (csrc/fastsvc_window.hip; decode.DecodeSession.convert_windowed) - a long utterance runs as overlapping
+ * windows, rows of ragged batches, and the windows' waveforms are cross-faded back into one.  The reference decodes whole
+ * utterances (decode_fastsvc.py:150-200) and has no counterpart.
+ *
+ * Assembly.  Batch row r is a slice of an utterance held in three packed float32 DEVICE buffers: n_frames[r] frames of the
+ * time-major ppg (frames x C) from element ppg_off[r] of `ppg` (ppg_elems floats), and the matching n_frames[r] * hop
+ * samples from element sig_off[r] of `lft` and of `sine` (sig_elems floats each: the two share one layout).  It becomes,
+ * all device float32, contiguous:
+ *   ppg_out (R, C, width)                 the slice transposed to channel-major, every column >= n_frames written as 0
+ *   lft_out, sine_out (R, 1, width * hop) the samples copied bit for bit, the tail written as 0
+ * 0 <= n_frames[r] <= width.  No alignment or % 4 requirement on any offset (16-byte requests where source and destination
+ * addresses allow, element requests elsewhere); no load touches a byte outside the row's own slices and no store a byte
+ * outside the three outputs.  `ppg_off`, `sig_off`, `n_frames` are HOST arrays of R entries, read during the call (their
+ * values travel in the kernel arguments).  Everything is checked on the host BEFORE anything is enqueued - null pointers,
+ * sizes out of range, n_frames > width, a slice that does not lie inside its buffer: FASTSVC_E_INVALID, with the row and
+ * the reason in fastsvc_last_error(); a failed launch is FASTSVC_E_HIP.  One launch per 64 rows
+ * (fastsvc_window_launch_count(R)), asynchronous on `stream`. */
+int fastsvc_window_launch_count(int32_t R);
+int fastsvc_window_assemble(const float* ppg, int64_t ppg_elems, const float* lft, const float* sine, int64_t sig_elems,
+                            const int64_t* ppg_off, const int64_t* sig_off, const int32_t* n_frames,
+                            float* ppg_out, float* lft_out, float* sine_out,
+                            int32_t R, int32_t C, int32_t hop, int32_t width, void* stream);
+
+/* Stitch.  y (B, width) device float32: row r holds a window's waveform, valid for n_samples[r] samples; its core - the
+ * samples of the utterance the window owns - is [core_lo[r], core_hi[r]) of the row.  A window that has a neighbour on a
+ * side shares with it a FADE ZONE of 2 * half samples centred on the boundary: [core_lo - half, core_lo + half) on the
+ * left, [core_hi - half, core_hi + half) on the right, clipped to n_samples (an utterance may end inside a zone).  Every
+ * sample of the utterance is written once: outside the zones the owning row's sample; sample j of a zone
+ *     (1 - w) * y_left + w * y_right,   w = (j + 0.5) / (2 * half),
+ * in float64, the two products and the sum rounded separately - decode.stitch_windows' values bit for bit.  The two rows
+ * of a zone may be in different calls, so each side of a row has a mode (left_mode[r], right_mode[r]):
+ *   0 NONE        no neighbour: the core's edge is the utterance's
+ *   1 STAGE       the neighbour runs in a LATER call: the row's zone samples are copied to stage + src and the zone is
+ *                 not written
+ *   2 FROM_STAGE  the neighbour ran in an EARLIER call on this stream and staged its samples at stage + src: this row
+ *                 writes the blended zone
+ *   3 FROM_Y      the neighbour is a row of this y: its zone samples start at y + src; this row writes the blended zone
+ *   4 SKIP        the neighbour is a row of this y and writes the zone (its side is FROM_Y)
+ * (src: left_src[r] / right_src[r], in float ELEMENTS; `stage` a device buffer of stage_elems floats, may be NULL when no
+ * mode uses it).  So a row writes ONE contiguous run - its core without the zones it does not resolve, with the ones it
+ * does - to element dst_off[r] of dst16 (PCM-16: rint(v * 32767.0) in float64, ties to even, saturated, NaN -> 0; for
+ * samples outside the zones exactly fastsvc_pcm16_pack's value) and / or of dstf (the float64 value rounded to float32);
+ * either may be NULL, both hold dst_elems elements.  16-byte stores where dst_off[r] % 8 == 0; runs must not overlap.
+ * With half == 0 every mode must be NONE and the result is the concatenation of the cores.
+ * `report` (may be NULL): a DEVICE array of n_utts entries; the float32 values of the samples row r writes are ADDED to
+ * report[utt[r]] (counts summed, the maximum of |y| taken - integer atomics only, so the result is bit-reproducible).
+ * Unlike fastsvc_pcm16_pack_checked the entries are NOT cleared: an utterance's windows arrive in several calls; clear
+ * them before the first.
+ * All row arrays are HOST arrays of B entries, read during the call.  Everything is checked on the host before anything is
+ * enqueued: null pointers, sizes, modes, a core or zone outside its row, a slot outside `stage`, neighbour samples outside
+ * y, a run outside [0, dst_elems), two runs of the call that overlap, utt[r] outside [0, n_utts) - FASTSVC_E_INVALID with the row and the reason in
+ * fastsvc_last_error(); a failed launch is FASTSVC_E_HIP.  One launch per 64 rows, asynchronous on `stream`. */
+int fastsvc_window_stitch(const float* y, int32_t B, int32_t width, const int32_t* n_samples,
+                          const int32_t* core_lo, const int32_t* core_hi, int32_t half,
+                          const int32_t* left_mode, const int32_t* right_mode, const int64_t* left_src, const int64_t* right_src,
+                          float* stage, int64_t stage_elems, const int64_t* dst_off, int16_t* dst16, float* dstf,
+                          int64_t dst_elems, const int32_t* utt, fastsvc_row_report* report, int32_t n_utts, void* stream);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

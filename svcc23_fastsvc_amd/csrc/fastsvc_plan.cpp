@@ -2968,6 +2968,8 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
         // The kernels address every tensor of ONE utterance through a 32-bit buffer descriptor and
         // 32-bit byte offsets ((row * pitch + t) * 4, 2*C rows for scale/shift): the largest of those
         // spans must stay below 2 GiB.  (C = 24 at the full rate: ~11 M samples = 7.7 min at 24 kHz.)
+        // synth.max_forward_frames restates this computation in Python (Generator and DecodeSession.convert
+        // refuse before anything is allocated or launched): change the two together.
         long worst = 4L * T;
         long Tk = T;
         for (int k = 0; k < P.n; ++k) { Tk /= P.down[k].scale; worst = std::max(worst, 2L * P.down[k].C * Tk * 4); }   // film_u / ss: 2C rows

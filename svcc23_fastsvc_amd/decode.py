@@ -18,6 +18,8 @@ are read here (``.h5`` as well when h5py is importable - it is not a dependency)
 the speakers in groups of N whose batches hold (utterance, speaker) rows (``convert_many``: for small source sets), ``--checked
 [--fallback bfloat16,float32]`` reports per utterance what the PCM-16 conversion hides and re-runs in a fallback storage the
 batches whose output is not finite, and ``--storage auto`` is float16 storage with ``--checked --fallback bfloat16``.
+``--window CORE[,CONTEXT[,FADE]]`` decodes every utterance as overlapping windows (``convert_windowed``): recordings longer
+than one forward takes, in buffers sized by the window.
 """
 from __future__ import annotations
 
@@ -147,6 +149,228 @@ def fanout_layout(chunk: Sequence[Tuple[int, int]], counts: Sequence[int], offse
             pos += int(counts[chunk[j][0]])
         runs.append((sp, int(offsets[chunk[by_spk[sp][0]][0]]), start, pos - start))
     return row_offsets, runs, pos
+
+
+def receptive_field_frames(cfg) -> int:
+    """Frames of input on either side of an output frame that can influence it, for a generator WITHOUT a speaker
+    embedding (with one, InstanceNorm couples a row's whole time axis): run on the frames ``[lo - R, hi + R)`` of an
+    utterance, the generator's output on ``[lo, hi)`` is the whole-utterance result.  Derived from the layer table
+    (``synth.layer_table``: a k = 3 convolution of dilation d reaches d samples of its own rate to either side), walking
+    the dataflow backwards from ``conv_last`` with the reach held in samples of the current rate:
+
+        up block i (output rate r_i = prod(scales[:i + 1]) samples a frame), reach H of its output:
+            its stretched input is read to  H + d(conv_block3) + d(conv_block2) + d(conv_block1) + d(upsample_block0 /
+            residual_block) samples; a stretch by s turns a reach of h into ceil(h / s) (window edges are frame edges, so
+            they are multiples of s at every rate), and conv_first adds its own;
+            the FiLM scale / shift are read to  H + d(conv_block3) + d(conv_block2) + d(conv_block1); the FiLM net adds
+            conv and conv_scale / conv_shift, the down net of that rate its three convolutions, every decimation by s
+            turns a reach of h into h * s, and the down nets of the higher rates add theirs, up to the full rate.
+
+    The answer is the largest of the reaches at the frame rate (ppg) and at the full rate (lft and the excitation, rounded
+    up to whole frames): 33 for the recipe's generator (scales 2, 4, 4, 5)."""
+    from .synth import layer_table
+    reach = {L.name: (L.ksize // 2) * L.dilation for L in layer_table(cfg) if L.kind != "linear"}
+    scales = [int(v) for v in cfg.upsampling_scales]
+    down_scales = [int(v) for v in cfg.down_scales]
+    n = len(scales)
+    hop = int(np.prod(scales))
+
+    def down_reach(k: int) -> int:
+        p = f"downsampling_lft.{k}"
+        return max(reach[f"{p}.residual_block.0"],
+                   reach[f"{p}.downsample_block.2"] + reach[f"{p}.downsample_block.4"] + reach[f"{p}.downsample_block.6"])
+
+    need = 0                                             # frames
+    H = reach["conv_last"]                               # reach of the last block's output, in its own samples
+    for i in range(n - 1, -1, -1):
+        p, k = f"upsampling_nets.{i}", n - 1 - i
+        blocks = reach[f"{p}.conv_block3.1"] + reach[f"{p}.conv_block2.1"] + reach[f"{p}.conv_block1.1"]
+        # conditioning: FiLM k at this block's rate, then down nets k, k - 1, ..., 0 back to the full rate
+        h = H + blocks + reach[f"film_lft.{k}.conv"] + max(reach[f"film_lft.{k}.conv_scale"], reach[f"film_lft.{k}.conv_shift"])
+        for j in range(k, -1, -1):
+            h = (h + down_reach(j)) * down_scales[j]
+        need = max(need, -(-h // hop))
+        # the block's own input, one rate down
+        h = H + blocks + max(reach[f"{p}.upsample_block0.2"], reach[f"{p}.residual_block.1"])
+        H = -(-h // scales[i]) + reach[f"{p}.conv_first"]
+    return max(need, H)
+
+
+def _check_window_sizes(core: int, context: int, fade: Optional[int] = None) -> None:
+    if core < 4 or core % 4 or context < 0 or context % 4:
+        raise ValueError(f"core and context must be multiples of 4 with core >= 4, got core {core}, context {context}")
+    if fade is not None and (fade < 0 or fade % 2 or fade > min(core, 2 * context)):
+        raise ValueError(f"fade must be even with 0 <= fade <= min(core, 2 * context) = {min(core, 2 * context)}, got {fade}")
+
+
+def window_plan(frames: Sequence[int], core: int, context: int) -> List[Tuple[int, int, int, int, int]]:
+    """Rows ``(utt, in_lo, in_hi, core_lo, core_hi)``, in frames, for ``DecodeSession.convert_windowed``: utterance u of F
+    frames has K = ceil(F / core) windows; window k owns the core ``[k core, min((k + 1) core, F))`` and reads ``[max(0, k
+    core - context), min(F, (k + 1) core + context))``.  An utterance with K = 1 is one row, the whole utterance.  Rows are
+    in utterance order, an utterance's windows ascending.  ``core`` and ``context`` are multiples of 4, ``core >= 4``."""
+    core, context = int(core), int(context)
+    _check_window_sizes(core, context)
+    rows = []
+    for u, F in enumerate(frames):
+        F = int(F)
+        if F < 1:
+            raise ValueError(f"utterance {u} has no frames")
+        for k in range(-(-F // core)):
+            lo, hi = k * core, min((k + 1) * core, F)
+            rows.append((u, max(0, lo - context), min(F, hi + context), lo, hi))
+    return rows
+
+
+def window_batches(rows: Sequence[Tuple[int, int, int, int, int]], max_batch: int = 32,
+                   pad_tolerance: float = 0.125) -> List[List[int]]:
+    """Batches of row indices into ``rows``: ``bucket_ragged`` over the rows' lengths ``in_hi - in_lo``, so windows of many
+    utterances share batches (longest first; rows of one length in ``rows``' order, which keeps an utterance's
+    consecutive windows next to each other)."""
+    return list(bucket_ragged(range(len(rows)), [r[2] - r[1] for r in rows], max_batch, pad_tolerance))
+
+
+def _window_groups(rows):
+    """utterance -> its row indices, ascending window."""
+    by_utt: Dict[int, List[int]] = {}
+    for r, row in enumerate(rows):
+        by_utt.setdefault(int(row[0]), []).append(r)
+    for u, rs in by_utt.items():
+        rs.sort(key=lambda r: rows[r][3])
+        for a, b in zip(rs, rs[1:]):
+            if rows[a][4] != rows[b][3]:
+                raise ValueError(f"utterance {u}: the cores of its windows do not follow each other")
+        if rows[rs[0]][3] != 0:
+            raise ValueError(f"utterance {u}: its first core does not start at frame 0")
+    return by_utt
+
+
+def _check_fade(rows, by_utt, hop: int, fade: int) -> int:
+    """``fade`` against the rows: even, at most the core, and both windows of every boundary cover its zone.  -> half a
+    zone in samples."""
+    fade = int(fade)
+    if fade < 0 or fade % 2:
+        raise ValueError(f"fade must be even and >= 0, got {fade}")
+    half = fade * hop // 2
+    for u, rs in by_utt.items():
+        F = rows[rs[-1]][4]
+        for a, b in zip(rs, rs[1:]):
+            edge = rows[a][4]
+            if fade > rows[a][4] - rows[a][3]:
+                raise ValueError(f"fade {fade} is longer than the core of {rows[a][4] - rows[a][3]} frames")
+            if rows[b][1] * hop > edge * hop - half or rows[a][2] * hop < min(edge * hop + half, F * hop):
+                raise ValueError(f"fade {fade} needs {fade // 2} frames of context on both sides of frame {edge} of "
+                                 f"utterance {u}")
+    return half
+
+
+def stitch_windows(ys: Sequence[np.ndarray], rows: Sequence[Tuple[int, int, int, int, int]], hop: int,
+                   fade: int) -> List[np.ndarray]:
+    """The numpy reference of the stitch, float64: ``ys[r]`` is the waveform of row r of ``rows`` (``window_plan``), its
+    ``(in_hi - in_lo) * hop`` samples; returns one float64 array per utterance (ascending utterance).  Outside the fade
+    zones, sample t of an utterance is the owning window's sample.  Around every interior boundary b = k core hop, with
+    fh = fade hop, the zone ``[b - fh / 2, b + fh / 2)`` (clipped to the utterance) holds ``(1 - w) y_{k-1} + w y_k`` with
+    ``w = (t - (b - fh / 2) + 0.5) / fh``: the two weights sum to 1 and neither reaches 0 or 1.  ``fade`` is even, ``0 <=
+    fade <= min(core, 2 context)``; ``fade = 0`` is plain concatenation of the cores.  PCM-16 of the result is
+    ``to_pcm16``'s rule on these float64 values; its float32 form is their rounding (``astype(np.float32)``)."""
+    hop = int(hop)
+    by_utt = _window_groups(rows)
+    half = _check_fade(rows, by_utt, hop, fade)
+    fh = 2 * half
+    out = []
+    for u in sorted(by_utt):
+        rs = by_utt[u]
+        T = rows[rs[-1]][4] * hop
+        res = np.empty(T, dtype=np.float64)
+        for r in rs:
+            _, in_lo, in_hi, lo, hi = rows[r]
+            y = np.asarray(ys[r]).reshape(-1)
+            if y.size < (in_hi - in_lo) * hop:
+                raise ValueError(f"row {r}: {y.size} samples, {(in_hi - in_lo) * hop} expected")
+            res[lo * hop: hi * hop] = y[(lo - in_lo) * hop: (hi - in_lo) * hop]
+        for a, b in zip(rs, rs[1:]):
+            z0 = rows[a][4] * hop - half
+            z1 = min(z0 + fh, T)
+            if z1 <= z0:
+                continue
+            w = (np.arange(z1 - z0, dtype=np.float64) + 0.5) / fh
+            ya = np.asarray(ys[a], dtype=np.float64).reshape(-1)[z0 - rows[a][1] * hop: z1 - rows[a][1] * hop]
+            yb = np.asarray(ys[b], dtype=np.float64).reshape(-1)[z0 - rows[b][1] * hop: z1 - rows[b][1] * hop]
+            with np.errstate(invalid="ignore"):
+                res[z0:z1] = (1.0 - w) * ya + w * yb
+        out.append(res)
+    return out
+
+
+def stitch_layout(rows: Sequence[Tuple[int, int, int, int, int]], batches: Sequence[Sequence[int]], hop: int, fade: int):
+    """How ``engine.window_stitch`` resolves every fade zone when the rows run batch by batch, in ``batches``' order:
+    ``(per_batch, stage_elems)``.  ``per_batch[k]`` is a dict of per-row lists for batch k (in the batch's row order) -
+    ``n_samples``, ``core_lo``, ``core_hi`` (samples of the row), ``left_mode`` / ``right_mode`` / ``left_src`` /
+    ``right_src`` (see ``fastsvc_window_stitch``), ``dst_off`` (the rows' written runs laid back to back in a per-batch
+    buffer of ``total`` samples), ``utt``, and ``runs``: per row ``(utt, t_lo, t_hi)``, the samples of the utterance it
+    writes - plus ``width`` (the batch's row length in samples) and ``half``.  Both windows of a boundary in one batch: the
+    left one blends straight from the forward's output.  In different batches: the one that runs first stages its zone
+    samples in a slot of ``2 half`` floats, the later one blends; ``stage_elems`` is the size of that buffer."""
+    hop = int(hop)
+    by_utt = _window_groups(rows)
+    half = _check_fade(rows, by_utt, hop, fade)
+    fh = 2 * half
+    where = {}
+    for k, chunk in enumerate(batches):
+        for j, r in enumerate(chunk):
+            if r in where:
+                raise ValueError(f"row {r} is in two batches")
+            where[r] = (k, j)
+    widths = [max(rows[r][2] - rows[r][1] for r in chunk) * hop for chunk in batches]
+    NONE, STAGE, FROM_STAGE, FROM_Y, SKIP = range(5)
+    lmode, rmode, lsrc, rsrc = {}, {}, {}, {}
+    slots = 0
+    for u, rs in by_utt.items():
+        if any(r not in where for r in rs):
+            if all(r not in where for r in rs):
+                continue
+            raise ValueError(f"utterance {u}: only some of its windows are in the batches")
+        if not half:
+            continue
+        for a, b in zip(rs, rs[1:]):
+            (ka, ja), (kb, jb) = where[a], where[b]
+            z0 = rows[a][4] * hop - half                 # the zone's first sample, in the utterance
+            if ka == kb:
+                rmode[a], rsrc[a] = FROM_Y, jb * widths[kb] + (z0 - rows[b][1] * hop)
+                lmode[b] = SKIP
+            elif ka < kb:
+                rmode[a], rsrc[a] = STAGE, slots * fh
+                lmode[b], lsrc[b] = FROM_STAGE, slots * fh
+                slots += 1
+            else:
+                lmode[b], lsrc[b] = STAGE, slots * fh
+                rmode[a], rsrc[a] = FROM_STAGE, slots * fh
+                slots += 1
+    per_batch = []
+    for k, chunk in enumerate(batches):
+        d = {key: [] for key in ("n_samples", "core_lo", "core_hi", "left_mode", "right_mode", "left_src", "right_src",
+                                 "dst_off", "utt", "runs")}
+        pos = 0
+        for r in chunk:
+            u, in_lo, in_hi, lo, hi = rows[r]
+            lm, rm = lmode.get(r, NONE), rmode.get(r, NONE)
+            T = rows[by_utt[u][-1]][4] * hop
+            t_lo = lo * hop - half if lm in (FROM_STAGE, FROM_Y) else min(lo * hop + half, T) if lm != NONE else lo * hop
+            t_hi = min(hi * hop + half, T) if rm in (FROM_STAGE, FROM_Y) else hi * hop - half if rm != NONE else hi * hop
+            t_hi = max(t_hi, t_lo)
+            d["n_samples"].append((in_hi - in_lo) * hop)
+            d["core_lo"].append((lo - in_lo) * hop)
+            d["core_hi"].append((hi - in_lo) * hop)
+            d["left_mode"].append(lm)
+            d["right_mode"].append(rm)
+            d["left_src"].append(lsrc.get(r, 0))
+            d["right_src"].append(rsrc.get(r, 0))
+            d["dst_off"].append(pos)
+            d["utt"].append(u)
+            d["runs"].append((u, t_lo, t_hi))
+            pos += -(-(t_hi - t_lo) // 8) * 8            # (every run starts on a 16-byte boundary of both destinations)
+        d["total"], d["width"], d["half"] = pos, widths[k], half
+        per_batch.append(d)
+    return per_batch, slots * fh
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
@@ -403,6 +627,9 @@ class DecodeSession:
         self.uploaded_bytes = {"init": 0, "convert": []}
         self.max_batch, self.pad_tolerance = int(max_batch), float(pad_tolerance)
         self._fan = None                             # (convert_many's resident extras, made by its first call)
+        # set to a dict to have convert_windowed leave what it made there (tests): "excitation", one device tensor per
+        # utterance, and "batches", per batch (its rows, the assembled excitation rows)
+        self._window_trace: Optional[Dict[str, object]] = None
         self._closed = False
         self._ready = None
         self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = None
@@ -496,7 +723,13 @@ class DecodeSession:
         if not self.n:
             return []
         from .engine import FastSVCError, gather_padded, gather_time_major, output_check, pcm16_pack, report_arrays
+        from .synth import TOO_LONG_HINT, max_forward_frames
         dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
+        cfg = getattr(self.model, "_cfg", None)
+        if cfg is not None and max(frames) > max_forward_frames(cfg):        # (the forward's own limit and words, before any launch)
+            i = int(np.argmax(frames))
+            raise FastSVCError(f"utterance {i} ({frames[i]} frames) is too long for the 32-bit tensor descriptors of the "
+                               f"kernels (one forward takes {max_forward_frames(cfg)} frames): split it" + TOO_LONG_HINT)
         checked = self.checked
         stream = torch.cuda.current_stream(dev)
         up = 0
@@ -639,6 +872,186 @@ class DecodeSession:
                                f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
         return out  # type: ignore[return-value]
 
+
+    @torch.no_grad()
+    def convert_windowed(self, trg_emb=None, trg_f0_stats: Optional[Sequence[float]] = None, core: int = 400,
+                         context: Optional[int] = None, fade: int = 8, pcm16: bool = True) -> List[np.ndarray]:
+        """Every utterance converted to one target speaker as overlapping WINDOWS - for utterances longer than one
+        forward takes (``synth.max_forward_frames``: 69 905 frames for the recipe's generator), and for sets whose
+        lengths differ so much that ``bucket_ragged`` cannot fill batches.  Returns what ``convert`` returns: one array per
+        utterance in the order of ``feats``, int16 (``pcm16=True``) or float32, views of one new array per call.
+
+        ``window_plan(frames, core, context)`` cuts every utterance into windows that own ``core`` frames and read
+        ``context`` more on each side (``context=None``: ``receptive_field_frames`` rounded up to a multiple of 4); an
+        utterance of at most ``core`` frames is one row, the whole utterance, and runs as ``convert`` runs it.  The windows
+        of ALL utterances are bucketed by length (``window_batches``), so device buffers are sized by ``max_batch x (core +
+        2 context)`` frames, never by the longest utterance - apart from what is per sample of the whole set: the resident
+        features, and this call's excitation (4 bytes a sample).  Per batch: one ``window_assemble``, one forward with
+        ``lengths``, one ``window_stitch`` into a per-batch packed buffer; downloads run one batch behind.
+
+        Excitation: the F0 shift (host, as in ``convert``) and the excitation are made ONCE per call for each whole
+        utterance - one ``signal_generator`` call per utterance, in the order of ``feats`` - and the windows take slices:
+        the sine phase and the noise are continuous across windows, and a window's excitation is bit for bit the slice of
+        its utterance's.
+
+        Stitching: ``stitch_windows``' rule - around every interior boundary the two windows are cross-faded linearly over
+        ``fade`` frames in float64 (``fade`` even, ``<= min(core, 2 context)``; 0 concatenates the cores).
+
+        What the result is.  WITHOUT a speaker embedding the generator is a convolution of finite reach, and with
+        ``context >= receptive_field_frames`` every window's core IS the whole-utterance result (to float32 kernel
+        arithmetic: the batching invariance the harness states), so the cross-fade blends two equal signals.  WITH an
+        embedding, InstanceNorm takes its statistics over the row: a window is normalised by ITS OWN mean and variance - as
+        training normalises one-second crops - so the windowed decode is a different, well-defined function: exactly
+        ``stitch_windows`` of every window run alone.  It is NOT the whole-utterance result at any context (DESIGN.md §4.9
+        has the measured differences).
+
+        A checked session reports per UTTERANCE, over the stitched samples (``last_report`` as after ``convert``); an
+        utterance with non-finite samples has ALL its windows run again in the next fallback storage, in batches of their
+        own.  ``uploaded_bytes["convert_windowed"]`` gets one entry per call: the packed f0 (4 bytes a frame) and the
+        embedding."""
+        if self._closed:
+            raise RuntimeError("DecodeSession is closed")
+        if not self.n:
+            return []
+        from .engine import FastSVCError, report_arrays, window_assemble, window_stitch
+        dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
+        core = int(core)
+        if context is None:
+            cfg = getattr(self.model, "_cfg", None)
+            if cfg is None:
+                raise ValueError("convert_windowed needs context= for a model without a generator configuration")
+            context = -(-receptive_field_frames(cfg) // 4) * 4
+        context, fade = int(context), int(fade)
+        _check_window_sizes(core, context, fade)
+        if len(getattr(self.signal_generator, "signal_types", ("sine",))) != 1:
+            raise ValueError("convert_windowed needs a signal generator with one signal type")
+        checked = self.checked
+        stream = torch.cuda.current_stream(dev)
+        self.forwards = 0
+        up = 0
+        emb_row = None
+        if trg_emb is not None:
+            emb_row = torch.as_tensor(np.asarray(trg_emb), dtype=torch.float32).reshape(1, -1).to(dev)
+            up += 4 * emb_row.numel()
+        shift = self.src_f0_stats is not None and trg_f0_stats is not None
+        total = sum(frames) * hop
+        f0_off = [o // hop for o in self._lft_off]       # (f0 packed like lft)
+        # ---- the excitation of every whole utterance, packed like lft
+        hf = self._h_f0.numpy()                          # (page-locked, at least sum(frames) floats)
+        for i in range(self.n):
+            f, n = self._f0[i], frames[i]
+            if f.size < n:
+                raise ValueError(f"utterance {i}: {f.size} f0 values, {n} expected")
+            if shift:
+                f = F0Statistics().convert(f, self.src_f0_stats[i], trg_f0_stats)
+            hf[f0_off[i]: f0_off[i] + n] = f[:n]
+        d_f0 = self._h_f0[: sum(frames)].to(dev, non_blocking=True)
+        up += 4 * sum(frames)
+        if self._ready is not None:                      # (the constructor's uploads, when no convert has waited for them yet)
+            for ev in self._ready:
+                stream.wait_event(ev)
+        d_sine = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+        for i in range(self.n):
+            n = frames[i]
+            e = self.signal_generator(d_f0[f0_off[i]: f0_off[i] + n].view(1, 1, n))
+            d_sine[self._lft_off[i]: self._lft_off[i] + n * hop].copy_(e.view(-1))
+            del e
+        trace = self._window_trace
+        if trace is not None:
+            trace.clear()
+            trace.update(excitation=[d_sine[self._lft_off[i]: self._lft_off[i] + frames[i] * hop].clone() for i in range(self.n)],
+                         batches=[])
+        rows = window_plan(frames, core, context)
+        by_utt: Dict[int, List[int]] = {}
+        for r, row in enumerate(rows):
+            by_utt.setdefault(row[0], []).append(r)
+        result = np.empty(total, dtype=np.int16 if pcm16 else np.float32)
+        d_rep = torch.zeros((self.n, 4), dtype=torch.int32, device=dev) if checked else None
+        n_down = [0, 0]
+
+        def run(row_ids: Sequence[int]) -> None:
+            """One pass over these rows (all windows of their utterances), stitched into ``result``."""
+            batches = [[row_ids[j] for j in chunk]
+                       for chunk in window_batches([rows[r] for r in row_ids], self.max_batch, self.pad_tolerance)]
+            layout, stage_elems = stitch_layout(rows, batches, hop, fade)
+            stage = torch.empty(max(stage_elems, 1), dtype=torch.float32, device=dev)
+            pending = {}
+
+            def finish(k: int) -> None:
+                host, done = pending.pop(k)
+                done.synchronize()
+                h, lay = host.numpy(), layout[k]
+                for (u, t_lo, t_hi), off in zip(lay["runs"], lay["dst_off"]):
+                    a = self._lft_off[u]
+                    result[a + t_lo: a + t_hi] = h[off: off + t_hi - t_lo]
+
+            for k, chunk in enumerate(batches):
+                lay = layout[k]
+                lens = [rows[r][2] - rows[r][1] for r in chunk]
+                width, B = lens[0], len(chunk)
+                ppg, lft, sine = window_assemble(
+                    self._d_ppg, self._d_lft, d_sine, [self._ppg_off[rows[r][0]] + rows[r][1] * C for r in chunk],
+                    [self._lft_off[rows[r][0]] + rows[r][1] * hop for r in chunk], lens, C, hop, width)
+                if trace is not None:
+                    trace["batches"].append(([rows[r] for r in chunk], sine.clone()))
+                emb = None if emb_row is None else emb_row.expand(B, -1).contiguous()
+                y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+                self.forwards += 1
+                packed = torch.empty(max(lay["total"], 1), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
+                window_stitch(y.view(B, width * hop), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"],
+                              lay["left_mode"], lay["right_mode"], lay["left_src"], lay["right_src"], lay["dst_off"],
+                              stage=stage, out_pcm=packed if pcm16 else None, out_float=None if pcm16 else packed,
+                              utt=lay["utt"], report=d_rep)
+                # (a page-locked set per parity, as float32 words; int16 samples are a view of them)
+                words = (packed.numel() + 1) // 2 if pcm16 else packed.numel()
+                host = self._down[n_down[0] & 1].get("w", (max(words, 1),))
+                n_down[0] += 1
+                host = host.view(torch.int16)[: packed.numel()] if pcm16 else host[: packed.numel()]
+                host.copy_(packed, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(stream)
+                pending[k] = (host, done)
+                if k >= 1:
+                    finish(k - 1)                    # (while batch k computes; before batch k + 1 reuses that download set)
+            finish(len(batches) - 1)
+
+        run(list(range(len(rows))))
+        stream.synchronize()
+        if self._ready is not None:                      # every upload has been waited for: the staging can go
+            self._ready = None
+            self._h_ppg = self._h_lft = None
+        still: List[int] = []
+        if checked:
+            rep = d_rep.cpu().numpy()
+            first = getattr(self.model, "activation_storage", "float32")
+            storage, tried = [first] * self.n, [[] for _ in range(self.n)]
+            flagged = [i for i in range(self.n) if rep[i, 0] > 0]
+            try:
+                for name in self.fallback:
+                    if not flagged:
+                        break
+                    self.model.use_activation_storage(name)
+                    d_rep[torch.as_tensor(flagged, device=dev)] = 0
+                    run([r for i in flagged for r in by_utt[i]])       # (the rare path: batches of the flagged windows only)
+                    stream.synchronize()
+                    rep = d_rep.cpu().numpy()
+                    for i in flagged:
+                        tried[i].append(storage[i])
+                        storage[i] = name
+                    flagged = [i for i in flagged if rep[i, 0] > 0]
+            finally:
+                if getattr(self.model, "activation_storage", first) != first:
+                    self.model.use_activation_storage(first)
+            nonfinite, clipped, max_abs = report_arrays(rep)
+            self.last_report = [dict(storage=storage[i], nonfinite=int(nonfinite[i]), clipped=int(clipped[i]),
+                                     max_abs=float(max_abs[i]), tried=tried[i]) for i in range(self.n)]
+            still = flagged
+        out = [result[self._lft_off[i]: self._lft_off[i] + frames[i] * hop] for i in range(self.n)]
+        self.uploaded_bytes.setdefault("convert_windowed", []).append(up)
+        if still and self.strict:
+            raise FastSVCError(f"utterances {still} still have non-finite samples after storages "
+                               f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
+        return out
 
     def _fanout_init(self) -> None:
         """convert_many's resident extras, made once: f0 packed like lft (utterance i's frames at ``_lft_off[i] / hop``),
@@ -893,7 +1306,22 @@ def main(argv=None) -> None:                                  # pragma: no cover
                     help="with --resident: convert the target speakers in groups of N by DecodeSession.convert_many, whose "
                          "batches hold (utterance, speaker) rows - for source sets smaller than --max-batch; same file "
                          "names (default 1: one convert per speaker)")
+    ap.add_argument("--window", default=None, metavar="CORE[,CONTEXT[,FADE]]",
+                    help="with --resident: decode every utterance as overlapping windows of CORE frames "
+                         "(DecodeSession.convert_windowed; CONTEXT frames read on each side, default the generator's "
+                         "receptive field; cross-fade over FADE frames, default 8) - for recordings longer than one forward "
+                         "takes; with a speaker embedding InstanceNorm then normalises per window")
     args = ap.parse_args(argv)
+    if args.window is not None:
+        if not args.resident or args.fanout > 1:
+            ap.error("--window works on the --resident route, without --fanout")
+        try:
+            parts = [int(v) for v in args.window.split(",")]
+            if not 1 <= len(parts) <= 3:
+                raise ValueError
+        except ValueError:
+            ap.error("--window takes CORE[,CONTEXT[,FADE]] in frames")
+        args.window = dict(zip(("core", "context", "fade"), parts))
     if args.fanout < 1:
         ap.error("--fanout needs a group size of at least 1")
     if args.fanout > 1 and not args.resident:
@@ -1013,7 +1441,8 @@ def _main_resident(args, config, model, sg, device, files) -> None:      # pragm
                 if src_stats is not None and trgspk is not None:
                     trg_stats = _read_f0_mean(args.trgf0stats, trgspk)
                 t0 = time.time()
-                pcm = session.convert(trg_emb, trg_stats)
+                pcm = session.convert(trg_emb, trg_stats) if args.window is None else \
+                    session.convert_windowed(trg_emb, trg_stats, **args.window)
                 spent[trgspk] += time.time() - t0
                 samples[trgspk] += sum(len(p) for p in pcm)
                 reports[trgspk] += session.last_report if args.checked else []

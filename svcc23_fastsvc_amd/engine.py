@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "fastsvc_pcm16_pack_checked", "fastsvc_output_check",
     "fastsvc_collate_launch_count", "fastsvc_collate_crops",
     "fastsvc_fanout_launch_count", "fastsvc_fanout_assemble",
+    "fastsvc_window_launch_count", "fastsvc_window_assemble", "fastsvc_window_stitch",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -178,6 +179,14 @@ def load_library():
     lib.fastsvc_fanout_assemble.argtypes = [vp, i64, vp, i64, vp, i64, i32] + [ctypes.POINTER(i64)] * 3 + [ctypes.POINTER(i32)] + \
         [vp, vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp] + [i32] * 5 + [vp]
     lib.fastsvc_fanout_assemble.restype = ctypes.c_int
+    lib.fastsvc_window_launch_count.argtypes = [i32]
+    lib.fastsvc_window_launch_count.restype = ctypes.c_int
+    lib.fastsvc_window_assemble.argtypes = [vp, i64, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                            vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.fastsvc_window_assemble.restype = ctypes.c_int
+    lib.fastsvc_window_stitch.argtypes = [vp, i32, i32] + [ctypes.POINTER(i32)] * 3 + [i32] + [ctypes.POINTER(i32)] * 2 + \
+        [ctypes.POINTER(i64)] * 2 + [vp, i64, ctypes.POINTER(i64), vp, vp, i64, ctypes.POINTER(i32), vp, i32, vp]
+    lib.fastsvc_window_stitch.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -505,9 +514,129 @@ def fanout_assemble(ppg: torch.Tensor, lft: torch.Tensor, f0: torch.Tensor, ppg_
     return tuple(outs)
 
 
+def window_launch_count(R: int) -> int:
+    """Launches one ``window_assemble`` (or ``window_stitch``) of R rows enqueues: one per 64 rows."""
+    return int(load_library().fastsvc_window_launch_count(int(R)))
+
+
+def window_assemble(ppg: torch.Tensor, lft: torch.Tensor, sine: torch.Tensor, ppg_off: Sequence[int], sig_off: Sequence[int],
+                    n_frames: Sequence[int], C: int, hop: int, width: int,
+                    out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """Assemble a decode batch whose rows are SLICES of utterances - the windows of ``DecodeSession.convert_windowed`` -
+    out of packed buffers, by ONE HIP launch per 64 rows on the current stream (fastsvc_window_assemble,
+    csrc/fastsvc_window.hip).
+
+    ``ppg``, ``lft``, ``sine`` are packed 1-D float32 device buffers, ``lft`` and ``sine`` of one size and layout.  Row r is
+    ``n_frames[r]`` frames: the time-major (n, C) ppg slice at element ``ppg_off[r]`` and the n * hop samples of ``lft`` and
+    ``sine`` at element ``sig_off[r]``.  Returns ``(ppg (R, C, width), lft (R, 1, width * hop), sine (R, 1, width * hop))``:
+    the ppg slice transposed (``gather_time_major``'s bits), the samples copied bit for bit, everything past a row's
+    length exactly zero.  No alignment requirement on the offsets.  ``out``: the same three, contiguous float32 tensors to
+    write into.  Anything out of range raises ``ValueError`` before a launch; fails loudly off the GPU."""
+    lib = load_library()
+    for name, t in (("ppg", ppg), ("lft", lft), ("sine", sine)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"window_assemble needs GPU tensors (no CPU fallback); {name} is on " +
+                               str(getattr(t, "device", type(t))))
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != ppg.device or t.dim() != 1:
+            raise ValueError(f"{name} must be a contiguous 1-D float32 tensor on {ppg.device}")
+    if lft.numel() != sine.numel():
+        raise ValueError("lft and sine must hold the same number of samples")
+    R = len(n_frames)
+    C, hop, width = int(C), int(hop), int(width)
+    if R == 0 or len(ppg_off) != R or len(sig_off) != R:
+        raise ValueError("window_assemble needs at least one row and two offsets per row")
+    shapes = [(R, C, width), (R, 1, width * hop), (R, 1, width * hop)]
+    if out is None:
+        out = [None] * 3
+    outs = []
+    for i, shp in enumerate(shapes):
+        t = out[i] if i < len(out) else None
+        if t is None:
+            outs.append(torch.empty(shp, dtype=torch.float32, device=ppg.device))
+        elif not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError("window_assemble needs GPU tensors (no CPU fallback) for out")
+        elif tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ppg.device:
+            raise ValueError(f"out[{i}] must be a contiguous float32 {shp} tensor on {ppg.device}")
+        else:
+            outs.append(t)
+    po = (ctypes.c_int64 * R)(*[int(v) for v in ppg_off])
+    so = (ctypes.c_int64 * R)(*[int(v) for v in sig_off])
+    nfr = (ctypes.c_int32 * R)(*[int(v) for v in n_frames])
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    with torch.cuda.device(ppg.device):
+        stream = torch.cuda.current_stream(ppg.device).cuda_stream
+        _check(lib, lib.fastsvc_window_assemble(ptr(ppg), ppg.numel(), ptr(lft), ptr(sine), lft.numel(), po, so, nfr,
+                                                *[ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
+               "fastsvc_window_assemble")
+    return tuple(outs)
+
+
+# a side of a window row in ``window_stitch`` (include/fastsvc_hip.h)
+STITCH_NONE, STITCH_STAGE, STITCH_FROM_STAGE, STITCH_FROM_Y, STITCH_SKIP = range(5)
+
+
+def window_stitch(y: torch.Tensor, n_samples: Sequence[int], core_lo: Sequence[int], core_hi: Sequence[int], half: int,
+                  left_mode: Sequence[int], right_mode: Sequence[int], left_src: Sequence[int], right_src: Sequence[int],
+                  dst_off: Sequence[int], stage: Optional[torch.Tensor] = None, out_pcm: Optional[torch.Tensor] = None,
+                  out_float: Optional[torch.Tensor] = None, utt: Optional[Sequence[int]] = None,
+                  report: Optional[torch.Tensor] = None) -> None:
+    """Cross-fade the window rows ``y`` (B, width) or (B, 1, width), float32 on the device, into packed destinations:
+    row r writes one contiguous run to element ``dst_off[r]`` of ``out_pcm`` (1-D int16) and / or ``out_float`` (1-D
+    float32, the same length).  The arguments are those of ``fastsvc_window_stitch`` (include/fastsvc_hip.h), which
+    ``decode.stitch_layout`` computes: the core ``[core_lo[r], core_hi[r])`` of the row in samples, ``half`` = half a fade
+    zone in samples, a mode per side (``STITCH_*``) with the zone's source in ``stage`` (1-D float32, kept between the
+    calls of one pass) or in ``y``.  The values are ``decode.stitch_windows``' (float64 cross-fade) and ``to_pcm16``'s, bit
+    for bit.  ``report``: an (n_utts, 4) int32 device tensor the written samples are ACCUMULATED into at row ``utt[r]``
+    (clear it before an utterance's first window).  One HIP launch per 64 rows on the current stream
+    (csrc/fastsvc_window.hip); anything out of range raises ``ValueError`` before a launch; fails loudly off the GPU."""
+    lib = load_library()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise FastSVCError("window_stitch needs a GPU tensor (no CPU fallback); got " + str(getattr(y, "device", type(y))))
+    if y.dim() == 3 and y.shape[1] == 1:
+        y = y[:, 0]
+    B = len(n_samples)
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous() or y.shape[0] != B or B == 0:
+        raise ValueError(f"y must be a contiguous float32 (B, width) tensor with one length per row; got {tuple(y.shape)} {y.dtype}")
+    per_row = (core_lo, core_hi, left_mode, right_mode, left_src, right_src, dst_off) + ((utt,) if report is not None else ())
+    if any(v is None or len(v) != B for v in per_row):
+        raise ValueError("window_stitch needs one entry per row in every row array")
+    if out_pcm is None and out_float is None:
+        raise ValueError("window_stitch needs out_pcm or out_float")
+    n_dst = None
+    for name, t, dtype in (("out_pcm", out_pcm, torch.int16), ("out_float", out_float, torch.float32), ("stage", stage, torch.float32)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"window_stitch needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
+        if t.dim() != 1 or t.dtype != dtype or not t.is_contiguous() or t.device != y.device:
+            raise ValueError(f"{name} must be a contiguous 1-D {dtype} tensor on {y.device}")
+        if name != "stage":
+            if n_dst is not None and n_dst != t.numel():
+                raise ValueError("out_pcm and out_float must hold the same number of samples")
+            n_dst = t.numel()
+    n_utts = 0
+    if report is not None:
+        n_utts = int(report.shape[0]) if isinstance(report, torch.Tensor) and report.dim() == 2 else 0
+        _report_tensor(report, n_utts, y.device)
+    i32s = lambda v: (ctypes.c_int32 * B)(*[int(x) for x in v])      # noqa: E731
+    i64s = lambda v: (ctypes.c_int64 * B)(*[int(x) for x in v])      # noqa: E731
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None      # noqa: E731
+    with torch.cuda.device(y.device):
+        stream = torch.cuda.current_stream(y.device).cuda_stream
+        _check(lib, lib.fastsvc_window_stitch(ptr(y), B, int(y.shape[1]), i32s(n_samples), i32s(core_lo), i32s(core_hi), int(half),
+                                              i32s(left_mode), i32s(right_mode), i64s(left_src), i64s(right_src),
+                                              ptr(stage), stage.numel() if stage is not None else 0, i64s(dst_off),
+                                              ptr(out_pcm), ptr(out_float), n_dst,
+                                              i32s(utt) if report is not None else None, ptr(report), n_utts,
+                                              ctypes.c_void_p(stream)), "fastsvc_window_stitch")
+
+
 def _check(lib, rc: int, what: str):
     if rc != 0:
         msg = lib.fastsvc_last_error().decode("utf-8", "replace")
+        if msg.endswith("split it"):                 # (the forward's limit on one utterance: say what does the splitting)
+            from .synth import TOO_LONG_HINT
+            msg += TOO_LONG_HINT
         if rc == -1:
             raise ValueError(f"{what}: {msg}")
         raise FastSVCError(f"{what} failed ({rc}): {msg}")

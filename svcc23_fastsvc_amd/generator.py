@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .engine import STORAGE_CODES, FastSVCError, Plan
-from .synth import GeneratorConfig
+from .synth import TOO_LONG_HINT, GeneratorConfig, max_forward_frames
 
 
 class _ParamHolder(nn.Module):
@@ -361,9 +361,12 @@ class FastSVCGenerator(nn.Module):
     def _forward_device(self, x, s, l, spk_emb, lengths, out=None):
         """The HIP forward proper (no autograd): packed weights, workspace sub-batching, C-ABI call."""
         hop = self._cfg.hop
+        B, _, F = x.shape
+        if F > max_forward_frames(self._cfg):        # (a restatement of the library's limit, before a workspace of that size is allocated)
+            raise FastSVCError(f"utterance of {F} frames is too long for the 32-bit tensor descriptors of the kernels (one "
+                               f"forward takes {max_forward_frames(self._cfg)} frames): split it" + TOO_LONG_HINT)
         blob = self.packed_weights(x.device)
         plan = self.plan
-        B, _, F = x.shape
         step = B
         Fw = plan.padded_frames(F)                 # (frame counts are run padded to a multiple of 4, as a ragged batch)
         while step > 1 and plan.workspace_bytes(step, Fw) > self.max_workspace_bytes:

@@ -175,6 +175,29 @@ def layer_table(cfg: GeneratorConfig) -> List[LayerSpec]:
     return layers
 
 
+def max_forward_frames(cfg: GeneratorConfig) -> int:
+    """The longest utterance, in frames, one forward takes: the kernels address every tensor of ONE utterance through
+    32-bit byte offsets, so the largest of them - the full-rate waveform, the 2 C rows of a conditioning chain's scale /
+    shift or of an up block, the ppg - must stay below 2 GiB (``forward_impl`` in csrc/fastsvc_plan.cpp makes the same
+    computation and returns FASTSVC_E_UNSUPPORTED beyond it; 4 bytes an element in every storage).  69 905 frames for the
+    recipe's generator at hop 160.  Longer utterances run as windows: ``DecodeSession.convert_windowed``."""
+    per_frame = 4 * cfg.hop
+    rate = cfg.hop
+    for s, c in zip(cfg.down_scales, cfg.down_channels):
+        rate //= s
+        per_frame = max(per_frame, 2 * c * rate * 4)
+    rate = 1
+    for s, c in zip(cfg.upsampling_scales, cfg.mid_channels):
+        rate *= s
+        per_frame = max(per_frame, 2 * c * rate * 4)
+    per_frame = max(per_frame, cfg.in_channels * 4)
+    return (0x7fffffff - 1) // per_frame
+
+
+TOO_LONG_HINT = (" - DecodeSession.convert_windowed (python -m svcc23_fastsvc_amd.decode --resident --window CORE) runs a "
+                 "long utterance as overlapping windows")
+
+
 def state_dict_keys(cfg: GeneratorConfig, weight_norm: bool = True) -> List[str]:
     keys: List[str] = []
     for L in layer_table(cfg):

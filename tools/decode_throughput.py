@@ -25,8 +25,15 @@ The fan-out leg (DECODE_LEGS=fanout only; profiles/decode_fanout.txt), float32 a
     fan-out     one convert_many() of the S speakers                }
 
 for the first U in {1, 8, 64} utterances with S = 16 speakers, and for U = 512 with S = 2 (the large-corpus case).
+The windowed leg (DECODE_LEGS=windowed only; profiles/decode_windowed.txt), float32 and bfloat16 storage, one resident session:
+
+    whole       convert()                                            } alternated, DECODE_REPS each, median
+    windowed    convert_windowed(core=400): windows of 400 + 2 x 36  }
+
+on the 512 utterances, and on ONE utterance of 30 000 frames (200 s).  The recomputed context makes (core + 2 context) /
+core the expected ratio for utterances much longer than a window.
     python tools/decode_throughput.py                  (DECODE_LEGS=session or =checked: one of the two parts only;
-                                                        DECODE_LEGS=fanout: the fan-out leg)"""
+                                                        DECODE_LEGS=fanout: the fan-out leg; =windowed: the windowed leg)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -183,6 +190,55 @@ def fanout_legs():
         f.write("\n".join(out) + "\n")
 
 
+def windowed_legs():
+    """convert against convert_windowed(core=400), same session, same process."""
+    CORE = 400
+    ctx = -(-Dc.receptive_field_frames(cfg) // 4) * 4
+    out = [f"windowed decode: DecodeSession.convert() against convert_windowed(core={CORE}) (context {ctx}, fade 8: "
+           f"(core + 2 context) / core = {(CORE + 2 * ctx) / CORE:.3f}); max_batch {MB}, F0 shift on, speaker embedding, int16 out, "
+           f"{reps} repetitions, legs alternated, median (min, max); {torch.cuda.get_device_name(0)}"]
+    r = np.random.default_rng(5)
+    F_long = 30000
+    long = [{"ppg": r.standard_normal((F_long, cfg.in_channels), dtype=np.float32),
+             "f0": np.where(r.random((F_long, 1)) < 0.3, 0.0, r.uniform(80, 400, (F_long, 1))),
+             "lft": r.uniform(-9, 1, (F_long * cfg.hop, 1)).astype(np.float32)}]
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for name, sub, fr in ((f"{len(feats)} utterances of 2 - 10 s", feats, frames), ("1 utterance of 30000 frames", long, [F_long])):
+            unit = sum(fr) * cfg.hop
+            rows = Dc.window_plan(fr, CORE, ctx)
+            with Dc.DecodeSession(m, sub, sg, dev, src[:len(sub)], max_batch=MB) as s:
+                whole = lambda: s.convert(emb, trg)                                          # noqa: E731
+                wind = lambda: s.convert_windowed(emb, trg, core=CORE)                       # noqa: E731
+                torch.cuda.reset_peak_memory_stats(dev)
+                want = whole()
+                torch.cuda.synchronize()
+                peak_w = torch.cuda.max_memory_allocated(dev)
+                torch.cuda.reset_peak_memory_stats(dev)
+                got = wind()                                                                 # (warm both; compare)
+                torch.cuda.synchronize()
+                peak_g = torch.cuda.max_memory_allocated(dev)
+                diff = max(int(np.abs(a.astype(np.int32) - b.astype(np.int32)).max()) for a, b in zip(want, got))
+                n_whole, n_wind = len(s.batches), s.forwards
+                work = sum(b - a for _, a, b, _, _ in rows) / sum(fr)
+                del want, got
+                t = {"whole": [], "wind": []}
+                for _ in range(reps):
+                    t["whole"].append(timed(whole)[0])
+                    t["wind"].append(timed(wind)[0])
+            mw, line_w = spread(f"{name}: whole    ({n_whole} forwards)", t["whole"], unit)
+            mg, line_g = spread(f"{name}: windowed ({n_wind} forwards)", t["wind"], unit)
+            out += [line_w, line_g,
+                    f"    windowed / whole time {mg / mw:.3f}; frames computed / frames of audio {work:.3f}; {len(rows)} windows; "
+                    f"largest PCM-16 difference to the whole-utterance result {diff} (per-window InstanceNorm statistics); peak "
+                    f"device memory whole {peak_w / 2 ** 20:.0f} MiB, windowed {peak_g / 2 ** 20:.0f} MiB"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_windowed.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 LEGS = os.environ.get("DECODE_LEGS", "all")
 for storage in (("float32", "bfloat16") if LEGS in ("all", "session") else ()):
     m = build_model(storage)
@@ -233,3 +289,5 @@ if LEGS in ("all", "checked"):
     checked_legs()
 if LEGS == "fanout":
     fanout_legs()
+if LEGS == "windowed":
+    windowed_legs()
