@@ -164,6 +164,43 @@ int fastsvc_forward(const fastsvc_plan* plan, const void* dev_blob,
                     float* out, int32_t B, int32_t F, const int32_t* lengths,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* fastsvc_forward with InstanceNorm statistics POOLED over groups of batch rows (csrc/fastsvc_normgroup.hip): what
+ * decode.DecodeSession.convert_windowed(norm="utterance") runs the windows of one utterance through.  The reference
+ * normalises whole utterances (fastsvc.py:134-139) and has no counterpart.  Arguments as fastsvc_forward, and
+ *   group    DEVICE, B int32: the index of the FIRST row of row b's group (group[b] <= b, group[group[b]] == group[b])
+ *   own_lo, own_hi   DEVICE, B int32 each, in frames: row b OWNS the frames [own_lo[b], own_hi[b]) of its lengths[b]
+ *            (F without lengths) valid ones, 0 <= own_lo < own_hi <= lengths[b]
+ *   scratch  DEVICE, >= fastsvc_norm_group_scratch_bytes(plan, B, F) bytes: the partial sums (not part of the workspace)
+ * At each of the three norm points of every up block, behind whichever launch produced the tensor, sum u and sum u^2
+ * are taken in float64 over the columns each row owns (chunks of 2048 columns from the start of the owned range, so a
+ * row's partial sums do not depend on the batch; no floating-point atomics: two runs give the same bits), added over
+ * the rows of the group in ascending (row, chunk) order and written to EVERY member row as S * len_b / N - len_b the
+ * row's own column count, which the consuming convolution divides by, N the group's owned columns.  Each member is thus
+ * normalised by the mean and biased variance of the group's owned columns.  Two extra launches per norm point.
+ * A row that is alone in its group and owns all its frames is a PASS-THROUGH row: nothing is read or written for it,
+ * and a batch of such rows gives fastsvc_forward's output bit for bit.  float32 storage: the bound the split-binary16
+ * staging scale of a normalised row is derived from grows from sqrt(len_b) to sqrt(N) for the member rows.
+ * spk_emb == NULL: there is no norm; the four extra arguments are ignored (may be NULL) and the launches and bytes are
+ * fastsvc_forward's.  The device arrays cannot be checked here - values out of range are clamped to the row, never
+ * followed outside it; the Python layer validates them on the host.  Too little scratch: FASTSVC_E_WORKSPACE. */
+size_t fastsvc_norm_group_scratch_bytes(const fastsvc_plan* plan, int32_t B, int32_t F);
+int fastsvc_forward_grouped(const fastsvc_plan* plan, const void* dev_blob,
+                            const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                            float* out, int32_t B, int32_t F, const int32_t* lengths,
+                            const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
+                            void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream);
+
+/* The same two launches for ONE tensor u (B, C, ld) of `storage` (0 float32, 1 bfloat16, 2 float16 elements), rows of
+ * lengths[b] * len_mul valid columns (lengths NULL: ld; ld a multiple of len_mul), row b owning the columns
+ * [own_lo[b], own_hi[b]) * len_mul: stats_out (B, C, 2) float64 DEVICE receives S1 * len_b / N and S2 * len_b / N for
+ * every row that is not a pass-through row; those rows' entries are left as they are.  No column at or beyond a row's
+ * valid length or outside its owned range is read; no alignment requirement on ld or own_lo * len_mul.
+ * scratch: DEVICE, >= B * C * ceil(ld / 2048) * 16 bytes.  All pointers DEVICE; asynchronous on `stream`. */
+int fastsvc_norm_group_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                             int32_t len_mul, const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
+                             double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Creates (and calibrates, see the conventions above: synchronises `stream`) the helper streams / events
  * fastsvc_forward may use for `stream` on the current device, so that the forward itself allocates nothing and
  * never synchronises (call once per stream, e.g. before graph capture or a latency-critical first call).

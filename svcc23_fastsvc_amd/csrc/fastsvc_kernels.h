@@ -354,6 +354,25 @@ hipError_t launch_stats_exact(const float* u, double* st, int B, int C, int ld, 
 hipError_t launch_amax_inputs(const float* sig, long sig_stride, const float* ppg, int B, int C, int F, int hop,
                               const int* lens, float* amax_in, float* zero, int nzero, hipStream_t stream);
 
+// ---- InstanceNorm sums pooled over groups of rows (fastsvc_normgroup.hip; fastsvc_forward_grouped) ----
+// Row b of a FiLM-affined (B, C, ld) tensor OWNS the columns [own_lo[b], own_hi[b]) * len_mul of its lens[b] * len_mul valid
+// ones (lens null: ld) and belongs to the group whose first row is group[b].  Two launches:
+//   partials: every owned range is cut into chunks of NORMGROUP_CHUNK columns from its own start, one wave sums one
+//             (row, channel, chunk) in float64 -> part[(b * chunks + k) * C + c][2], chunks = norm_group_chunks(ld).  The
+//             cut depends on the row alone, there are no atomics: a row's partials are the same bits in any batch.
+//   pool:     st[b][c] = (sum of the group's partials in ascending (row, chunk) order) * (lens[b] * len_mul) / N, N the
+//             group's owned columns - what a consumer that divides by the row's own length turns into the group's
+//             mean and variance.  amax_raise (float32 storage, may be null): the amax row of the block's speaker biases;
+//             entry b is raised by sqrt(N) - sqrt(lens[b] * len_mul), see DESIGN.md 4.9.
+// A row alone in its group that owns all its columns is a PASS-THROUGH row: nothing is read and nothing written for it.
+// All five device arrays hold B entries; out-of-range own_lo / own_hi are clamped to the row, group[] is only compared.
+constexpr int NORMGROUP_CHUNK = 2048;
+inline int norm_group_chunks(long ld) { return (int)((ld + NORMGROUP_CHUNK - 1) / NORMGROUP_CHUNK); }
+hipError_t launch_norm_group_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul,
+                                      const int* group, const int* own_lo, const int* own_hi, hipStream_t stream);
+hipError_t launch_norm_group_pool(const double* part, double* st, int B, int C, int ld, const int* lens, int len_mul,
+                                  const int* group, const int* own_lo, const int* own_hi, float* amax_raise, hipStream_t stream);
+
 // conv_last: 1x1, y[b][o][t] = bias[o] + sum_c w[o][c] * x[b][c][t]
 hipError_t launch_pointwise_out(const float* x, const float* w, const float* bias, float* y,
                                 int B, int C, int O, int T, const int* lens, int len_mul, hipStream_t stream);
@@ -389,6 +408,8 @@ hipError_t launch_pointwise_out(const float* x, const float* w, const float* bia
 hipError_t launch_act_convert(const float* src, float* dst_act, long n, hipStream_t stream); \
 hipError_t launch_cond_stage0(const CondStage0Params& p, hipStream_t stream); \
 hipError_t launch_cond_stage1(const CondStage1Params& p, hipStream_t stream); \
+hipError_t launch_norm_group_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul, \
+                                      const int* group, const int* own_lo, const int* own_hi, hipStream_t stream); \
 
 namespace bf16 { FASTSVC_ACT_LAUNCHERS }
 namespace f16 { FASTSVC_ACT_LAUNCHERS }

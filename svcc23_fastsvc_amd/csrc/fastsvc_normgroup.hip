@@ -1,0 +1,187 @@
+// fastsvc_normgroup.hip - InstanceNorm sums pooled over GROUPS of batch rows (fastsvc_forward_grouped; the windows of one
+// utterance in decode.DecodeSession.convert_windowed(norm="utterance")).
+//
+// Every norm point of an up block reads, per (row, channel), sum u and sum u^2 of a FiLM-affined tensor and divides them
+// by the row's own length (fastsvc_hx.hip / fastsvc_wx.hip / fastsvc_kernels.hip set-up).  Here the sums are taken over
+// the columns each row OWNS, pooled over the rows of a group and written back scaled by (row length / owned columns of
+// the group), so that those unchanged consumers normalise every row of a group by the GROUP's mean and variance
+// (fastsvc_kernels.h has the contract of the two launches, DESIGN.md 4.9 the argument why that is the whole utterance's).
+//
+// partials: a streaming read, HBM-bound.  The unit of work is one WAVE on one (row, channel, chunk of NORMGROUP_CHUNK
+// columns): 192 channels x 800 columns (block 0) are 192 waves a row, 24 x 64 000 (block 3) are 768 - no workgroup shape
+// tied to the row length, four independent waves per workgroup, no LDS, no barrier.  16-byte requests (4 float32 / 8
+// two-byte elements a lane) over the 16-byte aligned middle of the chunk, four in flight per lane; the up to 15 bytes in
+// front and behind go element-wise, so own_lo * len_mul may sit anywhere (block 0: 8 bytes into a word for odd own_lo).
+// Every element and every product in float64 (a float32 squared is exact there), lanes combined by a fixed butterfly:
+// no atomics, the same bits on every run and in every batch.
+// Compiled three times (build.py): float32, bfloat16 and binary16 activation storage; the pool is defined once.
+#include "fastsvc_kernels.h"
+
+namespace fastsvc {
+#ifdef FASTSVC_ACT_2B
+namespace FASTSVC_ACT_NS {
+#endif
+
+#include "fastsvc_device.inc"
+
+namespace {
+
+// the row's valid frames, its owned frames clamped into them, and whether it is a pass-through row (wave-uniform; every
+// lane looks at B / 64 entries of group[])
+struct NgRow { int len, lo, hi; bool pass; };
+__device__ __forceinline__ NgRow ng_row(int b, int B, int ld, const int* __restrict__ lens, int len_mul,
+                                        const int* __restrict__ group, const int* __restrict__ own_lo,
+                                        const int* __restrict__ own_hi, int lane) {
+    NgRow r;
+    const int F = ld / len_mul;
+    r.len = lens ? min(max(lens[b], 0), F) : F;
+    r.lo = min(max(own_lo[b], 0), r.len);
+    r.hi = min(max(own_hi[b], r.lo), r.len);
+    const int g = group[b];
+    bool other = false;
+    for (int q = lane; q < B; q += 64) other |= (q != b && group[q] == g);
+    r.pass = g == b && !__any(other) && r.lo == 0 && r.hi == r.len;
+    return r;
+}
+
+constexpr int NG_VEC = 16 / (int)sizeof(act_t);      // elements of one 16-byte request
+
+__device__ __forceinline__ void ng_acc(double& s1, double& s2, float v) {
+    const double d = (double)v;
+    s1 += d; s2 += d * d;
+}
+// one 16-byte request: 8 two-byte elements as four dwords, or four float32
+#ifdef FASTSVC_ACT_2B
+typedef u32x4 ng_vec_t;
+#else
+typedef f32x4 ng_vec_t;
+#endif
+__device__ __forceinline__ void ng_acc16(double& s1, double& s2, const ng_vec_t w) {
+#ifdef FASTSVC_ACT_2B
+    ng_acc(s1, s2, a16_lo(w.x)); ng_acc(s1, s2, a16_hi(w.x));
+    ng_acc(s1, s2, a16_lo(w.y)); ng_acc(s1, s2, a16_hi(w.y));
+    ng_acc(s1, s2, a16_lo(w.z)); ng_acc(s1, s2, a16_hi(w.z));
+    ng_acc(s1, s2, a16_lo(w.w)); ng_acc(s1, s2, a16_hi(w.w));
+#else
+    ng_acc(s1, s2, w.x); ng_acc(s1, s2, w.y); ng_acc(s1, s2, w.z); ng_acc(s1, s2, w.w);
+#endif
+}
+__device__ __forceinline__ float ng_elem(const act_t* p) {
+#ifdef FASTSVC_ACT_2B
+    return a16_lo((unsigned)*p);
+#else
+    return *p;
+#endif
+}
+
+__global__ __launch_bounds__(256)
+void norm_group_partials_kernel(const act_t* __restrict__ u, double* __restrict__ part, int B, int C, int ld,
+                                const int* __restrict__ lens, int len_mul, const int* __restrict__ group,
+                                const int* __restrict__ own_lo, const int* __restrict__ own_hi, int chunks) {
+    const int lane = threadIdx.x & 63;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);          // (chunk, channel) of row b, channel fastest
+    const int b = blockIdx.y;
+    const int k = item / C, c = item - k * C;
+    if (k >= chunks) return;
+    const NgRow r = ng_row(b, B, ld, lens, len_mul, group, own_lo, own_hi, lane);
+    if (r.pass) return;
+    const long lo = (long)r.lo * len_mul + (long)k * NORMGROUP_CHUNK;
+    const long end = (long)r.hi * len_mul;
+    if (lo >= end) return;                                           // (the pool reads only the chunks a row has)
+    const int n = (int)min((long)NORMGROUP_CHUNK, end - lo);
+    const act_t* p = u + ((long)b * C + c) * ld + lo;
+    // [0, head) element-wise up to the next 16-byte boundary, nvec 16-byte requests, then the rest element-wise
+    const int head = min(n, (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(act_t)));
+    const int nvec = (n - head) / NG_VEC;
+    const int tail0 = head + nvec * NG_VEC;
+    double s1 = 0.0, s2 = 0.0;
+    if (lane < head) ng_acc(s1, s2, ng_elem(p + lane));
+    const ng_vec_t* pv = reinterpret_cast<const ng_vec_t*>(p + head);
+    int j = lane;
+    for (; j + 192 < nvec; j += 256) {                               // four requests in flight per lane
+        const ng_vec_t w0 = pv[j], w1 = pv[j + 64], w2 = pv[j + 128], w3 = pv[j + 192];
+        ng_acc16(s1, s2, w0); ng_acc16(s1, s2, w1); ng_acc16(s1, s2, w2); ng_acc16(s1, s2, w3);
+    }
+    for (; j < nvec; j += 64) ng_acc16(s1, s2, pv[j]);
+    if (tail0 + lane < n) ng_acc(s1, s2, ng_elem(p + tail0 + lane));
+    #pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { s1 += __shfl_xor(s1, d); s2 += __shfl_xor(s2, d); }
+    if (lane == 0) {
+        double* o = part + (((long)b * chunks + k) * C + c) * 2;
+        o[0] = s1; o[1] = s2;
+    }
+}
+
+#ifndef FASTSVC_ACT_2B
+// one thread per (row, channel): the partials are (row, chunk, channel) with the channel fastest, so a wave's reads are
+// one contiguous run per (row, chunk)
+__global__ __launch_bounds__(64)
+void norm_group_pool_kernel(const double* __restrict__ part, double* __restrict__ st, int B, int C, int ld,
+                            const int* __restrict__ lens, int len_mul, const int* __restrict__ group,
+                            const int* __restrict__ own_lo, const int* __restrict__ own_hi, int chunks,
+                            float* __restrict__ amax_raise) {
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x * 64 + lane, b = blockIdx.y;
+    const NgRow me = ng_row(b, B, ld, lens, len_mul, group, own_lo, own_hi, lane);
+    if (me.pass) return;
+    const int F = ld / len_mul;
+    const int g = group[b];
+    double s1 = 0.0, s2 = 0.0;
+    long N = 0;
+    for (int q = 0; q < B; ++q) {
+        if (group[q] != g) continue;
+        const int len = lens ? min(max(lens[q], 0), F) : F;
+        const int lo = min(max(own_lo[q], 0), len), hi = min(max(own_hi[q], lo), len);
+        const long cols = (long)(hi - lo) * len_mul;
+        N += cols;
+        const int nk = (int)((cols + NORMGROUP_CHUNK - 1) / NORMGROUP_CHUNK);
+        if (c < C)
+            for (int k = 0; k < nk; ++k) {
+                const double* o = part + (((long)q * chunks + k) * C + c) * 2;
+                s1 += o[0]; s2 += o[1];
+            }
+    }
+    const double L = (double)((long)me.len * len_mul);
+    if (c < C && N > 0) {
+        st[((long)b * C + c) * 2 + 0] = s1 * L / (double)N;
+        st[((long)b * C + c) * 2 + 1] = s2 * L / (double)N;
+    }
+    // the consumer bounds the normalised row by max |p| + sqrt(L); with the group's statistics it is sqrt(N): slot 0 of the
+    // entry takes the entry's maximum plus the difference, rounded up (readers take the maximum of the slots)
+#ifndef FASTSVC_EXP_NG_NORAISE      // (A/B builds: what tests/test_decode_window_norm_gpu.py's loud window does without the adjustment)
+    if (amax_raise && c == 0 && (double)N > L) {
+        float* e = amax_raise + (long)b * AMAX_ENTRY;
+        float m = 0.f;
+        #pragma unroll
+        for (int s = 0; s < AMAX_W; ++s) m = fmaxf(m, e[s * AMAX_STRIDE]);
+        const float d = (float)(sqrt((double)N) - sqrt(L));
+        e[0] = (m + d) * 1.00001f;
+    }
+#endif
+}
+#endif
+
+}  // namespace
+
+hipError_t launch_norm_group_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul,
+                                      const int* group, const int* own_lo, const int* own_hi, hipStream_t stream) {
+    const int chunks = norm_group_chunks(ld);
+    const unsigned gx = (unsigned)(((long)chunks * C + 3) / 4);
+    hipLaunchKernelGGL(norm_group_partials_kernel, dim3(gx, (unsigned)B), dim3(256), 0, stream,
+                       reinterpret_cast<const act_t*>(u), part, B, C, ld, lens, len_mul, group, own_lo, own_hi, chunks);
+    return hipGetLastError();
+}
+
+#ifndef FASTSVC_ACT_2B
+hipError_t launch_norm_group_pool(const double* part, double* st, int B, int C, int ld, const int* lens, int len_mul,
+                                  const int* group, const int* own_lo, const int* own_hi, float* amax_raise, hipStream_t stream) {
+    hipLaunchKernelGGL(norm_group_pool_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)B), dim3(64), 0, stream,
+                       part, st, B, C, ld, lens, len_mul, group, own_lo, own_hi, norm_group_chunks(ld), amax_raise);
+    return hipGetLastError();
+}
+#endif
+
+#ifdef FASTSVC_ACT_2B
+}  // namespace FASTSVC_ACT_NS
+#endif
+}  // namespace fastsvc

@@ -1855,6 +1855,12 @@ struct CallCtx {
     // utterance sat at 3.4e-3 of the output's range where the float32 reference is 4e-5 from float64
     // (tools/stress_parity.py, seed 75).  Float32 storage only.  (fastsvc_kernels.hip speaks of it as g_exact_f32.)
     bool exact_f32 = false;
+    // fastsvc_forward_grouped: InstanceNorm sums pooled over groups of rows (fastsvc_normgroup.hip).  Device arrays of B
+    // entries and the caller's scratch for the chunk partials; all null in every other entry point.
+    const int32_t* ng_group = nullptr;
+    const int32_t* ng_lo = nullptr;
+    const int32_t* ng_hi = nullptr;
+    double* ng_part = nullptr;
 };
 
 #ifdef FASTSVC_TIMELINE
@@ -3329,8 +3335,25 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
             // B x C one-wave workgroups that leave at once for the longer ones: not worth it on big batches, where a
             // decode harness's length buckets never put a 1-frame utterance anyway)
             const bool small_ragged = lengths && P.storage == 0 && F <= 64;
-            if (!spk || !(cc.exact_f32 || small_ragged)) return hipSuccess;
-            return launch_stats_exact(ut, stp, B, u.C, (int)Tout, lengths, (int)(Tout / F), 4, stream);
+            if (!spk) return hipSuccess;
+            hipError_t e = hipSuccess;
+            if (cc.exact_f32 || small_ragged)
+                e = launch_stats_exact(ut, stp, B, u.C, (int)Tout, lengths, (int)(Tout / F), 4, stream);
+            // Grouped rows (fastsvc_forward_grouped): the sums over the columns each row owns, pooled over its group and
+            // scaled to the row's own length, overwrite whatever stands in the row's slots - the conv's sums or the exact
+            // ones above, which stay those of the pass-through rows.  Two launches per norm point.  Behind the block's
+            // FIRST producer the pool also raises the rows' entries of the speaker biases' amax row (float32 storage):
+            // the bound of a normalised row is then sqrt(owned columns of the group), not sqrt(row length), and every
+            // consumer of the block that reads it runs behind this launch.
+            if (e == hipSuccess && cc.ng_group) {
+                const int m = (int)(Tout / F);
+                e = FASTSVC_BY_STORAGE(P.storage, launch_norm_group_partials)(ut, cc.ng_part, B, u.C, (int)Tout, lengths, m,
+                                                                              cc.ng_group, cc.ng_lo, cc.ng_hi, stream);
+                if (e == hipSuccess)
+                    e = launch_norm_group_pool(cc.ng_part, stp, B, u.C, (int)Tout, lengths, m, cc.ng_group, cc.ng_lo, cc.ng_hi,
+                                               (P.storage == 0 && stp == st) ? am_p : nullptr, stream);
+            }
+            return e;
         };
         HIP_TRY(exact_stats(u1, st));
         p = base;                                                  // xmid = conv_d3(lrelu(norm(u1))) + xr
@@ -3472,6 +3495,56 @@ int fastsvc_forward(const fastsvc_plan* plan, const void* dev_blob,
     CallCtx cc;
     return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
                         workspace_bytes, stream, nullptr);
+}
+
+size_t fastsvc_norm_group_scratch_bytes(const fastsvc_plan* plan, int32_t B, int32_t F) {
+    if (!plan || B < 1 || F < 1) return 0;
+    size_t worst = 0;
+    long Ti = F;
+    for (int i = 0; i < plan->n; ++i) {
+        Ti *= plan->up[i].scale;
+        worst = std::max(worst, (size_t)B * plan->up[i].C * norm_group_chunks(Ti) * 2 * sizeof(double));
+    }
+    return worst;
+}
+
+int fastsvc_forward_grouped(const fastsvc_plan* plan, const void* dev_blob,
+                            const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                            float* out, int32_t B, int32_t F, const int32_t* lengths,
+                            const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
+                            void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+    CallCtx cc;
+    if (spk_emb) {                                     // (without an embedding there is no norm: fastsvc_forward's launches and bytes)
+        if (!group || !own_lo || !own_hi || !scratch) return fail(FASTSVC_E_INVALID, "null argument");
+        if (!plan || B < 1 || F < 1) return fail(FASTSVC_E_INVALID, "B and F must be >= 1");
+        if (scratch_bytes < fastsvc_norm_group_scratch_bytes(plan, B, F))
+            return fail(FASTSVC_E_WORKSPACE, "norm-group scratch too small (fastsvc_norm_group_scratch_bytes)");
+        cc.ng_group = group; cc.ng_lo = own_lo; cc.ng_hi = own_hi;
+        cc.ng_part = static_cast<double*>(scratch);
+    }
+    return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
+                        workspace_bytes, stream, nullptr);
+}
+
+int fastsvc_norm_group_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                             int32_t len_mul, const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
+                             double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!u || !group || !own_lo || !own_hi || !stats_out || !scratch) return fail(FASTSVC_E_INVALID, "null argument");
+    if (storage != 0 && storage != 1 && storage != 2)
+        return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
+    if (B < 1 || B > 65535 || C < 1 || ld < 1 || len_mul < 1 || ld % len_mul != 0)
+        return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535, C >= 1 and a pitch ld that is a positive multiple of len_mul");
+    if ((long)C * norm_group_chunks(ld) > 0x7fffffffL / 2)
+        return fail(FASTSVC_E_UNSUPPORTED, "too many (channel, chunk) items for one launch");
+    if (scratch_bytes < (size_t)B * C * norm_group_chunks(ld) * 2 * sizeof(double))
+        return fail(FASTSVC_E_WORKSPACE, "norm-group scratch too small: B * C * ceil(ld / 2048) * 16 bytes");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(scratch);
+    HIP_TRY(FASTSVC_BY_STORAGE(storage, launch_norm_group_partials)(static_cast<const float*>(u), part, B, C, ld, lengths, len_mul,
+                                                                    group, own_lo, own_hi, s));
+    HIP_TRY(launch_norm_group_pool(part, stats_out, B, C, ld, lengths, len_mul, group, own_lo, own_hi, nullptr, s));
+    return FASTSVC_OK;
 }
 
 int fastsvc_autotune(const fastsvc_plan* plan, const void* dev_blob,

@@ -229,6 +229,54 @@ def window_batches(rows: Sequence[Tuple[int, int, int, int, int]], max_batch: in
     return list(bucket_ragged(range(len(rows)), [r[2] - r[1] for r in rows], max_batch, pad_tolerance))
 
 
+def grouped_window_batches(rows: Sequence[Tuple[int, int, int, int, int]], max_batch: int = 32) -> List[List[int]]:
+    """Batches of row indices into ``rows`` that hold WHOLE utterances, for ``convert_windowed(norm="utterance")``: all
+    windows of an utterance sit in one batch, adjacent and ascending, so that one forward sees every row whose InstanceNorm
+    sums it pools.  Utterances are packed first-fit by window count, most windows first (ties in utterance order); a
+    batch is as wide as its longest row and ragged through ``lengths``.  An utterance with more windows than ``max_batch``
+    raises ``ValueError``: its intermediates would have to be kept across batches, which is not built, and per-window
+    statistics are never substituted silently."""
+    max_batch = int(max_batch)
+    by_utt = _window_groups(rows)
+    batches: List[List[int]] = []
+    for u in sorted(by_utt, key=lambda u: (-len(by_utt[u]), u)):
+        rs = by_utt[u]
+        if len(rs) > max_batch:
+            raise ValueError(f"utterance {u} has {len(rs)} windows but max_batch is {max_batch}: with norm=\"utterance\" all "
+                             f"windows of an utterance run in one batch - a larger core or a larger max_batch fits it")
+        for chunk in batches:
+            if len(chunk) + len(rs) <= max_batch:
+                chunk.extend(rs)
+                break
+        else:
+            batches.append(list(rs))
+    return batches
+
+
+def pool_norm_sums(s1, s2, owned: Sequence[int], lens: Sequence[int], group: Sequence[int]):
+    """The numpy reference of the pool-and-scatter rule of csrc/fastsvc_normgroup.hip, float64.  ``s1``, ``s2`` (B, C): the
+    sums of u and of u^2 over the columns each row OWNS; ``owned[b]`` that many columns, ``lens[b]`` the row's own valid
+    columns, ``group[b]`` the index of the first row of b's group.  Returns ``(q1, q2)`` (B, C): for every row the sums of
+    its group, added in ascending row order, times ``lens[b] / N`` with N the group's owned columns - so that ``q1 /
+    lens[b]`` is the group's mean and ``q2 / lens[b] - mean^2`` its biased variance, whatever the row's own length.  A row
+    alone in its group that owns all its columns keeps its own sums, bit for bit."""
+    s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+    B = len(group)
+    q1, q2 = s1.copy(), s2.copy()
+    for b in range(B):
+        members = [r for r in range(B) if group[r] == group[b]]
+        if members == [b] and int(owned[b]) == int(lens[b]):
+            continue
+        N = sum(int(owned[r]) for r in members)
+        t1, t2 = np.zeros_like(s1[b]), np.zeros_like(s2[b])
+        for r in members:
+            t1 = t1 + s1[r]
+            t2 = t2 + s2[r]
+        q1[b] = t1 * float(lens[b]) / float(N)
+        q2[b] = t2 * float(lens[b]) / float(N)
+    return q1, q2
+
+
 def _window_groups(rows):
     """utterance -> its row indices, ascending window."""
     by_utt: Dict[int, List[int]] = {}
@@ -875,7 +923,8 @@ class DecodeSession:
 
     @torch.no_grad()
     def convert_windowed(self, trg_emb=None, trg_f0_stats: Optional[Sequence[float]] = None, core: int = 400,
-                         context: Optional[int] = None, fade: int = 8, pcm16: bool = True) -> List[np.ndarray]:
+                         context: Optional[int] = None, fade: int = 8, pcm16: bool = True,
+                         norm: str = "window") -> List[np.ndarray]:
         """Every utterance converted to one target speaker as overlapping WINDOWS - for utterances longer than one
         forward takes (``synth.max_forward_frames``: 69 905 frames for the recipe's generator), and for sets whose
         lengths differ so much that ``bucket_ragged`` cannot fill batches.  Returns what ``convert`` returns: one array per
@@ -897,13 +946,21 @@ class DecodeSession:
         Stitching: ``stitch_windows``' rule - around every interior boundary the two windows are cross-faded linearly over
         ``fade`` frames in float64 (``fade`` even, ``<= min(core, 2 context)``; 0 concatenates the cores).
 
-        What the result is.  WITHOUT a speaker embedding the generator is a convolution of finite reach, and with
-        ``context >= receptive_field_frames`` every window's core IS the whole-utterance result (to float32 kernel
-        arithmetic: the batching invariance the harness states), so the cross-fade blends two equal signals.  WITH an
-        embedding, InstanceNorm takes its statistics over the row: a window is normalised by ITS OWN mean and variance - as
-        training normalises one-second crops - so the windowed decode is a different, well-defined function: exactly
-        ``stitch_windows`` of every window run alone.  It is NOT the whole-utterance result at any context (DESIGN.md §4.9
-        has the measured differences).
+        What the result is.  Three cases.  WITHOUT a speaker embedding the generator is a convolution of
+        finite reach, and with ``context >= receptive_field_frames`` every window's core IS the whole-utterance result (to
+        float32 kernel arithmetic: the batching invariance the harness states), so the cross-fade blends two equal signals;
+        ``norm`` changes nothing.  WITH an embedding and ``norm="window"`` (the default), InstanceNorm takes its statistics
+        over the row: a window is normalised by ITS OWN mean and variance - as training normalises one-second crops - so
+        the windowed decode is a different, well-defined function: exactly ``stitch_windows`` of every window run alone,
+        NOT the whole-utterance result at any context.  WITH an embedding and ``norm="utterance"``, every norm point takes
+        its sums over the frames each window OWNS (its core), pools them over the windows of the utterance and normalises
+        every window by the utterance's mean and variance (``Generator.forward(norm_groups=...)``,
+        csrc/fastsvc_normgroup.hip): InstanceNorm is then the same per-channel affine in every window, the generator is
+        again of finite reach, and with ``context >= receptive_field_frames`` the result is the whole-utterance one, what
+        ``convert`` returns, to float32 kernel arithmetic.  For that the windows of an utterance must share a forward:
+        batches hold whole utterances (``grouped_window_batches``), and an utterance with more windows than ``max_batch``
+        raises ``ValueError`` before anything runs - choose a larger ``core`` or ``max_batch``.  An utterance of one
+        window runs exactly as in ``convert``.
 
         A checked session reports per UTTERANCE, over the stitched samples (``last_report`` as after ``convert``); an
         utterance with non-finite samples has ALL its windows run again in the next fallback storage, in batches of their
@@ -923,11 +980,17 @@ class DecodeSession:
             context = -(-receptive_field_frames(cfg) // 4) * 4
         context, fade = int(context), int(fade)
         _check_window_sizes(core, context, fade)
+        if norm not in ("window", "utterance"):
+            raise ValueError(f"norm must be \"window\" or \"utterance\", got {norm!r}")
+        grouped = norm == "utterance"
         if len(getattr(self.signal_generator, "signal_types", ("sine",))) != 1:
             raise ValueError("convert_windowed needs a signal generator with one signal type")
         checked = self.checked
         stream = torch.cuda.current_stream(dev)
         self.forwards = 0
+        rows = window_plan(frames, core, context)
+        if grouped:
+            grouped_window_batches(rows, self.max_batch)     # (an utterance that does not fit a batch: refused before anything runs)
         up = 0
         emb_row = None
         if trg_emb is not None:
@@ -961,18 +1024,25 @@ class DecodeSession:
             trace.clear()
             trace.update(excitation=[d_sine[self._lft_off[i]: self._lft_off[i] + frames[i] * hop].clone() for i in range(self.n)],
                          batches=[])
-        rows = window_plan(frames, core, context)
         by_utt: Dict[int, List[int]] = {}
         for r, row in enumerate(rows):
             by_utt.setdefault(row[0], []).append(r)
         result = np.empty(total, dtype=np.int16 if pcm16 else np.float32)
         d_rep = torch.zeros((self.n, 4), dtype=torch.int32, device=dev) if checked else None
         n_down = [0, 0]
+        # norm="utterance": the partial sums' scratch, once per call, for the largest batch any pass can form
+        norm_scratch = None
+        plan = getattr(self.model, "plan", None)
+        if grouped and emb_row is not None and plan is not None:
+            widest = max(r[2] - r[1] for r in rows)
+            norm_scratch = torch.empty(max(plan.norm_group_scratch_bytes(min(self.max_batch, len(rows)), plan.padded_frames(widest)), 1),
+                                       dtype=torch.uint8, device=dev)
 
         def run(row_ids: Sequence[int]) -> None:
             """One pass over these rows (all windows of their utterances), stitched into ``result``."""
-            batches = [[row_ids[j] for j in chunk]
-                       for chunk in window_batches([rows[r] for r in row_ids], self.max_batch, self.pad_tolerance)]
+            sub = [rows[r] for r in row_ids]
+            batches = [[row_ids[j] for j in chunk] for chunk in
+                       (grouped_window_batches(sub, self.max_batch) if grouped else window_batches(sub, self.max_batch, self.pad_tolerance))]
             layout, stage_elems = stitch_layout(rows, batches, hop, fade)
             stage = torch.empty(max(stage_elems, 1), dtype=torch.float32, device=dev)
             pending = {}
@@ -988,14 +1058,21 @@ class DecodeSession:
             for k, chunk in enumerate(batches):
                 lay = layout[k]
                 lens = [rows[r][2] - rows[r][1] for r in chunk]
-                width, B = lens[0], len(chunk)
+                width, B = max(lens), len(chunk)
                 ppg, lft, sine = window_assemble(
                     self._d_ppg, self._d_lft, d_sine, [self._ppg_off[rows[r][0]] + rows[r][1] * C for r in chunk],
                     [self._lft_off[rows[r][0]] + rows[r][1] * hop for r in chunk], lens, C, hop, width)
                 if trace is not None:
                     trace["batches"].append(([rows[r] for r in chunk], sine.clone()))
                 emb = None if emb_row is None else emb_row.expand(B, -1).contiguous()
-                y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+                if grouped:
+                    # a row's group is its utterance; it owns its core, counted from its own first frame
+                    first = {}
+                    groups = ([first.setdefault(rows[r][0], j) for j, r in enumerate(chunk)],
+                              [rows[r][3] - rows[r][1] for r in chunk], [rows[r][4] - rows[r][1] for r in chunk])
+                    y = self.model(ppg, sine, lft, emb, lengths=lens, norm_groups=groups, norm_scratch=norm_scratch).to(torch.float32)
+                else:
+                    y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
                 self.forwards += 1
                 packed = torch.empty(max(lay["total"], 1), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
                 window_stitch(y.view(B, width * hop), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"],
@@ -1310,7 +1387,11 @@ def main(argv=None) -> None:                                  # pragma: no cover
                     help="with --resident: decode every utterance as overlapping windows of CORE frames "
                          "(DecodeSession.convert_windowed; CONTEXT frames read on each side, default the generator's "
                          "receptive field; cross-fade over FADE frames, default 8) - for recordings longer than one forward "
-                         "takes; with a speaker embedding InstanceNorm then normalises per window")
+                         "takes; with a speaker embedding InstanceNorm then normalises per window, see --window-norm")
+    ap.add_argument("--window-norm", choices=("window", "utterance"), default="window",
+                    help="with --window: InstanceNorm statistics per window (default) or pooled over all windows of an "
+                         "utterance, which reproduces the whole-utterance result; an utterance then needs at most "
+                         "--max-batch windows")
     args = ap.parse_args(argv)
     if args.window is not None:
         if not args.resident or args.fanout > 1:
@@ -1321,7 +1402,9 @@ def main(argv=None) -> None:                                  # pragma: no cover
                 raise ValueError
         except ValueError:
             ap.error("--window takes CORE[,CONTEXT[,FADE]] in frames")
-        args.window = dict(zip(("core", "context", "fade"), parts))
+        args.window = dict(zip(("core", "context", "fade"), parts), norm=args.window_norm)
+    elif args.window_norm != "window":
+        ap.error("--window-norm needs --window")
     if args.fanout < 1:
         ap.error("--fanout needs a group size of at least 1")
     if args.fanout > 1 and not args.resident:

@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "fastsvc_plan_set_storage", "fastsvc_plan_get_storage",
     "fastsvc_weight_blob_bytes", "fastsvc_pack_weights", "fastsvc_workspace_bytes",
     "fastsvc_pack_device_scratch_bytes", "fastsvc_pack_device_launch_count", "fastsvc_pack_weights_device",
-    "fastsvc_forward", "fastsvc_autotune", "fastsvc_tuned_count", "fastsvc_tuned_get", "fastsvc_tuned_set",
+    "fastsvc_forward", "fastsvc_forward_grouped", "fastsvc_norm_group_scratch_bytes", "fastsvc_norm_group_stats", "fastsvc_autotune", "fastsvc_tuned_count", "fastsvc_tuned_get", "fastsvc_tuned_set",
     "fastsvc_forward_profile", "fastsvc_workspace_tap", "fastsvc_forward_launch_count",
     "fastsvc_flops_per_sample", "fastsvc_signal_scratch_bytes", "fastsvc_signal_generate",
     "fastsvc_stream_prepare", "fastsvc_stream_release", "fastsvc_split_half", "fastsvc_plan_set_workspace_mode",
@@ -117,6 +117,12 @@ def load_library():
     lib.fastsvc_workspace_bytes.restype = sz
     lib.fastsvc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
     lib.fastsvc_forward.restype = ctypes.c_int
+    lib.fastsvc_norm_group_scratch_bytes.argtypes = [vp, i32, i32]
+    lib.fastsvc_norm_group_scratch_bytes.restype = sz
+    lib.fastsvc_forward_grouped.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp, sz, vp]
+    lib.fastsvc_forward_grouped.restype = ctypes.c_int
+    lib.fastsvc_norm_group_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastsvc_norm_group_stats.restype = ctypes.c_int
     lib.fastsvc_loudness_frames.argtypes = [i32, i32]
     lib.fastsvc_loudness_frames.restype = i32
     lib.fastsvc_loudness_scratch_bytes.argtypes = [i32, i32, i32]
@@ -631,6 +637,66 @@ def window_stitch(y: torch.Tensor, n_samples: Sequence[int], core_lo: Sequence[i
                                               ctypes.c_void_p(stream)), "fastsvc_window_stitch")
 
 
+def check_norm_groups(norm_groups, lens: Sequence[int]):
+    """Validate ``norm_groups = (group, own_lo, own_hi)`` - three sequences of B ints, as ``fastsvc_forward_grouped`` takes
+    them - against the rows' frame counts ``lens``, on the host (the library gets device arrays it cannot check): row b
+    owns the frames ``[own_lo[b], own_hi[b])`` with ``0 <= own_lo < own_hi <= lens[b]``, and ``group[b]`` is the index of
+    the first row of b's group, so ``group[b] <= b`` and ``group[group[b]] == group[b]``.  Returns the three as lists of
+    ints; ``ValueError`` names the first row that breaks a rule."""
+    try:
+        group, own_lo, own_hi = ([int(v) for v in seq] for seq in norm_groups)
+    except (TypeError, ValueError):
+        raise ValueError("norm_groups must be (group, own_lo, own_hi), three sequences of ints") from None
+    B = len(lens)
+    if len(group) != B or len(own_lo) != B or len(own_hi) != B:
+        raise ValueError(f"norm_groups must hold {B} entries each, got {len(group)}, {len(own_lo)}, {len(own_hi)}")
+    for b in range(B):
+        if not 0 <= own_lo[b] < own_hi[b] <= int(lens[b]):
+            raise ValueError(f"row {b}: owned frames [{own_lo[b]}, {own_hi[b]}) must satisfy 0 <= own_lo < own_hi <= "
+                             f"{int(lens[b])}, the row's frame count")
+        if not 0 <= group[b] <= b:
+            raise ValueError(f"row {b}: group[{b}] = {group[b]} must be the index of the first row of its group, so in [0, {b}]")
+        if group[group[b]] != group[b]:
+            raise ValueError(f"row {b}: group[{b}] = {group[b]} is not the first row of a group (group[{group[b]}] = "
+                             f"{group[group[b]]})")
+    return group, own_lo, own_hi
+
+
+def norm_group_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: int, norm_groups, stats: torch.Tensor) -> torch.Tensor:
+    """InstanceNorm sums of one tensor pooled over groups of rows (``fastsvc_norm_group_stats``,
+    csrc/fastsvc_normgroup.hip): ``u`` (B, C, ld) float32, bfloat16 or float16 on the device, row b valid for ``lens[b] *
+    len_mul`` columns (``None``: ``ld``), ``norm_groups = (group, own_lo, own_hi)`` in frames.  ``stats`` (B, C, 2)
+    float64 receives, for every row that is not alone in its group owning all its frames, the group's sums over the owned
+    columns times ``lens[b] * len_mul / N`` - ``decode.pool_norm_sums``' values; the other rows' entries are left
+    untouched.  Two launches on the current stream.  Returns ``stats``."""
+    lib = load_library()
+    if not isinstance(u, torch.Tensor) or not u.is_cuda:
+        raise FastSVCError("norm_group_stats needs GPU tensors (no CPU fallback); got " + str(getattr(u, "device", type(u))))
+    codes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+    if u.dim() != 3 or u.dtype not in codes or not u.is_contiguous():
+        raise ValueError(f"u must be a contiguous (B, C, ld) float32 / bfloat16 / float16 tensor; got {tuple(u.shape)} {u.dtype}")
+    B, C, ld = u.shape
+    len_mul = int(len_mul)
+    if len_mul < 1 or ld % len_mul:
+        raise ValueError(f"the pitch {ld} must be a multiple of len_mul {len_mul}")
+    if lens is not None and (len(lens) != B or min(lens) < 1 or max(lens) * len_mul > ld):
+        raise ValueError(f"lens must hold {B} frame counts in [1, {ld // len_mul}]")
+    if not isinstance(stats, torch.Tensor) or stats.device != u.device or stats.dtype != torch.float64 or \
+            tuple(stats.shape) != (B, C, 2) or not stats.is_contiguous():
+        raise ValueError(f"stats must be a contiguous float64 {(B, C, 2)} tensor on {u.device}")
+    group, own_lo, own_hi = check_norm_groups(norm_groups, lens if lens is not None else [ld // len_mul] * B)
+    dev = u.device
+    ints = torch.tensor([group, own_lo, own_hi] + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
+    scratch = torch.empty(B * C * (-(-ld // 2048)) * 16, dtype=torch.uint8, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib, lib.fastsvc_norm_group_stats(ptr(u), codes[u.dtype], B, C, ld, ptr(ints[3]) if lens is not None else None,
+                                                 len_mul, ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(stats), ptr(scratch),
+                                                 scratch.numel(), ctypes.c_void_p(stream)), "fastsvc_norm_group_stats")
+    return stats
+
+
 def _check(lib, rc: int, what: str):
     if rc != 0:
         msg = lib.fastsvc_last_error().decode("utf-8", "replace")
@@ -811,6 +877,10 @@ class Plan:
 
     def workspace_bytes(self, B: int, F: int) -> int:
         return int(self.lib.fastsvc_workspace_bytes(self._h, B, F))
+
+    def norm_group_scratch_bytes(self, B: int, F: int) -> int:
+        """Bytes of device scratch one forward with ``norm_groups`` needs for its partial sums."""
+        return int(self.lib.fastsvc_norm_group_scratch_bytes(self._h, B, F))
 
     def padded_frames(self, F: int) -> int:
         """Frame count the library actually runs for an F-frame batch: the next multiple of 4 (the padded batch is run
@@ -1003,12 +1073,20 @@ class Plan:
     def forward(self, blob: torch.Tensor, ppg: torch.Tensor, sine: torch.Tensor, lft: torch.Tensor,
                 spk_emb: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None, profile: Optional[list] = None,
-                autotune: bool = False, lengths=None) -> torch.Tensor:
+                autotune: bool = False, lengths=None, norm_groups=None,
+                norm_scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Enqueue one forward on the current HIP stream of ``ppg.device``; returns (B, O, T).
 
         ``lengths`` (B frame counts, 1 <= n <= F; sequence or int tensor) makes the batch ragged:
         inputs stay padded to F, utterance b is computed exactly as if run alone with lengths[b]
         frames and ``out[b, :, lengths[b]*hop:]`` is zero.
+
+        ``norm_groups = (group, own_lo, own_hi)`` (three sequences of B ints, ``check_norm_groups``) pools the InstanceNorm
+        statistics over groups of rows (``fastsvc_forward_grouped``): row b owns the frames ``[own_lo[b], own_hi[b])`` and is
+        normalised by the mean and variance of the owned frames of all rows whose ``group`` entry equals its own.  Rows alone
+        in their group that own all their frames run exactly as without it.  Not with ``profile`` or ``autotune``.
+        ``norm_scratch``: a uint8 device tensor of at least ``norm_group_scratch_bytes(B, padded_frames(F))`` bytes for the
+        partial sums (allocated per call when missing).
 
         With ``profile`` (a list) the launches are bracketed by hipEvents on that stream, the
         stream is synchronised and one dict per kernel launch is appended to the list.
@@ -1033,6 +1111,12 @@ class Plan:
         ppg, sine, lft = (t.to(torch.float32).contiguous() for t in (ppg, sine, lft))
         if spk_emb is not None:
             spk_emb = spk_emb.to(torch.float32).contiguous()
+        if norm_groups is not None:
+            if profile is not None or autotune:
+                raise ValueError("norm_groups runs neither profiled nor under autotune")
+            if isinstance(lengths, torch.Tensor):
+                raise ValueError("norm_groups needs lengths on the host (the owned ranges are checked against them)")
+            norm_groups = check_norm_groups(norm_groups, [F] * B if lengths is None else [int(v) for v in lengths])
         if F % 4 != 0 and profile is None and (self.storage != "float32" or self.pad_odd_lengths):
             # bfloat16 / float16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0
             # (three of four real utterances are not); float32 storage runs such rows on its slower kernels.  Pad to
@@ -1069,7 +1153,7 @@ class Plan:
                     raise ValueError("autotune times full-length batches: call it without lengths")
                 self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None, autotune=True)
             self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None,
-                         lengths=[F] * B if lengths is None else lengths)
+                         lengths=[F] * B if lengths is None else lengths, norm_groups=norm_groups, norm_scratch=norm_scratch)
             if out is None:
                 return py[..., :T].contiguous()
             out.copy_(py[..., :T])
@@ -1113,6 +1197,15 @@ class Plan:
                 ntr = ctypes.c_int32(0)
                 rc = self.lib.fastsvc_autotune(*common[:9], common[10], common[11], common[12], ctypes.byref(ntr))
                 self.last_autotune_trials = int(ntr.value)
+            elif norm_groups is not None and spk_emb is not None:
+                need = self.norm_group_scratch_bytes(B, F)
+                if norm_scratch is None or norm_scratch.numel() * norm_scratch.element_size() < need or norm_scratch.device != dev:
+                    norm_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+                ng = self._stage_lengths(torch.tensor(norm_groups, dtype=torch.int32).reshape(-1), 3 * B, dev)
+                rc = self.lib.fastsvc_forward_grouped(*common[:10], *[ctypes.c_void_p(ng[i * B:].data_ptr()) for i in range(3)],
+                                                      common[10], common[11], ctypes.c_void_p(norm_scratch.data_ptr()),
+                                                      norm_scratch.numel() * norm_scratch.element_size(), common[12])
+                workspace = (workspace, ng, norm_scratch)
             elif profile is None:
                 rc = self.lib.fastsvc_forward(*common)
             else:

@@ -32,8 +32,17 @@ The windowed leg (DECODE_LEGS=windowed only; profiles/decode_windowed.txt), floa
 
 on the 512 utterances, and on ONE utterance of 30 000 frames (200 s).  The recomputed context makes (core + 2 context) /
 core the expected ratio for utterances much longer than a window.
+The window-norm leg (DECODE_LEGS=window_norm only; profiles/decode_window_norm.txt), float32 and bfloat16 storage, one
+resident session, max_batch 64, speaker embedding:
+
+    whole       convert()                                                } alternated, DECODE_REPS each, median
+    window      convert_windowed(core=400)                    per-window  }
+    utterance   convert_windowed(core=400, norm="utterance")  pooled      }
+
+on 64 utterances of 2 000 frames and on ONE utterance of 24 000 frames (60 windows: one batch).
     python tools/decode_throughput.py                  (DECODE_LEGS=session or =checked: one of the two parts only;
-                                                        DECODE_LEGS=fanout: the fan-out leg; =windowed: the windowed leg)"""
+                                                        DECODE_LEGS=fanout: the fan-out leg; =windowed: the windowed leg;
+                                                        =window_norm: the window-norm leg)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -239,6 +248,51 @@ def windowed_legs():
         f.write("\n".join(out) + "\n")
 
 
+def window_norm_legs():
+    """convert, convert_windowed(core=400) and convert_windowed(core=400, norm="utterance"), same session, same process."""
+    CORE, mb = 400, 64
+    out = [f"window-norm decode: DecodeSession.convert() against convert_windowed(core={CORE}) with norm=\"window\" and "
+           f"norm=\"utterance\"; max_batch {mb}, F0 shift on, speaker embedding, int16 out, {reps} repetitions, legs alternated, "
+           f"median (min, max); {torch.cuda.get_device_name(0)}"]
+    r = np.random.default_rng(7)
+
+    def utt(F):
+        return {"ppg": r.standard_normal((F, cfg.in_channels), dtype=np.float32),
+                "f0": np.where(r.random((F, 1)) < 0.3, 0.0, r.uniform(80, 400, (F, 1))),
+                "lft": r.uniform(-9, 1, (F * cfg.hop, 1)).astype(np.float32)}
+    sets = (("64 utterances of 2000 frames", [utt(2000) for _ in range(64)]), ("1 utterance of 24000 frames", [utt(24000)]))
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for name, sub in sets:
+            unit = sum(len(f["ppg"]) for f in sub) * cfg.hop
+            with Dc.DecodeSession(m, sub, sg, dev, [[5.0, 1.0]] * len(sub), max_batch=mb) as s:
+                legs = {"whole": lambda: s.convert(emb, trg),
+                        "window": lambda: s.convert_windowed(emb, trg, core=CORE),
+                        "utterance": lambda: s.convert_windowed(emb, trg, core=CORE, norm="utterance")}
+                res, nfw = {}, {}
+                for k, fn in legs.items():                                                   # (warm all three; compare)
+                    res[k] = fn()
+                    nfw[k] = len(s.batches) if k == "whole" else s.forwards
+                diff = {k: max(int(np.abs(a.astype(np.int32) - b.astype(np.int32)).max()) for a, b in zip(res["whole"], res[k]))
+                        for k in ("window", "utterance")}
+                del res
+                t = {k: [] for k in legs}
+                for _ in range(reps):
+                    for k, fn in legs.items():
+                        t[k].append(timed(fn)[0])
+            med = {}
+            for k in legs:
+                med[k], line = spread(f"{name}: {k:9s} ({nfw[k]} forwards)", t[k], unit)
+                out.append(line)
+            out.append(f"    norm=utterance / norm=window time {med['utterance'] / med['window']:.3f}; largest PCM-16 difference to "
+                       f"convert(): norm=window {diff['window']}, norm=utterance {diff['utterance']}")
+            print("\n".join(out[-4:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_window_norm.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 LEGS = os.environ.get("DECODE_LEGS", "all")
 for storage in (("float32", "bfloat16") if LEGS in ("all", "session") else ()):
     m = build_model(storage)
@@ -291,3 +345,5 @@ if LEGS == "fanout":
     fanout_legs()
 if LEGS == "windowed":
     windowed_legs()
+if LEGS == "window_norm":
+    window_norm_legs()
