@@ -265,6 +265,8 @@ typedef struct fastsvc_launch_record {
     double flops;
     double bytes;
     float ms;
+    int32_t x2_path;   /* up.<i>.d3x, 2-byte storage, stretch 4 / 5: how the second operand was fetched - 1 element loads,
+                          2 through the raw LDS tile; 0 everywhere else.  (Takes the struct's former tail padding.) */
 } fastsvc_launch_record;
 
 int fastsvc_forward_profile(const fastsvc_plan* plan, const void* dev_blob,

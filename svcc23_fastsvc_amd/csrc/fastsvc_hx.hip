@@ -639,6 +639,27 @@ constexpr bool hx_carry(int MODE, bool tailk, int S, int NT) {
     return FASTSVC_HX_CARRY != 0 && hx_w8(MODE, tailk, S) && MODE == MODE_DIRECT && S == 1 && NT == 128;
 }
 
+// Second operand at S = 4 / 5, 2-byte storage (F_X2_GATHER): the unit's input columns are fetched UNSTRETCHED
+// into a raw LDS tile by 16-byte requests - 8 consecutive columns of one channel row, the first one rounded down to a
+// multiple of 8: 32 rows x 8 pieces = ONE request per staging thread where the element loads are eight - and the
+// stretched commit gathers its 8 channels of one column from there (8 two-byte LDS reads) instead of from memory.
+// The commit's lane map, the stretched window and everything behind it are those of the element loads: same bits.
+// Tile: [4 groups of 8 channel rows][8 rows][64 columns x 2 B]; a group is 32 bytes longer than its rows, so that the
+// four channel octets a gather instruction reads (16 consecutive columns each) start 8 banks apart.
+// The 64 columns from j0 = floor(t_start / S) & ~7 on cover every window row when W <= 56 S + 1 (conv_hx_x2_gather_ok):
+// row r < W reads column floor((t_start + r) / S) <= j0 + 7 + floor((W + S - 2) / S).
+constexpr int HX_X2G_COLS = 64;
+constexpr int HX_X2G_ROW = HX_X2G_COLS * 2;
+constexpr int HX_X2G_GROUP = 8 * HX_X2G_ROW + 32;
+constexpr int HX_X2G_BYTES = 4 * HX_X2G_GROUP;
+constexpr bool hx_x2_gather(int MODE, int S) {
+#ifdef FASTSVC_ACT_2B
+    return MODE == MODE_DIRECT && (S == 4 || S == 5);
+#else
+    return false;
+#endif
+}
+
 template <int MW, int NW, int WM, int WN, int MODE, int EPI, int S, bool WSTATIC, bool TAILK = false>
 __global__ __launch_bounds__(512, (hx_min_waves<MW, NW, MODE, EPI, S, TAILK>()))
 void conv_hx_kernel(const ConvParams p0) {
@@ -653,6 +674,7 @@ void conv_hx_kernel(const ConvParams p0) {
     // against 954 - the second window's LDS and the twelve resident fragments cost the second workgroup of the CU;
     // C = 48: 555 against 585 us.)
     constexpr bool XR = MODE == MODE_DIRECT && S > 1;
+    constexpr bool XG = XR && hx_x2_gather(MODE, S);                   // the second operand may come through the raw LDS tile
     constexpr int NT = 16 * NW * WN;                                   // (input-rate) columns per workgroup tile
     // MODE_CHAIN: the first conv also produces the second one's halo (<= 4 columns per side): its tile starts 4
     // columns early and is one 16-column MFMA tile longer (computed by the last wave along time)
@@ -727,7 +749,8 @@ void conv_hx_kernel(const ConvParams p0) {
     }
     double* sstat = reinterpret_cast<double*>(smem_raw);                               // [WM*MW*16][2]
     float2* ncoef = reinterpret_cast<float2*>(smem_raw + sizeof(double) * 2 * 16 * MW * WM);   // [CINp + 8]: the last 8 are (0, 0)
-    unsigned char* tiles = reinterpret_cast<unsigned char*>(ncoef + CINp + 8);         // [2][HX_NP][W rows][64 B]
+    unsigned char* x2raw = reinterpret_cast<unsigned char*>(ncoef + CINp + 8);         // XG with F_X2_GATHER: the raw tile (see hx_x2_gather)
+    unsigned char* tiles = x2raw + ((XG && (p0.flags & F_X2_GATHER)) ? HX_X2G_BYTES : 0);          // [2][HX_NP][W rows][64 B]
     // small per-workgroup constants (static LDS; HX_STATIC_LDS bounds them for the launcher's size checks)
     __shared__ unsigned s_amax, s_cnt;                 // workgroup's largest |value| written (ConvParams::amax_out), waves done
     __shared__ float s_inv[HX_NP == 2 ? 2 * 16 * MW * WM : 4];        // inverse operand scales [conv | second DEC2 output][channel]
@@ -1113,7 +1136,8 @@ void conv_hx_kernel(const ConvParams p0) {
         // commit is two byte-permutes per column and S 8-byte LDS writes; rows outside the window go to the lane's own
         // 8 bytes of the spare rows.  Measured at cfg3 (round 6): up.0.d3x (S = 2, C = 192) 210 -> 186 us; S = 4: 259 -> 260
         // (C = 96), 508 -> 518 (C = 48); S = 5 (C = 24): 885 -> 910 - there ONE wave commits 4 S rows per lane where four
-        // shared S each, and the staging waves' instruction count is what paces the narrow layers: S = 2 only.
+        // shared S each, and the staging waves' instruction count is what paces the narrow layers: S = 2 only.  (S = 4 / 5
+        // get their wide requests through a raw LDS tile that leaves the commit's lane map alone: hx_x2_gather.)
         constexpr bool XW = XR && W8 && S == 2;
         const int xq4 = ptid & 7, xg4 = ptid >> 3;
         auto ploadX = [&](int un, act1_t (&px)[XJ][8]) {
@@ -1213,8 +1237,91 @@ void conv_hx_kernel(const ConvParams p0) {
         };
         if constexpr (XR) {
             pwin_t pa[ITEMS][8];
-            act1_t xb[XJ][8];
             unsigned oka = 0;
+            bool gathered = false;
+#ifdef FASTSVC_ACT_2B
+            if constexpr (XG) {
+                // ---- second operand through the raw LDS tile (see hx_x2_gather).  ONE wave-uniform branch around the whole
+                // staging loop, as the halo carry has it; inside, requests and commits are straight-line.
+                gathered = (flags & F_X2_GATHER) != 0;
+                if (gathered) {
+                    typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
+                    // raw piece = (channel row g_rr, columns j0 + 8 g_pc .. + 8): one 16-byte request per thread and unit
+                    const int g_rr = ptid >> 3, g_pc = ptid & 7;
+                    const int g_dst = (g_rr >> 3) * HX_X2G_GROUP + (g_rr & 7) * HX_X2G_ROW + g_pc * 16;
+                    auto gloadX = [&](int un, u32x4w& w, int& nv) {
+                        const int tl = xl_tl, ch = xl_ch;
+                        pos_next(xl_tl, xl_ch);
+                        const int t_start = (tile0 + tl) * NT - halo_al;
+                        const int g0 = (t_start + 8 * S) / S - 8;                     // floor(t_start / S), t_start >= -32
+                        const int jc = (g0 & ~7) + 8 * g_pc;                          // a multiple of 8: the piece starts inside the row or not at all
+                        const bool ok = ((unsigned)jc < (unsigned)x2T) & (g_rr < p.CIN - ch * HX_KC) & (un < nunits);
+                        nv = ok ? min(8, x2T - jc) : 0;                               // columns of the piece inside the utterance's row
+                        w = __builtin_amdgcn_raw_buffer_load_b128(x2r, ok ? (g_rr * p.ldx2 + jc) * 2 : OOB_OFF, ch * HX_KC * p.ldx2 * 2, FASTSVC_LD_AUX);
+                    };
+                    // the piece into the raw tile, what lies behind the row end zeroed (the conv's zero padding; behind it
+                    // the pitch holds nobody's data); one half BEFORE the commit that gathers from it: the unit barrier
+                    // in between publishes it, and the tile is written in the halves in which nobody reads it
+                    auto gstoreX = [&](const u32x4w& w, int nv) {
+                        u32x4w v = w;
+                        asm volatile("" : "+v"(v));            // (the masking stays where the store stands, see pcommit)
+                        #pragma unroll
+                        for (int k = 0; k < 4; ++k) v[k] &= nv >= 2 * k + 2 ? 0xffffffffu : nv == 2 * k + 1 ? 0x0000ffffu : 0u;
+                        *reinterpret_cast<u32x4w*>(x2raw + g_dst) = v;
+                        __builtin_amdgcn_sched_barrier(0);
+                    };
+                    // item and rows of the element loads' commit (octet xoct of column g0 + xg -> S rows of 16 bytes)
+                    auto gcommitX = [&](unsigned char* tile) {
+                        const int tl = xc_tl;
+                        pos_next(xc_tl, xc_ch);
+                        const int t_start = (tile0 + tl) * NT - halo_al;
+                        const int g0 = (t_start + 8 * S) / S - 8;
+                        const int r0 = (g0 + xg) * S - t_start;
+                        // (columns behind the tile belong to rows >= W, which go to the spare row)
+                        const unsigned char* src = x2raw + xoct * HX_X2G_GROUP + min((g0 & 7) + xg, HX_X2G_COLS - 1) * 2;
+                        hx8 h;
+                        #pragma unroll
+                        for (int c = 0; c < 8; ++c)
+                            h[c] = (hx_t)act_unpack1((act1_t)*reinterpret_cast<const unsigned short*>(src + c * HX_X2G_ROW));
+                        #pragma unroll
+                        for (int ph = 0; ph < S; ++ph) {
+                            const int r = r0 + ph;
+                            *reinterpret_cast<hx8*>(tile + hx_lds_off((unsigned)r < (unsigned)W ? r : W, xoct)) = h;
+                        }
+                    };
+                    u32x4w xw;
+                    int xn = 0;
+                    unsigned okn = 0;
+                    pload(0, pa, oka);
+                    gloadX(1, xw, xn);
+                    stamp(2);
+                    setup_shared();
+                    pcommit(0, pa, oka, tiles);
+                    gstoreX(xw, xn);
+                    if constexpr (!WSTATIC) pload(2, pa, okn);
+                    stamp(3);
+                    __syncthreads();                       // unit 0 staged, unit 1's raw tile written
+                    stamp(4);
+                    for (int u = 0; u < nunits; u += 2) {   // (requests where the element loads' stand, see below)
+                        if constexpr (WSTATIC) pload(u + 2, pa, oka);
+                        gcommitX(tiles + bufsz);
+                        if constexpr (!WSTATIC) gloadX(u + 3, xw, xn);
+                        stamp(5);
+                        __syncthreads();                   // end of unit u
+                        stamp(6);
+                        if constexpr (WSTATIC) gloadX(u + 3, xw, xn); else oka = okn;
+                        pcommit(u + 2, pa, oka, tiles);
+                        gstoreX(xw, xn);
+                        if constexpr (!WSTATIC) pload(u + 4, pa, okn);
+                        stamp(5);
+                        __syncthreads();                   // end of unit u + 1
+                        stamp(6);
+                    }
+                }
+            }
+#endif
+            if (!gathered) {
+            act1_t xb[XJ][8];
             // one register set per operand, each re-requested right after its commit: the main window of tile t + 1 is
             // requested under tile t's x2 unit (the long one: it carries the consumers' epilogue) and committed under tile
             // t + 1's - a whole tile of lead (requested in the half BEFORE its commit it had the main unit's 1-2k cycles)
@@ -1243,6 +1350,7 @@ void conv_hx_kernel(const ConvParams p0) {
                 stamp(5);
                 __syncthreads();                       // end of unit u + 1
                 stamp(6);
+            }
             }
         } else {
         // staged polyphase epilogue: this staging wave runs pass 2 for the channel tiles its consumer partner (wave - 4)
@@ -2108,6 +2216,11 @@ static hipError_t hx_launch_shape(const ConvParams& p, int nsig, hipStream_t str
                 return hipErrorInvalidValue;
             if (w8 && p.s2 == 2 && W / p.s2 + 5 > 128) return hipErrorInvalidValue;   // (the second operand's 32 groups of 4 columns per tile)
             if (w8 && !conv_hx_x2_rows_ok(p)) return hipErrorInvalidValue;
+            // F_X2_GATHER: the raw tile of the second operand in front of the windows (see hx_x2_gather)
+            if (p.flags & F_X2_GATHER) {
+                if (!hx_x2_gather(MODE_DIRECT, p.s2) || !conv_hx_x2_gather_ok(p, NT)) return hipErrorInvalidValue;
+                est += HX_X2G_BYTES;
+            }
 #define FASTSVC_HXX(sv, stat) if (p.s2 == sv) return hx_launch_instance<&conv_hx_kernel<MW, NW, WM, WN, MODE_DIRECT, EPI_AFF, sv, stat>>(grid, smem + est, stream, p);
             if constexpr (MW * NW <= 12) {                                         // (larger tiles spill with this epilogue)
                 if constexpr (MW == 2) { if (p.nch32 == 1) { FASTSVC_HXX(5, true) } }
@@ -2171,6 +2284,11 @@ hipError_t launch_conv_hx(const ConvParams& p, const ConvLaunch& cfg, hipStream_
 #ifndef FASTSVC_ACT_2B      // storage-independent host query: defined once
 bool conv_hx_x2_ok(int MW, int nch32, int s2) { return MW == 2 ? (nch32 == 1 && s2 == 5) : MW == 3 ? (s2 == 2 || s2 == 4) : false; }
 bool conv_hx_x2_rows_ok(const ConvParams& p) { return p.s2 != 2 || ((p.lens ? p.x2len_mul : p.x2_T) & 3) == 0; }
+bool conv_hx_x2_gather_ok(const ConvParams& p, int NT) {
+    const int W = NT + 2 * ((p.dil + 7) & ~7);
+    return (p.s2 == 4 || p.s2 == 5) && (p.ldx2 & 7) == 0 && (p.x2_b & 7) == 0 && (reinterpret_cast<uintptr_t>(p.x2) & 15) == 0 &&
+           W <= (HX_X2G_COLS - 8) * p.s2 + 1;
+}
 bool conv_hx_tail_ok(int mode, int MW, int epi_kind, int S) { return hx_tail_instance(MW, mode, epi_kind, S); }
 
 bool conv_hx_shape(int mode, int MW, int NW, int WM, int WN) {

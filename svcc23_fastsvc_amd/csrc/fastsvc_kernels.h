@@ -75,7 +75,11 @@ enum : int {
     F_PRE_NORM = 4,     // u = (u - mean) * rstd + p         (fastsvc.py:134-139)
     F_POST_LRELU = 8,   // LeakyReLU(0.2) on conv + bias
     F_STATS = 16,       // accumulate sum / sum-of-squares of (scale_out * y + shift_out) per (b, co)
-    F_AFF_OUT = 32      // also write u = scale_out * y + shift_out to y2 (the next conv's input)
+    F_AFF_OUT = 32,     // also write u = scale_out * y + shift_out to y2 (the next conv's input)
+    // launch_conv_hx, second operand (ConvParams::x2), 2-byte storage, s2 = 4 / 5: the staging waves fetch x2 by 16-byte
+    // requests into a raw LDS tile and gather the stretched window from there (conv_hx_x2_gather_ok must hold); without
+    // it: eight element loads per item
+    F_X2_GATHER = 64
 };
 
 constexpr float LRELU_SLOPE = 0.2f;
@@ -320,6 +324,10 @@ bool conv_hx_x2_ok(int MW, int nch32, int s2);
 // request 4 of its columns at once and test the row end once per group, so its rows (every utterance's own row of a
 // ragged batch: lens[b] * x2len_mul) must be a multiple of 4 long - else the columns past the end reach the last outputs
 bool conv_hx_x2_rows_ok(const ConvParams& p);
+// ... and whether a 2-byte-storage launch with workgroup tiles of NT columns may set F_X2_GATHER: s2 = 4 / 5,
+// every 16-byte piece of x2 aligned (pitch and batch stride multiples of 8 elements, base on 16 bytes), and the window
+// served by the raw tile's 64 columns (NT + 2 halo <= 56 s2 + 1)
+bool conv_hx_x2_gather_ok(const ConvParams& p, int NT);
 
 // the wide-layer kernel in which every wave multiplies (fastsvc_wx.hip): MODE_DIRECT, 48-channel groups (MW = 3), the
 // weights once per workgroup and unit through LDS; bfloat16 storage.  cfg.pipe is ignored; same ConvParams as launch_conv_hx.

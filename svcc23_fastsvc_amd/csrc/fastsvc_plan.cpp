@@ -1941,6 +1941,12 @@ void table_record(const fastsvc_plan& P, const char* key, const fastsvc_plan::Ch
 // the layer), 2 Winograd MW = 2, 3 half-precision MFMA (fastsvc_hx.hip), 6 the wide layers' kernel (fastsvc_wx.hip)
 struct Cand { int NW, WM, WN, algo; };
 
+// Algorithms of an "up.<i>.d3x" entry that mean the fused launch (run_d3x): 3, and 7 / 8, which also pin how the staging
+// waves fetch the stretched second operand in 2-byte storage (7: element loads, 8: 16-byte requests through the raw LDS
+// tile wherever conv_hx_x2_gather_ok allows it); under 3 the stretch factor's default below decides.
+inline bool d3x_fused_algo(int algo) { return algo == 3 || algo == 7 || algo == 8; }
+inline bool d3x_gather_default(int s2) { return s2 == 4 || s2 == 5; }
+
 struct EventPair {                                     // (destroyed on every way out of a timing loop: ADVICE r5)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~EventPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
@@ -2234,15 +2240,23 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
     char key[96];
     std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
     bool have = false, fused = true;
+    int x2_path = 3;                                       // the entry's algorithm where it names the second operand's path (7 / 8)
     Cand best = cands[0];
     fastsvc_plan::Choice ch;
     if (table_entry(*cc.plan, key, ch)) {
         // (the shape whatever the entry's algorithm says)
-        if (ch.algo != 3 && env().d3x != 2) { have = true; fused = false; }
+        if (d3x_fused_algo(ch.algo)) x2_path = ch.algo;
+        else if (env().d3x != 2) { have = true; fused = false; }
         for (const Cand& cd : cands)
             if (cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && ch.tpw >= 1 && ch.tpw <= 64) { best = cd; p.tpw = ch.tpw; have = true; }
     }
     auto ntx_of = [&](const Cand& cd) { return (long)(p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN); };
+    // how the staging waves fetch the second operand (F_X2_GATHER): through the raw LDS tile wherever the launch
+    // qualifies and the stretch factor has it by default; a table entry says otherwise with algorithm 7 (element loads)
+    // or 8 (the raw tile wherever the launch qualifies)
+    auto gather_for = [&](const Cand& cd) {
+        return (act_2b && x2_path != 7 && (x2_path == 8 || d3x_gather_default(p.s2)) && conv_hx_x2_gather_ok(p, 16 * cd.NW * cd.WN)) ? (int)F_X2_GATHER : 0;
+    };
     if (what == 2) {
         if (have || !cc.tuning) return hipSuccess;
         float best_ms = 1e30f;
@@ -2250,7 +2264,7 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
         q.flags &= ~F_STATS;                               // (the trial launches do not accumulate InstanceNorm sums)
         ConvLaunch Lq{c.MW, 0, 0, 0, 1, 2};
         hipError_t e = time_candidates(cands, stream, cc.trials,
-                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; return ntx_of(cd); },
+                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; q.flags = (q.flags & ~F_X2_GATHER) | gather_for(cd); return ntx_of(cd); },
                                        [&](int tpw) { q.tpw = tpw; return launch(q, Lq); }, best, p.tpw, best_ms);
         if (e != hipSuccess) return e;
         // (sep_ms times the two separate launches back to back on ONE stream; in production the residual conv runs on the side
@@ -2268,7 +2282,8 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
             fastsvc_plan::Choice pr{0, 0, 0, 0, -1};
             std::lock_guard<std::mutex> lock(cc.plan->tune_mu);
             if (cc.plan->prior_for(layer, p.B, p.T, act_2b, pr)) {
-                if (pr.algo != 3 && env().d3x != 2) fused = false;
+                if (d3x_fused_algo(pr.algo)) x2_path = pr.algo;
+                else if (env().d3x != 2) fused = false;
                 for (const Cand& cd : cands) if (cd.NW == pr.NW && cd.WM == pr.WM && cd.WN == pr.WN) best = cd;
             }
         }
@@ -2278,6 +2293,7 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
     done = true;
     if (what == 0) return hipSuccess;
     ConvLaunch L{c.MW, best.NW, best.WM, best.WN, 1, 2};
+    p.flags = (p.flags & ~F_X2_GATHER) | gather_for(best);
     double flops = 0.0, bytes = 0.0;
     char kname[48] = "";
     if (prof) {
@@ -2288,7 +2304,11 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
         std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,0,4,%d,%s>", L.MW, L.NW, L.WM, L.WN, p.s2, prod_tag(stg));
     }
     const long wgs = ((ntx_of(best) + p.tpw - 1) / p.tpw) * (long)(c.ngroups / L.WM) * p.B;
-    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() { return launch(p, L); }, &p, &L, wgs, 2 * p.nch32);
+    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() {
+        // (the record of this launch: which way its second operand came, 2-byte storage at s2 = 4 / 5)
+        if (prof && act_2b && (p.s2 == 4 || p.s2 == 5)) prof->recs.back().x2_path = (p.flags & F_X2_GATHER) ? 2 : 1;
+        return launch(p, L);
+    }, &p, &L, wgs, 2 * p.nch32);
 }
 
 // Stage 0 of the conditioning nets as ONE launch (fastsvc_cond.hip): raw signals -> ss.0 and the compact h_0[..., ::s_1].

@@ -71,7 +71,7 @@ class _Config(ctypes.Structure):
 
 class _LaunchRecord(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_char * 64), ("kernel", ctypes.c_char * 40),
-                ("flops", ctypes.c_double), ("bytes", ctypes.c_double), ("ms", ctypes.c_float)]
+                ("flops", ctypes.c_double), ("bytes", ctypes.c_double), ("ms", ctypes.c_float), ("x2_path", ctypes.c_int32)]
 
 
 class _Tensor(ctypes.Structure):
@@ -1215,7 +1215,8 @@ class Plan:
                 if rc == 0:
                     for i in range(n.value):
                         profile.append(dict(layer=recs[i].layer.decode(), kernel=recs[i].kernel.decode(),
-                                            flops=recs[i].flops, bytes=recs[i].bytes, ms=recs[i].ms))
+                                            flops=recs[i].flops, bytes=recs[i].bytes, ms=recs[i].ms,
+                                            x2_path=("", "element", "gather")[recs[i].x2_path]))
         _check(self.lib, rc, "fastsvc_forward")
         self._last_workspace = (workspace, lens_dev)      # keep alive until the stream has consumed them
         return out
