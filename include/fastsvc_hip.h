@@ -487,6 +487,54 @@ int fastsvc_window_stitch(const float* y, int32_t B, int32_t width, const int32_
                           float* stage, int64_t stage_elems, const int64_t* dst_off, int16_t* dst16, float* dstf,
                           int64_t dst_elems, const int32_t* utt, fastsvc_row_report* report, int32_t n_utts, void* stream);
 
+/* Live streams (csrc/fastsvc_stream.hip; decode.StreamSession) - an utterance whose features arrive a few frames at a time.
+ * The reference decodes whole files (decode_fastsvc.py:150-200) and has no counterpart.
+ *
+ * State, all DEVICE, for n_streams slots; `cap` (a multiple of 4) frames are retained per stream, frame p at index p % cap:
+ *   ppg_ring (n_streams, cap, C)   time-major        lft_ring, exc_ring (n_streams, cap * hop)        float32, 16-byte aligned
+ *   phase    (n_streams, 2)        float64: the sine phase C_f in cycles, in [0, 1), of the stream's next frame, in the
+ *                                  entry the last push WROTE (a push reads entry parity[i] and writes entry parity[i] ^ 1:
+ *                                  the caller alternates it per stream and push that appends at least one frame)
+ *
+ * Push.  Entry i appends n[i] frames (0 <= n[i] <= max_push <= min(cap, 1024); 0 changes nothing) to stream stream[i] (every
+ * stream at most once per call), which held pos[i] frames before.  The frames come from the packed float32 DEVICE buffer
+ * `upload` (upload_elems floats), from element up_off[i]: the time-major ppg n x C, then f0 n, then lft n x hop.  ppg and
+ * lft are copied bit for bit into the rings at frame index pos[i] % cap (a chunk wraps at most once); the excitation of
+ * the chunk is synthesised into exc_ring by the same launch: fastsvc_signal_generate's "sine" signal for
+ *     C_{f+1} = frac(C_f + hop * rad_f),   rad_f = (f0_f / sample_rate) % 1 in float32,
+ * run in float64 by one lane over the chunk, starting from phase[stream][parity] - or from 0 when first[i] is set, which
+ * reads nothing: opening a slot needs no clearing - and then the closed form of the whole-utterance synthesis per sample.
+ * hop * rad_f is a float32 times a small integer, and while the partial sums stay below 2^16 no float64 add rounds
+ * (DESIGN.md 4.10), so with noise_amp == 0 the samples are bit for bit fastsvc_signal_generate's on the whole f0.  Noise is keyed by seed[i] and the ABSOLUTE sample index
+ * pos[i] * hop + k: it depends neither on the slot nor on how the stream was cut into pushes.
+ * 16-byte requests where source and destination addresses allow (C % 4 == 0, up_off and n multiples of 4), element
+ * requests elsewhere; plain vector stores, no atomics; no load outside the entry's slice of `upload` and the phase entry,
+ * no store outside the stream's own rings and phase pair.  All per-entry arrays are HOST arrays of S entries, read during
+ * the call (their values travel in the kernel arguments).  Everything is checked on the host BEFORE anything is enqueued -
+ * null or misaligned pointers, sizes, n[i] > max_push, a stream out of range or pushed twice, a slice that leaves
+ * `upload`: FASTSVC_E_INVALID with the stream and the reason in fastsvc_last_error(), and nothing has changed; a failed
+ * launch is FASTSVC_E_HIP.  One launch per 64 entries (fastsvc_stream_launch_count(S)), none when every n[i] is 0;
+ * asynchronous on `stream_`.
+ *
+ * Assembly.  fastsvc_window_assemble's outputs for rows cut from the rings: row r is the n_frames[r] frames from frame
+ * first_frame[r] of stream stream[r], read modulo cap ->
+ *   ppg_out (R, C, width)                 transposed to channel-major, every column >= n_frames written as 0
+ *   lft_out, sine_out (R, 1, width * hop) copied bit for bit, the tail written as 0
+ * pos[s] (HOST, n_streams entries) is the number of frames stream s holds: a row must lie inside the retained frames
+ * [pos[s] - cap, pos[s]) of its stream and 0 <= n_frames[r] <= min(width, cap), else FASTSVC_E_INVALID with the row and the
+ * reason, before anything is enqueued.  No load outside the rings, no store outside the three outputs.  One launch per 64
+ * rows (fastsvc_stream_launch_count(R)), asynchronous on `stream_`. */
+int fastsvc_stream_launch_count(int32_t R);
+int fastsvc_stream_push(const float* upload, int64_t upload_elems, int32_t S, const int32_t* stream, const int32_t* n,
+                        const int64_t* up_off, const int64_t* pos, const int32_t* first, const int32_t* parity,
+                        const uint64_t* seed, float* ppg_ring, float* lft_ring, float* exc_ring, double* phase,
+                        int32_t n_streams, int32_t cap, int32_t max_push, int32_t C, int32_t hop,
+                        float sample_rate, float sine_amp, float noise_amp, void* stream_);
+int fastsvc_stream_assemble(const float* ppg_ring, const float* lft_ring, const float* exc_ring, int32_t n_streams, int32_t cap,
+                            const int64_t* pos, const int32_t* stream, const int64_t* first_frame, const int32_t* n_frames,
+                            float* ppg_out, float* lft_out, float* sine_out,
+                            int32_t R, int32_t C, int32_t hop, int32_t width, void* stream_);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

@@ -17,21 +17,7 @@
 
 namespace {
 
-constexpr double TWO_PI = 6.283185307179586476925286766559;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ float gauss(uint64_t seed, uint64_t idx) {
-    const uint64_t h = mix64(mix64(idx ^ seed) + seed);
-    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
-    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.2831853f * u2);
-}
+#include "fastsvc_signal.inc"      // mix64, gauss, frame_rad, phase_step, sine_sample: shared with fastsvc_stream.hip
 
 // one workgroup per utterance: exclusive scan of hop * rad_f over the frames, kept mod 1 in f64
 __global__ __launch_bounds__(256)
@@ -44,8 +30,7 @@ void frame_phase_kernel(const float* __restrict__ f0, double* __restrict__ cf, i
     const int lo = tid * per, hi = min(F, lo + per);
     double s = 0.0;
     for (int i = lo; i < hi; ++i) {
-        const float rad = fmodf(f[i] / sr, 1.0f);              // (f0 / sample_rate) % 1 in fp32, as the reference
-        s += (double)hop * (double)rad;
+        s += (double)hop * (double)frame_rad(f[i], sr);
     }
     part[tid] = s;
     __syncthreads();
@@ -57,9 +42,7 @@ void frame_phase_kernel(const float* __restrict__ f0, double* __restrict__ cf, i
     double run = part[tid];
     for (int i = lo; i < hi; ++i) {
         c[i] = run;
-        const float rad = fmodf(f[i] / sr, 1.0f);
-        run += (double)hop * (double)rad;
-        run -= floor(run);
+        run = phase_step(run, frame_rad(f[i], sr), hop);
     }
 }
 
@@ -83,11 +66,7 @@ void synth_kernel(const float* __restrict__ f0, const double* __restrict__ cf, f
         float v;
         const uint64_t ctr = ((uint64_t)(b * 4 + k) << 40) + (uint64_t)t;
         if (a.types[k] == 1) {
-            const float rad = fmodf(f0v / sr, 1.0f);
-            double ph = cf[(long)b * F + fr] + (double)(j + 1) * (double)rad;
-            ph -= floor(ph);
-            v = vuv * (float)sin(ph * TWO_PI) * sine_amp;
-            if (noise_amp > 0.f) v += gauss(seed, ctr) * (vuv * noise_amp + (1.0f - vuv) * noise_amp / 3.0f);
+            v = sine_sample(f0v, cf[(long)b * F + fr], j, sr, sine_amp, noise_amp, seed, ctr);
         } else if (a.types[k] == 0) {
             v = gauss(seed ^ 0x5851F42D4C957F2Dull, ctr);
         } else {

@@ -19,7 +19,9 @@ the speakers in groups of N whose batches hold (utterance, speaker) rows (``conv
 [--fallback bfloat16,float32]`` reports per utterance what the PCM-16 conversion hides and re-runs in a fallback storage the
 batches whose output is not finite, and ``--storage auto`` is float16 storage with ``--checked --fallback bfloat16``.
 ``--window CORE[,CONTEXT[,FADE]]`` decodes every utterance as overlapping windows (``convert_windowed``): recordings longer
-than one forward takes, in buffers sized by the window.
+than one forward takes, in buffers sized by the window.  ``--stream PUSH[,CORE[,CONTEXT[,FADE]]] [--streams N]`` feeds the
+dumps as N concurrent simulated LIVE streams, PUSH frames per call (``StreamSession``: features arrive chunk by chunk,
+samples come back as soon as their window has its context).
 """
 from __future__ import annotations
 
@@ -419,6 +421,119 @@ def stitch_layout(rows: Sequence[Tuple[int, int, int, int, int]], batches: Seque
         d["total"], d["width"], d["half"] = pos, widths[k], half
         per_batch.append(d)
     return per_batch, slots * fh
+
+
+def stream_ready_rows(seen: int, ended: bool, core: int, context: int, done: int) -> List[Tuple[int, int, int, int]]:
+    """The windows of a live stream that can run now: rows ``(in_lo, in_hi, core_lo, core_hi)``, in frames, for the windows
+    ``done, done + 1, ...`` (``done`` windows ran before) that are READY when ``seen`` frames have arrived.  Window k is
+    ready when ``(k + 1) core + context`` frames have arrived - everything it reads is there - or the stream has ended
+    and ``k core < seen``; it reads ``[max(0, k core - context), min(seen, (k + 1) core + context))``.  Whatever the push
+    schedule, a stream's rows are, one after the other, exactly ``window_plan([F], core, context)`` for its final length
+    F: a window that runs before the end has all its context, one that runs at the end is clipped by F as the plan
+    clips it."""
+    seen, core, context, k = int(seen), int(core), int(context), int(done)
+    rows = []
+    while seen >= (k + 1) * core + context or (ended and k * core < seen):
+        lo, hi = k * core, min((k + 1) * core, seen)
+        rows.append((max(0, lo - context), min(seen, (k + 1) * core + context), lo, hi))
+        k += 1
+    return rows
+
+
+def stream_ring_frames(core: int, context: int, max_push: int) -> int:
+    """Frames a live stream retains on the device: ``core + 2 context + max_push`` rounded up to a multiple of 4.  After
+    every push all ready windows run, so the oldest window that has not run, k, lacks a frame: ``seen < (k + 1) core +
+    context``.  The next push brings at most ``max_push`` frames, and window k reads from ``k core - context``: the frames
+    still needed span less than ``core + 2 context + max_push``, so a ring of that many never overwrites one."""
+    return -(-(int(core) + 2 * int(context) + int(max_push)) // 4) * 4
+
+
+class StreamStitchLayout:
+    """``stitch_layout``, incrementally: the streams' rows arrive batch by batch (a ``StreamSession.push`` is one batch
+    per forward) and nobody knows the final length yet.  ``batch(rows, seen)`` returns for these rows what
+    ``stitch_layout(rows_of_the_whole_streams, batches_so_far_and_later, hop, fade)`` puts into that batch's dict - the
+    same ``n_samples``, ``core_lo``, ``core_hi``, modes, ``FROM_Y`` sources, ``dst_off``, ``runs``, ``total``, ``width``,
+    ``half`` - except for where the staged zones live: every stream has TWO slots of ``2 half`` floats (``stage_elems``
+    floats in all, allocated once).  A stream has at most one zone staged at a time, and a batch reads at most one slot
+    of a stream (its first window of the batch, ``FROM_STAGE``) and writes at most one (its last, ``STAGE``) - in rows
+    of one launch that nothing orders.  So a ``STAGE`` always takes the slot the stream did NOT write last: it is never
+    the slot a row of the same batch reads.  ``pending[s]`` is the window of stream s whose right zone is staged and
+    waits for its neighbour, ``written[s]`` the slot (0 / 1) it is in.
+
+    A row is ``(stream, k, in_lo, in_hi, core_lo, core_hi, last)``: window k of the stream, and whether it is the
+    stream's last one.  Rows of a stream must come in window order; ``seen[stream]`` is the stream's frame count (its
+    final one when it has ended), which clips a zone the stream ends in."""
+
+    def __init__(self, n_streams: int, hop: int, fade: int):
+        fade = int(fade)
+        if fade < 0 or fade % 2:
+            raise ValueError(f"fade must be even and >= 0, got {fade}")
+        self.n_streams, self.hop, self.half = int(n_streams), int(hop), fade * int(hop) // 2
+        self.stage_elems = self.n_streams * 2 * 2 * self.half
+        self.pending: List[Optional[int]] = [None] * self.n_streams
+        self.written = [1] * self.n_streams              # (the slot a stream staged into last; its first goes to slot 0)
+
+    def reset(self, stream: int) -> None:
+        """A new stream takes the slot: nothing is staged."""
+        self.pending[stream] = None
+
+    def slot(self, stream: int, which: int) -> int:
+        """First element of slot ``which`` (0 / 1) of the stream."""
+        return (2 * stream + which) * 2 * self.half
+
+    def batch(self, rows, seen):
+        hop, half = self.hop, self.half
+        NONE, STAGE, FROM_STAGE, FROM_Y, SKIP = range(5)
+        where = {(r[0], r[1]): j for j, r in enumerate(rows)}
+        if len(where) != len(rows):
+            raise ValueError("a window is in the batch twice")
+        width = max(r[3] - r[2] for r in rows) * hop
+        d = {key: [] for key in ("n_samples", "core_lo", "core_hi", "left_mode", "right_mode", "left_src", "right_src",
+                                 "dst_off", "utt", "runs")}
+        pending, written = list(self.pending), list(self.written)
+        pos = 0
+        for s, k, in_lo, in_hi, lo, hi, last in rows:
+            T = int(seen[s]) * hop
+            lm = rm = NONE
+            ls = rs = 0
+            if half and k > 0:
+                if (s, k - 1) in where:
+                    if where[(s, k - 1)] > where[(s, k)]:
+                        raise ValueError(f"stream {s}: window {k} comes before window {k - 1}")
+                    lm = SKIP
+                elif pending[s] == k - 1:
+                    lm, ls = FROM_STAGE, self.slot(s, written[s])
+                    pending[s] = None
+                else:
+                    raise ValueError(f"stream {s}: window {k} runs, but window {k - 1} has not staged its fade zone")
+            if half and not last:
+                if (s, k + 1) in where:
+                    b = rows[where[(s, k + 1)]]
+                    rm, rs = FROM_Y, where[(s, k + 1)] * width + (hi * hop - half - b[2] * hop)
+                else:
+                    written[s] ^= 1                      # (not the slot the stream's first row of this batch may read)
+                    rm, rs = STAGE, self.slot(s, written[s])
+                    pending[s] = k
+            t_lo = lo * hop - half if lm == FROM_STAGE else min(lo * hop + half, T) if lm != NONE else lo * hop
+            t_hi = min(hi * hop + half, T) if rm == FROM_Y else hi * hop - half if rm != NONE else hi * hop
+            t_hi = max(t_hi, t_lo)
+            d["n_samples"].append((in_hi - in_lo) * hop)
+            d["core_lo"].append((lo - in_lo) * hop)
+            d["core_hi"].append((hi - in_lo) * hop)
+            d["left_mode"].append(lm)
+            d["right_mode"].append(rm)
+            d["left_src"].append(ls)
+            d["right_src"].append(rs)
+            d["dst_off"].append(pos)
+            d["utt"].append(s)
+            d["runs"].append((s, t_lo, t_hi))
+            pos += -(-(t_hi - t_lo) // 8) * 8            # (every run starts on a 16-byte boundary of both destinations)
+        d["total"], d["width"], d["half"] = pos, width, half
+        self.pending, self.written = pending, written    # (only a batch that was laid out whole changes the state)
+        return d
+
+
+stream_stitch_layout = StreamStitchLayout           # (the incremental counterpart of ``stitch_layout``, under its name)
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
@@ -1346,6 +1461,294 @@ class DecodeSession:
         return out
 
 
+class StreamSession:
+    """Live conversion: features arrive a few frames at a time, for up to ``n_streams`` streams at once, and samples
+    come back as soon as the windows that own them can run.
+
+        with StreamSession(model, sg, device, n_streams=8) as s:
+            a = s.open(trg_emb, src_stats, trg_stats)
+            while ...:
+                out = s.push({a: dict(ppg=..., f0=..., lft=...)})      # {a: int16 samples, possibly none yet}
+            tail = s.end([a])[a]
+
+    A stream is an utterance whose length F is unknown until it ends.  Its windows are ``window_plan([F], core,
+    context)`` (``context=None``: ``receptive_field_frames`` rounded up to a multiple of 4; the sizes follow
+    ``convert_windowed``'s rules), window k runs in the push after which it is ready (``stream_ready_rows``), and the
+    windows are cross-faded by ``stitch_windows``' rule: everything a stream returned, concatenated, is samples ``[0, F
+    hop)``, each exactly once, and equals ``stitch_windows`` of its windows.  WITHOUT a speaker embedding that is the
+    whole-utterance result (to float32 kernel arithmetic); WITH one it is ``convert_windowed(norm="window")``'s function:
+    InstanceNorm normalises every window by its own statistics (whole-utterance or running statistics are out of scope
+    here: they need frames that have not arrived).
+
+    State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
+    ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
+    upload buffer with a page-locked twin and one page-locked download buffer.  Per ``push``: one upload, one
+    ``stream_push`` launch (appends to the rings and synthesises the chunk's excitation, csrc/fastsvc_stream.hip) and, if
+    any window became ready, per ``max_batch`` rows one ``stream_assemble``, one forward with ``lengths``, one
+    ``window_stitch`` and one download.  A push that completes no window runs no forward (``forwards`` counts them).
+
+    Excitation: the phase is carried from push to push in float64 and equals the whole-utterance scan bit for bit, so
+    with ``noise_amp == 0`` the streamed excitation IS ``signal_generator`` on the whole f0.  The noise is keyed by the
+    stream's ``seed`` (mixed with the generator's) and the absolute sample index: it depends neither on the slot nor on
+    the push sizes - and is another draw than ``signal_generator``'s, as ``convert_many``'s already is.  The F0 shift is
+    ``F0Statistics.convert`` on the host per chunk, as in ``DecodeSession.convert``.
+
+    Latency, in frames of input (``latency_frames``, ``latency_frames_max``): a sample of frame t is returned by the
+    push that delivers frame ``(t // core + 1) core + context - 1`` - its window's last context frame; the last ``fade /
+    2`` frames of every core wait for the next window as well and return with frame ``(t // core + 2) core + context -
+    1``; ``end`` returns everything still held; ``fade=0`` holds nothing back.  So ``core + context`` is the typical and
+    ``2 core + context`` the worst delay.
+
+    ``push`` validates everything before it uploads or enqueues anything: a ``ValueError`` leaves the session as it
+    was.  Not thread-safe.  ``out_channels`` must be 1 and the signal generator's only signal "sine".  Not built: checked /
+    fallback reports, graph capture of the per-push chain, several GPUs."""
+
+    def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
+                 fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32):
+        from .engine import FastSVCError, STREAM_MAX_PUSH
+        self.model, self.signal_generator = model, signal_generator
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise FastSVCError("StreamSession needs a GPU device (no CPU fallback); got " + str(self.device))
+        cfg = getattr(model, "_cfg", None)
+        if cfg is None:
+            raise ValueError("StreamSession needs a model with a generator configuration (FastSVCGenerator)")
+        if int(getattr(model, "out_channels", 1)) != 1:
+            raise ValueError("StreamSession supports out_channels == 1 only")
+        if list(getattr(signal_generator, "signal_types", ["sine"])) != ["sine"]:
+            raise ValueError("StreamSession needs a signal generator whose only signal type is \"sine\"")
+        self.hop = hop = int(signal_generator.hop_size)
+        self.core = core = int(core)
+        self.context = context = -(-receptive_field_frames(cfg) // 4) * 4 if context is None else int(context)
+        self.fade = fade = int(fade)
+        _check_window_sizes(core, context, fade)
+        self.max_push = max_push = core if max_push is None else int(max_push)
+        self.n_streams, self.max_batch, self.pcm16 = int(n_streams), int(max_batch), bool(pcm16)
+        if self.n_streams < 1 or self.max_batch < 1:
+            raise ValueError("StreamSession needs n_streams >= 1 and max_batch >= 1")
+        if not 1 <= max_push <= STREAM_MAX_PUSH:
+            raise ValueError(f"max_push must be in [1, {STREAM_MAX_PUSH}], got {max_push}")
+        self.channels = C = int(cfg.in_channels)
+        self._takes_emb = bool(cfg.use_spk_emb)
+        self.cap = cap = stream_ring_frames(core, context, max_push)
+        dev, n = self.device, self.n_streams
+        self._ppg = torch.empty((n, cap, C), dtype=torch.float32, device=dev)
+        self._lft = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
+        self._exc = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
+        self._phase = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        self._layout = StreamStitchLayout(n, hop, fade)
+        self._stage = torch.empty(max(self._layout.stage_elems, 1), dtype=torch.float32, device=dev)
+        self._emb = torch.zeros((n, max(int(cfg.spk_emb_size), 1)), dtype=torch.float32, device=dev)
+        self._slice = -(-max_push * (C + 1 + hop) // 4) * 4              # (every stream's slice starts 16-byte aligned)
+        self._h_up = torch.empty(n * self._slice, dtype=torch.float32, pin_memory=True)
+        self._d_up = torch.empty(n * self._slice, dtype=torch.float32, device=dev)
+        # a push returns at most the frames a ring holds per stream; every row's run is padded to 8 samples
+        self._h_down = torch.empty(n * (cap * hop + 8 * (cap // core + 2)), dtype=torch.float32, pin_memory=True)
+        self._up_done: Optional[torch.cuda.Event] = None
+        self._emb_rows: Dict[tuple, torch.Tensor] = {}                       # row slots of a forward -> their index tensor
+        self._slots: List[Optional[Dict[str, object]]] = [None] * n          # per slot: the open stream's host state
+        self._ids: Dict[int, int] = {}                                       # open id -> slot
+        self._next_id = 0
+        self.forwards = 0
+        # set to a dict to have push leave what it made there (tests): "excitation", per stream id the device tensors of
+        # its chunks' excitation in order, and "forwards", per forward (its rows, the assembled excitation rows)
+        self._stream_trace: Optional[Dict[str, object]] = None
+        self._closed = False
+
+    latency_frames = property(lambda self: self.core + self.context, doc="the typical delay, in frames of input: core + context")
+    latency_frames_max = property(lambda self: 2 * self.core + self.context,
+                                  doc="the worst delay (the last fade / 2 frames of a core): 2 core + context")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        """Wait for the session's device work and release its device and page-locked buffers."""
+        if self._closed:
+            return
+        self._closed = True
+        torch.cuda.current_stream(self.device).synchronize()
+        self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = None
+        self._h_up = self._d_up = self._h_down = self._up_done = None
+        self._slots, self._ids = [None] * self.n_streams, {}
+
+    def open(self, trg_emb=None, src_f0_stats: Optional[Sequence[float]] = None, trg_f0_stats: Optional[Sequence[float]] = None,
+             seed: int = 0) -> int:
+        """A new stream in a free slot -> its id (ids are never reused; a slot is, after ``end``).  ``trg_emb``: the target
+        speaker's embedding or None - every open stream must agree on having one, because a forward takes ``spk_emb`` for
+        all its rows or for none.  ``src_f0_stats`` and ``trg_f0_stats`` ([mean, std] of log F0): both or neither."""
+        if self._closed:
+            raise RuntimeError("StreamSession is closed")
+        free = [s for s in range(self.n_streams) if self._slots[s] is None]
+        if not free:
+            raise ValueError(f"all {self.n_streams} stream slots are busy")
+        has_emb = trg_emb is not None
+        if has_emb and not self._takes_emb:
+            raise ValueError("the model does not take a speaker embedding")
+        if any(st["emb"] != has_emb for st in self._slots if st is not None):
+            raise ValueError("every open stream needs a speaker embedding, or none does")
+        if (src_f0_stats is None) != (trg_f0_stats is None):
+            raise ValueError("an F0 shift needs src_f0_stats and trg_f0_stats")
+        s = free[0]
+        if has_emb:
+            e = np.asarray(trg_emb, dtype=np.float32).reshape(-1)
+            if e.size != self._emb.shape[1]:
+                raise ValueError(f"trg_emb must hold {self._emb.shape[1]} values, got {e.size}")
+            self._emb[s].copy_(torch.from_numpy(np.ascontiguousarray(e)))
+        sid = self._next_id
+        self._next_id += 1
+        key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
+        self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, seed=key,
+                              stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
+        self._ids[sid] = s
+        self._layout.reset(s)
+        return sid
+
+    def end(self, ids) -> Dict[int, np.ndarray]:
+        """``push({}, end=ids)``: flush these streams and free their slots."""
+        return self.push({}, end=ids)
+
+    @torch.no_grad()
+    def push(self, chunks, end=()) -> Dict[int, np.ndarray]:
+        """Append a chunk to every stream of ``chunks`` - ``{id: dict(ppg=(n, C), f0=(n,) | (n, 1), lft=(n hop,) | (n hop,
+        1))}``, ``0 <= n <= max_push`` - run every window that became ready, and return ``{id: samples}`` for every id of
+        ``chunks`` and ``end``: the stream's next samples, int16 (``pcm16``) or float32, a new array, empty when no
+        window of the stream ran.  Streams in ``end`` end after their chunk: their remaining windows run in this call
+        and their slots are free afterwards."""
+        if self._closed:
+            raise RuntimeError("StreamSession is closed")
+        from .engine import stream_assemble, stream_push, window_stitch
+        hop, C, core, context = self.hop, self.channels, self.core, self.context
+        end = [int(i) for i in end]
+        # ---- validation: nothing is touched before every chunk has passed
+        for sid in list(chunks) + end:
+            if sid not in self._ids:
+                raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
+        if len(set(end)) != len(end):
+            raise ValueError("a stream is listed twice in end")
+        parts = {}
+        for sid, ch in chunks.items():
+            try:
+                ppg, f0, lft = (np.asarray(ch[key]) for key in ("ppg", "f0", "lft"))
+            except (KeyError, TypeError) as e:
+                raise ValueError(f"stream {sid}: a chunk is a dict with ppg, f0 and lft") from e
+            if ppg.ndim != 2 or ppg.shape[1] != C:
+                raise ValueError(f"stream {sid}: ppg must be (n, {C}), got {ppg.shape}")
+            n = int(ppg.shape[0])
+            if n > self.max_push:
+                raise ValueError(f"stream {sid}: {n} frames in one push, max_push is {self.max_push}")
+            if f0.shape not in ((n,), (n, 1)):
+                raise ValueError(f"stream {sid}: f0 must be ({n},) or ({n}, 1), got {f0.shape}")
+            if lft.shape not in ((n * hop,), (n * hop, 1)):
+                raise ValueError(f"stream {sid}: lft must be ({n * hop},) or ({n * hop}, 1), got {lft.shape}")
+            parts[sid] = (n, ppg, f0.reshape(-1), lft.reshape(-1))
+        ids = list(dict.fromkeys(list(chunks) + end))
+        dev = self.device
+        stream = torch.cuda.current_stream(dev)
+        trace = self._stream_trace
+        # ---- one upload, one stream_push
+        pushed = [sid for sid in chunks if parts[sid][0] > 0]
+        if pushed:
+            if self._up_done is not None:
+                self._up_done.synchronize()              # (the page-locked twin is still being read by the last upload)
+            h = self._h_up.numpy()
+            args = {key: [] for key in ("streams", "n", "up_off", "pos", "first", "parity", "seed")}
+            for j, sid in enumerate(pushed):
+                n, ppg, f0, lft = parts[sid]
+                st = self._slots[self._ids[sid]]
+                if st["stats"] is not None:
+                    f0 = F0Statistics().convert(np.asarray(f0, dtype=np.float64), st["stats"][0], st["stats"][1])
+                o = j * self._slice
+                h[o: o + n * C] = ppg.reshape(-1)
+                h[o + n * C: o + n * C + n] = f0
+                h[o + n * C + n: o + n * (C + 1 + hop)] = lft
+                for key, v in zip(args, (self._ids[sid], n, o, st["seen"], st["first"], st["parity"], st["seed"])):
+                    args[key].append(v)
+            used = len(pushed) * self._slice
+            self._d_up[:used].copy_(self._h_up[:used], non_blocking=True)
+            self._up_done = torch.cuda.Event()
+            self._up_done.record(stream)
+            sg = self.signal_generator
+            stream_push(self._d_up, args["streams"], args["n"], args["up_off"], args["pos"], args["first"], args["parity"],
+                        args["seed"], self._ppg, self._lft, self._exc, self._phase, self.max_push, float(sg.sample_rate),
+                        float(sg.sine_amp), float(sg.noise_amp))
+            for sid in pushed:
+                st = self._slots[self._ids[sid]]
+                n = parts[sid][0]
+                if trace is not None:
+                    idx = (torch.arange(st["seen"], st["seen"] + n, device=dev) % self.cap)
+                    trace.setdefault("excitation", {}).setdefault(sid, []).append(
+                        self._exc[self._ids[sid]].view(self.cap, hop)[idx].reshape(-1))
+                st["seen"] += n
+                st["first"] = False
+                st["parity"] ^= 1
+        # ---- the windows that are ready now, in slot order, a stream's ascending
+        rows = []
+        for sid in sorted(ids, key=lambda i: self._ids[i]):
+            s = self._ids[sid]
+            st = self._slots[s]
+            ended = sid in end
+            ready = stream_ready_rows(st["seen"], ended, core, context, st["done"])
+            for j, (in_lo, in_hi, lo, hi) in enumerate(ready):
+                k = st["done"] + j
+                rows.append((s, k, in_lo, in_hi, lo, hi, ended and hi == st["seen"]))
+            st["done"] += len(ready)
+        seen = [0 if st is None else st["seen"] for st in self._slots]
+        pieces: Dict[int, list] = {self._ids[sid]: [] for sid in ids}
+        down = []
+        off = 0
+        for c0 in range(0, len(rows), self.max_batch):
+            chunk = rows[c0: c0 + self.max_batch]
+            lay = self._layout.batch(chunk, seen)
+            lens = [r[3] - r[2] for r in chunk]
+            width, B = max(lens), len(chunk)
+            ppg, lft, sine = stream_assemble(self._ppg, self._lft, self._exc, seen, [r[0] for r in chunk],
+                                             [r[2] for r in chunk], lens, width)
+            if trace is not None:
+                trace.setdefault("forwards", []).append(([(self._slots[r[0]]["id"],) + tuple(r[2:6]) for r in chunk], sine.clone()))
+            emb = None
+            if self._slots[chunk[0][0]]["emb"]:
+                slots = tuple(r[0] for r in chunk)       # (the steady state repeats one tuple: its index tensor is uploaded once)
+                if slots not in self._emb_rows:
+                    if len(self._emb_rows) >= 256:
+                        self._emb_rows.clear()
+                    self._emb_rows[slots] = torch.as_tensor(slots, dtype=torch.int64, device=dev)
+                emb = self._emb.index_select(0, self._emb_rows[slots])
+            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+            self.forwards += 1
+            packed = torch.empty(max(lay["total"], 1), dtype=torch.int16 if self.pcm16 else torch.float32, device=dev)
+            window_stitch(y.view(B, width * hop), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"],
+                          lay["left_mode"], lay["right_mode"], lay["left_src"], lay["right_src"], lay["dst_off"],
+                          stage=self._stage, out_pcm=packed if self.pcm16 else None, out_float=None if self.pcm16 else packed)
+            # (the page-locked buffer as float32 words; int16 samples are a view of them, every batch on a word boundary)
+            words = (lay["total"] + 1) // 2 if self.pcm16 else lay["total"]
+            host = self._h_down[off: off + words]
+            host = host.view(torch.int16)[: lay["total"]] if self.pcm16 else host
+            if lay["total"]:
+                host.copy_(packed[: lay["total"]], non_blocking=True)
+            down.append((host, lay))
+            off += words
+        if down:
+            stream.synchronize()
+            for host, lay in down:
+                h = host.numpy()
+                for (s, t_lo, t_hi), o in zip(lay["runs"], lay["dst_off"]):
+                    pieces[s].append(h[o: o + t_hi - t_lo])
+        dtype = np.int16 if self.pcm16 else np.float32
+        out = {}
+        for sid in ids:
+            ps = pieces[self._ids[sid]]
+            out[sid] = np.concatenate(ps) if ps else np.empty(0, dtype=dtype)      # (a copy: never the page-locked buffer)
+        for sid in end:
+            s = self._ids.pop(sid)
+            self._slots[s] = None
+            self._layout.reset(s)
+        return out
+
+
 def _read_f0_mean(stats_dir: str, name: str) -> np.ndarray:
     import yaml
     with open(os.path.join(stats_dir, f"{name}.yml")) as f:
@@ -1392,7 +1795,26 @@ def main(argv=None) -> None:                                  # pragma: no cover
                     help="with --window: InstanceNorm statistics per window (default) or pooled over all windows of an "
                          "utterance, which reproduces the whole-utterance result; an utterance then needs at most "
                          "--max-batch windows")
+    ap.add_argument("--stream", default=None, metavar="PUSH[,CORE[,CONTEXT[,FADE]]]",
+                    help="with --resident: feed the dumps as simulated LIVE streams, PUSH frames per stream and call "
+                         "(StreamSession: windows of CORE frames, default 32, run as soon as their CONTEXT has arrived, "
+                         "default the generator's receptive field; cross-fade over FADE frames, default 8); same file names; "
+                         "with a speaker embedding InstanceNorm normalises per window, as with --window")
+    ap.add_argument("--streams", type=int, default=1, help="with --stream: dumps converted side by side (default 1)")
     args = ap.parse_args(argv)
+    if args.stream is not None:
+        if not args.resident or args.fanout > 1 or args.window is not None or args.checked or args.fallback is not None \
+                or args.storage == "auto":
+            ap.error("--stream works on the --resident route, without --fanout, --window, --checked and --storage auto")
+        try:
+            parts = [int(v) for v in args.stream.split(",")]
+            if not 1 <= len(parts) <= 4 or parts[0] < 1 or args.streams < 1:
+                raise ValueError
+        except ValueError:
+            ap.error("--stream takes PUSH[,CORE[,CONTEXT[,FADE]]] in frames, --streams a count of at least 1")
+        args.stream = dict(zip(("max_push", "core", "context", "fade"), parts), n_streams=args.streams)
+    elif args.streams != 1:
+        ap.error("--streams needs --stream")
     if args.window is not None:
         if not args.resident or args.fanout > 1:
             ap.error("--window works on the --resident route, without --fanout")
@@ -1434,7 +1856,7 @@ def main(argv=None) -> None:                                  # pragma: no cover
     files = sorted(glob.glob(os.path.join(args.dumpdir, "*.npz")) + glob.glob(os.path.join(args.dumpdir, "*.h5")))
     if args.resident:
         os.makedirs(args.outdir, exist_ok=True)
-        _main_resident(args, config, model, sg, device, files)
+        (_main_stream if args.stream is not None else _main_resident)(args, config, model, sg, device, files)
         return
     feats = [load_features(p) for p in files]
     utt_ids = [os.path.splitext(os.path.basename(p))[0] for p in files]
@@ -1536,6 +1958,45 @@ def _main_resident(args, config, model, sg, device, files) -> None:      # pragm
             print(f"{len(files)} utterances -> {trgspk}: RTF = {spent[trgspk] / (samples[trgspk] / config['sampling_rate']):.5f}")
         if args.checked:
             print(f"{trgspk}: " + summarize_reports(reports[trgspk], args.storage))
+
+
+def _main_stream(args, config, model, sg, device, files) -> None:        # pragma: no cover - exercised on a GPU box
+    """The CLI's speaker loop over simulated live streams: ``--streams`` dumps at a time run side by side through one
+    ``StreamSession``, each delivering ``PUSH`` frames per call until it ends; the pieces a stream returned, concatenated,
+    are its file."""
+    embs = dict(np.load(args.spk_emb)) if args.spk_emb else {}
+    hop, n, step = int(config["hop_size"]), args.stream["n_streams"], args.stream["max_push"]
+    with StreamSession(model, sg, device, **args.stream) as session:
+        for trgspk in config.get("convert_to_speakers", [None]):
+            trg_emb = embs.get(trgspk) if config["generator_params"].get("use_spk_emb") else None
+            shift = bool(args.srcf0stats and args.trgf0stats and trgspk is not None)
+            trg_stats = _read_f0_mean(args.trgf0stats, trgspk) if shift else None
+            spent, samples = 0.0, 0
+            for g in range(0, len(files), n):
+                paths = files[g: g + n]
+                feats = [load_features(p) for p in paths]
+                utt_ids = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+                frames = [int(np.asarray(u["ppg"]).shape[0]) for u in feats]
+                t0 = time.time()
+                ids = [session.open(trg_emb, _read_f0_mean(args.srcf0stats, u.split("_")[0]) if shift else None, trg_stats, seed=g + j)
+                       for j, u in enumerate(utt_ids)]
+                pieces = [[] for _ in paths]
+                for a in range(0, max(frames), step):
+                    live = [j for j, f in enumerate(frames) if a < f]
+                    out = session.push({ids[j]: dict(ppg=np.asarray(feats[j]["ppg"])[a: a + step],
+                                                     f0=np.asarray(feats[j]["f0"]).reshape(-1)[a: min(a + step, frames[j])],
+                                                     lft=np.asarray(feats[j]["lft"]).reshape(-1)[a * hop: min(a + step, frames[j]) * hop])
+                                        for j in live}, end=[ids[j] for j in live if a + step >= frames[j]])
+                    for j in live:
+                        pieces[j].append(out[ids[j]])
+                session.end([ids[j] for j, f in enumerate(frames) if f == 0])        # (a dump without frames: free its slot)
+                spent += time.time() - t0
+                for utt, ps in zip(utt_ids, pieces):
+                    y = np.concatenate(ps) if ps else np.zeros(0, np.int16)
+                    samples += y.size
+                    write_wav(os.path.join(args.outdir, f"{utt}_{trgspk}_gen.wav"), y, config["sampling_rate"])
+            if samples:
+                print(f"{len(files)} streams -> {trgspk}: RTF = {spent / (samples / config['sampling_rate']):.5f}")
 
 
 def summarize_reports(reports: Sequence[Dict[str, object]], storage: str) -> str:

@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "fastsvc_collate_launch_count", "fastsvc_collate_crops",
     "fastsvc_fanout_launch_count", "fastsvc_fanout_assemble",
     "fastsvc_window_launch_count", "fastsvc_window_assemble", "fastsvc_window_stitch",
+    "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -193,6 +194,15 @@ def load_library():
     lib.fastsvc_window_stitch.argtypes = [vp, i32, i32] + [ctypes.POINTER(i32)] * 3 + [i32] + [ctypes.POINTER(i32)] * 2 + \
         [ctypes.POINTER(i64)] * 2 + [vp, i64, ctypes.POINTER(i64), vp, vp, i64, ctypes.POINTER(i32), vp, i32, vp]
     lib.fastsvc_window_stitch.restype = ctypes.c_int
+    lib.fastsvc_stream_launch_count.argtypes = [i32]
+    lib.fastsvc_stream_launch_count.restype = ctypes.c_int
+    lib.fastsvc_stream_push.argtypes = [vp, i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                        ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64), vp, vp, vp, vp] + \
+        [i32] * 5 + [ctypes.c_float] * 3 + [vp]
+    lib.fastsvc_stream_push.restype = ctypes.c_int
+    lib.fastsvc_stream_assemble.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i64),
+                                            ctypes.POINTER(i32), vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.fastsvc_stream_assemble.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -635,6 +645,135 @@ def window_stitch(y: torch.Tensor, n_samples: Sequence[int], core_lo: Sequence[i
                                               ptr(out_pcm), ptr(out_float), n_dst,
                                               i32s(utt) if report is not None else None, ptr(report), n_utts,
                                               ctypes.c_void_p(stream)), "fastsvc_window_stitch")
+
+
+def stream_launch_count(R: int) -> int:
+    """Launches one ``stream_push`` of R streams (that append something) or ``stream_assemble`` of R rows enqueues: one
+    per 64."""
+    return int(load_library().fastsvc_stream_launch_count(int(R)))
+
+
+STREAM_MAX_PUSH = 1024      # frames of one chunk the push kernel takes (their phase prefixes live in LDS)
+
+
+def _stream_rings(who: str, ppg_ring, lft_ring, exc_ring):
+    """The three rings of ``decode.StreamSession``: (n_streams, cap, C), (n_streams, cap * hop) twice -> (n_streams, cap, C, hop)."""
+    for name, t in (("ppg_ring", ppg_ring), ("lft_ring", lft_ring), ("exc_ring", exc_ring)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"{who} needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != ppg_ring.device:
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {ppg_ring.device}")
+    if ppg_ring.dim() != 3 or lft_ring.dim() != 2 or exc_ring.shape != lft_ring.shape or lft_ring.shape[0] != ppg_ring.shape[0]:
+        raise ValueError("the rings must be (n_streams, cap, C), (n_streams, cap * hop) and (n_streams, cap * hop)")
+    n_streams, cap, C = (int(v) for v in ppg_ring.shape)
+    if cap < 4 or cap % 4 or lft_ring.shape[1] % cap or lft_ring.shape[1] == 0:
+        raise ValueError(f"the rings' capacity must be a multiple of 4 frames and divide the sample rings, got {cap}")
+    return n_streams, cap, C, int(lft_ring.shape[1]) // cap
+
+
+def stream_push(upload: torch.Tensor, streams: Sequence[int], n: Sequence[int], up_off: Sequence[int], pos: Sequence[int],
+                first: Sequence[int], parity: Sequence[int], seed: Sequence[int], ppg_ring: torch.Tensor, lft_ring: torch.Tensor,
+                exc_ring: torch.Tensor, phase: torch.Tensor, max_push: int, sample_rate: float, sine_amp: float,
+                noise_amp: float) -> None:
+    """Append chunks to the rings of live streams and synthesise their excitation, by ONE HIP launch per 64 streams on
+    the current stream (fastsvc_stream_push, csrc/fastsvc_stream.hip; none when every chunk is empty).
+
+    Entry i appends ``n[i]`` frames (``0 <= n[i] <= max_push``) to stream ``streams[i]`` (each at most once), which held
+    ``pos[i]`` frames: from element ``up_off[i]`` of ``upload`` (1-D float32 on the device) the time-major ppg ``n x C``,
+    then f0 ``n``, then lft ``n x hop``.  ``ppg_ring (n_streams, cap, C)``, ``lft_ring`` / ``exc_ring (n_streams, cap *
+    hop)``: frame p of a stream at index ``p % cap``.  ``phase (n_streams, 2)`` float64: the push reads entry
+    ``parity[i]`` (or starts at 0 when ``first[i]``) and writes entry ``parity[i] ^ 1``.  ``seed[i]`` keys the noise
+    together with the absolute sample index.  Anything out of range raises ``ValueError`` before a launch and changes
+    nothing; fails loudly off the GPU."""
+    lib = load_library()
+    n_streams, cap, C, hop = _stream_rings("stream_push", ppg_ring, lft_ring, exc_ring)
+    for name, t, dtype, dim in (("upload", upload, torch.float32, 1), ("phase", phase, torch.float64, 2)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"stream_push needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
+        if t.dtype != dtype or not t.is_contiguous() or t.device != ppg_ring.device or t.dim() != dim:
+            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {ppg_ring.device}")
+    if tuple(phase.shape) != (n_streams, 2):
+        raise ValueError(f"phase must be ({n_streams}, 2), got {tuple(phase.shape)}")
+    S = len(streams)
+    max_push = int(max_push)
+    if S == 0 or any(len(v) != S for v in (n, up_off, pos, first, parity, seed)):
+        raise ValueError("stream_push needs at least one stream and one entry per stream in every array")
+    if not 1 <= max_push <= min(cap, STREAM_MAX_PUSH):
+        raise ValueError(f"max_push must be in [1, min(cap {cap}, {STREAM_MAX_PUSH})], got {max_push}")
+    if len(set(int(s) for s in streams)) != S:
+        raise ValueError("stream_push takes every stream at most once per call")
+    for i in range(S):
+        s, k, o = int(streams[i]), int(n[i]), int(up_off[i])
+        if not 0 <= s < n_streams:
+            raise ValueError(f"stream {s} outside [0, {n_streams})")
+        if not 0 <= k <= max_push:
+            raise ValueError(f"stream {s}: {k} frames, outside [0, max_push {max_push}]")
+        if o < 0 or o + k * (C + 1 + hop) > upload.numel():
+            raise ValueError(f"stream {s}: its slice [{o}, +{k * (C + 1 + hop)}) leaves the upload buffer of {upload.numel()} elements")
+        if int(pos[i]) < 0:
+            raise ValueError(f"stream {s}: position {int(pos[i])} out of range")
+    i32s = lambda v: (ctypes.c_int32 * S)(*[int(x) for x in v])      # noqa: E731
+    i64s = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])      # noqa: E731
+    seeds = (ctypes.c_uint64 * S)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seed])
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    with torch.cuda.device(ppg_ring.device):
+        stream = torch.cuda.current_stream(ppg_ring.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_push(ptr(upload), upload.numel(), S, i32s(streams), i32s(n), i64s(up_off), i64s(pos),
+                                            i32s([1 if v else 0 for v in first]), i32s([int(v) & 1 for v in parity]), seeds,
+                                            ptr(ppg_ring), ptr(lft_ring), ptr(exc_ring), ptr(phase), n_streams, cap, max_push, C, hop,
+                                            ctypes.c_float(float(sample_rate)), ctypes.c_float(float(sine_amp)),
+                                            ctypes.c_float(float(noise_amp)), ctypes.c_void_p(stream)), "fastsvc_stream_push")
+
+
+def stream_assemble(ppg_ring: torch.Tensor, lft_ring: torch.Tensor, exc_ring: torch.Tensor, pos: Sequence[int],
+                    streams: Sequence[int], first_frame: Sequence[int], n_frames: Sequence[int], width: int,
+                    out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """Assemble a decode batch whose rows are cut from the rings of live streams, by ONE HIP launch per 64 rows on the
+    current stream (fastsvc_stream_assemble, csrc/fastsvc_stream.hip).  Row r is the ``n_frames[r]`` frames from frame
+    ``first_frame[r]`` of stream ``streams[r]``, read modulo the rings' capacity; ``pos[s]`` is how many frames stream s
+    holds.  Returns ``window_assemble``'s three: ``(ppg (R, C, width), lft (R, 1, width * hop), sine (R, 1, width *
+    hop))``, everything past a row's length exactly zero.  ``out``: the same three, to write into.  A row outside the
+    retained frames ``[pos - cap, pos)`` of its stream, or anything else out of range, raises ``ValueError`` before a
+    launch; fails loudly off the GPU."""
+    lib = load_library()
+    n_streams, cap, C, hop = _stream_rings("stream_assemble", ppg_ring, lft_ring, exc_ring)
+    R, width = len(n_frames), int(width)
+    if R == 0 or len(streams) != R or len(first_frame) != R or len(pos) != n_streams or width < 1:
+        raise ValueError("stream_assemble needs at least one row, a stream and a first frame per row, and a position per stream")
+    for r in range(R):
+        s, f, k = int(streams[r]), int(first_frame[r]), int(n_frames[r])
+        if not 0 <= s < n_streams:
+            raise ValueError(f"row {r}: stream {s} outside [0, {n_streams})")
+        if not 0 <= k <= min(width, cap):
+            raise ValueError(f"row {r} has {k} frames, outside [0, min(width {width}, cap {cap})]")
+        p = int(pos[s])
+        if f < 0 or f < p - cap or f + k > p:
+            raise ValueError(f"row {r}: frames [{f}, {f + k}) are not retained by stream {s}, which holds [{max(0, p - cap)}, {p})")
+    shapes = [(R, C, width), (R, 1, width * hop), (R, 1, width * hop)]
+    if out is None:
+        out = [None] * 3
+    outs = []
+    for i, shp in enumerate(shapes):
+        t = out[i] if i < len(out) else None
+        if t is None:
+            outs.append(torch.empty(shp, dtype=torch.float32, device=ppg_ring.device))
+        elif not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError("stream_assemble needs GPU tensors (no CPU fallback) for out")
+        elif tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous() or t.device != ppg_ring.device:
+            raise ValueError(f"out[{i}] must be a contiguous float32 {shp} tensor on {ppg_ring.device}")
+        else:
+            outs.append(t)
+    ps = (ctypes.c_int64 * n_streams)(*[int(v) for v in pos])
+    st = (ctypes.c_int32 * R)(*[int(v) for v in streams])
+    ff = (ctypes.c_int64 * R)(*[int(v) for v in first_frame])
+    nfr = (ctypes.c_int32 * R)(*[int(v) for v in n_frames])
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    with torch.cuda.device(ppg_ring.device):
+        stream = torch.cuda.current_stream(ppg_ring.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_assemble(ptr(ppg_ring), ptr(lft_ring), ptr(exc_ring), n_streams, cap, ps, st, ff, nfr,
+                                                *[ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
+               "fastsvc_stream_assemble")
+    return tuple(outs)
 
 
 def check_norm_groups(norm_groups, lens: Sequence[int]):

@@ -1,0 +1,154 @@
+"""Host-to-host time of one StreamSession.push that completes ONE window per stream - the steady state of live
+conversion, where every stream delivers `core` frames per push - for 1, 8 and 32 streams, core 32 and 100, activation
+storage float32 and bfloat16, speaker embedding, F0 shift on, int16 out.
+
+Next to it, the yardstick: what the decode path could already do with the features RESIDENT on the device - one batch of
+the same rows (one mid-utterance window of core + 2 context frames per stream) through convert_windowed's own chain:
+window_assemble out of packed buffers that hold the features and a ready-made excitation, one forward with `lengths`,
+window_stitch (one zone staged, one blended, as between pushes) and the download of the int16 samples, ending in a
+synchronise.  The push does that and, before it, packs the chunk on the host, uploads it, appends it to the rings and
+synthesises its excitation.
+
+A repetition times STREAM_PUSHES (default 20) consecutive pushes, each host-to-host (a push ends in a synchronise), and
+the same number of yardstick batches; the two legs alternate, STREAM_REPS (default 5) repetitions, and the medians of
+the repetitions' means are reported with their spread.  Real-time factor: seconds of audio a push delivers (streams x
+core x hop / sample rate) over the push time.  The figures go to profiles/decode_stream.txt.
+
+    python tools/stream_latency.py"""
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+import svcc23_fastsvc_amd as A
+from svcc23_fastsvc_amd import synth as S, decode as Dc
+from svcc23_fastsvc_amd.engine import window_assemble, window_stitch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+dev = torch.device("cuda:0")
+cfg = S.FULL_CONFIG
+hop, C, SR, FADE = cfg.hop, cfg.in_channels, 24000, 8
+reps = max(int(os.environ.get("STREAM_REPS", "5")), 1)
+pushes = max(int(os.environ.get("STREAM_PUSHES", "20")), 1)
+ctx = -(-Dc.receptive_field_frames(cfg) // 4) * 4
+sg = A.SignalGenerator(sample_rate=SR, hop_size=hop, noise_amp=0.0, signal_types=["sine"])
+rng = np.random.default_rng(11)
+emb = rng.standard_normal(cfg.spk_emb_size).astype(np.float32)
+
+
+def build_model(storage):
+    m = A.FastSVCGenerator(in_channels=cfg.in_channels, mid_channels=list(cfg.mid_channels), upsampling_scales=list(cfg.upsampling_scales),
+                           out_channels=cfg.out_channels, spk_emb_size=cfg.spk_emb_size, use_spk_emb=True)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in S.synth_state_dict(cfg, 1).items()})
+    m.remove_weight_norm()
+    m.activation_storage = storage
+    return m.eval().to(dev)
+
+
+def features(F):
+    f0 = np.where(rng.random((F, 1)) < 0.3, 0.0, rng.uniform(80, 400, (F, 1)))
+    return {"ppg": rng.standard_normal((F, C), dtype=np.float32), "f0": f0, "lft": rng.uniform(-9, 1, (F * hop, 1)).astype(np.float32)}
+
+
+def spread(name, seconds, audio):
+    v = np.array(seconds) * 1e3
+    med = float(np.median(v))
+    return med, f"{name:44s} median {med:8.3f} ms  (min {v.min():8.3f}, max {v.max():8.3f})  {audio / (med / 1e3):8.1f} x real time"
+
+
+class Yardstick:
+    """N utterances resident as packed device buffers (ppg time-major, lft, excitation); batch k is window k of every one."""
+
+    def __init__(self, model, N, core, K):
+        self.model, self.N, self.core = model, N, core
+        F = (K + 3) * core                           # (window K still has its whole right context)
+        self.rows = Dc.window_plan([F] * N, core, ctx)
+        per = -(-F // core)
+        self.batches = [[u * per + k for u in range(N)] for k in range(per)]
+        self.layout, stage_elems = Dc.stitch_layout(self.rows, self.batches, hop, FADE)
+        feats = [features(F) for _ in range(N)]
+        self.ppg = torch.from_numpy(np.concatenate([f["ppg"].reshape(-1) for f in feats])).to(dev)
+        self.lft = torch.from_numpy(np.concatenate([f["lft"].reshape(-1) for f in feats])).to(dev)
+        f0 = torch.from_numpy(np.stack([Dc.F0Statistics().convert(f["f0"].reshape(-1), [5.0, 1.0], [5.3, 1.0]) for f in feats])
+                              .astype(np.float32)).to(dev)
+        self.sine = sg(f0.view(N, 1, F)).reshape(-1).contiguous()
+        self.F = F
+        self.stage = torch.empty(max(stage_elems, 1), dtype=torch.float32, device=dev)
+        self.emb = torch.from_numpy(np.tile(emb, (N, 1))).to(dev)
+        self.host = torch.empty(N * (core + FADE) * hop + 8 * N, dtype=torch.int16, pin_memory=True)
+        self.K = K
+
+    @torch.no_grad()
+    def batch(self, k):
+        """Window k (1 <= k <= K: full context on both sides) of every utterance."""
+        chunk, lay = self.batches[k], self.layout[k]
+        rows = [self.rows[r] for r in chunk]
+        lens = [r[2] - r[1] for r in rows]
+        width = max(lens)
+        ppg, lft, sine = window_assemble(self.ppg, self.lft, self.sine, [(u * self.F + r[1]) * C for u, r in enumerate(rows)],
+                                         [(u * self.F + r[1]) * hop for u, r in enumerate(rows)], lens, C, hop, width)
+        y = self.model(ppg, sine, lft, self.emb, lengths=lens).to(torch.float32)
+        packed = torch.empty(max(lay["total"], 1), dtype=torch.int16, device=dev)
+        window_stitch(y.view(len(rows), width * hop), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"], lay["left_mode"],
+                      lay["right_mode"], lay["left_src"], lay["right_src"], lay["dst_off"], stage=self.stage, out_pcm=packed)
+        self.host[: lay["total"]].copy_(packed[: lay["total"]], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return lens
+
+
+def main():
+    out = [f"stream latency: one StreamSession.push that completes one window per stream (every stream delivers `core` frames), "
+           f"host to host, against one batch of the same rows through window_assemble + forward + window_stitch + download with "
+           f"the features and the excitation already resident (the yardstick); context {ctx}, fade {FADE}, speaker embedding, F0 "
+           f"shift on, int16 out; {pushes} pushes / batches per repetition, {reps} repetitions, legs alternated, median of the "
+           f"repetitions' means (min, max); {torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    K = 8
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for core in (32, 100):
+            for N in (1, 8, 32):
+                src = [features(core * 8) for _ in range(N)]
+                yard = Yardstick(m, N, core, K)
+                with Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core) as s:
+                    ids = [s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)]
+                    step = [0]
+
+                    def push():
+                        a = (step[0] % 8) * core
+                        step[0] += 1
+                        return s.push({i: dict(ppg=f["ppg"][a: a + core], f0=f["f0"][a: a + core], lft=f["lft"][a * hop: (a + core) * hop])
+                                       for i, f in zip(ids, src)})
+                    for _ in range(6):                   # (fill the context, warm every shape)
+                        got = push()
+                    before = s.forwards
+                    got = push()
+                    assert s.forwards == before + 1 and all(v.size == core * hop for v in got.values())
+                    for k in range(1, 4):
+                        lens = yard.batch(k)
+                    assert lens == [core + 2 * ctx] * N
+                    t = {"push": [], "yard": []}
+                    for _ in range(reps):
+                        t0 = time.perf_counter()
+                        for _ in range(pushes):
+                            push()
+                        t["push"].append((time.perf_counter() - t0) / pushes)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for j in range(pushes):
+                            yard.batch(1 + j % K)
+                        t["yard"].append((time.perf_counter() - t0) / pushes)
+                    s.end(ids)
+                audio = N * core * hop / SR
+                mp, line_p = spread(f"{N:2d} streams, core {core:3d}: push", t["push"], audio)
+                my, line_y = spread(f"{N:2d} streams, core {core:3d}: resident batch", t["yard"], audio)
+                out += [line_p, line_y, f"    push / resident batch {mp / my:.3f}; a push delivers {audio * 1e3:.1f} ms of audio "
+                                        f"({core * hop / SR * 1e3:.1f} ms per stream)"]
+                print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
+if __name__ == "__main__":
+    main()
