@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import argparse
 import glob
+import math
 import os
 import time
 import wave
@@ -116,6 +117,63 @@ def flagged_batches(batches: Sequence[Sequence[int]], flagged, among: Optional[S
     flagged = set(int(i) for i in flagged)
     ks = range(len(batches)) if among is None else sorted(set(int(k) for k in among))
     return [k for k in ks if any(int(i) in flagged for i in batches[k])]
+
+
+def storage_fallback(model, fallback: Sequence[str], n_units: int, is_flagged, rerun):
+    """The storage fallback of every checked convert: ``(storage, tried, still)`` for the units ``0 .. n_units - 1`` of a
+    pass (utterances, or (utterance, speaker) rows) that has just run in the model's own storage.  ``is_flagged(i)`` says
+    whether unit i's latest result has non-finite samples.  For every name of ``fallback``, while units are flagged, the
+    model is switched to that storage and ``rerun(name, flagged)`` has to run the flagged units again, each of them, and
+    have ``is_flagged`` see the new results; what it runs beside them is its own business.  ``storage[i]`` is the storage
+    unit i's result comes from, ``tried[i]`` the storages that left it flagged before, in order, ``still`` the units
+    flagged after the last fallback.  The model is back in its first storage afterwards, also when ``rerun`` raises, and
+    is never touched when nothing is flagged.  No device work in here: a pure host function."""
+    first = getattr(model, "activation_storage", "float32")
+    storage, tried = [first] * n_units, [[] for _ in range(n_units)]
+    flagged = [i for i in range(n_units) if is_flagged(i)]
+    try:
+        for name in fallback:
+            if not flagged:
+                break
+            model.use_activation_storage(name)
+            rerun(name, flagged)
+            for i in flagged:
+                tried[i].append(storage[i])
+                storage[i] = name
+            flagged = [i for i in flagged if is_flagged(i)]
+    finally:
+        if getattr(model, "activation_storage", first) != first:
+            model.use_activation_storage(first)
+    return storage, tried, flagged
+
+
+def _rerun_in_batches(row_batches: Sequence[Sequence[int]], run):
+    """``storage_fallback``'s ``rerun`` for a pass whose units sit in batches that run as a whole (``row_batches[k]``: the
+    units of batch k): every round ``run`` gets ``[(k, positions in batch k of its flagged units), ...]`` for the batches,
+    among those of the round before, that hold a flagged unit (``flagged_batches``) - a unit flagged in a round was
+    flagged in every round before, so its batch is always among them."""
+    again = None
+
+    def rerun(name, flagged):
+        nonlocal again
+        again = flagged_batches(row_batches, flagged, again)
+        hit = set(flagged)
+        run([(k, [j for j, r in enumerate(row_batches[k]) if r in hit]) for k in again])
+    return rerun
+
+
+def _report_dicts(rep, storage: Sequence[str], tried: Sequence[List[str]]) -> List[Dict[str, object]]:
+    """``last_report``'s dicts, one per unit, from the units' downloaded report rows (n, 4)."""
+    from .engine import report_arrays
+    nonfinite, clipped, max_abs = report_arrays(rep)
+    return [dict(storage=storage[i], nonfinite=int(nonfinite[i]), clipped=int(clipped[i]), max_abs=float(max_abs[i]),
+                 tried=tried[i]) for i in range(len(storage))]
+
+
+def _raise_still_nonfinite(model, fallback: Sequence[str], units: str, still) -> None:
+    from .engine import FastSVCError
+    raise FastSVCError(f"{units} {still} still have non-finite samples after storages "
+                       f"{[getattr(model, 'activation_storage', 'float32')] + list(fallback)} (strict=True)")
 
 
 def fanout_batches(frames: Sequence[int], n_speakers: int, max_batch: int = 32,
@@ -351,6 +409,37 @@ def stitch_windows(ys: Sequence[np.ndarray], rows: Sequence[Tuple[int, int, int,
     return out
 
 
+NONE, STAGE, FROM_STAGE, FROM_Y, SKIP = range(5)     # a window side's mode in ``fastsvc_window_stitch`` (``STITCH_*``)
+
+
+def _emit_rows(specs, hop: int, half: int, width: int, grow_left, grow_right):
+    """The stitch layout dict of one batch (see ``stitch_layout``) from its rows' ``(u, T, in_lo, in_hi, core_lo, core_hi,
+    left_mode, right_mode, left_src, right_src)``: window of utterance / stream ``u``, which has ``T`` samples; the window in
+    frames.  The run a row writes is its core, moved OUT by half a zone on a side whose mode is in ``grow_left`` /
+    ``grow_right`` (the row writes that zone), IN by half a zone on any other side that has a neighbour, and clipped to
+    the utterance; the runs lie back to back in the batch's buffer."""
+    d = {key: [] for key in ("n_samples", "core_lo", "core_hi", "left_mode", "right_mode", "left_src", "right_src",
+                             "dst_off", "utt", "runs")}
+    pos = 0
+    for u, T, in_lo, in_hi, lo, hi, lm, rm, ls, rs in specs:
+        t_lo = lo * hop - half if lm in grow_left else min(lo * hop + half, T) if lm != NONE else lo * hop
+        t_hi = min(hi * hop + half, T) if rm in grow_right else hi * hop - half if rm != NONE else hi * hop
+        t_hi = max(t_hi, t_lo)
+        d["n_samples"].append((in_hi - in_lo) * hop)
+        d["core_lo"].append((lo - in_lo) * hop)
+        d["core_hi"].append((hi - in_lo) * hop)
+        d["left_mode"].append(lm)
+        d["right_mode"].append(rm)
+        d["left_src"].append(ls)
+        d["right_src"].append(rs)
+        d["dst_off"].append(pos)
+        d["utt"].append(u)
+        d["runs"].append((u, t_lo, t_hi))
+        pos += -(-(t_hi - t_lo) // 8) * 8                # (every run starts on a 16-byte boundary of both destinations)
+    d["total"], d["width"], d["half"] = pos, width, half
+    return d
+
+
 def stitch_layout(rows: Sequence[Tuple[int, int, int, int, int]], batches: Sequence[Sequence[int]], hop: int, fade: int):
     """How ``engine.window_stitch`` resolves every fade zone when the rows run batch by batch, in ``batches``' order:
     ``(per_batch, stage_elems)``.  ``per_batch[k]`` is a dict of per-row lists for batch k (in the batch's row order) -
@@ -371,7 +460,6 @@ def stitch_layout(rows: Sequence[Tuple[int, int, int, int, int]], batches: Seque
                 raise ValueError(f"row {r} is in two batches")
             where[r] = (k, j)
     widths = [max(rows[r][2] - rows[r][1] for r in chunk) * hop for chunk in batches]
-    NONE, STAGE, FROM_STAGE, FROM_Y, SKIP = range(5)
     lmode, rmode, lsrc, rsrc = {}, {}, {}, {}
     slots = 0
     for u, rs in by_utt.items():
@@ -395,31 +483,16 @@ def stitch_layout(rows: Sequence[Tuple[int, int, int, int, int]], batches: Seque
                 lmode[b], lsrc[b] = STAGE, slots * fh
                 rmode[a], rsrc[a] = FROM_STAGE, slots * fh
                 slots += 1
+    # (whichever window of a boundary blends it, from the stage or from the forward's output, writes the zone)
+    blends = (FROM_STAGE, FROM_Y)
+    T = {u: rows[rs[-1]][4] * hop for u, rs in by_utt.items()}
     per_batch = []
     for k, chunk in enumerate(batches):
-        d = {key: [] for key in ("n_samples", "core_lo", "core_hi", "left_mode", "right_mode", "left_src", "right_src",
-                                 "dst_off", "utt", "runs")}
-        pos = 0
+        specs = []
         for r in chunk:
             u, in_lo, in_hi, lo, hi = rows[r]
-            lm, rm = lmode.get(r, NONE), rmode.get(r, NONE)
-            T = rows[by_utt[u][-1]][4] * hop
-            t_lo = lo * hop - half if lm in (FROM_STAGE, FROM_Y) else min(lo * hop + half, T) if lm != NONE else lo * hop
-            t_hi = min(hi * hop + half, T) if rm in (FROM_STAGE, FROM_Y) else hi * hop - half if rm != NONE else hi * hop
-            t_hi = max(t_hi, t_lo)
-            d["n_samples"].append((in_hi - in_lo) * hop)
-            d["core_lo"].append((lo - in_lo) * hop)
-            d["core_hi"].append((hi - in_lo) * hop)
-            d["left_mode"].append(lm)
-            d["right_mode"].append(rm)
-            d["left_src"].append(lsrc.get(r, 0))
-            d["right_src"].append(rsrc.get(r, 0))
-            d["dst_off"].append(pos)
-            d["utt"].append(u)
-            d["runs"].append((u, t_lo, t_hi))
-            pos += -(-(t_hi - t_lo) // 8) * 8            # (every run starts on a 16-byte boundary of both destinations)
-        d["total"], d["width"], d["half"] = pos, widths[k], half
-        per_batch.append(d)
+            specs.append((u, T[u], in_lo, in_hi, lo, hi, lmode.get(r, NONE), rmode.get(r, NONE), lsrc.get(r, 0), rsrc.get(r, 0)))
+        per_batch.append(_emit_rows(specs, hop, half, widths[k], blends, blends))
     return per_batch, slots * fh
 
 
@@ -483,17 +556,13 @@ class StreamStitchLayout:
 
     def batch(self, rows, seen):
         hop, half = self.hop, self.half
-        NONE, STAGE, FROM_STAGE, FROM_Y, SKIP = range(5)
         where = {(r[0], r[1]): j for j, r in enumerate(rows)}
         if len(where) != len(rows):
             raise ValueError("a window is in the batch twice")
         width = max(r[3] - r[2] for r in rows) * hop
-        d = {key: [] for key in ("n_samples", "core_lo", "core_hi", "left_mode", "right_mode", "left_src", "right_src",
-                                 "dst_off", "utt", "runs")}
         pending, written = list(self.pending), list(self.written)
-        pos = 0
+        specs = []
         for s, k, in_lo, in_hi, lo, hi, last in rows:
-            T = int(seen[s]) * hop
             lm = rm = NONE
             ls = rs = 0
             if half and k > 0:
@@ -514,21 +583,10 @@ class StreamStitchLayout:
                     written[s] ^= 1                      # (not the slot the stream's first row of this batch may read)
                     rm, rs = STAGE, self.slot(s, written[s])
                     pending[s] = k
-            t_lo = lo * hop - half if lm == FROM_STAGE else min(lo * hop + half, T) if lm != NONE else lo * hop
-            t_hi = min(hi * hop + half, T) if rm == FROM_Y else hi * hop - half if rm != NONE else hi * hop
-            t_hi = max(t_hi, t_lo)
-            d["n_samples"].append((in_hi - in_lo) * hop)
-            d["core_lo"].append((lo - in_lo) * hop)
-            d["core_hi"].append((hi - in_lo) * hop)
-            d["left_mode"].append(lm)
-            d["right_mode"].append(rm)
-            d["left_src"].append(ls)
-            d["right_src"].append(rs)
-            d["dst_off"].append(pos)
-            d["utt"].append(s)
-            d["runs"].append((s, t_lo, t_hi))
-            pos += -(-(t_hi - t_lo) // 8) * 8            # (every run starts on a 16-byte boundary of both destinations)
-        d["total"], d["width"], d["half"] = pos, width, half
+            specs.append((s, int(seen[s]) * hop, in_lo, in_hi, lo, hi, lm, rm, ls, rs))
+        # (a stream's windows run in order: the left zone is written only when blended from the stage, the right one only
+        # when blended from the forward's output)
+        d = _emit_rows(specs, hop, half, width, (FROM_STAGE,), (FROM_Y,))
         self.pending, self.written = pending, written    # (only a batch that was laid out whole changes the state)
         return d
 
@@ -572,12 +630,59 @@ class _PinnedSet:
         self.bufs: Dict[str, torch.Tensor] = {}
 
     def get(self, key: str, shape) -> torch.Tensor:
-        need = int(np.prod(shape))
+        need = math.prod(shape)
         buf = self.bufs.get(key)
         if buf is None or buf.numel() < need:
             buf = torch.empty(max(need, 1), dtype=torch.float32, pin_memory=True)
             self.bufs[key] = buf
-        return buf[:need].view(*shape)
+        return buf[:need].view(*shape) if len(shape) > 1 else buf[:need]
+
+    def samples(self, total: int, pcm16: bool, at: int = 0):
+        """Room for the ``total`` samples of one download from word ``at`` of buffer "w" -> (the samples, the word behind
+        them).  int16 samples are a view of the float32 words, so one buffer serves both kinds and every batch starts on a
+        word boundary.  (A buffer that holds earlier batches, ``at > 0``, has to be large enough already: growing drops them.)"""
+        end = at + ((total + 1) // 2 if pcm16 else total)
+        words = self.get("w", (end,))
+        if at:
+            words = words[at:]
+        return (words.view(torch.int16)[:total] if pcm16 else words), end
+
+
+def _one_behind(stream, down, steps, enqueue, take) -> None:
+    """The download pipeline of a pass.  For every entry of ``steps``, ``enqueue(pinned, *step)`` puts the step on
+    ``stream``, whole - its downloads, into the page-locked set ``pinned = down[j & 1]``, last - and returns the
+    arguments with which ``take`` copies the results out of the set.  ``take`` runs one step behind, once the event
+    recorded behind the step's downloads has passed: while step j computes, step j - 1 is taken out, before step j + 1
+    reuses its set.  Every step has been taken out when this returns."""
+    behind = None
+    for j, step in enumerate(steps):
+        taken = enqueue(down[j & 1], *step)
+        done = torch.cuda.Event()
+        done.record(stream)
+        if behind is not None:
+            behind[0].synchronize()
+            take(*behind[1])
+        behind = (done, taken)
+    if behind is not None:
+        behind[0].synchronize()
+        take(*behind[1])
+
+
+def _stitch_to_host(y, lay, stage, pcm16: bool, pinned: _PinnedSet, report=None, at: int = 0):
+    """One forward's window rows ``y`` stitched by the layout dict ``lay`` (``stitch_layout``, ``StreamStitchLayout``) into
+    a new packed device buffer, int16 or float32, and its download queued on the current stream into ``pinned`` from word
+    ``at`` -> ``pinned.samples``' pair: the ``lay["total"]`` samples there, row r's run at ``lay["dst_off"][r]``, and the word
+    behind them.  ``report``: see ``engine.window_stitch``."""
+    from .engine import window_stitch
+    total = lay["total"]
+    packed = torch.empty(max(total, 1), dtype=torch.int16 if pcm16 else torch.float32, device=y.device)
+    window_stitch(y.view(len(lay["n_samples"]), lay["width"]), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"],
+                  lay["left_mode"], lay["right_mode"], lay["left_src"], lay["right_src"], lay["dst_off"], stage=stage,
+                  out_pcm=packed if pcm16 else None, out_float=None if pcm16 else packed, utt=lay["utt"], report=report)
+    host, end = pinned.samples(total, pcm16, at)
+    if total:
+        host.copy_(packed[:total], non_blocking=True)
+    return host, end
 
 
 @torch.no_grad()
@@ -712,6 +817,14 @@ def pack_blocks(arrays: Sequence[np.ndarray], counts: Sequence[int], offsets: Se
         dst[offsets[i]: offsets[i] + n] = a[:n]
 
 
+def _check_open(session) -> bool:
+    """The prologue of every convert: a closed session raises ``RuntimeError``; -> whether there is anything to convert.
+    (A function of the session, not a method: the converts are also called on stand-ins that have its attributes only.)"""
+    if session._closed:
+        raise RuntimeError("DecodeSession is closed")
+    return bool(session.n)
+
+
 class DecodeSession:
     """A data set kept on the device across target speakers: ``ppg`` and ``lft`` (99.7 % of the input bytes, the same for
     every speaker) cross the bus once, in the dump's own time-major layout and unpadded; every ``convert`` re-runs only
@@ -739,6 +852,10 @@ class DecodeSession:
         held for the session's life    4 * sum_i F_i * (C + hop) bytes                         (packed ppg + lft)
         transient, one batch at a time 4 * B_k * Fmax_k * (C + 1 + 3 * hop) bytes              (ppg, f0, lft, sine, y)
                                        + 2 * hop * sum_{i in batch} F_i (packed int16) + the forward's workspace
+    Page-locked host memory: the padded f0 of every batch (4 * sum_k B_k * Fmax_k bytes, for the session's life), the packed
+    ppg + lft until the first pass, and TWO download sets used by batch parity, each grown to the largest batch it has
+    taken - the packed int16 samples (or the float32 waveforms) of one batch.  ``convert``, ``convert_many`` and
+    ``convert_windowed`` share them, and the checked ones a report buffer of 16 bytes a row.
 
     ``uploaded_bytes`` counts the host-to-device copies: ``["init"]`` by the constructor, ``["convert"]`` one entry per
     ``convert`` (the padded f0 of every batch plus the embedding).  Kernel descriptors (offsets, lengths: 12 - 16 bytes per
@@ -787,6 +904,7 @@ class DecodeSession:
         self.n = len(feats)
         self.frames = [int(np.asarray(u["ppg"]).shape[0]) for u in feats]
         self.batches: List[List[int]] = list(bucket_ragged(range(self.n), self.frames, max_batch, pad_tolerance)) if feats else []
+        self._rows = [[(i, 0) for i in chunk] for chunk in self.batches]     # (convert's batches as the rows of a one-speaker fan-out)
         self.uploaded_bytes = {"init": 0, "convert": []}
         self.max_batch, self.pad_tolerance = int(max_batch), float(pad_tolerance)
         self._fan = None                             # (convert_many's resident extras, made by its first call)
@@ -795,7 +913,7 @@ class DecodeSession:
         self._window_trace: Optional[Dict[str, object]] = None
         self._closed = False
         self._ready = None
-        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = None
+        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_f0 = None
         if not feats:
             return
         if int(getattr(model, "out_channels", 1)) != 1:
@@ -850,11 +968,9 @@ class DecodeSession:
         # (C = 1 rows for gather_padded: views of the packed upload, made once)
         self._lft_rows = [[self._d_lft[self._lft_off[i]: self._lft_off[i] + lft_counts[i]].view(1, -1) for i in chunk]
                           for chunk in self.batches]
-        self._down = [_PinnedSet(), _PinnedSet()]
-        self._row_base, pos = [], 0                  # (a batch's reports: rows [_row_base[k], + len(batch)) of _h_rep)
-        for chunk in self.batches:
-            self._row_base.append(pos)
-            pos += len(chunk)
+        self._down = [_PinnedSet(), _PinnedSet()]    # (every pass's download staging, by batch parity)
+        self._counts, self._total = lft_counts, lft_total            # (samples per utterance, and of one speaker's result)
+        self._row_layouts = [fanout_layout(chunk, lft_counts, self._lft_off) for chunk in self._rows]   # (convert's batches never change)
 
     def __enter__(self):
         return self
@@ -870,8 +986,140 @@ class DecodeSession:
         if self.n and self.device.type == "cuda":
             self._copy_stream.synchronize()
             torch.cuda.current_stream(self.device).synchronize()
-        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_pcm = self._h_f0 = self._h_rep = None
+        self._h_ppg = self._h_lft = self._d_ppg = self._d_lft = self._h_f0 = self._h_rep = None
         self._lft_rows = self._down = self._ready = self._fan = None
+
+    def _emb_row(self, trg_emb) -> Optional[torch.Tensor]:
+        """The target speaker's embedding as a (1, E) device tensor, or None."""
+        if trg_emb is None:
+            return None
+        return torch.as_tensor(np.asarray(trg_emb), dtype=torch.float32).reshape(1, -1).to(self.device)
+
+    def _wait_for_uploads(self, stream) -> None:
+        """``stream`` waits for ALL the constructor's uploads, when no pass has waited for them yet."""
+        for ev in self._ready or ():
+            stream.wait_event(ev)
+
+    def _uploads_waited(self) -> None:
+        """After a pass's ``stream.synchronize()``: every upload of the constructor has been waited for, its staging can go."""
+        if self._ready is not None:
+            self._ready = None
+            self._h_ppg = self._h_lft = None
+
+    def _pack_f0(self, dst: np.ndarray, trg_f0_stats: Optional[Sequence[float]] = None) -> List[int]:
+        """f0 packed like lft into ``dst`` (float32 by assignment) -> the offsets: utterance i's frames at ``_lft_off[i] /
+        hop``.  With ``trg_f0_stats`` and source statistics, shifted on the host as ``convert`` shifts it."""
+        f0_off = [o // self.hop for o in self._lft_off]
+        shift = self.src_f0_stats is not None and trg_f0_stats is not None
+        for i, f in enumerate(self._f0):
+            n = self.frames[i]
+            if f.size < n:
+                raise ValueError(f"utterance {i}: {f.size} f0 values, {n} expected")
+            if shift:
+                f = F0Statistics().convert(f, self.src_f0_stats[i], trg_f0_stats)
+            dst[f0_off[i]: f0_off[i] + n] = f[:n]
+        return f0_off
+
+    def _host_report(self, n_rows: int) -> torch.Tensor:
+        """Page-locked room for the (n_rows, 4) reports of a checked pass, grown on demand and kept."""
+        if self._h_rep is None or self._h_rep.shape[0] < n_rows:
+            self._h_rep = torch.empty((n_rows, 4), dtype=torch.int32, pin_memory=True)
+        return self._h_rep[:n_rows]
+
+    def _row_pass(self, stream, batches: Sequence[Sequence[Tuple[int, int]]], n_spk: int, assemble, layout, pcm16: bool):
+        """The pass under ``convert`` and ``convert_many``: the batches of ``(utterance, speaker)`` rows, one forward each,
+        downloads one batch behind, and - a checked session - the storage fallback -> ``(out, reports, still)``:
+        ``out[speaker][utterance]`` the arrays the two return, ``reports[speaker][utterance]`` the ``last_report`` dicts
+        (None unless checked), ``still`` the pairs left non-finite.
+
+        ``assemble(k, first_pass)`` puts batch k's inputs on the current stream and returns ``(ppg, f0, lft, emb, lens,
+        fmax)`` (``first_pass`` False: a fallback run of the batch); ``layout(k)`` is batch k's ``fanout_layout``.  Then, per
+        batch: the excitation, the forward, ``pcm16_pack`` into that layout (or ``output_check`` with ``pcm16=False``), the
+        download of the samples and of the reports.  In the result, speaker s starts at ``s * total`` and is laid out as ``_lft_off`` says.
+        A fallback run computes the batch whole and replaces the flagged rows' samples and reports only."""
+        from .engine import output_check, pcm16_pack
+        dev, hop, checked = self.device, self.hop, self.checked
+        counts, total = self._counts, self._total    # (samples per utterance; one speaker's samples)
+        if checked:
+            row_batches, pos = [], 0                 # (batch k's rows as rows of the pass: where their reports go)
+            for chunk in batches:
+                row_batches.append(list(range(pos, pos + len(chunk))))
+                pos += len(chunk)
+            h_rep = self._host_report(pos)
+        if pcm16:
+            result = np.empty(n_spk * total, dtype=np.int16)
+        else:
+            out: List[List[Optional[np.ndarray]]] = [[None] * self.n for _ in range(n_spk)]
+
+        def take(k: int, host: torch.Tensor, rows: Optional[Sequence[int]]) -> None:
+            """Batch k's samples out of the page-locked buffer (``rows``: those rows of it only)."""
+            chunk, h = batches[k], host.numpy()
+            if pcm16:
+                offs, runs, _ = layout(k)
+                if rows is None:
+                    for sp, first, start, count in runs:
+                        result[sp * total + first: sp * total + first + count] = h[start: start + count]
+                else:
+                    for j in rows:
+                        u, sp = chunk[j]
+                        a = sp * total + self._lft_off[u]
+                        result[a: a + counts[u]] = h[offs[j]: offs[j] + counts[u]]
+                return
+            for j in (range(len(chunk)) if rows is None else rows):
+                u, sp = chunk[j]
+                out[sp][u] = h[j].reshape(-1)[: counts[u]].copy()
+
+        def enqueue(pinned: _PinnedSet, k: int, rows: Optional[Sequence[int]] = None):
+            """Batch k on the stream, whole.  ``rows`` (a fallback run): only those rows' reports replace the first pass's."""
+            R = len(batches[k])
+            ppg, f0, lft, emb, lens, fmax = assemble(k, rows is None)
+            sine = self.signal_generator(f0)
+            emb = None if emb is None else emb.contiguous()      # (an expanded row becomes (R, E) here, behind the excitation)
+            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+            self.forwards += 1
+            report = torch.empty((R, 4), dtype=torch.int32, device=dev) if checked else None
+            if pcm16:
+                offs, _, count = layout(k)
+                packed = torch.empty(max(count, 1), dtype=torch.int16, device=dev)
+                pcm16_pack(y.view(R, fmax * hop), [n * hop for n in lens], offs, out=packed, report=report)
+                host = pinned.samples(count, True)[0]
+                if count:
+                    host.copy_(packed[:count], non_blocking=True)
+            else:
+                host = pinned.get("w", tuple(y.shape))
+                host.copy_(y, non_blocking=True)
+                if checked:
+                    output_check(y.view(R, fmax * hop), [n * hop for n in lens], out=report)
+            if checked:
+                r0 = row_batches[k][0]
+                if rows is None:
+                    h_rep[r0: r0 + R].copy_(report, non_blocking=True)
+                else:
+                    for j in rows:
+                        h_rep[r0 + j].copy_(report[j], non_blocking=True)
+            return k, host, rows
+
+        _one_behind(stream, self._down, [(k,) for k in range(len(batches))], enqueue, take)
+        stream.synchronize()
+        self._uploads_waited()
+        reports, still = None, []
+        if checked:
+            rep = h_rep.numpy()
+            pairs = [pair for chunk in batches for pair in chunk]            # (row of the pass -> (utterance, speaker))
+
+            def run(work) -> None:                   # (the rare path; its events make ``rep`` current before it returns)
+                _one_behind(stream, self._down, work, enqueue, take)
+
+            storage, tried, flagged = storage_fallback(self.model, self.fallback, len(pairs), lambda r: rep[r, 0] > 0,
+                                                       _rerun_in_batches(row_batches, run))
+            reports = [[None] * self.n for _ in range(n_spk)]
+            for (u, sp), d in zip(pairs, _report_dicts(rep, storage, tried)):
+                reports[sp][u] = d
+            still = [pairs[r] for r in flagged]
+        if pcm16:
+            out = [[result[sp * total + self._lft_off[i]: sp * total + self._lft_off[i] + counts[i]] for i in range(self.n)]
+                   for sp in range(n_spk)]
+        return out, reports, still
 
     @torch.no_grad()
     def convert(self, trg_emb=None, trg_f0_stats: Optional[Sequence[float]] = None, pcm16: bool = True) -> List[np.ndarray]:
@@ -881,11 +1129,9 @@ class DecodeSession:
                      call, a copy of the page-locked download buffer (made batch by batch while later batches compute),
                      so they stay valid after the next ``convert`` and after ``close``.
         pcm16=False  float32 arrays, copies: exactly what ``decode_utterances`` returns."""
-        if self._closed:
-            raise RuntimeError("DecodeSession is closed")
-        if not self.n:
+        if not _check_open(self):
             return []
-        from .engine import FastSVCError, gather_padded, gather_time_major, output_check, pcm16_pack, report_arrays
+        from .engine import FastSVCError, gather_padded, gather_time_major
         from .synth import TOO_LONG_HINT, max_forward_frames
         dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
         cfg = getattr(self.model, "_cfg", None)
@@ -893,52 +1139,22 @@ class DecodeSession:
             i = int(np.argmax(frames))
             raise FastSVCError(f"utterance {i} ({frames[i]} frames) is too long for the 32-bit tensor descriptors of the "
                                f"kernels (one forward takes {max_forward_frames(cfg)} frames): split it" + TOO_LONG_HINT)
-        checked = self.checked
         stream = torch.cuda.current_stream(dev)
-        up = 0
         self.forwards = 0
-        emb_row = None
-        if trg_emb is not None:
-            emb_row = torch.as_tensor(np.asarray(trg_emb), dtype=torch.float32).reshape(1, -1).to(dev)
-            up += 4 * emb_row.numel()
+        emb_row = self._emb_row(trg_emb)
+        up = 0 if emb_row is None else 4 * emb_row.numel()
         shift = self.src_f0_stats is not None and trg_f0_stats is not None
         hf_all = self._h_f0.numpy()
-        if pcm16 and self._h_pcm is None:
-            self._h_pcm = torch.empty(max(sum(frames) * hop, 1), dtype=torch.int16, pin_memory=True)
-        if checked and self._h_rep is None:
-            self._h_rep = torch.empty((self.n, 4), dtype=torch.int32, pin_memory=True)
-        out: List[Optional[np.ndarray]] = [None] * self.n
-        result = np.empty(sum(frames) * hop, dtype=np.int16) if pcm16 else None
-        pending = {}
 
-        def finish(k: int, rows: Optional[Sequence[int]] = None) -> None:
-            """Take batch k's samples out of the page-locked buffers (``rows``: those rows of it only)."""
-            host_y, done = pending.pop(k)
-            done.synchronize()
-            chunk = self.batches[k]
-            if pcm16:
-                if rows is None:
-                    lo, hi = host_y
-                    result[lo:hi] = self._h_pcm.numpy()[lo:hi]
-                else:
-                    for j in rows:
-                        lo, hi = self._lft_off[chunk[j]], self._lft_off[chunk[j]] + frames[chunk[j]] * hop
-                        result[lo:hi] = self._h_pcm.numpy()[lo:hi]
-                return
-            y = host_y.numpy()
-            for j in (range(len(chunk)) if rows is None else rows):
-                i = chunk[j]
-                out[i] = y[j].reshape(-1)[: frames[i] * hop].copy()
-
-        def enqueue(k: int, rows: Optional[Sequence[int]] = None) -> int:
-            """Batch k on the stream, whole: f0 up, assembly, forward, packing, downloads.  ``rows`` (a fallback run): the
-            padded f0 is still in its page-locked slot from the first pass, and only those rows' samples and reports come
-            down.  Returns the bytes uploaded."""
+        def assemble(k: int, first_pass: bool):
+            """f0 up, shifted on the host, and the batch out of the packed upload.  On a fallback run the padded f0 is still
+            in its page-locked slot from the first pass."""
+            nonlocal up
             chunk = self.batches[k]
             fmax, B = frames[chunk[0]], len(chunk)
             lens = [frames[i] for i in chunk]
             base = self._f0_base[k]
-            if rows is None:
+            if first_pass:
                 hf = hf_all[base: base + B * fmax].reshape(B, 1, fmax)
                 for j, i in enumerate(chunk):
                     f, n = self._f0[i], frames[i]
@@ -947,94 +1163,20 @@ class DecodeSession:
                     hf[j, 0, :n] = f
                     hf[j, 0, n:] = 0
             f0 = self._h_f0[base: base + B * fmax].view(B, 1, fmax).to(dev, non_blocking=True)
-            if self._ready is not None:
+            up += 4 * B * fmax
+            if self._ready is not None:              # (the first pass: this batch's upload only, the later ones are in flight)
                 stream.wait_event(self._ready[k])
             ppg = gather_time_major(self._d_ppg, [self._ppg_off[i] for i in chunk], lens, C, fmax)
             lft = gather_padded(self._lft_rows[k], fmax * hop)
-            sine = self.signal_generator(f0)
-            emb = None if emb_row is None else emb_row.expand(B, -1).contiguous()
-            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
-            self.forwards += 1
-            report = torch.empty((B, 4), dtype=torch.int32, device=dev) if checked else None
-            if pcm16:
-                lo = self._lft_off[chunk[0]]
-                total = sum(lens) * hop
-                packed = torch.empty(max(total, 1), dtype=torch.int16, device=dev)
-                pcm16_pack(y.view(B, fmax * hop), [n * hop for n in lens], [self._lft_off[i] - lo for i in chunk], out=packed,
-                           report=report)
-                if rows is None:
-                    if total:
-                        self._h_pcm[lo: lo + total].copy_(packed[:total], non_blocking=True)
-                else:
-                    for j in rows:
-                        a, n = self._lft_off[chunk[j]], lens[j] * hop
-                        if n:
-                            self._h_pcm[a: a + n].copy_(packed[a - lo: a - lo + n], non_blocking=True)
-                host_y = (lo, lo + total)
-            else:
-                host_y = self._down[k & 1].get("y", tuple(y.shape))
-                host_y.copy_(y, non_blocking=True)
-                if checked:
-                    output_check(y.view(B, fmax * hop), [n * hop for n in lens], out=report)
-            if checked:
-                r0 = self._row_base[k]
-                if rows is None:
-                    self._h_rep[r0: r0 + B].copy_(report, non_blocking=True)
-                else:
-                    for j in rows:
-                        self._h_rep[r0 + j].copy_(report[j], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(stream)
-            pending[k] = (host_y, done)
-            return 4 * B * fmax
+            return ppg, f0, lft, None if emb_row is None else emb_row.expand(B, -1), lens, fmax
 
-        for k in range(len(self.batches)):
-            up += enqueue(k)
-            if k >= 1:
-                finish(k - 1)                        # (while batch k computes; before batch k + 1 reuses that download set)
-        finish(len(self.batches) - 1)
-        stream.synchronize()
-        if self._ready is not None:                  # every upload has been waited for: the staging can go
-            self._ready = None
-            self._h_ppg = self._h_lft = None
-        still = []
-        if checked:
-            row_of = {i: self._row_base[k] + j for k, chunk in enumerate(self.batches) for j, i in enumerate(chunk)}
-            rep = self._h_rep.numpy()
-            first = getattr(self.model, "activation_storage", "float32")
-            storage, tried = [first] * self.n, [[] for _ in range(self.n)]
-            flagged = [i for i in range(self.n) if rep[row_of[i], 0] > 0]
-            again = None
-            try:
-                for name in self.fallback:
-                    again = flagged_batches(self.batches, flagged, again)
-                    if not again:
-                        break
-                    self.model.use_activation_storage(name)
-                    for k in again:                  # (the rare path: one batch at a time)
-                        rows = [j for j, i in enumerate(self.batches[k]) if i in flagged]
-                        up += enqueue(k, rows)
-                        finish(k, rows)
-                        for j in rows:
-                            i = self.batches[k][j]
-                            tried[i].append(storage[i])
-                            storage[i] = name
-                    flagged = [i for i in flagged if rep[row_of[i], 0] > 0]
-            finally:
-                if getattr(self.model, "activation_storage", first) != first:
-                    self.model.use_activation_storage(first)
-            nonfinite, clipped, max_abs = report_arrays(rep)
-            self.last_report = [dict(storage=storage[i], nonfinite=int(nonfinite[row_of[i]]), clipped=int(clipped[row_of[i]]),
-                                     max_abs=float(max_abs[row_of[i]]), tried=tried[i]) for i in range(self.n)]
-            still = flagged
-        if pcm16:
-            out = [result[self._lft_off[i]: self._lft_off[i] + frames[i] * hop] for i in range(self.n)]
+        out, reports, still = self._row_pass(stream, self._rows, 1, assemble, self._row_layouts.__getitem__, pcm16)
+        if self.checked:
+            self.last_report = reports[0]
         self.uploaded_bytes["convert"].append(up)
         if still and self.strict:
-            raise FastSVCError(f"utterances {still} still have non-finite samples after storages "
-                               f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
-        return out  # type: ignore[return-value]
-
+            _raise_still_nonfinite(self.model, self.fallback, "utterances", sorted(u for u, _ in still))
+        return out[0]
 
     @torch.no_grad()
     def convert_windowed(self, trg_emb=None, trg_f0_stats: Optional[Sequence[float]] = None, core: int = 400,
@@ -1081,11 +1223,9 @@ class DecodeSession:
         utterance with non-finite samples has ALL its windows run again in the next fallback storage, in batches of their
         own.  ``uploaded_bytes["convert_windowed"]`` gets one entry per call: the packed f0 (4 bytes a frame) and the
         embedding."""
-        if self._closed:
-            raise RuntimeError("DecodeSession is closed")
-        if not self.n:
+        if not _check_open(self):
             return []
-        from .engine import FastSVCError, report_arrays, window_assemble, window_stitch
+        from .engine import window_assemble
         dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
         core = int(core)
         if context is None:
@@ -1106,28 +1246,14 @@ class DecodeSession:
         rows = window_plan(frames, core, context)
         if grouped:
             grouped_window_batches(rows, self.max_batch)     # (an utterance that does not fit a batch: refused before anything runs)
-        up = 0
-        emb_row = None
-        if trg_emb is not None:
-            emb_row = torch.as_tensor(np.asarray(trg_emb), dtype=torch.float32).reshape(1, -1).to(dev)
-            up += 4 * emb_row.numel()
-        shift = self.src_f0_stats is not None and trg_f0_stats is not None
+        emb_row = self._emb_row(trg_emb)
+        up = 0 if emb_row is None else 4 * emb_row.numel()
         total = sum(frames) * hop
-        f0_off = [o // hop for o in self._lft_off]       # (f0 packed like lft)
         # ---- the excitation of every whole utterance, packed like lft
-        hf = self._h_f0.numpy()                          # (page-locked, at least sum(frames) floats)
-        for i in range(self.n):
-            f, n = self._f0[i], frames[i]
-            if f.size < n:
-                raise ValueError(f"utterance {i}: {f.size} f0 values, {n} expected")
-            if shift:
-                f = F0Statistics().convert(f, self.src_f0_stats[i], trg_f0_stats)
-            hf[f0_off[i]: f0_off[i] + n] = f[:n]
+        f0_off = self._pack_f0(self._h_f0.numpy(), trg_f0_stats)     # (page-locked, at least sum(frames) floats)
         d_f0 = self._h_f0[: sum(frames)].to(dev, non_blocking=True)
         up += 4 * sum(frames)
-        if self._ready is not None:                      # (the constructor's uploads, when no convert has waited for them yet)
-            for ev in self._ready:
-                stream.wait_event(ev)
+        self._wait_for_uploads(stream)
         d_sine = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
         for i in range(self.n):
             n = frames[i]
@@ -1144,7 +1270,6 @@ class DecodeSession:
             by_utt.setdefault(row[0], []).append(r)
         result = np.empty(total, dtype=np.int16 if pcm16 else np.float32)
         d_rep = torch.zeros((self.n, 4), dtype=torch.int32, device=dev) if checked else None
-        n_down = [0, 0]
         # norm="utterance": the partial sums' scratch, once per call, for the largest batch any pass can form
         norm_scratch = None
         plan = getattr(self.model, "plan", None)
@@ -1160,18 +1285,15 @@ class DecodeSession:
                        (grouped_window_batches(sub, self.max_batch) if grouped else window_batches(sub, self.max_batch, self.pad_tolerance))]
             layout, stage_elems = stitch_layout(rows, batches, hop, fade)
             stage = torch.empty(max(stage_elems, 1), dtype=torch.float32, device=dev)
-            pending = {}
 
-            def finish(k: int) -> None:
-                host, done = pending.pop(k)
-                done.synchronize()
-                h, lay = host.numpy(), layout[k]
+            def take(host: torch.Tensor, lay) -> None:
+                h = host.numpy()
                 for (u, t_lo, t_hi), off in zip(lay["runs"], lay["dst_off"]):
                     a = self._lft_off[u]
                     result[a + t_lo: a + t_hi] = h[off: off + t_hi - t_lo]
 
-            for k, chunk in enumerate(batches):
-                lay = layout[k]
+            def enqueue(pinned: _PinnedSet, k: int):
+                chunk, lay = batches[k], layout[k]
                 lens = [rows[r][2] - rows[r][1] for r in chunk]
                 width, B = max(lens), len(chunk)
                 ppg, lft, sine = window_assemble(
@@ -1189,60 +1311,29 @@ class DecodeSession:
                 else:
                     y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
                 self.forwards += 1
-                packed = torch.empty(max(lay["total"], 1), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
-                window_stitch(y.view(B, width * hop), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"],
-                              lay["left_mode"], lay["right_mode"], lay["left_src"], lay["right_src"], lay["dst_off"],
-                              stage=stage, out_pcm=packed if pcm16 else None, out_float=None if pcm16 else packed,
-                              utt=lay["utt"], report=d_rep)
-                # (a page-locked set per parity, as float32 words; int16 samples are a view of them)
-                words = (packed.numel() + 1) // 2 if pcm16 else packed.numel()
-                host = self._down[n_down[0] & 1].get("w", (max(words, 1),))
-                n_down[0] += 1
-                host = host.view(torch.int16)[: packed.numel()] if pcm16 else host[: packed.numel()]
-                host.copy_(packed, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(stream)
-                pending[k] = (host, done)
-                if k >= 1:
-                    finish(k - 1)                    # (while batch k computes; before batch k + 1 reuses that download set)
-            finish(len(batches) - 1)
+                return _stitch_to_host(y, lay, stage, pcm16, pinned, d_rep)[0], lay
+
+            _one_behind(stream, self._down, [(k,) for k in range(len(batches))], enqueue, take)
+            stream.synchronize()
 
         run(list(range(len(rows))))
-        stream.synchronize()
-        if self._ready is not None:                      # every upload has been waited for: the staging can go
-            self._ready = None
-            self._h_ppg = self._h_lft = None
+        self._uploads_waited()
         still: List[int] = []
         if checked:
             rep = d_rep.cpu().numpy()
-            first = getattr(self.model, "activation_storage", "float32")
-            storage, tried = [first] * self.n, [[] for _ in range(self.n)]
-            flagged = [i for i in range(self.n) if rep[i, 0] > 0]
-            try:
-                for name in self.fallback:
-                    if not flagged:
-                        break
-                    self.model.use_activation_storage(name)
-                    d_rep[torch.as_tensor(flagged, device=dev)] = 0
-                    run([r for i in flagged for r in by_utt[i]])       # (the rare path: batches of the flagged windows only)
-                    stream.synchronize()
-                    rep = d_rep.cpu().numpy()
-                    for i in flagged:
-                        tried[i].append(storage[i])
-                        storage[i] = name
-                    flagged = [i for i in flagged if rep[i, 0] > 0]
-            finally:
-                if getattr(self.model, "activation_storage", first) != first:
-                    self.model.use_activation_storage(first)
-            nonfinite, clipped, max_abs = report_arrays(rep)
-            self.last_report = [dict(storage=storage[i], nonfinite=int(nonfinite[i]), clipped=int(clipped[i]),
-                                     max_abs=float(max_abs[i]), tried=tried[i]) for i in range(self.n)]
-            still = flagged
+
+            def rerun(name, flagged) -> None:        # (the rare path: batches of the flagged utterances' windows only)
+                nonlocal rep
+                d_rep[torch.as_tensor(flagged, device=dev)] = 0
+                run([r for i in flagged for r in by_utt[i]])
+                rep = d_rep.cpu().numpy()
+
+            storage, tried, still = storage_fallback(self.model, self.fallback, self.n, lambda i: rep[i, 0] > 0, rerun)
+            self.last_report = _report_dicts(rep, storage, tried)
         out = [result[self._lft_off[i]: self._lft_off[i] + frames[i] * hop] for i in range(self.n)]
         self.uploaded_bytes.setdefault("convert_windowed", []).append(up)
         if still and self.strict:
-            raise FastSVCError(f"utterances {still} still have non-finite samples after storages "
-                               f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
+            _raise_still_nonfinite(self.model, self.fallback, "utterances", still)
         return out
 
     def _fanout_init(self) -> None:
@@ -1250,14 +1341,10 @@ class DecodeSession:
         float32, the values ``convert`` uploads batch by batch; the (n, 2) float64 table of source statistics; and the
         layout as the ctypes arrays every ``fanout_assemble`` reads."""
         import ctypes
-        hop, frames, C = self.hop, self.frames, self.channels
-        f0_off = [o // hop for o in self._lft_off]
+        frames = self.frames
         h = np.empty(max(sum(frames), 1), dtype=np.float32)
-        for i, f in enumerate(self._f0):
-            if f.size < frames[i]:
-                raise ValueError(f"utterance {i}: {f.size} f0 values, {frames[i]} expected")
-            h[f0_off[i]: f0_off[i] + frames[i]] = f[: frames[i]]
-        fan = {"f0": torch.from_numpy(h).to(self.device), "src": None, "stage": [None, None]}
+        f0_off = self._pack_f0(h)
+        fan = {"f0": torch.from_numpy(h).to(self.device), "src": None}
         up = 4 * sum(frames)
         if self.src_f0_stats is not None:
             table = np.ascontiguousarray(np.asarray(self.src_f0_stats, dtype=np.float64).reshape(self.n, 2))
@@ -1299,16 +1386,12 @@ class DecodeSession:
         is run again whole in the next fallback storage and only the flagged rows are replaced; ``last_report`` becomes
         a list per speaker of the per-utterance dicts; ``strict`` names the ``(utterance, speaker)`` pairs; the model's
         storage is restored also when a forward raises."""
-        if self._closed:
-            raise RuntimeError("DecodeSession is closed")
         speakers = list(speakers)
         S = len(speakers)
-        if not self.n or not S:
+        if not _check_open(self) or not S:
             return [[] for _ in speakers]
-        from .engine import FastSVCError, fanout_assemble, output_check, pcm16_pack, report_arrays
+        from .engine import fanout_assemble
         dev, hop, frames, C = self.device, self.hop, self.frames, self.channels
-        checked = self.checked
-        stream = torch.cuda.current_stream(dev)
         embs, stats = [e for e, _ in speakers], [t for _, t in speakers]
         for name, vals in (("an embedding", embs), ("F0 statistics", stats)):
             if any(v is None for v in vals) and not all(v is None for v in vals):
@@ -1329,135 +1412,31 @@ class DecodeSession:
                 np.stack([np.asarray(t, dtype=np.float64).reshape(-1)[:2] for t in stats]))).to(dev)
             up += 8 * stats_table.numel()
         batches = fanout_batches(frames, S, self.max_batch, self.pad_tolerance)
-        row_base, pos = [], 0                        # (batch k's rows are rows [row_base[k], + len(batch)) of the pass)
-        for chunk in batches:
-            row_base.append(pos)
-            pos += len(chunk)
-        total = sum(frames) * hop                    # (one speaker's samples: speaker s starts at s * total)
-        h_rep = torch.empty((self.n * S, 4), dtype=torch.int32, pin_memory=True) if checked else None
-        out: List[List[Optional[np.ndarray]]] = [[None] * self.n for _ in range(S)]
-        result = np.empty(S * total, dtype=np.int16) if pcm16 else None
-        if self._ready is not None:                  # (the constructor's uploads, when no convert has waited for them yet)
-            for ev in self._ready:
-                stream.wait_event(ev)
-        plans, pending = {}, {}
+        stream = torch.cuda.current_stream(dev)
+        self._wait_for_uploads(stream)
 
-        def plan(k: int):
-            if k not in plans:
-                plans[k] = fanout_layout(batches[k], [f * hop for f in frames], self._lft_off)
-            return plans[k]
-
-        def finish(k: int, rows: Optional[Sequence[int]] = None) -> None:
-            """Take batch k's samples out of the page-locked buffers (``rows``: those rows of it only)."""
-            host_y, done = pending.pop(k)
-            done.synchronize()
+        def assemble(k: int, first_pass: bool):
             chunk = batches[k]
-            if pcm16:
-                offs, runs, _ = plan(k)
-                h = host_y.numpy()
-                if rows is None:
-                    for sp, first, start, count in runs:
-                        result[sp * total + first: sp * total + first + count] = h[start: start + count]
-                else:
-                    for j in rows:
-                        u, sp = chunk[j]
-                        a, n = sp * total + self._lft_off[u], frames[u] * hop
-                        result[a: a + n] = h[offs[j]: offs[j] + n]
-                return
-            y = host_y.numpy()
-            for j in (range(len(chunk)) if rows is None else rows):
-                u, sp = chunk[j]
-                out[sp][u] = y[j].reshape(-1)[: frames[u] * hop].copy()
-
-        def enqueue(k: int, rows: Optional[Sequence[int]] = None) -> None:
-            """Batch k on the stream, whole: assembly, excitation, forward, packing, downloads.  ``rows`` (a fallback
-            run): only those rows' reports replace the first pass's."""
-            chunk = batches[k]
-            R, fmax = len(chunk), frames[chunk[0][0]]
-            lens = [frames[u] for u, _ in chunk]
+            fmax = frames[chunk[0][0]]
             ppg, lft, f0, emb = fanout_assemble(self._d_ppg, self._d_lft, fan["f0"], fan["ppg_off"], fan["lft_off"],
                                                 fan["f0_off"], fan["frames"], [u for u, _ in chunk], [sp for _, sp in chunk],
                                                 C, hop, fmax, src_stats=fan["src"] if shift else None,
                                                 spk_stats=stats_table, spk_emb=emb_table, n_spk=S)
-            sine = self.signal_generator(f0)
-            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
-            self.forwards += 1
-            report = torch.empty((R, 4), dtype=torch.int32, device=dev) if checked else None
-            if pcm16:
-                offs, _, count = plan(k)
-                packed = torch.empty(max(count, 1), dtype=torch.int16, device=dev)
-                pcm16_pack(y.view(R, fmax * hop), [n * hop for n in lens], offs, out=packed, report=report)
-                host_y = fan["stage"][k & 1]
-                if host_y is None or host_y.numel() < packed.numel():
-                    host_y = fan["stage"][k & 1] = torch.empty(packed.numel(), dtype=torch.int16, pin_memory=True)
-                host_y = host_y[: packed.numel()]
-                host_y.copy_(packed, non_blocking=True)
-            else:
-                host_y = self._down[k & 1].get("y", tuple(y.shape))
-                host_y.copy_(y, non_blocking=True)
-                if checked:
-                    output_check(y.view(R, fmax * hop), [n * hop for n in lens], out=report)
-            if checked:
-                r0 = row_base[k]
-                if rows is None:
-                    h_rep[r0: r0 + R].copy_(report, non_blocking=True)
-                else:
-                    for j in rows:
-                        h_rep[r0 + j].copy_(report[j], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(stream)
-            pending[k] = (host_y, done)
+            return ppg, f0, lft, emb, [frames[u] for u, _ in chunk], fmax
 
-        for k in range(len(batches)):
-            enqueue(k)
-            if k >= 1:
-                finish(k - 1)                        # (while batch k computes; before batch k + 1 reuses that download set)
-        finish(len(batches) - 1)
-        stream.synchronize()
-        if self._ready is not None:                  # every upload has been waited for: the staging can go
-            self._ready = None
-            self._h_ppg = self._h_lft = None
-        still: List[Tuple[int, int]] = []
-        if checked:
-            pairs = [pair for chunk in batches for pair in chunk]            # (row of the pass -> (utterance, speaker))
-            row_batches = [list(range(row_base[k], row_base[k] + len(chunk))) for k, chunk in enumerate(batches)]
-            rep = h_rep.numpy()
-            first = getattr(self.model, "activation_storage", "float32")
-            storage, tried = [first] * len(pairs), [[] for _ in pairs]
-            flagged = [r for r in range(len(pairs)) if rep[r, 0] > 0]
-            again = None
-            try:
-                for name in self.fallback:
-                    again = flagged_batches(row_batches, flagged, again)
-                    if not again:
-                        break
-                    self.model.use_activation_storage(name)
-                    for k in again:                  # (the rare path: one batch at a time)
-                        rows = [j for j, r in enumerate(row_batches[k]) if r in flagged]
-                        enqueue(k, rows)
-                        finish(k, rows)
-                        for j in rows:
-                            r = row_batches[k][j]
-                            tried[r].append(storage[r])
-                            storage[r] = name
-                    flagged = [r for r in flagged if rep[r, 0] > 0]
-            finally:
-                if getattr(self.model, "activation_storage", first) != first:
-                    self.model.use_activation_storage(first)
-            nonfinite, clipped, max_abs = report_arrays(rep)
-            report_of: List[List[Optional[Dict[str, object]]]] = [[None] * self.n for _ in range(S)]
-            for r, (u, sp) in enumerate(pairs):
-                report_of[sp][u] = dict(storage=storage[r], nonfinite=int(nonfinite[r]), clipped=int(clipped[r]),
-                                        max_abs=float(max_abs[r]), tried=tried[r])
-            self.last_report = report_of
-            still = [pairs[r] for r in flagged]
-        if pcm16:
-            out = [[result[sp * total + self._lft_off[i]: sp * total + self._lft_off[i] + frames[i] * hop]
-                    for i in range(self.n)] for sp in range(S)]
+        layouts = {}
+
+        def layout(k: int):
+            if k not in layouts:
+                layouts[k] = fanout_layout(batches[k], self._counts, self._lft_off)
+            return layouts[k]
+
+        out, reports, still = self._row_pass(stream, batches, S, assemble, layout, pcm16)
+        if self.checked:
+            self.last_report = reports
         self.uploaded_bytes["convert_many"].append(up)
         if still and self.strict:
-            raise FastSVCError(f"(utterance, speaker) pairs {still} still have non-finite samples after storages "
-                               f"{[getattr(self.model, 'activation_storage', 'float32')] + list(self.fallback)} (strict=True)")
+            _raise_still_nonfinite(self.model, self.fallback, "(utterance, speaker) pairs", still)
         return out
 
 
@@ -1543,7 +1522,8 @@ class StreamSession:
         self._h_up = torch.empty(n * self._slice, dtype=torch.float32, pin_memory=True)
         self._d_up = torch.empty(n * self._slice, dtype=torch.float32, device=dev)
         # a push returns at most the frames a ring holds per stream; every row's run is padded to 8 samples
-        self._h_down = torch.empty(n * (cap * hop + 8 * (cap // core + 2)), dtype=torch.float32, pin_memory=True)
+        self._h_down = _PinnedSet()
+        self._h_down.get("w", (n * (cap * hop + 8 * (cap // core + 2)),))
         self._up_done: Optional[torch.cuda.Event] = None
         self._emb_rows: Dict[tuple, torch.Tensor] = {}                       # row slots of a forward -> their index tensor
         self._slots: List[Optional[Dict[str, object]]] = [None] * n          # per slot: the open stream's host state
@@ -1620,7 +1600,7 @@ class StreamSession:
         and their slots are free afterwards."""
         if self._closed:
             raise RuntimeError("StreamSession is closed")
-        from .engine import stream_assemble, stream_push, window_stitch
+        from .engine import stream_assemble, stream_push
         hop, C, core, context = self.hop, self.channels, self.core, self.context
         end = [int(i) for i in end]
         # ---- validation: nothing is touched before every chunk has passed
@@ -1704,7 +1684,7 @@ class StreamSession:
             chunk = rows[c0: c0 + self.max_batch]
             lay = self._layout.batch(chunk, seen)
             lens = [r[3] - r[2] for r in chunk]
-            width, B = max(lens), len(chunk)
+            width = max(lens)
             ppg, lft, sine = stream_assemble(self._ppg, self._lft, self._exc, seen, [r[0] for r in chunk],
                                              [r[2] for r in chunk], lens, width)
             if trace is not None:
@@ -1719,18 +1699,8 @@ class StreamSession:
                 emb = self._emb.index_select(0, self._emb_rows[slots])
             y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
             self.forwards += 1
-            packed = torch.empty(max(lay["total"], 1), dtype=torch.int16 if self.pcm16 else torch.float32, device=dev)
-            window_stitch(y.view(B, width * hop), lay["n_samples"], lay["core_lo"], lay["core_hi"], lay["half"],
-                          lay["left_mode"], lay["right_mode"], lay["left_src"], lay["right_src"], lay["dst_off"],
-                          stage=self._stage, out_pcm=packed if self.pcm16 else None, out_float=None if self.pcm16 else packed)
-            # (the page-locked buffer as float32 words; int16 samples are a view of them, every batch on a word boundary)
-            words = (lay["total"] + 1) // 2 if self.pcm16 else lay["total"]
-            host = self._h_down[off: off + words]
-            host = host.view(torch.int16)[: lay["total"]] if self.pcm16 else host
-            if lay["total"]:
-                host.copy_(packed[: lay["total"]], non_blocking=True)
+            host, off = _stitch_to_host(y, lay, self._stage, self.pcm16, self._h_down, at=off)
             down.append((host, lay))
-            off += words
         if down:
             stream.synchronize()
             for host, lay in down:

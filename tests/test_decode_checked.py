@@ -1,5 +1,6 @@
 """CPU-side tests of the checked decode path: the host reference of the per-row output report (decode.output_report),
-the choice of the batches a checked session runs again (decode.flagged_batches), and the refusal of CPU devices.  No
+the choice of the batches a checked session runs again (decode.flagged_batches), the storage fallback every checked
+convert drives (decode.storage_fallback, with a fake model and scripted flags), and the refusal of CPU devices.  No
 kernel is launched here; the kernels and the session are checked on the GPU in tests/test_decode_checked_gpu.py."""
 from fractions import Fraction
 
@@ -105,6 +106,140 @@ def test_flagged_batches_picks_whole_batches():
     assert Dc.flagged_batches(batches, [6, 0], first) == [3]                   # (batch 1 was not among the first round's)
     assert Dc.flagged_batches(batches, [], first) == []
     assert Dc.flagged_batches([], [1]) == []
+
+
+class _FakeModel:
+    """What ``storage_fallback`` needs of a model: the attribute, and a switch that records its calls."""
+
+    def __init__(self, storage="float16"):
+        self.activation_storage = storage
+        self.calls = []
+
+    def use_activation_storage(self, name):
+        self.calls.append(name)
+        self.activation_storage = name
+
+
+def _scripted(model, clears):
+    """``is_flagged`` / ``rerun`` over scripted flags: ``clears[unit]`` is the storage that clears the unit (None: none
+    does; a unit that is not in it was never flagged).  ``rerun`` records ``(name, the model's storage, flagged)``."""
+    flagged, rounds = set(clears), []
+
+    def rerun(name, units):
+        rounds.append((name, getattr(model, "activation_storage", None), list(units)))
+        for i in units:
+            if clears[i] == name:
+                flagged.discard(i)
+    return (lambda i: i in flagged), rerun, rounds
+
+
+def test_fallback_driver_leaves_a_clean_pass_alone():
+    m = _FakeModel()
+    is_flagged, rerun, rounds = _scripted(m, {})
+    storage, tried, still = Dc.storage_fallback(m, ("bfloat16", "float32"), 4, is_flagged, rerun)
+    assert storage == ["float16"] * 4 and tried == [[], [], [], []] and still == []
+    assert m.calls == [] and rounds == []                                       # no switch, no rerun, no restore
+
+
+def test_fallback_driver_walks_the_storages_with_the_units_still_flagged():
+    m = _FakeModel()
+    is_flagged, rerun, rounds = _scripted(m, {1: "bfloat16", 3: "float32", 4: "bfloat16", 5: "float32"})
+    storage, tried, still = Dc.storage_fallback(m, ("bfloat16", "float32"), 6, is_flagged, rerun)
+    assert rounds == [("bfloat16", "bfloat16", [1, 3, 4, 5]), ("float32", "float32", [3, 5])]     # exactly the still-flagged units
+    assert storage == ["float16", "bfloat16", "float16", "float32", "bfloat16", "float32"]
+    assert tried == [[], ["float16"], [], ["float16", "bfloat16"], ["float16"], ["float16", "bfloat16"]]
+    assert still == []
+    assert m.calls == ["bfloat16", "float32", "float16"] and m.activation_storage == "float16"    # restored, once, at the end
+    # everything cleared by the first fallback: the second is never switched to
+    m = _FakeModel()
+    is_flagged, rerun, rounds = _scripted(m, {0: "bfloat16"})
+    assert Dc.storage_fallback(m, ("bfloat16", "float32"), 2, is_flagged, rerun) == (["bfloat16", "float16"], [["float16"], []], [])
+    assert m.calls == ["bfloat16", "float16"] and len(rounds) == 1
+
+
+def test_fallback_driver_names_what_the_last_storage_left_flagged():
+    m = _FakeModel()
+    is_flagged, rerun, rounds = _scripted(m, {0: None, 2: "float32", 3: None})
+    storage, tried, still = Dc.storage_fallback(m, ("bfloat16", "float32"), 4, is_flagged, rerun)
+    assert still == [0, 3]
+    assert [storage[i] for i in still] == ["float32", "float32"]                # the last name tried
+    assert [tried[i] for i in still] == [["float16", "bfloat16"]] * 2
+    assert storage[1] == "float16" and storage[2] == "float32" and tried[1] == []
+    assert [r[2] for r in rounds] == [[0, 2, 3], [0, 2, 3]]
+    assert m.activation_storage == "float16"
+
+
+def test_fallback_driver_without_fallbacks_only_reports():
+    class Bare:                                                                 # (no switch at all: it must not be needed)
+        activation_storage = "float16"
+    is_flagged, rerun, rounds = _scripted(Bare(), {1: None})
+    assert Dc.storage_fallback(Bare(), (), 3, is_flagged, rerun) == (["float16"] * 3, [[], [], []], [1])
+    assert rounds == []
+
+
+def test_fallback_driver_restores_the_storage_when_a_rerun_raises():
+    m = _FakeModel()
+    is_flagged, rerun, rounds = _scripted(m, {0: None})
+
+    def failing(name, units):
+        rerun(name, units)
+        if len(rounds) == 2:
+            raise RuntimeError("the forward failed")
+    with pytest.raises(RuntimeError, match="the forward failed"):
+        Dc.storage_fallback(m, ("bfloat16", "float32"), 1, is_flagged, failing)
+    assert m.calls == ["bfloat16", "float32", "float16"] and m.activation_storage == "float16"
+
+
+def test_fallback_driver_takes_a_model_without_the_attribute_for_float32():
+    class M:
+        def __init__(self):
+            self.calls = []
+
+        def use_activation_storage(self, name):
+            self.calls.append(name)
+    m = M()
+    is_flagged, rerun, _ = _scripted(m, {1: "bfloat16"})
+    assert Dc.storage_fallback(m, ("bfloat16",), 2, is_flagged, rerun) == (["float32", "bfloat16"], [[], ["float32"]], [])
+    assert m.calls == ["bfloat16"]                  # (nothing says that the storage changed: nothing to restore)
+    assert Dc.storage_fallback(M(), ("bfloat16",), 2, lambda i: False, rerun)[0] == ["float32", "float32"]
+
+
+def test_batch_narrowing_reruns_every_flagged_unit_in_every_round():
+    """The ``rerun`` of the batch methods, as ``convert`` builds it: whole batches, chosen by ``flagged_batches`` among
+    those of the round before.  Whatever clears when, each round's batches hold every unit still flagged (a unit flagged
+    now was flagged in every earlier round, so its batch was run in every earlier round), hold nothing but batches
+    with a flagged unit, and name exactly the flagged units' positions."""
+    batches = [[4, 2], [0, 5], [1], [3, 6, 7]]
+    for clears in ({2: "bfloat16", 6: "float32", 7: None}, {0: None, 1: None}, {i: "float32" for i in range(8)},
+                   {5: "bfloat16"}, {4: "float32", 3: "bfloat16", 7: "float32", 1: "bfloat16"}):
+        m = _FakeModel()
+        is_flagged, mark, rounds = _scripted(m, clears)
+        runs = []
+
+        def run(work, mark=mark, runs=runs, m=m):
+            runs.append(work)
+            mark(m.activation_storage, [batches[k][j] for k, js in work for j in js])
+        storage, tried, still = Dc.storage_fallback(m, ("bfloat16", "float32"), 8, is_flagged, Dc._rerun_in_batches(batches, run))
+        expect = sorted(clears)                                                 # (the units flagged before each round)
+        for name, work in zip(("bfloat16", "float32"), runs):
+            assert [k for k, _ in work] == Dc.flagged_batches(batches, expect)
+            assert sorted(batches[k][j] for k, js in work for j in js) == expect
+            assert all(js for _, js in work)
+            expect = [i for i in expect if clears[i] != name]
+        assert len(runs) == (0 if not clears else 1 if all(v == "bfloat16" for v in clears.values()) else 2)
+        assert still == sorted(i for i, v in clears.items() if v is None)
+        for i in range(8):
+            assert storage[i] == ("float16" if i not in clears else clears[i] or "float32")
+
+
+def test_report_dicts_and_the_strict_error():
+    rep = np.array([[0, 2, np.float32(1.5).view(np.int32), 0], [3, 0, np.float32(0.25).view(np.int32), 0]], dtype=np.int32)
+    assert Dc._report_dicts(rep, ["float16", "bfloat16"], [[], ["float16"]]) == [
+        dict(storage="float16", nonfinite=0, clipped=2, max_abs=1.5, tried=[]),
+        dict(storage="bfloat16", nonfinite=3, clipped=0, max_abs=0.25, tried=["float16"])]
+    with pytest.raises(A.FastSVCError) as e:
+        Dc._raise_still_nonfinite(_FakeModel(), ("bfloat16",), "utterances", [1])
+    assert str(e.value) == "utterances [1] still have non-finite samples after storages ['float16', 'bfloat16'] (strict=True)"
 
 
 def test_checked_session_needs_a_gpu_like_the_unchecked_one():
