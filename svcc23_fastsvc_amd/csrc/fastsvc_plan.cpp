@@ -1953,6 +1953,57 @@ struct EventPair {                                     // (destroyed on every wa
     bool create() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
 };
 
+inline bool is_wino(int algo) { return algo == 1 || algo == 2; }
+
+// The candidate with this tile shape - and, with algo >= 0, this algorithm - or none.  (A route's candidates are distinct
+// in what is compared, so there is at most one.)
+const Cand* find_shape(const std::vector<Cand>& cands, int NW, int WM, int WN, int algo) {
+    const Cand* hit = nullptr;
+    for (const Cand& cd : cands)
+        if (cd.NW == NW && cd.WM == WM && cd.WN == WN && (algo < 0 || cd.algo == algo)) hit = &cd;
+    return hit;
+}
+
+// A loaded table may be stale: an entry's shape counts only where this launch is compiled for it (need_algo: with the
+// entry's algorithm) and its tiles per workgroup lie in 1..64.  What else an entry has to say is the calling route's rule.
+const Cand* match_table_shape(const std::vector<Cand>& cands, const fastsvc_plan::Choice& ch, bool need_algo) {
+    if (ch.tpw < 1 || ch.tpw > 64) return nullptr;
+    return find_shape(cands, ch.NW, ch.WM, ch.WN, need_algo ? ch.algo : -1);
+}
+
+// Columns of a candidate's tile (the Winograd variants produce output pairs), tiles per row of T columns, and the grid:
+// every `tpw` tiles of a row are one workgroup, `rows` = channel-group rows x signals x utterances
+inline int tile_columns(const Cand& cd) { return (is_wino(cd.algo) ? 32 : 16) * cd.NW * cd.WN; }
+inline long tiles_per_row(long T, const Cand& cd) { return (T + tile_columns(cd) - 1) / tile_columns(cd); }
+inline long workgroup_count(long ntx, int tpw, long rows) { return ((ntx + tpw - 1) / tpw) * rows; }
+
+// Compile-time epilogue kind of a pipelined 3-tap launch, by the launchers' own rule (launch_conv_pipe): 4 FiLM-affine
+// output and / or InstanceNorm sums, 3 rank-1 residual, 2 residual tensor, 1 plain - the stretched launches have 1 and 4
+// only; 0 for every other launch.  `p` as the caller describes the layer (a Winograd candidate is a MODE_DIRECT launch here).
+int epilogue_kind(const PackedConv& c, const ConvParams& p) {
+    const bool stretched = p.mode == MODE_STRETCH || p.mode == MODE_POLY;
+    if (c.ntaps != 3 || !(p.mode == MODE_DIRECT || stretched)) return 0;
+    if (p.flags & (F_STATS | F_AFF_OUT)) return 4;
+    return stretched ? 1 : p.r1x ? 3 : p.res ? 2 : 1;
+}
+
+// Kernel names of the profile records and of FASTSVC_VERBOSE_SHAPES: the template arguments of the instance that runs.
+// (tests/golden/launch_routes.json compares them byte for byte.)
+typedef char KernelName[48];
+// conv_hx<MW, NW, WM, WN, mode, epilogue kind, stretch factor, products[, tail]>; tail: the row-end (TAILK) instance
+void name_hx(KernelName& out, const ConvLaunch& L, int mode, int kind, int s, int storage, bool tail = false) {
+    std::snprintf(out, sizeof(out), "conv_hx<%d,%d,%d,%d,%d,%d,%d,%s%s>", L.MW, L.NW, L.WM, L.WN, mode, kind, s, prod_tag(storage),
+                  tail ? ",tail" : "");
+}
+void name_wx(KernelName& out, const ConvLaunch& L, int kind, int storage) {
+    std::snprintf(out, sizeof(out), "conv_wx<%d,%d,%d,%d,%d,%s>", L.MW, L.NW, L.WM, L.WN, kind, prod_tag(storage));
+}
+// (last argument: polyphase stretch / Winograd dilation)
+void name_mfma_ws(KernelName& out, const ConvLaunch& L, int mode, int ntaps, int kind, int s_or_dil) {
+    std::snprintf(out, sizeof(out), "conv_mfma_ws<%d,%d,%d,%d,%d,%d,%d,%d>", L.MW, L.NW, L.WM, L.WN, mode, ntaps, kind, s_or_dil);
+}
+void name_mfma(KernelName& out, const ConvLaunch& L) { std::snprintf(out, sizeof(out), "conv_mfma<%d,%d,1,4>", L.MW, L.NW); }
+
 // A tuning pass times every (shape, tiles-per-workgroup) on the device: one warm launch, then 3 timed ones.
 // `prepare(cd)` sets the candidate up and returns its tile count per row (a larger tpw changes nothing), `launch(tpw)`
 // launches it.  The first candidate wins a tie; best / best_tpw keep what they held when nothing was timed.
@@ -2002,6 +2053,22 @@ int time_separate(hipStream_t on, bool warm, RunFn&& run, double& ms_each) {
     return rc;
 }
 
+// A fused route against the separate launches it replaces.  In a tuning pass (time_it) the separate launches run first,
+// timed - that also tunes their own shapes - and `fused(sep_ms, done)` times its shapes against them; the launch table
+// keeps the winner.  What `fused` does not run (done = false) runs as `separate(pr)`.
+template <class FusedFn, class SeparateFn>
+int fused_or_separate(hipStream_t on, bool time_it, Profiler* pr, const char* layer, FusedFn&& fused, SeparateFn&& separate) {
+    double sep_ms = 0.0;
+    if (time_it) {
+        const int rc = time_separate(on, true, [&]() { return separate(nullptr); }, sep_ms);
+        if (rc != FASTSVC_OK) return rc;
+    }
+    bool done = false;
+    const hipError_t e = fused(sep_ms, done);
+    if (e != hipSuccess) return fail(FASTSVC_E_HIP, std::string(layer) + ": " + hipGetErrorString(e));
+    return done ? (int)FASTSVC_OK : separate(pr);
+}
+
 // A fused route has no table entry: tiles per workgroup such that the grid - ceil(ntx / tpw) * rows workgroups, in rounds
 // of 256 - fills the CUs about evenly (a workgroup costs a start of 4 plus 2 per tile and 32-channel chunk)
 int fill_tpw(long ntx, long rows, int nch32, int tpw_max) {
@@ -2025,6 +2092,52 @@ int cond_tpw(long ntx, int B, long slots) {
     // (per-utterance rounding: ceil(ntx / tpw) * B workgroups must not spill into one more round)
     while (tpw < ntx && ((ntx + tpw - 1) / tpw) * B > slots * rounds) ++tpw;
     return (int)std::min<long>(tpw, ntx);
+}
+
+// ---- what the two whole-stage conditioning launches share (Q: CondStage0Params / CondStage1Params) ----
+
+// The stage's c2 / c3 / FiLM conv of either signal and the K-concatenated heads: fragments of the storage's set, biases,
+// inverse weight scales, (l1, bmax) bounds behind the stage's first conv (bnd[0], the caller's), the per-channel bound tables
+template <class Q>
+void cond_fill_tables(Q& q, const float* blob, const DownStage& d, int prec) {
+    const PackedConv* layers[3] = {d.c2, d.c3, d.film};
+    for (int s = 0; s < 2; ++s) {
+        for (int l = 0; l < 3; ++l) {
+            q.w[l][s] = blob + layers[l][s].hx_off[prec];
+            q.bias[l][s] = blob + layers[l][s].b_off;
+            q.winv[l][s] = blob + layers[l][s].hx_inv_off;
+            q.bnd[l + 1][s] = blob + layers[l][s].bnd_off;
+        }
+        q.cbnd[s] = d.cbnd_off[s] ? blob + d.cbnd_off[s] : nullptr;
+    }
+    q.w5 = blob + d.heads.hx_off[prec]; q.b5 = blob + d.heads.b_off; q.winv5 = blob + d.heads.hx_inv_off;
+}
+
+// Tile variant of the phase kernel: short tiles (1) where the long ones (NTb columns) would leave CUs without a workgroup -
+// a batch below one round of the `slots` resident workgroups; FASTSVC_COND_SMALL says otherwise
+int cond_small_tiles(long T, int B, int NTb, long slots) {
+    return env().cond_small >= 0 ? env().cond_small : (((T + NTb - 1) / NTb) * B < slots ? 1 : 0);
+}
+
+// Whether the stage's layer pipeline may run: `mode` (FASTSVC_COND_PIPE: 0 never, 2 always - tests, A/B) unless a
+// launch-table entry "cond.<stage>|B|T[|b]" decides for this batch shape with algorithm 4 (phase kernel) / 5 (pipeline)
+int cond_pipe_mode(const fastsvc_plan& P, int stage, int B, long T, int mode) {
+    char key[96];
+    std::snprintf(key, sizeof(key), "cond.%d|%d|%ld%s", stage, B, T, key_suffix(P.storage));
+    fastsvc_plan::Choice ch;
+    if (table_entry(P, key, ch)) mode = ch.algo == 4 ? 0 : ch.algo == 5 ? 2 : mode;
+    return mode;
+}
+
+// Chunks (NTp columns) per workgroup of the layer pipeline, 0: the phase kernel runs.  ONE round of the 256 resident
+// workgroups (two rounds of half the run measured 1-3 % slower: tools/cond_pipe_tpw.sh), and only where that gives a
+// workgroup a run of at least `min_run` chunks to fill its pipeline over (pipe_mode 2: whatever the run)
+long cond_pipe_chunks(int pipe_mode, long T, int B, int NTp, long min_run) {
+    if (!pipe_mode || env().cond_small >= 0) return 0;
+    const long nchunks = (T + NTp - 1) / NTp;
+    const long per_utt = std::max<long>(1, 256L / B);
+    const long k = (nchunks + per_utt - 1) / per_utt;
+    return (k >= min_run || pipe_mode == 2) ? k : 0;
 }
 
 // The end of every route: the launch - bracketed by the profiler where the forward has one (kernel / flops / bytes are only
@@ -2102,20 +2215,17 @@ hipError_t run_chain(CallCtx& cc, const PackedConv& a, const PackedConv& c, cons
     Cand best = cands[0];
     fastsvc_plan::Choice ch;
     if (table_entry(*cc.plan, key, ch)) {
-        // (a shape only from an algorithm-3 entry)
         if (ch.algo != 3 && env().chain != 2) { have = true; fused = false; }      // FASTSVC_CHAIN=2: fused regardless (A/B)
-        for (const Cand& cd : cands)
-            if (ch.algo == 3 && cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && ch.tpw >= 1 && ch.tpw <= 64) {
-                best = cd; p.tpw = ch.tpw; have = true;
-            }
+        // (a shape only from an algorithm-3 entry)
+        if (const Cand* cd = ch.algo == 3 ? match_table_shape(cands, ch, true) : nullptr) { best = *cd; p.tpw = ch.tpw; have = true; }
     }
-    auto ntx_of = [&](const Cand& cd) { return (long)(p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN); };
+    const long rows = (long)nsig * p.B;
     if (!have && cc.tuning) {
         float best_ms = 1e30f;
         ConvParams q = p;                                  // (these trials run with the launch's own flags)
         ConvLaunch Lq{c.MW, 0, 0, 0, nsig, 2};
         hipError_t e = time_candidates(cands, stream, cc.trials,
-                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; return ntx_of(cd); },
+                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; return tiles_per_row(p.T, cd); },
                                        [&](int tpw) { q.tpw = tpw; return launch(q, Lq); }, best, p.tpw, best_ms);
         if (e != hipSuccess) return e;
         fused = sep_ms <= 0.0 || best_ms / 3.0 < sep_ms;
@@ -2123,12 +2233,12 @@ hipError_t run_chain(CallCtx& cc, const PackedConv& a, const PackedConv& c, cons
         have = true;
     }
     // no table entry: the widest tile that exists, workgroups sized so that the grid fills the CUs about evenly
-    if (!have) p.tpw = fill_tpw(ntx_of(best), (long)nsig * p.B, c.nch32, 16);
+    if (!have) p.tpw = fill_tpw(tiles_per_row(p.T, best), rows, c.nch32, 16);
     if (!fused) return hipSuccess;
     ConvLaunch L{c.MW, best.NW, best.WM, best.WN, nsig, 2};
     done = true;
     double flops = 0.0, bytes = 0.0;
-    char kname[48] = "";
+    KernelName kname = "";
     if (prof) {
         const double cols = (double)p.T * p.B * nsig;
         // (split input = the FiLM net: its first conv is block-diagonal over the two signals, half the dense count)
@@ -2137,10 +2247,9 @@ hipError_t run_chain(CallCtx& cc, const PackedConv& a, const PackedConv& c, cons
         if (p.res) el += (double)c.cout * p.T;
         if (p.r1x) el += (double)p.T;
         bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(a.w_floats + a.b_floats + c.w_floats + c.b_floats) * nsig;
-        std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,%d,%d,1,%s>", L.MW, L.NW, L.WM, L.WN, p.mode,
-                      p.r1x ? 3 : p.res ? 2 : 1, prod_tag(stg));
+        name_hx(kname, L, p.mode, p.r1x ? 3 : p.res ? 2 : 1, 1, stg);
     }
-    const long wgs = ((ntx_of(best) + p.tpw - 1) / p.tpw) * (long)nsig * p.B;
+    const long wgs = workgroup_count(tiles_per_row(p.T, best), p.tpw, rows);
     return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() { return launch(p, L); }, &p, &L, wgs, p.nch32);
 }
 
@@ -2189,13 +2298,13 @@ hipError_t run_uphead(const CallCtx& cc, const UpStage& u, const float* blob, Co
     if (!fused) return hipSuccess;
     done = true;
     double flops = 0.0, bytes = 0.0;
-    char kname[48] = "";
+    KernelName kname = "";
     if (prof) {
         const double cin = u.Cin, C = u.C, Ti = (double)p.x_T, To = Ti * u.scale;
         flops = (2.0 * 3.0 * cin * C * Ti + 2.0 * 2.0 * 3.0 * C * C * To) * p.B;
         bytes = 4.0 * (cin * Ti + 4.0 * C * To) * p.B +
                 4.0 * (double)(u.first.w_floats + u.res.w_floats + u.up.w_floats + 3 * u.res.b_floats);
-        std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,8,4,%d,x3>", L.MW, L.NW, L.WM, L.WN, u.scale);
+        name_hx(kname, L, MODE_UPHEAD, 4, u.scale, stg);
     }
     return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() { return launch_conv_hx(p, L, stream); });
 }
@@ -2247,10 +2356,8 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
         // (the shape whatever the entry's algorithm says)
         if (d3x_fused_algo(ch.algo)) x2_path = ch.algo;
         else if (env().d3x != 2) { have = true; fused = false; }
-        for (const Cand& cd : cands)
-            if (cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && ch.tpw >= 1 && ch.tpw <= 64) { best = cd; p.tpw = ch.tpw; have = true; }
+        if (const Cand* cd = match_table_shape(cands, ch, false)) { best = *cd; p.tpw = ch.tpw; have = true; }
     }
-    auto ntx_of = [&](const Cand& cd) { return (long)(p.T + 16 * cd.NW * cd.WN - 1) / (16 * cd.NW * cd.WN); };
     // how the staging waves fetch the second operand (F_X2_GATHER): through the raw LDS tile wherever the launch
     // qualifies and the stretch factor has it by default; a table entry says otherwise with algorithm 7 (element loads)
     // or 8 (the raw tile wherever the launch qualifies)
@@ -2264,7 +2371,7 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
         q.flags &= ~F_STATS;                               // (the trial launches do not accumulate InstanceNorm sums)
         ConvLaunch Lq{c.MW, 0, 0, 0, 1, 2};
         hipError_t e = time_candidates(cands, stream, cc.trials,
-                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; q.flags = (q.flags & ~F_X2_GATHER) | gather_for(cd); return ntx_of(cd); },
+                                       [&](const Cand& cd) { Lq.NW = cd.NW; Lq.WM = cd.WM; Lq.WN = cd.WN; q.flags = (q.flags & ~F_X2_GATHER) | gather_for(cd); return tiles_per_row(p.T, cd); },
                                        [&](int tpw) { q.tpw = tpw; return launch(q, Lq); }, best, p.tpw, best_ms);
         if (e != hipSuccess) return e;
         // (sep_ms times the two separate launches back to back on ONE stream; in production the residual conv runs on the side
@@ -2284,10 +2391,10 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
             if (cc.plan->prior_for(layer, p.B, p.T, act_2b, pr)) {
                 if (d3x_fused_algo(pr.algo)) x2_path = pr.algo;
                 else if (env().d3x != 2) fused = false;
-                for (const Cand& cd : cands) if (cd.NW == pr.NW && cd.WM == pr.WM && cd.WN == pr.WN) best = cd;
+                if (const Cand* cd = find_shape(cands, pr.NW, pr.WM, pr.WN, -1)) best = *cd;
             }
         }
-        p.tpw = fill_tpw(ntx_of(best), (long)(c.ngroups / best.WM) * p.B, c.nch32, 24);
+        p.tpw = fill_tpw(tiles_per_row(p.T, best), (long)(c.ngroups / best.WM) * p.B, c.nch32, 24);
     }
     if (!fused) return hipSuccess;
     done = true;
@@ -2295,15 +2402,15 @@ hipError_t run_d3x(CallCtx& cc, const UpStage& u, const float* blob, ConvParams 
     ConvLaunch L{c.MW, best.NW, best.WM, best.WN, 1, 2};
     p.flags = (p.flags & ~F_X2_GATHER) | gather_for(best);
     double flops = 0.0, bytes = 0.0;
-    char kname[48] = "";
+    KernelName kname = "";
     if (prof) {
         const double cols = (double)p.T * p.B;
         flops = 2.0 * 2.0 * 3.0 * c.cin * c.cout * cols;      // both convs at the OUTPUT rate, as the reference runs them
         const double el = (double)c.cin * p.T + (double)c.cin * p.x2_T + 4.0 * c.cout * p.T;   // u1, a | xmid, u2, scale, shift
         bytes = (act_2b ? 2.0 : 4.0) * el * p.B + 4.0 * 2.0 * (double)(c.w_floats + c.b_floats);
-        std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,0,4,%d,%s>", L.MW, L.NW, L.WM, L.WN, p.s2, prod_tag(stg));
+        name_hx(kname, L, MODE_DIRECT, 4, p.s2, stg);
     }
-    const long wgs = ((ntx_of(best) + p.tpw - 1) / p.tpw) * (long)(c.ngroups / L.WM) * p.B;
+    const long wgs = workgroup_count(tiles_per_row(p.T, best), p.tpw, (long)(c.ngroups / L.WM) * p.B);
     return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops, bytes, [&]() {
         // (the record of this launch: which way its second operand came, 2-byte storage at s2 = 4 / 5)
         if (prof && act_2b && (p.s2 == 4 || p.s2 == 5)) prof->recs.back().x2_path = (p.flags & F_X2_GATHER) ? 2 : 1;
@@ -2328,58 +2435,29 @@ hipError_t run_cond_stage0(const CallCtx& cc, const float* blob, const float* si
     q.x = sig; q.x_sig = sig_stride; q.x_b = T;
     q.B = B; q.C = d.C; q.T = (int)T; q.ld = (int)T;
     q.lens = lengths; q.len_mul = (int)(T / F);
-    const PackedConv* layers[3] = {d.c2, d.c3, d.film};
+    cond_fill_tables(q, blob, d, prec);
     for (int s = 0; s < 2; ++s) {
         q.in1_w[s] = blob + d.c1_raw[s].w_off; q.in1_b[s] = blob + d.c1_raw[s].b_off;
         q.r1w[s] = blob + d.r_raw[s].w_off; q.r1b[s] = blob + d.r_raw[s].b_off;
-        for (int l = 0; l < 3; ++l) {
-            q.w[l][s] = blob + layers[l][s].hx_off[prec];
-            q.bias[l][s] = blob + layers[l][s].b_off;
-            q.winv[l][s] = blob + layers[l][s].hx_inv_off;
-            q.bnd[l + 1][s] = blob + layers[l][s].bnd_off;
-        }
         q.bnd[0][s] = blob + d.c1_raw[s].bnd_off;
         q.bnd_r[s] = blob + d.r_raw[s].bnd_off;
-        q.cbnd[s] = d.cbnd_off[s] ? blob + d.cbnd_off[s] : nullptr;
     }
-    q.w5 = blob + d.heads.hx_off[prec]; q.b5 = blob + d.heads.b_off; q.winv5 = blob + d.heads.hx_inv_off;
     q.amax_in = P.storage == 0 ? amax_in : nullptr; q.amax_hd = P.storage == 0 ? amax_hd : nullptr;
     q.ss = ss; q.ss_b = 2L * d.C * T;
     q.hd = hd; q.hd_ld = (int)(T / d1.scale); q.hd_s = d1.scale;
     q.hd_b = (long)d.C * q.hd_ld; q.hd_sig = (long)B * q.hd_b;
-    // short tiles where the long ones would leave CUs without a workgroup (a batch below one round of them)
     const long slots_all = P.storage != 0 ? 512 : 256;     // workgroups resident at a time (LDS: two per CU in 2-byte storage, one in float32)
-    {
-        const int NTb = cond_stage0_tile_columns(0);
-        q.small = env().cond_small >= 0 ? env().cond_small : (((T + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
-    }
+    q.small = cond_small_tiles(T, B, cond_stage0_tile_columns(0), slots_all);
     // The layer pipeline (cond_stage0_pipe_kernel; q.small = 2, tpw = chunks per workgroup) where a workgroup gets a long
-    // run of chunks - its fill costs 5 + 8 / N steps -: one or two rounds of the 256 resident workgroups (one per CU).
-    // FASTSVC_COND_PIPE = 0: never, 2: always (tests, A/B); a launch-table entry "cond.0|B|T[|b]" with algorithm 4
-    // (phase kernel) / 5 (pipeline) decides for one batch shape.
-    int pipe_mode = env().cond_pipe;
-    {
-        char key[96];
-        std::snprintf(key, sizeof(key), "cond.0|%d|%ld%s", B, (long)T, key_suffix(P.storage));
-        fastsvc_plan::Choice ch;
-        if (table_entry(P, key, ch)) pipe_mode = ch.algo == 4 ? 0 : ch.algo == 5 ? 2 : pipe_mode;
+    // run of chunks - its fill costs 5 + 8 / N steps: from 24 chunks.
+    // (the pipeline addresses both signals' hd rows of an utterance through ONE 32-bit-offset descriptor)
+    const bool hd_fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * (P.storage != 0 ? 2L : 4L) < (1L << 31);
+    const long kc = cond_pipe_chunks(cond_pipe_mode(P, 0, B, T, env().cond_pipe), T, B, cond_stage0_tile_columns(P.storage != 0 ? 3 : 2), 24);
+    if (kc && hd_fits) { q.small = 2; q.tpw = (int)std::min<long>(env().cond_tpw > 0 ? env().cond_tpw : kc, 0xffff); }
+    if (q.small != 2) {
+        const int NT = cond_stage0_tile_columns(q.small);
+        q.tpw = env().cond_tpw > 0 ? env().cond_tpw : cond_tpw((T + NT - 1) / NT, B, slots_all);
     }
-    if (pipe_mode && env().cond_small < 0) {
-        const int NTp = cond_stage0_tile_columns(P.storage != 0 ? 3 : 2);
-        const long nchunks = (T + NTp - 1) / NTp;
-        long kc = 0;
-        {   // ONE round of the 256 resident workgroups (two rounds of half the run measured 1-3 % slower: tools/cond_pipe_tpw.sh)
-            const long per_utt = std::max<long>(1, 256L / B);
-            const long k = (nchunks + per_utt - 1) / per_utt;
-            if (k >= 24 || pipe_mode == 2) kc = k;
-        }
-        // (the pipeline addresses both signals' hd rows of an utterance through ONE 32-bit-offset descriptor)
-        const bool hd_fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * (P.storage != 0 ? 2L : 4L) < (1L << 31);
-        if (kc && hd_fits) { q.small = 2; q.tpw = (int)std::min<long>(env().cond_tpw > 0 ? env().cond_tpw : kc, 0xffff); }
-    }
-    const int NT = q.small == 2 ? 0 : cond_stage0_tile_columns(q.small);
-    const long ntx = q.small == 2 ? 0 : (T + NT - 1) / NT;
-    if (q.small != 2) q.tpw = env().cond_tpw > 0 ? env().cond_tpw : cond_tpw(ntx, B, slots_all);
     q.tpw |= env().cond_dbg << 16;
     static unsigned long long* trace_buf = nullptr;
 #ifdef FASTSVC_COND_TRACE
@@ -2436,55 +2514,29 @@ hipError_t run_cond_stage1(const CallCtx& cc, const float* blob, const float* x,
     q.x = x; q.ldx = (int)T1; q.x_b = (long)d.Cin * T1; q.x_sig = (long)B * q.x_b;
     q.B = B; q.C = d.C; q.Cin = d.Cin; q.T = (int)T1; q.ld = (int)T1;
     q.lens = lengths; q.len_mul = (int)(T1 / F);
-    const PackedConv* layers[3] = {d.c2, d.c3, d.film};
+    cond_fill_tables(q, blob, d, prec);
     for (int s = 0; s < 2; ++s) {
         q.w1[s] = blob + d.rc1[s].hx_off[prec]; q.b1[s] = blob + d.rc1[s].b_off; q.br[s] = blob + d.rc1[s].b2_off;
         q.winv1[s] = blob + d.rc1[s].hx_inv_off;
-        for (int l = 0; l < 3; ++l) {
-            q.w[l][s] = blob + layers[l][s].hx_off[prec];
-            q.bias[l][s] = blob + layers[l][s].b_off;
-            q.winv[l][s] = blob + layers[l][s].hx_inv_off;
-            q.bnd[l + 1][s] = blob + layers[l][s].bnd_off;
-        }
         q.bnd[0][s] = blob + d.c1[s].bnd_off;
         q.bnd_r[s] = blob + d.r[s].bnd_off;
-        q.cbnd[s] = d.cbnd_off[s] ? blob + d.cbnd_off[s] : nullptr;
     }
-    q.w5 = blob + d.heads.hx_off[prec]; q.b5 = blob + d.heads.b_off; q.winv5 = blob + d.heads.hx_inv_off;
     q.amax_in = P.storage == 0 ? amax_in : nullptr; q.amax_hd = P.storage == 0 ? amax_hd : nullptr;
     q.ss = ss; q.ss_b = 2L * d.C * T1;
     q.hd = hd; q.hd_ld = (int)(T1 / d2.scale); q.hd_s = d2.scale;
     q.hd_b = (long)d.C * q.hd_ld; q.hd_sig = (long)B * q.hd_b;
-    // short tiles where the long ones would leave CUs without a workgroup (a batch below one round of them)
     const long slots_all = P.storage != 0 ? 512 : 256;
-    {
-        const int NTb = cond_stage1_tile_columns(0);
-        q.small = env().cond_small >= 0 ? env().cond_small : (((T1 + NTb - 1) / NTb) * B < slots_all ? 1 : 0);
-    }
+    q.small = cond_small_tiles(T1, B, cond_stage1_tile_columns(0), slots_all);
     // the layer pipeline (cond_stage1_pipe_kernel, 2-byte storage only; q.small = 2, tpw = 32-column chunks per workgroup):
-    // its fill is 11 steps, so only for long runs; "cond.1|B|T1|b" ("|h") in the launch table forces either (algorithm 4 / 5)
-    int pipe_mode = P.storage != 0 ? env().cond_pipe : 0;
-    if (P.storage != 0) {
-        char key[96];
-        std::snprintf(key, sizeof(key), "cond.1|%d|%ld%s", B, (long)T1, key_suffix(P.storage));
-        fastsvc_plan::Choice ch;
-        if (table_entry(P, key, ch)) pipe_mode = ch.algo == 4 ? 0 : ch.algo == 5 ? 2 : pipe_mode;
+    // its fill is 11 steps, so only for runs from 16 chunks (8 x 600 frames, 19 chunks each: 58 vs 94 us for the phase kernel)
+    const int pipe_mode = P.storage != 0 ? cond_pipe_mode(P, 1, B, T1, env().cond_pipe) : 0;
+    const bool fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * 2L < (1L << 31) && (long)d.Cin * T1 * 2L < (1L << 31);
+    const long kc = cond_pipe_chunks(pipe_mode, T1, B, cond_stage1_tile_columns(2), 16);
+    if (kc && fits) { q.small = 2; q.tpw = (int)std::min<long>(env().cond1_tpw > 0 ? env().cond1_tpw : kc, 0xffff); }
+    if (q.small != 2) {
+        const int NT = cond_stage1_tile_columns(q.small);
+        q.tpw = env().cond1_tpw > 0 ? env().cond1_tpw : cond_tpw((T1 + NT - 1) / NT, B, slots_all);
     }
-    if (pipe_mode && env().cond_small < 0) {
-        const int NTp = cond_stage1_tile_columns(2);
-        const long nchunks = (T1 + NTp - 1) / NTp;
-        long kc = 0;
-        {
-            const long per_utt = std::max<long>(1, 256L / B);
-            const long k = (nchunks + per_utt - 1) / per_utt;
-            if (k >= 16 || pipe_mode == 2) kc = k;          // (8 x 600 frames, 19 chunks each: 58 vs 94 us for the phase kernel)
-        }
-        const bool fits = ((long)B * q.hd_b + (long)d.C * q.hd_ld) * 2L < (1L << 31) && (long)d.Cin * T1 * 2L < (1L << 31);
-        if (kc && fits) { q.small = 2; q.tpw = (int)std::min<long>(env().cond1_tpw > 0 ? env().cond1_tpw : kc, 0xffff); }
-    }
-    const int NT = q.small == 2 ? 0 : cond_stage1_tile_columns(q.small);
-    const long ntx = q.small == 2 ? 0 : (T1 + NT - 1) / NT;
-    if (q.small != 2) q.tpw = env().cond1_tpw > 0 ? env().cond1_tpw : cond_tpw(ntx, B, slots_all);
     done = true;
     double flops = 0.0, bytes = 0.0;
     std::string kname;
@@ -2500,18 +2552,332 @@ hipError_t run_cond_stage1(const CallCtx& cc, const float* blob, const float* x,
                        [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage1)(q, stream); });
 }
 
+// ---- run_conv: one convolution (or lft / sine pair) as one launch, step by step ----
+
+hipError_t launch_any(int stg, const ConvParams& q, const ConvLaunch& Lq, hipStream_t st) {
+    if (Lq.pipe == 3) return FASTSVC_BY_STORAGE(stg, launch_conv_wx)(q, Lq, st);
+    if (Lq.pipe == 2) return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, st);
+    return FASTSVC_BY_STORAGE(stg, launch_conv)(q, Lq, st);
+}
+
+// The launch of a candidate: kernel family by algorithm, the 32-channel Winograd grouping with its own tile count
+ConvLaunch launch_of(const Cand& cd, int MW, int nsig) {
+    return ConvLaunch{cd.algo == 2 ? 2 : MW, cd.NW, cd.WM, cd.WN, nsig, cd.algo == 6 ? 3 : cd.algo == 3 ? 2 : 1};
+}
+
+// What the launch may run as, and the facts the later steps need
+struct ConvCands {
+    std::vector<Cand> list;
+    int epi_kind = 0;            // epilogue_kind of the launch
+    bool hx_ok = false;          // the half-precision MFMA variants exist for this call
+    bool wino_ok = false;        // ... the Winograd variants
+    bool wx_force = false;       // FASTSVC_WX=2 and the layer has a shape of the wide-layer kernel: nothing else runs
+    bool last_ok = false;        // p.last_w: the list is cut down to the instances that compute conv_last as well
+};
+
+// The pipelined launches' candidate shapes: the f32-input MFMA kernel's by channel-group count, the Winograd, half-precision
+// and wide-layer variants where this call qualifies, then what conv_last and rows with a ragged end leave of them.
+// `p` describes the launch (run_conv) up to its shape.
+ConvCands conv_candidates(const CallCtx& cc, const PackedConv& c, const ConvParams& p) {
+    ConvCands cs;
+    std::vector<Cand>& cands = cs.list;
+    const bool poly = p.mode == MODE_POLY;
+    const bool act_2b = cc.storage != 0;
+    const int epi_kind = cs.epi_kind = epilogue_kind(c, p);
+    if (poly) {
+        if (c.MW == 3 && c.ngroups % 2 == 0) cands = {{1, 2, 2}, {1, 1, 4}};
+        else if (c.MW == 3) cands = {{1, 1, 4}};
+        else cands = {{2, 1, 4}, {1, 1, 4}};
+    }
+    else if (c.MW == 3 && c.ngroups % 4 == 0) cands = {{4, 4, 1}, {2, 4, 1}, {4, 2, 2}, {2, 2, 2}, {1, 2, 2}, {4, 1, 4}, {2, 1, 4}, {1, 1, 4}};
+    else if (c.MW == 3 && c.ngroups % 2 == 0) cands = {{4, 2, 2}, {2, 2, 2}, {1, 2, 2}, {4, 1, 4}, {2, 1, 4}, {1, 1, 4}};
+    else cands = {{4, 1, 4}, {2, 1, 4}, {1, 1, 4}};
+    if (p.mode == MODE_DEC2) {                      // two accumulator sets: compiled for NW <= 2
+        std::vector<Cand> keep;
+        for (const Cand& cd : cands) if (cd.NW <= 2) keep.push_back(cd);
+        cands.swap(keep);
+    }
+    // Winograd F(2,3) variants of the same launch (fastsvc_kernels.h, MODE_WINO)
+    const bool wino_ok = cs.wino_ok = c.wino && env().wino != 0 && p.mode == MODE_DIRECT && (!p.r1x || c.MW == 2) &&
+                                      !(p.flags & (F_STATS | F_AFF_OUT | F_PRE_AFFINE));
+    if (wino_ok) {
+        const size_t nd = cands.size();
+        for (size_t i = 0; i < nd; ++i)
+            if (cands[i].NW <= (c.MW == 2 ? 1 : 2)) cands.push_back(Cand{cands[i].NW, cands[i].WM, cands[i].WN, 1});
+        if (c.wino2) {
+            const int ng2 = c.cout / 32;
+            cands.push_back(Cand{1, 1, 4, 2});
+            if (ng2 % 2 == 0) cands.push_back(Cand{1, 2, 2, 2});
+            if (ng2 % 4 == 0) cands.push_back(Cand{1, 4, 1, 2});
+        }
+    }
+    // Half-precision MFMA variants (split-half f16 products in float32 storage, bf16 products in bfloat16
+    // storage): FASTSVC_HX=0 switches them off (A/B), they need rows that are a multiple of 4 long
+    const bool hx_mode = (p.mode == MODE_DIRECT && p.x_T == p.T) || (p.mode == MODE_POLY && c.hxp_off[0]) ||
+                         (p.mode == MODE_DEC2 && (p.x_T & 3) == 0);
+    // ragged batch whose rows run at the frame rate or twice it (len_mul 1 or 2): an utterance's own row length
+    // need not be a multiple of 4.  The TAILK instances handle that (producers zero what lies past the row end
+    // after the prologue, epilogues keep it out of the sums) as long as the row PITCHES are a multiple of 4
+    const bool ragged_tail = p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0);
+    const bool hx_tail_ok = !ragged_tail || ((p.ldx & 3) == 0 && (p.ldy & 3) == 0 &&
+                                             conv_hx_tail_ok(p.mode, c.MW, epi_kind, poly ? p.s : 1));
+    const bool hx_ok = cs.hx_ok = env().hx != 0 && !p.no_hx && !cc.exact_f32 && c.hx && hx_mode && c.ntaps == 3 && (p.T & 3) == 0 &&
+                                  c.dil <= 28 && !(p.flags & F_PRE_AFFINE) && hx_tail_ok;
+    if (hx_ok) {
+        static const int shapes[][3] = {{8, 4, 1}, {4, 4, 1}, {6, 2, 2}, {4, 2, 2}, {2, 2, 2}, {3, 1, 4}, {2, 1, 4}};
+        for (const auto& sh : shapes)
+            if (conv_hx_shape(p.mode, c.MW, sh[0], sh[1], sh[2]) && c.ngroups % sh[1] == 0 &&
+                !(p.mode == MODE_DIRECT && epi_kind >= 3 && sh[0] * c.MW > 12))   // FiLM-affine / rank-1 epilogues: those tiles spill
+                cands.push_back(Cand{sh[0], sh[1], sh[2], 3});
+    }
+    // The wide-layer kernel (fastsvc_wx.hip, algorithm 6): every wave multiplies, weights through LDS.  Direct launches of
+    // the 48-channel-group layers (C >= 96) in bfloat16 storage with a plain / residual / FiLM-affine epilogue.
+    // FASTSVC_WX = 0: off, 2: wherever it exists (A/B, tests), else by the launch table / tuning
+    ConvParams pw = p;
+    pw.nch32 = c.nch32;                              // (what conv_geometry sets for the candidate)
+    const bool wx_ok = hx_ok && env().wx != 0 && act_2b && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
+                       conv_wx_supported(pw);
+    bool wx_have = false;                            // ... and the layer has a shape of it
+    if (wx_ok) {
+        static const int wshapes[][3] = {{6, 4, 2}};
+        for (const auto& sh : wshapes)
+            if (conv_wx_shape(p.mode, c.MW, sh[0], sh[1], sh[2]) && c.ngroups % sh[1] == 0 && conv_wx_fits(c.nch32, c.dil)) {
+                cands.push_back(Cand{sh[0], sh[1], sh[2], 6});
+                wx_have = true;
+            }
+    }
+    cs.wx_force = env().wx == 2 && wx_have;
+    if (p.last_w) {
+        // conv_last rides on the half-precision instances with one workgroup row of channel groups; it saves a
+        // launch and a write + read of the block's output, more than any shape of the other family wins back:
+        // only those candidates, timed as they will run (no store of the C-channel tensor)
+        std::vector<Cand> keep;
+        if (hx_ok && c.ngroups == 1 && p.mode == MODE_DIRECT && p.res && !p.r1x && !(p.flags & (F_STATS | F_AFF_OUT)))
+            for (const Cand& cd : cands) if (cd.algo == 3 && cd.WM == 1) keep.push_back(cd);
+        if (!keep.empty()) { cands.swap(keep); cs.last_ok = true; }
+    }
+    if ((p.T & 3) != 0 || (p.lens && (p.len_mul & 3) != 0)) {
+        // rows that are not a multiple of 4 long (with a ragged batch: ANY utterance's own length,
+        // whatever the padded maximum is): only the variants compiled with the row-end handling
+        std::vector<Cand> keep;
+        for (const Cand& cd : cands)
+            if (cd.algo == 6 ? false : cd.algo == 3 ? (p.T & 3) == 0 :            // (hx candidates are only there when hx_tail_ok)
+                conv_ws_tail_ok(cd.algo == 2 ? 2 : c.MW, cd.NW, is_wino(cd.algo) ? (int)MODE_WINO : p.mode, epi_kind,
+                                poly ? p.s : 1)) keep.push_back(cd);
+        if (!keep.empty()) cands.swap(keep);       // (never empty: NW <= 2 variants always have it)
+    }
+    return cs;
+}
+
+inline int round_to(int v, int rem, int mod) { int r = v / mod * mod + rem; return r < v ? r + mod : r; }
+
+// What a candidate adds to the launch's parameters: the weights of its format and the LDS geometry - row stride (== 16
+// mod 32) and, for Winograd, the phase-plane stride that keeps the component reads conflict-free (planes land 16/D banks
+// apart).  q: the launch as described for the layer; a Winograd candidate turns it into a MODE_WINO launch.
+void conv_geometry(const Cand& cd, const PackedConv& c, const float* blob, int stg, ConvParams& q) {
+    if (cd.algo == 3 || cd.algo == 6) {
+        const int prec = stg;                   // fragment set = storage
+        const bool poly = q.mode == MODE_POLY;
+        q.whx = blob + (poly ? c.hxp_off[prec] : c.hx_off[prec]); q.whx_sig = c.hx_pair[prec]; q.nch32 = c.nch32;
+        const size_t inv_off = poly ? c.hxp_inv_off : c.hx_inv_off;
+        q.whx_inv = (prec == 0 && inv_off) ? blob + inv_off : nullptr; q.whx_inv_sig = c.hx_inv_pair;
+        q.stagger = env().stagger;
+        q.xs = 0; q.ps = 0;
+    } else if (cd.algo >= 1) {
+        const int NTo = 32 * cd.NW * cd.WN, D = c.dil;
+        const int Q = (NTo + 16) / (2 * D);
+        const int ps = D == 1 ? (Q + 1) / 2 * 2 : D == 2 ? round_to(Q, 8, 32) : round_to(Q, 12, 32);
+        q.ps = ps;
+        q.xs = round_to(2 * D * ps, 16, 32);
+        q.mode = MODE_WINO; q.Q = c.Qw;
+        if (cd.algo == 2) { q.w = blob + c.ww2_off; q.w_sig = c.ww2_pair; q.ngroups = c.cout / 32; }
+        else { q.w = blob + c.ww_off; q.w_sig = c.ww_pair; }
+    } else {
+        const int halo = c.ntaps == 3 ? c.dil : 0;
+        const int W = 16 * cd.NW * cd.WN + 2 * ((halo + 3) & ~3);
+        q.xs = (W + 15) / 32 * 32 + 16;
+        q.ps = 0;
+    }
+}
+
+// A tuning pass: every (shape, tiles-per-workgroup) timed on the device; the InstanceNorm sums are not accumulated by the
+// trial launches (the real launch does that once).  FASTSVC_WX=2: only the wide-layer kernel's shapes.
+hipError_t conv_tune(CallCtx& cc, const PackedConv& c, const float* blob, const ConvParams& p, int nsig, const ConvCands& cs,
+                     hipStream_t stream, Cand& best, int& best_tpw) {
+    std::vector<Cand> trial;
+    for (const Cand& cd : cs.list)
+        if (!(cs.wx_force && cd.algo != 6)) trial.push_back(cd);
+    float best_ms = 1e30f;
+    ConvParams q = p;
+    ConvLaunch Lq{};
+    return time_candidates(trial, stream, cc.trials,
+        [&](const Cand& cd) {
+            q = p; q.flags &= ~F_STATS;
+            conv_geometry(cd, c, blob, cc.storage, q);
+            Lq = launch_of(cd, c.MW, nsig);
+            return tiles_per_row(p.T, cd);
+        },
+        [&](int tpw) { q.tpw = tpw; return launch_any(cc.storage, q, Lq, stream); }, best, best_tpw, best_ms);
+}
+
+// No entry for this (B, T): the tile shape and algorithm of the table entry of this layer with the nearest
+// problem size, where one exists and this launch is compiled for it - a layer's best shape moves slowly with
+// the size (the tuned tables agree on it across batch shapes far more often than the model below finds it:
+// tools/costmodel_gap.py) - and only the tiles per workgroup from the model.  True: `cands` is cut down to that shape.
+bool conv_prior(const fastsvc_plan& P, const char* key, const char* layer, const ConvParams& p, bool act_2b, std::vector<Cand>& cands) {
+    fastsvc_plan::Choice pr{0, 0, 0, 0, -1};
+    {
+        std::lock_guard<std::mutex> lock(P.tune_mu);
+        auto it = P.priors.find(key);
+        if (it != P.priors.end()) pr = it->second;
+        else {
+            if (!P.prior_for(layer, p.B, p.T, act_2b, pr)) pr.algo = -1;
+            P.priors[key] = pr;
+        }
+    }
+    const Cand* cd = pr.algo >= 0 ? find_shape(cands, pr.NW, pr.WM, pr.WN, pr.algo) : nullptr;
+    if (!cd) return false;
+    const Cand only = *cd;
+    cands.assign(1, only);
+    return true;
+}
+
+// ---- the cost models: a workgroup costs a fixed start-up (launch, slot set-up, first window in flight) plus tpw * k
+// units, a unit being bounded by the consumer wave's MFMA stream or by the producers' window traffic; the grid runs in
+// ceil(workgroups / resident slots) rounds ----
+struct ModelPick { double t; int tpw; };               // tpw 0: nothing of the candidate beat the bar
+
+// Tiles per workgroup 1..tpw_max under that model.  `bar`: the best time so far, of any candidate; a count wins only by more
+// than 0.1 % - over the bar, then over the earlier counts: the first of equals stays, across candidates in list order.
+ModelPick scan_tpw(long ntx, long rows, long slots, int k, double unit_us, int tpw_max, double bar) {
+    ModelPick best{bar, 0};
+    for (int tpw = 1; tpw <= tpw_max; ++tpw) {
+        const long wgs = workgroup_count(ntx, tpw, rows);
+        const long rounds = (wgs + slots - 1) / slots;
+        const double t = rounds * (env().startup_us + tpw * k * unit_us);
+        if (t < best.t * 0.999) best = ModelPick{t, tpw};
+    }
+    return best;
+}
+
+// Half-precision MFMA kernels - a data-movement model: one workgroup per CU; a unit moves its window in and (per tile) its
+// outputs; the matrix work (3 taps x NW x MW x 1|3 products of 16 cycles) hides under it
+ModelPick model_hx(const PackedConv& c, const ConvParams& p, const Cand& cd, long zb, bool act_2b, double bar) {
+    const bool poly = p.mode == MODE_POLY;
+    const int halo = c.ntaps == 3 ? c.dil : 0;
+    const int NT = tile_columns(cd);
+    const long gy = c.ngroups / cd.WM;
+    const double win = NT + 2.0 * ((halo + 3) & ~3);
+    const double esz = act_2b ? 2.0 : 4.0;
+    const double out_streams = (p.y ? 1 : 0) + ((p.flags & F_AFF_OUT) ? 3 : 0) + (p.res ? 1 : 0);
+    const double bytes_unit = 32.0 * win * esz + 16.0 * c.MW * cd.WM * NT * (poly ? p.s : 1) * esz *
+                              (out_streams + (p.mode == MODE_DEC2 ? 1 : 0)) / c.nch32;
+    const double mem_us = bytes_unit / (4.5e6 / 256.0);
+    const double mfma_us = (poly ? 5.0 : p.mode == MODE_DEC2 ? 4.0 : 3.0) * cd.NW * c.MW * (act_2b ? 1 : 3) * 17.0 / 2.0e3;
+    const double unit_us = mem_us > mfma_us ? mem_us : mfma_us;
+    return scan_tpw(tiles_per_row(p.T, cd), gy * zb, 256, c.nch32, unit_us, 24, bar);
+}
+
+// f32-input MFMA kernel and its Winograd variants: MFMA stream of one consumer wave vs bytes the 256 producer threads move
+// vs the packed weights the consumer waves stream from L2
+ModelPick model_ws(const PackedConv& c, const ConvParams& p, const Cand& cd, long zb, int epi_kind, double bar) {
+    const bool poly = p.mode == MODE_POLY;
+    const int halo = c.ntaps == 3 ? c.dil : 0;
+    const int NT = tile_columns(cd);
+    const int cMW = cd.algo == 2 ? 2 : c.MW;
+    const long gy = ((cd.algo == 2 ? c.cout / 32 : c.ngroups) + cd.WM - 1) / cd.WM;
+    const int resident = conv_ws_resident(cMW, cd.NW, cd.algo >= 1 ? (int)MODE_WINO : p.mode, epi_kind);   // VGPR budget, see the kernel
+    const long slots = 256L * resident;
+    const double mfma_us = 6.0 * (cd.algo >= 1 ? 4 : c.ntaps) * cd.NW * cMW * 32.0 / 2.2e3;
+    const double win = NT + 2.0 * ((halo + 3) & ~3);
+    const double bytes_unit = c.KC * win * 4.0 + (double)16 * cMW * cd.WM * NT * (poly ? p.s : 1) * 4.0 *
+                              ((p.y ? 1 : 0) + ((p.flags & F_AFF_OUT) ? 3 : 0) + (p.res ? 1 : 0)) / c.nchunks;
+    const double mem_us = bytes_unit / (5.0e6 / 256.0 / resident);    // ~5 TB/s shared by all slots
+    // packed weights streamed from L2 by the four consumer waves (per unit, per workgroup):
+    // ~16 TB/s of L2 shared by all resident workgroups; this is what punishes small NW
+    const double wbytes_unit = 4.0 * 6.0 * c.ntaps * 64.0 * cMW * 4.0;
+    const double l2_us = wbytes_unit / (16.0e6 / 256.0 / resident);
+    double unit_us = mfma_us > mem_us ? mfma_us : mem_us;
+    if (l2_us > unit_us) unit_us = l2_us;
+    unit_us /= (resident == 2 ? 1.6 : 1.0);
+    return scan_tpw(tiles_per_row(p.T, cd), gy * zb, slots, c.nchunks, unit_us, 16, bar);
+}
+
+// Neither table nor tuning: shape and tiles per workgroup from the models, candidates in list order.  Which family is
+// modelled at all: the half-precision MFMA variant wherever the layer has one; else Winograd wherever the layer has it, the
+// 32-channel grouping (two workgroups per CU) when that exists - measured better than direct on cfg1 and cfg2 (0.56 vs
+// 0.62 ms, 2.24 vs 2.32 ms) - while C = 24 layers (MW == 2) stay direct: their Winograd variant loses to the scalar
+// phase-plane staging.  FASTSVC_WINO = 0 / 1 / 2 forces direct / layer grouping / 32-channel grouping.  A prior's shape
+// (prior_pick) is modelled whatever its family.
+void conv_model_pick(const PackedConv& c, const ConvParams& p, const ConvCands& cs, bool prior_pick, long zb, bool act_2b,
+                     Cand& best, int& best_tpw) {
+    const int wino_pref = env().wino >= 0 ? env().wino : (c.MW == 2 ? 0 : 2);
+    double best_t = 1e30;
+    for (const Cand& cd : cs.list) {
+        if (cd.algo == 6) {
+            // no model of its own: taken by table / prior, or wherever it exists with FASTSVC_WX=2 (first shape that fits,
+            // one round of workgroups where the batch allows)
+            if (!(prior_pick || cs.wx_force)) continue;
+            const long ntx = tiles_per_row(p.T, cd);
+            const long gy = c.ngroups / cd.WM;
+            int tpw = 1;
+            while (tpw < 64 && workgroup_count(ntx, tpw, gy * zb) > 256) ++tpw;
+            if (best_t > 0.0) { best_t = 0.0; best = cd; best_tpw = tpw; }
+            continue;
+        }
+        if (cs.wx_force) continue;
+        if (!prior_pick && cs.hx_ok != (cd.algo == 3)) continue;
+        if (cd.algo != 3 && !prior_pick) {
+            if ((cd.algo >= 1) != (cs.wino_ok && wino_pref >= 1)) continue;
+            if (wino_pref >= 1 && cs.wino_ok && c.wino2 && (cd.algo == 2) != (wino_pref == 2)) continue;
+        }
+        const ModelPick m = cd.algo == 3 ? model_hx(c, p, cd, zb, act_2b, best_t) : model_ws(c, p, cd, zb, cs.epi_kind, best_t);
+        if (m.tpw) { best_t = m.t; best = cd; best_tpw = m.tpw; }
+    }
+}
+
+// Profile record of the launch: algorithmic work of the layer as the reference defines it (3 taps at the OUTPUT rate for
+// the stretched convs, whichever way they are computed) and the bytes its tensors and weights come to
+void conv_account(const PackedConv& c, const ConvParams& p, long T_out, int nsig, bool act_2b, double& flops, double& bytes) {
+    const double cols = (double)T_out * p.B * nsig;
+    flops = 2.0 * (c.dec2 ? 4 : c.ntaps) * c.cin * c.cout * cols;    // DEC2: k=3 conv + 1x1
+    double in_cols = (double)T_out;                     // source columns actually needed
+    if (p.mode == MODE_STRETCH || p.mode == MODE_POLY) in_cols = (double)p.x_T;
+    double el = (double)c.cin * in_cols;
+    if (p.y) el += (double)c.cout * T_out;
+    if (p.mode == MODE_DEC2 && p.y2) el += (double)c.cout * T_out;     // the decimating pair's second output (the 1x1 residual conv's)
+    if (p.flags & F_AFF_OUT) el += (double)c.cout * T_out;
+    if (p.flags & F_PRE_AFFINE) el += 2.0 * c.cin * T_out;
+    if (p.res) el += (double)c.cout * T_out;
+    if (p.r1x) el += (double)T_out;
+    if (p.flags & (F_STATS | F_AFF_OUT)) el += 2.0 * c.cout * T_out;
+    bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(c.w_floats + c.b_floats) * nsig;
+    if (p.last_w) {                                   // + conv_last: C -> 1, float32 waveform out (the C-channel tensor is not written: p.y is null)
+        flops += 2.0 * c.cout * cols;
+        bytes += 4.0 * cols;
+    }
+}
+
+// ... and its kernel name, by family.  poly / epi_kind: of the launch as described for the layer (p.mode may be MODE_WINO by now)
+void conv_name(KernelName& out, const ConvLaunch& L, const PackedConv& c, const ConvParams& p, bool poly, int epi_kind, int stg) {
+    if (L.pipe == 3) name_wx(out, L, epi_kind, stg);
+    else if (L.pipe == 2)
+        name_hx(out, L, p.mode, p.mode == MODE_DEC2 ? 1 : epi_kind, poly ? p.s : 1, stg,
+                p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0));
+    else if (L.pipe) name_mfma_ws(out, L, p.mode, c.ntaps, epi_kind, poly ? p.s : p.mode == MODE_WINO ? c.dil : 1);
+    else name_mfma(out, L);
+}
+
+// c: the layer, or its lft / sine pair (nsig = 2: one launch for both, the pair's strides derived here).
 // last_fused: whether the launch also computed conv_last (ConvParams::last_w accepted)
-hipError_t run_conv(CallCtx& cc, const PackedConv& c, const float* blob, ConvParams p, int nsig, long pair_w_stride,
-                    long pair_b_stride, hipStream_t stream, Profiler* prof, const char* layer, bool* last_fused = nullptr) {
-    p.CIN = c.cin; p.KC = c.KC; p.nchunks = c.nchunks;
-    p.w = blob + c.w_off; p.w_sig = pair_w_stride;
+hipError_t run_conv(CallCtx& cc, const PackedConv* pair, const float* blob, ConvParams p, int nsig, hipStream_t stream,
+                    Profiler* prof, const char* layer, bool* last_fused = nullptr) {
+    const PackedConv& c = pair[0];
     const int stg = cc.storage;
     const bool act_2b = stg != 0;            // 2-byte elements (bfloat16 or float16 storage)
-    auto launch = [&](const ConvParams& q, const ConvLaunch& Lq, hipStream_t st) {
-        if (Lq.pipe == 3) return FASTSVC_BY_STORAGE(stg, launch_conv_wx)(q, Lq, st);
-        if (Lq.pipe == 2) return FASTSVC_BY_STORAGE(stg, launch_conv_hx)(q, Lq, st);
-        return FASTSVC_BY_STORAGE(stg, launch_conv)(q, Lq, st);
-    };
+    // ---- the layer: weights, biases, row pitches ----
+    p.CIN = c.cin; p.KC = c.KC; p.nchunks = c.nchunks;
+    p.w = blob + c.w_off; p.w_sig = nsig == 2 ? (long)(pair[1].w_off - c.w_off) : 0;
     const long T_out = p.T;                                  // output columns (accounting below)
     if (p.mode == MODE_STRETCH && c.poly && !env().no_poly && c.dil == 1 && (long)p.x_T * p.s == p.T) {
         // Stretch2d + conv at the INPUT rate (polyphase): tiles walk the input columns
@@ -2527,287 +2893,57 @@ hipError_t run_conv(CallCtx& cc, const PackedConv& c, const float* blob, ConvPar
     p.ldx = p.x_T;
     p.ldy = (int)T_out;
     if (p.lens) { p.len_mul = p.T / p.frames_ld; p.xlen_mul = p.x_T / p.frames_ld; }
-    p.bias = blob + c.b_off; p.bias_sig = pair_b_stride;
+    p.bias = blob + c.b_off; p.bias_sig = nsig == 2 ? (long)(pair[1].b_off - c.b_off) : 0;
     if (c.dec2) { p.bias2 = blob + c.b2_off; p.bias2_sig = c.b2_pair; }
     p.Q = c.Q; p.ngroups = c.ngroups; p.COUT = c.cout;
     p.ntaps = c.ntaps; p.dil = c.dil;
     p.vec = (p.T % 4 == 0) ? 1 : 0;
     p.dbg = env().dbg;
-    const int halo = c.ntaps == 3 ? c.dil : 0;
     const long zb = (long)nsig * p.B;
     ConvLaunch L{c.MW, 4, 1, 4, nsig, 0};
     p.tpw = 1;
+    int epi_kind = 0;
+    long wgs = 0;                                            // (per-wave stamps of the diagnostic build: the pipelined launches only)
     if (conv_pipe_supported(p)) {
-        // Tile shape and tiles-per-workgroup from a small cost model: a workgroup costs a fixed
-        // start-up (launch, slot set-up, first window in flight) plus tpw * nchunks units, a unit
-        // being bounded by the consumer wave's MFMA stream or by the producers' window traffic;
-        // the grid runs in ceil(workgroups / resident slots) rounds.
-        // compile-time epilogue kind of the launch (same rule as launch_conv_pipe)
-        int epi_kind = 0;
-        if (c.ntaps == 3 && (p.mode == MODE_DIRECT || p.mode == MODE_STRETCH || poly)) {
-            const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
-            epi_kind = aff ? 4 : ((p.mode == MODE_STRETCH || poly) ? 1 : p.r1x ? 3 : p.res ? 2 : 1);
-        }
-        auto is_wino = [](int algo) { return algo == 1 || algo == 2; };
-        std::vector<Cand> cands;
-        if (poly) {
-            if (c.MW == 3 && c.ngroups % 2 == 0) cands = {{1, 2, 2}, {1, 1, 4}};
-            else if (c.MW == 3) cands = {{1, 1, 4}};
-            else cands = {{2, 1, 4}, {1, 1, 4}};
-        }
-        else if (c.MW == 3 && c.ngroups % 4 == 0) cands = {{4, 4, 1}, {2, 4, 1}, {4, 2, 2}, {2, 2, 2}, {1, 2, 2}, {4, 1, 4}, {2, 1, 4}, {1, 1, 4}};
-        else if (c.MW == 3 && c.ngroups % 2 == 0) cands = {{4, 2, 2}, {2, 2, 2}, {1, 2, 2}, {4, 1, 4}, {2, 1, 4}, {1, 1, 4}};
-        else cands = {{4, 1, 4}, {2, 1, 4}, {1, 1, 4}};
-        if (p.mode == MODE_DEC2) {                      // two accumulator sets: compiled for NW <= 2
-            std::vector<Cand> keep;
-            for (const Cand& cd : cands) if (cd.NW <= 2) keep.push_back(cd);
-            cands.swap(keep);
-        }
-        // Winograd F(2,3) variants of the same launch (fastsvc_kernels.h, MODE_WINO)
-        const bool wino_ok = c.wino && env().wino != 0 && p.mode == MODE_DIRECT && (!p.r1x || c.MW == 2) &&
-                             !(p.flags & (F_STATS | F_AFF_OUT | F_PRE_AFFINE));
-        if (wino_ok) {
-            const size_t nd = cands.size();
-            for (size_t i = 0; i < nd; ++i)
-                if (cands[i].NW <= (c.MW == 2 ? 1 : 2)) cands.push_back(Cand{cands[i].NW, cands[i].WM, cands[i].WN, 1});
-            if (c.wino2) {
-                const int ng2 = c.cout / 32;
-                cands.push_back(Cand{1, 1, 4, 2});
-                if (ng2 % 2 == 0) cands.push_back(Cand{1, 2, 2, 2});
-                if (ng2 % 4 == 0) cands.push_back(Cand{1, 4, 1, 2});
-            }
-        }
-        // Half-precision MFMA variants (split-half f16 products in float32 storage, bf16 products in bfloat16
-        // storage): FASTSVC_HX=0 switches them off (A/B), they need rows that are a multiple of 4 long
-        const bool hx_mode = (p.mode == MODE_DIRECT && p.x_T == p.T) || (p.mode == MODE_POLY && c.hxp_off[0]) ||
-                             (p.mode == MODE_DEC2 && (p.x_T & 3) == 0);
-        // ragged batch whose rows run at the frame rate or twice it (len_mul 1 or 2): an utterance's own row length
-        // need not be a multiple of 4.  The TAILK instances handle that (producers zero what lies past the row end
-        // after the prologue, epilogues keep it out of the sums) as long as the row PITCHES are a multiple of 4
-        const bool ragged_tail = p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0);
-        const bool hx_tail_ok = !ragged_tail || ((p.ldx & 3) == 0 && (p.ldy & 3) == 0 &&
-                                                 conv_hx_tail_ok(p.mode, c.MW, epi_kind, poly ? p.s : 1));
-        const bool hx_ok = env().hx != 0 && !p.no_hx && !cc.exact_f32 && c.hx && hx_mode && c.ntaps == 3 && (p.T & 3) == 0 &&
-                           c.dil <= 28 && !(p.flags & F_PRE_AFFINE) && hx_tail_ok;
-        if (hx_ok) {
-            static const int shapes[][3] = {{8, 4, 1}, {4, 4, 1}, {6, 2, 2}, {4, 2, 2}, {2, 2, 2}, {3, 1, 4}, {2, 1, 4}};
-            for (const auto& sh : shapes)
-                if (conv_hx_shape(p.mode, c.MW, sh[0], sh[1], sh[2]) && c.ngroups % sh[1] == 0 &&
-                    !(p.mode == MODE_DIRECT && epi_kind >= 3 && sh[0] * c.MW > 12))   // FiLM-affine / rank-1 epilogues: those tiles spill
-                    cands.push_back(Cand{sh[0], sh[1], sh[2], 3});
-        }
-        // The wide-layer kernel (fastsvc_wx.hip, algorithm 6): every wave multiplies, weights through LDS.  Direct launches of
-        // the 48-channel-group layers (C >= 96) in bfloat16 storage with a plain / residual / FiLM-affine epilogue.
-        // FASTSVC_WX = 0: off, 2: wherever it exists (A/B, tests), else by the launch table / tuning
-        ConvParams pw = p;
-        pw.nch32 = c.nch32;                              // (what geometry() sets for the candidate)
-        const bool wx_ok = hx_ok && env().wx != 0 && act_2b && c.MW == 3 && (epi_kind == 1 || epi_kind == 2 || epi_kind == 4) &&
-                           conv_wx_supported(pw);
-        bool wx_have = false;                            // ... and the layer has a shape of it
-        if (wx_ok) {
-            static const int wshapes[][3] = {{6, 4, 2}};
-            for (const auto& sh : wshapes)
-                if (conv_wx_shape(p.mode, c.MW, sh[0], sh[1], sh[2]) && c.ngroups % sh[1] == 0 && conv_wx_fits(c.nch32, c.dil)) {
-                    cands.push_back(Cand{sh[0], sh[1], sh[2], 6});
-                    wx_have = true;
-                }
-        }
-        const bool wx_force = env().wx == 2 && wx_have;
+        // ---- the shape: launch table, else a tuning pass, else the nearest entry's shape and the cost models ----
+        ConvCands cs = conv_candidates(cc, c, p);
+        epi_kind = cs.epi_kind;
         if (p.last_w) {
-            // conv_last rides on the half-precision instances with one workgroup row of channel groups; it saves a
-            // launch and a write + read of the block's output, more than any shape of the other family wins back:
-            // only those candidates, timed as they will run (no store of the C-channel tensor)
-            std::vector<Cand> keep;
-            if (hx_ok && c.ngroups == 1 && p.mode == MODE_DIRECT && p.res && !p.r1x && !(p.flags & (F_STATS | F_AFF_OUT)))
-                for (const Cand& cd : cands) if (cd.algo == 3 && cd.WM == 1) keep.push_back(cd);
-            if (!keep.empty()) { cands.swap(keep); p.y = nullptr; }
+            if (cs.last_ok) p.y = nullptr;                   // (the C-channel tensor is then not stored)
             else p.last_w = nullptr;
         }
-        if ((p.T & 3) != 0 || (p.lens && (p.len_mul & 3) != 0)) {
-            // rows that are not a multiple of 4 long (with a ragged batch: ANY utterance's own length,
-            // whatever the padded maximum is): only the variants compiled with the row-end handling
-            std::vector<Cand> keep;
-            for (const Cand& cd : cands)
-                if (cd.algo == 6 ? false : cd.algo == 3 ? (p.T & 3) == 0 :            // (hx candidates are only there when hx_tail_ok)
-                    conv_ws_tail_ok(cd.algo == 2 ? 2 : c.MW, cd.NW, is_wino(cd.algo) ? (int)MODE_WINO : p.mode, epi_kind,
-                                    poly ? p.s : 1)) keep.push_back(cd);
-            if (!keep.empty()) cands.swap(keep);       // (never empty: NW <= 2 variants always have it)
-        }
-        auto round_to = [](int v, int rem, int mod) { int r = v / mod * mod + rem; return r < v ? r + mod : r; };
-        // LDS geometry of a candidate: row stride (== 16 mod 32) and, for Winograd, the phase-plane
-        // stride that keeps the component reads conflict-free (planes land 16/D banks apart)
-        auto geometry = [&](const Cand& cd, ConvParams& q) {
-            if (cd.algo == 3 || cd.algo == 6) {
-                const int prec = stg;                   // fragment set = storage
-                q.whx = blob + (p.mode == MODE_POLY ? c.hxp_off[prec] : c.hx_off[prec]); q.whx_sig = c.hx_pair[prec]; q.nch32 = c.nch32;
-                const size_t inv_off = p.mode == MODE_POLY ? c.hxp_inv_off : c.hx_inv_off;
-                q.whx_inv = (prec == 0 && inv_off) ? blob + inv_off : nullptr; q.whx_inv_sig = c.hx_inv_pair;
-                q.stagger = env().stagger;
-                q.xs = 0; q.ps = 0;
-            } else if (cd.algo >= 1) {
-                const int NTo = 32 * cd.NW * cd.WN, D = c.dil;
-                const int Q = (NTo + 16) / (2 * D);
-                const int ps = D == 1 ? (Q + 1) / 2 * 2 : D == 2 ? round_to(Q, 8, 32) : round_to(Q, 12, 32);
-                q.ps = ps;
-                q.xs = round_to(2 * D * ps, 16, 32);
-                q.mode = MODE_WINO; q.Q = c.Qw;
-                if (cd.algo == 2) { q.w = blob + c.ww2_off; q.w_sig = c.ww2_pair; q.ngroups = c.cout / 32; }
-                else { q.w = blob + c.ww_off; q.w_sig = c.ww_pair; }
-            } else {
-                const int W = 16 * cd.NW * cd.WN + 2 * ((halo + 3) & ~3);
-                q.xs = (W + 15) / 32 * 32 + 16;
-                q.ps = 0;
-            }
-        };
         char key[96];
         // 2-byte storage compiles some variants under a different register budget: its own entries ("|b"; float16: "|h", then "|b")
         std::snprintf(key, sizeof(key), "%s|%d|%d%s", layer, p.B, p.T, key_suffix(stg));
         bool have = false;
-        Cand best = cands[0];
+        Cand best = cs.list[0];
         fastsvc_plan::Choice ch;
         if (table_entry(*cc.plan, key, ch)) {
-            // a loaded table may be stale: only shapes this launch is compiled for are taken, algorithm included
-            for (const Cand& cd : cands)
-                if (cd.NW == ch.NW && cd.WM == ch.WM && cd.WN == ch.WN && cd.algo == ch.algo && ch.tpw >= 1 && ch.tpw <= 64 &&
-                    !(env().hx == 2 && hx_ok && cd.algo != 3 && cd.algo != 6) &&   // FASTSVC_HX=2: older tables do not hold it back
-                    !(wx_force && cd.algo != 6)) {
-                    best = cd; p.tpw = ch.tpw;
-                    have = true;
-                }
+            const Cand* cd = match_table_shape(cs.list, ch, true);
+            if (cd && !(env().hx == 2 && cs.hx_ok && cd->algo != 3 && cd->algo != 6) &&   // FASTSVC_HX=2: older tables do not hold it back
+                !(cs.wx_force && cd->algo != 6)) {
+                best = *cd; p.tpw = ch.tpw;
+                have = true;
+            }
         }
         if (!have && cc.tuning) {
-            // time every (shape, tiles-per-workgroup) on the device; InstanceNorm sums are not
-            // accumulated by the trial launches (the real launch below does that once)
-            std::vector<Cand> trial;
-            for (const Cand& cd : cands)
-                if (!(wx_force && cd.algo != 6)) trial.push_back(cd);     // FASTSVC_WX=2: only the wide-layer kernel's shapes
-            float best_ms = 1e30f;
-            ConvParams q = p;
-            ConvLaunch Lq = L;
-            hipError_t e = time_candidates(trial, stream, cc.trials,
-                [&](const Cand& cd) {
-                    q = p; q.flags &= ~F_STATS;
-                    geometry(cd, q);
-                    Lq = ConvLaunch{cd.algo == 2 ? 2 : c.MW, cd.NW, cd.WM, cd.WN, nsig, cd.algo == 6 ? 3 : cd.algo == 3 ? 2 : 1};
-                    const int NT = (is_wino(cd.algo) ? 32 : 16) * cd.NW * cd.WN;
-                    return (long)(p.T + NT - 1) / NT;
-                },
-                [&](int tpw) { q.tpw = tpw; return launch(q, Lq, stream); }, best, p.tpw, best_ms);
+            int tpw = p.tpw;
+            const hipError_t e = conv_tune(cc, c, blob, p, nsig, cs, stream, best, tpw);
             if (e != hipSuccess) return e;
+            p.tpw = tpw;
             table_record(*cc.plan, key, fastsvc_plan::Choice{best.NW, best.WM, best.WN, p.tpw, best.algo});
             have = true;
         }
-        // No entry for this (B, T): the tile shape and algorithm of the table entry of this layer with the nearest
-        // problem size, where one exists and this launch is compiled for it - a layer's best shape moves slowly with
-        // the size (the tuned tables agree on it across batch shapes far more often than the model below finds it:
-        // tools/costmodel_gap.py) - and only the tiles per workgroup from the model.
-        bool prior_pick = false;
-        if (!have && env().prior && !wx_force) {
-            fastsvc_plan::Choice pr{0, 0, 0, 0, -1};
-            {
-                std::lock_guard<std::mutex> lock(cc.plan->tune_mu);
-                auto it = cc.plan->priors.find(key);
-                if (it != cc.plan->priors.end()) pr = it->second;
-                else {
-                    if (!cc.plan->prior_for(layer, p.B, p.T, act_2b, pr)) pr.algo = -1;
-                    cc.plan->priors[key] = pr;
-                }
-            }
-            if (pr.algo >= 0)
-                for (const Cand& cd : cands)
-                    if (cd.NW == pr.NW && cd.WM == pr.WM && cd.WN == pr.WN && cd.algo == pr.algo) {
-                        const Cand only = cd;
-                        cands.assign(1, only);
-                        prior_pick = true;
-                        break;
-                    }
-        }
         if (!have) {
-        // Tile shape and tiles-per-workgroup from a small cost model: a workgroup costs a fixed
-        // start-up (launch, slot set-up, first window in flight) plus tpw * nchunks units, a unit
-        // being bounded by the consumer wave's MFMA stream or by the producers' window traffic;
-        // the grid runs in ceil(workgroups / resident slots) rounds.
-        double best_t = 1e30;
-        for (const Cand& cd : cands) {
-            // Without a table entry the model takes Winograd wherever the layer has it, the 32-channel
-            // grouping (two workgroups per CU) when that exists - measured better than direct on cfg1
-            // and cfg2 (0.56 vs 0.62 ms, 2.24 vs 2.32 ms).  C = 24 layers (MW == 2) stay direct: their
-            // Winograd variant loses to the scalar phase-plane staging.  FASTSVC_WINO = 0 / 1 / 2
-            // forces direct / layer grouping / 32-channel grouping.
-            const int wino_pref = env().wino >= 0 ? env().wino : (c.MW == 2 ? 0 : 2);
-            if (cd.algo == 6) {
-                // no model of its own: taken by table / prior, or wherever it exists with FASTSVC_WX=2 (first shape that fits,
-                // one round of workgroups where the batch allows)
-                if (!(prior_pick || wx_force)) continue;
-                const int NT = 16 * cd.NW * cd.WN;
-                const long ntx = (p.T + NT - 1) / NT;
-                const long gy = c.ngroups / cd.WM;
-                int tpw = 1;
-                while (tpw < 64 && ((ntx + tpw - 1) / tpw) * gy * zb > 256) ++tpw;
-                if (best_t > 0.0) { best_t = 0.0; best = cd; p.tpw = tpw; }
-                continue;
-            }
-            if (wx_force) continue;
-            if (!prior_pick && hx_ok != (cd.algo == 3)) continue;          // the half-precision MFMA variant wherever the layer has one
-            if (cd.algo == 3) {
-                // data-movement model: one workgroup per CU; a unit moves its window in and (per tile) its
-                // outputs; the matrix work (3 taps x NW x MW x 1|3 products of 16 cycles) hides under it
-                const int NT = 16 * cd.NW * cd.WN;
-                const long ntx = (p.T + NT - 1) / NT;
-                const long gy = c.ngroups / cd.WM;
-                const double win = NT + 2.0 * ((halo + 3) & ~3);
-                const double esz = act_2b ? 2.0 : 4.0;
-                const double out_streams = (p.y ? 1 : 0) + ((p.flags & F_AFF_OUT) ? 3 : 0) + (p.res ? 1 : 0);
-                const double bytes_unit = 32.0 * win * esz + 16.0 * c.MW * cd.WM * NT * (poly ? p.s : 1) * esz *
-                                          (out_streams + (p.mode == MODE_DEC2 ? 1 : 0)) / c.nch32;
-                const double mem_us = bytes_unit / (4.5e6 / 256.0);
-                const double mfma_us = (poly ? 5.0 : p.mode == MODE_DEC2 ? 4.0 : 3.0) * cd.NW * c.MW * (act_2b ? 1 : 3) * 17.0 / 2.0e3;
-                const double unit_us = mem_us > mfma_us ? mem_us : mfma_us;
-                for (int tpw = 1; tpw <= 24; ++tpw) {
-                    const long wgs = ((ntx + tpw - 1) / tpw) * gy * zb;
-                    const long rounds = (wgs + 255) / 256;
-                    const double t = rounds * (env().startup_us + tpw * c.nch32 * unit_us);
-                    if (t < best_t * 0.999) { best_t = t; best = cd; p.tpw = tpw; }
-                }
-                continue;
-            }
-            if (!prior_pick) {
-                if ((cd.algo >= 1) != (wino_ok && wino_pref >= 1)) continue;
-                if (wino_pref >= 1 && wino_ok && c.wino2 && (cd.algo == 2) != (wino_pref == 2)) continue;
-            }
-            const int NT = (cd.algo >= 1 ? 32 : 16) * cd.NW * cd.WN;
-            const int cMW = cd.algo == 2 ? 2 : c.MW;
-            const long ntx = (p.T + NT - 1) / NT;
-            const long gy = ((cd.algo == 2 ? c.cout / 32 : c.ngroups) + cd.WM - 1) / cd.WM;
-            const int resident = conv_ws_resident(cMW, cd.NW, cd.algo >= 1 ? (int)MODE_WINO : p.mode, epi_kind);   // VGPR budget, see the kernel
-            const long slots = 256L * resident;
-            // unit time: MFMA stream of one consumer wave vs bytes the 256 producer threads move
-            const double mfma_us = 6.0 * (cd.algo >= 1 ? 4 : c.ntaps) * cd.NW * cMW * 32.0 / 2.2e3;
-            const double win = NT + 2.0 * ((halo + 3) & ~3);
-            const double bytes_unit = c.KC * win * 4.0 + (double)16 * cMW * cd.WM * NT * (poly ? p.s : 1) * 4.0 *
-                                      ((p.y ? 1 : 0) + ((p.flags & F_AFF_OUT) ? 3 : 0) + (p.res ? 1 : 0)) / c.nchunks;
-            const double mem_us = bytes_unit / (5.0e6 / 256.0 / resident);    // ~5 TB/s shared by all slots
-            // packed weights streamed from L2 by the four consumer waves (per unit, per workgroup):
-            // ~16 TB/s of L2 shared by all resident workgroups; this is what punishes small NW
-            const double wbytes_unit = 4.0 * 6.0 * c.ntaps * 64.0 * cMW * 4.0;
-            const double l2_us = wbytes_unit / (16.0e6 / 256.0 / resident);
-            double unit_us = mfma_us > mem_us ? mfma_us : mem_us;
-            if (l2_us > unit_us) unit_us = l2_us;
-            unit_us /= (resident == 2 ? 1.6 : 1.0);
-            for (int tpw = 1; tpw <= 16; ++tpw) {
-                const long wgs = ((ntx + tpw - 1) / tpw) * gy * zb;
-                const long rounds = (wgs + slots - 1) / slots;
-                const double t = rounds * (env().startup_us + tpw * c.nchunks * unit_us);
-                if (t < best_t * 0.999) { best_t = t; best = cd; p.tpw = tpw; }
-            }
+            const bool prior_pick = env().prior && !cs.wx_force && conv_prior(*cc.plan, key, layer, p, act_2b, cs.list);
+            conv_model_pick(c, p, cs, prior_pick, zb, act_2b, best, p.tpw);
         }
-        }
-        L.pipe = best.algo == 6 ? 3 : best.algo == 3 ? 2 : 1;
-        L.NW = best.NW; L.WM = best.WM; L.WN = best.WN;
-        if (best.algo == 2) L.MW = 2;
-        geometry(best, p);
+        L = launch_of(best, c.MW, nsig);
+        conv_geometry(best, c, blob, stg, p);
+        wgs = workgroup_count(tiles_per_row(p.T, best), p.tpw, ((p.ngroups + L.WM - 1) / L.WM) * zb);
     } else {
         p.last_w = nullptr;
+        const int halo = c.ntaps == 3 ? c.dil : 0;
         int NW = 4;
         while (NW > 1 && ((p.T + 64 * NW - 1) / (64 * NW)) * zb * c.ngroups < 768) NW >>= 1;
         L.NW = NW;
@@ -2816,57 +2952,13 @@ hipError_t run_conv(CallCtx& cc, const PackedConv& c, const float* blob, ConvPar
     }
     if (last_fused) *last_fused = p.last_w != nullptr;      // (the candidates were restricted to the instances that have it)
     double flops_all = 0.0, bytes = 0.0;
-    char kname[48] = "";
+    KernelName kname = "";
     if (prof) {
-        // algorithmic work of the layer as the reference defines it (3 taps at the OUTPUT rate for
-        // the stretched convs, whichever way they are computed)
-        const double cols = (double)T_out * p.B * nsig;
-        flops_all = 2.0 * (c.dec2 ? 4 : c.ntaps) * c.cin * c.cout * cols;    // DEC2: k=3 conv + 1x1
-        double in_cols = (double)T_out;                     // source columns actually needed
-        if (p.mode == MODE_STRETCH || poly) in_cols = (double)p.x_T;
-        double el = (double)c.cin * in_cols;
-        if (p.y) el += (double)c.cout * T_out;
-        if (p.mode == MODE_DEC2 && p.y2) el += (double)c.cout * T_out;     // the decimating pair's second output (the 1x1 residual conv's)
-        if (p.flags & F_AFF_OUT) el += (double)c.cout * T_out;
-        if (p.flags & F_PRE_AFFINE) el += 2.0 * c.cin * T_out;
-        if (p.res) el += (double)c.cout * T_out;
-        if (p.r1x) el += (double)T_out;
-        if (p.flags & (F_STATS | F_AFF_OUT)) el += 2.0 * c.cout * T_out;
-        bytes = (act_2b ? 2.0 : 4.0) * el * p.B * nsig + 4.0 * (double)(c.w_floats + c.b_floats) * nsig;
-        if (p.last_w) {                                   // + conv_last: C -> 1, float32 waveform out (the C-channel tensor is not written: p.y is null)
-            flops_all += 2.0 * c.cout * cols;
-            bytes += 4.0 * cols;
-        }
-        if (L.pipe == 3) {
-            const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
-            std::snprintf(kname, sizeof(kname), "conv_wx<%d,%d,%d,%d,%d,%s>", L.MW, L.NW, L.WM, L.WN, aff ? 4 : p.res ? 2 : 1, prod_tag(stg));
-        } else if (L.pipe == 2) {
-            const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
-            const int kind = aff ? 4 : p.r1x ? 3 : p.res ? 2 : 1;
-            const bool tail_inst = p.lens && (((p.len_mul | p.xlen_mul) & 3) != 0);      // the row-end (TAILK) instance
-            std::snprintf(kname, sizeof(kname), "conv_hx<%d,%d,%d,%d,%d,%d,%d,%s%s>", L.MW, L.NW, L.WM, L.WN, p.mode,
-                          p.mode == MODE_DEC2 ? 1 : poly ? (aff ? 4 : 1) : kind, poly ? p.s : 1, prod_tag(stg),
-                          tail_inst ? ",tail" : "");
-        } else if (L.pipe)
-        {
-            // same rule as launch_conv_pipe: compile-time epilogue kind of the 3-tap DIRECT / STRETCH launches
-            int kind = 0;
-            if (c.ntaps == 3 && (p.mode == MODE_DIRECT || p.mode == MODE_STRETCH || poly || p.mode == MODE_WINO)) {
-                const bool aff = (p.flags & (F_STATS | F_AFF_OUT)) != 0;
-                kind = aff ? 4 : ((p.mode == MODE_STRETCH || poly) ? 1 : p.r1x ? 3 : p.res ? 2 : 1);
-            }
-            // the template arguments of the instance that runs (last one: polyphase stretch / Winograd dilation)
-            std::snprintf(kname, sizeof(kname), "conv_mfma_ws<%d,%d,%d,%d,%d,%d,%d,%d>", L.MW, L.NW, L.WM, L.WN,
-                          p.mode, c.ntaps, kind, poly ? p.s : p.mode == MODE_WINO ? c.dil : 1);
-        }
-        else
-            std::snprintf(kname, sizeof(kname), "conv_mfma<%d,%d,1,4>", L.MW, L.NW);
+        conv_account(c, p, T_out, nsig, act_2b, flops_all, bytes);
+        conv_name(kname, L, c, p, poly, epi_kind, stg);
     }
     else if (act_2b && !L.pipe) return hipErrorNotSupported;   // the scalar kernel exists for float32 storage only
-    // (per-wave stamps of the diagnostic build: the pipelined launches only)
-    const int NT = (p.mode == MODE_WINO ? 32 : 16) * L.NW * L.WN;
-    const long wgs = (((p.T + NT - 1) / NT + p.tpw - 1) / p.tpw) * ((p.ngroups + L.WM - 1) / L.WM) * zb;
-    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops_all, bytes, [&]() { return launch(p, L, stream); },
+    return launch_tail(prof, stream, layer, kname, p.tpw, -1, flops_all, bytes, [&]() { return launch_any(stg, p, L, stream); },
                        L.pipe ? &p : nullptr, &L, wgs, p.nchunks);
 }
 
@@ -2958,9 +3050,9 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
     // created after an RCCL communicator the same schedule ran cfg2 in 2.54 ms instead of 1.43.  Default: bit 1 from
     // ~1.5e5 samples per call where the context says it pays, one stream otherwise; FASTSVC_STREAMS=<mask> forces a
     // mask (0: one stream), FASTSVC_SERIAL one stream.
-    int64_t hop_all = 1;
-    for (int i = 0; i < plan->n; ++i) hop_all *= plan->cfg.upsampling_scales[i];
-    int streams_mask = env().serial ? 0 : env().streams >= 0 ? (env().streams & 3) : ((int64_t)B * F * hop_all >= 150000 ? 2 : 0);
+    int64_t hop = 1;                                       // samples per frame
+    for (int i = 0; i < plan->n; ++i) hop *= plan->cfg.upsampling_scales[i];
+    int streams_mask = env().serial ? 0 : env().streams >= 0 ? (env().streams & 3) : ((int64_t)B * F * hop >= 150000 ? 2 : 0);
     // per-launch profiling and autotuning run on ONE stream so that every kernel is timed alone
     ExecCtx* ctx = (streams_mask == 0 || cc.tuning || prof) ? nullptr : exec_ctx_for(stream);
     std::unique_lock<std::mutex> ctx_lock;
@@ -2987,8 +3079,6 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
         return reinterpret_cast<float*>(wsb + ws.find(name)->off_bytes);
     };
     const int n = P.n;
-    int64_t hop = 1;
-    for (int i = 0; i < n; ++i) hop *= P.cfg.upsampling_scales[i];
     const long T = (long)hop * F;
     {
         // The kernels address every tensor of ONE utterance through a 32-bit buffer descriptor and
@@ -3021,6 +3111,15 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
     if (sig_bytes % (std::ptrdiff_t)sizeof(float) != 0) return fail(FASTSVC_E_INVALID, "sine / lft must be 4-byte aligned");
     const long sig_stride = (long)(sig_bytes / (std::ptrdiff_t)sizeof(float));
     const bool no_scan = env().no_amax_scan;                     // A/B timing only: inputs then count as unit-scale
+    // the rank-1 residual of stage 0, r = conv1x1(raw signal), added by the launch that writes h_0
+    auto set_rank1_residual = [&](const DownStage& d, ConvParams& p) -> int {
+        p.r1x = sigbuf; p.r1x_sig = sig_stride; p.r1x_b = T;
+        p.r1w = blob + d.r_raw[0].w_off; p.r1b = blob + d.r_raw[0].b_off;
+        p.r1_sig = (long)(d.r_raw[1].w_off - d.r_raw[0].w_off);
+        if ((d.r_raw[1].b_off - d.r_raw[0].b_off) != (d.r_raw[1].w_off - d.r_raw[0].w_off))
+            return fail(FASTSVC_E_INVALID, "internal: rank-1 pair strides");
+        return FASTSVC_OK;
+    };
     if (P.storage == 0 && !no_scan) {
         // float32 storage: largest magnitudes of the inputs (scales of the split-binary16 staging) and zeroed amax
         // rows of the intermediates - ONE small launch, first thing on the caller's stream (everything else is
@@ -3105,15 +3204,14 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
                     p.mode = MODE_DEC2;
                     p.y = c1; p.y_sig = tsig; p.y_b = tb;
                     p.y2 = r; p.y2_sig = tsig; p.y2_b = tb;
-                    HIP_TRY(run_conv(cc, d.rc1[0], blob, p, 2, (long)(d.rc1[1].w_off - d.rc1[0].w_off),
-                                     (long)(d.rc1[1].b_off - d.rc1[0].b_off), stream, pr, ("down." + s + ".c1_res1x1").c_str()));
+                    HIP_TRY(run_conv(cc, d.rc1, blob, p, 2, stream, pr, ("down." + s + ".c1_res1x1").c_str()));
                 } else {
-                p.y = r; p.y_sig = tsig; p.y_b = tb;
-                HIP_TRY(order_after(stream, s_side));                  // h_{k-1} is ready
-                HIP_TRY(run_conv(cc, d.r[0], blob, p, 2, (long)(d.r[1].w_off - d.r[0].w_off), (long)(d.r[1].b_off - d.r[0].b_off), s_side, pr, ("down." + s + ".res1x1").c_str()));
-                p.flags = F_PRE_LRELU;                                 // c1 = conv3_d1(lrelu(h_{k-1}[::s]))
-                p.y = c1;
-                HIP_TRY(run_conv(cc, d.c1[0], blob, p, 2, (long)(d.c1[1].w_off - d.c1[0].w_off), (long)(d.c1[1].b_off - d.c1[0].b_off), stream, pr, ("down." + s + ".c1").c_str()));
+                    p.y = r; p.y_sig = tsig; p.y_b = tb;
+                    HIP_TRY(order_after(stream, s_side));                  // h_{k-1} is ready
+                    HIP_TRY(run_conv(cc, d.r, blob, p, 2, s_side, pr, ("down." + s + ".res1x1").c_str()));
+                    p.flags = F_PRE_LRELU;                                 // c1 = conv3_d1(lrelu(h_{k-1}[::s]))
+                    p.y = c1;
+                    HIP_TRY(run_conv(cc, d.c1, blob, p, 2, stream, pr, ("down." + s + ".c1").c_str()));
                 }
             }
             {
@@ -3124,11 +3222,8 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
                 ConvParams p3 = p;                                     // h = conv3_d4(lrelu(c2)) + r
                 p3.y = h; p3.y_sig = tsig; p3.y_b = tb; p3.amax_out = am_h;
                 if (k == 0) {
-                    p3.r1x = sigbuf; p3.r1x_sig = sig_stride; p3.r1x_b = T;
-                    p3.r1w = blob + d.r_raw[0].w_off; p3.r1b = blob + d.r_raw[0].b_off;
-                    p3.r1_sig = (long)(d.r_raw[1].w_off - d.r_raw[0].w_off);
-                    if ((d.r_raw[1].b_off - d.r_raw[0].b_off) != (d.r_raw[1].w_off - d.r_raw[0].w_off))
-                        return fail(FASTSVC_E_INVALID, "internal: rank-1 pair strides");
+                    const int rc = set_rank1_residual(d, p3);
+                    if (rc != FASTSVC_OK) return rc;
                 } else {
                     p3.res = buf("down_r." + s); p3.res_sig = tsig; p3.res_b = tb;
                     HIP_TRY(order_after(s_side, stream));              // r is ready
@@ -3137,24 +3232,18 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
                 const long b3 = (long)(d.c3[1].b_off - d.c3[0].b_off);
                 auto separate = [&](Profiler* pr) -> int {
                     p.y = c2; p.y_sig = tsig; p.y_b = tb;
-                    HIP_TRY(run_conv(cc, d.c2[0], blob, p, 2, (long)(d.c2[1].w_off - d.c2[0].w_off), (long)(d.c2[1].b_off - d.c2[0].b_off), stream, pr, n2.c_str()));
+                    HIP_TRY(run_conv(cc, d.c2, blob, p, 2, stream, pr, n2.c_str()));
                     ConvParams q = p3;
                     q.x = c2; q.bnd_path[1] = blob + d.c2[0].bnd_off; q.bnd_sig[1] = d.c2[0].bnd_pair;   // ... and c2 behind it
-                    HIP_TRY(run_conv(cc, d.c3[0], blob, q, 2, (long)(d.c3[1].w_off - d.c3[0].w_off), b3, stream, pr, n3.c_str()));
+                    HIP_TRY(run_conv(cc, d.c3, blob, q, 2, stream, pr, n3.c_str()));
                     return FASTSVC_OK;
                 };
                 // one launch for the pair where the stage has the fused variant (c2 then never reaches memory);
                 // a tuning pass times it against the two launches and the table keeps the winner
-                double sep_ms = 0.0;
-                if (cc.tuning && !pr && d.c3[0].hxc_off[0]) {
-                    const int rc = time_separate(stream, true, [&]() { return separate(nullptr); }, sep_ms);
-                    if (rc != FASTSVC_OK) return rc;
-                }
-                bool fused = false;
-                HIP_TRY(run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, b3, stream, pr, n23.c_str(), sep_ms, fused));
-                if (!fused) { const int rc = separate(pr); if (rc != FASTSVC_OK) return rc; }
+                return fused_or_separate(stream, cc.tuning && !pr && d.c3[0].hxc_off[0], pr, n23.c_str(),
+                    [&](double sep_ms, bool& done) { return run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, b3, stream, pr, n23.c_str(), sep_ms, done); },
+                    separate);
             }
-            return FASTSVC_OK;
         };
         // The WHOLE stage - chain and FiLM net of both signals - as one launch where it has the variant (compact
         // workspace: h_0 itself is then not materialised, stage 1 reads the compact decimated copy)
@@ -3181,27 +3270,25 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
         }
         // Stage 0 as ONE launch where it has the variant (MODE_CHAIN1): the staging waves compute the 1 -> C conv
         // from the raw signal, so neither c1 nor c2 reaches memory; a tuning pass times it against the other path
-        bool stage_fused = false;
         if (k == 0 && d.c3[0].hxc_off[0]) {
             ConvParams p3 = base;
             p3.x = sigbuf; p3.x_sig = sig_stride; p3.x_b = T; p3.x_T = (int)Tk;
             p3.flags = F_PRE_LRELU;
             p3.y = h; p3.y_sig = tsig; p3.y_b = tb;
             p3.amax_in = amax_inb; p3.amax_out = am_h;
-            p3.r1x = sigbuf; p3.r1x_sig = sig_stride; p3.r1x_b = T;
-            p3.r1w = blob + d.r_raw[0].w_off; p3.r1b = blob + d.r_raw[0].b_off;
-            p3.r1_sig = (long)(d.r_raw[1].w_off - d.r_raw[0].w_off);
-            if ((d.r_raw[1].b_off - d.r_raw[0].b_off) != (d.r_raw[1].w_off - d.r_raw[0].w_off))
-                return fail(FASTSVC_E_INVALID, "internal: rank-1 pair strides");
-            double sep_ms = 0.0;
-            if (cc.tuning && !prof) {
-                const int rc = time_separate(stream, true, [&]() { return stage_unfused(nullptr); }, sep_ms);
-                if (rc != FASTSVC_OK) return rc;
-            }
-            HIP_TRY(run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, (long)(d.c3[1].b_off - d.c3[0].b_off), stream, prof,
-                              "down.0.c123", sep_ms, stage_fused, d.c1_raw));
+            const int rc1 = set_rank1_residual(d, p3);
+            if (rc1 != FASTSVC_OK) return rc1;
+            const int rc = fused_or_separate(stream, cc.tuning && !prof, prof, "down.0.c123",
+                [&](double sep_ms, bool& done) {
+                    return run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, (long)(d.c3[1].b_off - d.c3[0].b_off), stream, prof,
+                                     "down.0.c123", sep_ms, done, d.c1_raw);
+                },
+                stage_unfused);
+            if (rc != FASTSVC_OK) return rc;
+        } else {
+            const int rc = stage_unfused(prof);
+            if (rc != FASTSVC_OK) return rc;
         }
-        if (!stage_fused) { const int rc = stage_unfused(prof); if (rc != FASTSVC_OK) return rc; }
         {
             // the FiLM net of the LAST stage feeds the first up block: critical path, caller's stream;
             // the others are only needed by later up blocks: helper stream
@@ -3216,32 +3303,31 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
                 p.flags = F_POST_LRELU;
                 p.y = u; p.y_sig = tb; p.y_b = 2 * tb;
                 p.amax_in = am_h;
-                HIP_TRY(run_conv(cc, d.film[0], blob, p, 2, (long)(d.film[1].w_off - d.film[0].w_off), (long)(d.film[1].b_off - d.film[0].b_off), sf, pr, nconv.c_str()));
+                HIP_TRY(run_conv(cc, d.film, blob, p, 2, sf, pr, nconv.c_str()));
                 ConvParams q = base;                               // [scale ; shift] summed over both signals
                 q.x = u; q.x_sig = 0; q.x_b = 2 * tb; q.x_T = (int)Tk;
                 q.y = ssb; q.y_sig = 0; q.y_b = 2 * tb;
                 // u = [lrelu(conv_lft(h_lft)) ; lrelu(conv_sine(h_sine))]: the larger of the two halves' bounds
                 q.amax_in = am_h; q.amax_in_sig = 0; q.amax_in2 = B;
                 q.bnd_path[0] = blob + d.film[0].bnd_off; q.bnd_sig[0] = d.film[0].bnd_pair;
-                HIP_TRY(run_conv(cc, d.heads, blob, q, 1, 0, 0, sf, pr, nheads.c_str()));
+                HIP_TRY(run_conv(cc, &d.heads, blob, q, 1, sf, pr, nheads.c_str()));
                 return FASTSVC_OK;
             };
             // the whole FiLM net of the stage in one launch where it has the variant: the 2C-channel intermediate
             // stays in LDS (block-diagonal first conv over both chains' outputs, then the heads)
-            bool film_fused = false;
             if (d.filmc.hxc_off[0] && ((long)tsig + (long)d.C * Tk) * 4 < (1L << 31)) {
-                double sep_ms = 0.0;
-                if (cc.tuning && !prof) {
-                    const int rc = time_separate(sf, true, [&]() { return film_separate(nullptr); }, sep_ms);
-                    if (rc != FASTSVC_OK) return rc;
-                }
                 ConvParams p3 = base;
                 p3.x = h; p3.x_sig = tsig; p3.x_b = tb; p3.x_T = (int)Tk; p3.xsplit = d.C;
                 p3.y = ssb; p3.y_sig = 0; p3.y_b = 2 * tb;
                 p3.amax_in = am_h; p3.amax_in2 = B;                 // channels [lft ; sine]: the larger of the two chains' maxima
-                HIP_TRY(run_chain(cc, d.filmc, d.filmc, blob, p3, 1, 0, sf, prof, nchain.c_str(), sep_ms, film_fused));
+                const int rc = fused_or_separate(sf, cc.tuning && !prof, prof, nchain.c_str(),
+                    [&](double sep_ms, bool& done) { return run_chain(cc, d.filmc, d.filmc, blob, p3, 1, 0, sf, prof, nchain.c_str(), sep_ms, done); },
+                    film_separate);
+                if (rc != FASTSVC_OK) return rc;
+            } else {
+                const int rc = film_separate(prof);
+                if (rc != FASTSVC_OK) return rc;
             }
-            if (!film_fused) { const int rc = film_separate(prof); if (rc != FASTSVC_OK) return rc; }
             if (sf != stream && ctx) {
                 ss_ready[k] = ctx->ev[evi++ % ctx->ev.size()];
                 HIP_TRY(hipEventRecord(ss_ready[k], sf));
@@ -3327,26 +3413,26 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
         if (!head_fused) HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 0, 0.0, d3_fused));
         ConvParams p = base;
         if (!head_fused) {
-        p = base;                                                  // a = conv_first(x)
-        p.x = x; p.x_b = (long)Cx * Tin; p.x_T = (int)Tin;
-        p.y = a; p.y_b = (long)u.C * Tin; p.T = (int)Tin;
-        p.amax_in = am_x;
-        HIP_TRY(run_conv(cc, u.first, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".conv_first").c_str()));
+            p = base;                                                  // a = conv_first(x)
+            p.x = x; p.x_b = (long)Cx * Tin; p.x_T = (int)Tin;
+            p.y = a; p.y_b = (long)u.C * Tin; p.T = (int)Tin;
+            p.amax_in = am_x;
+            HIP_TRY(run_conv(cc, &u.first, blob, p, 1, stream, prof, ("up." + s + ".conv_first").c_str()));
 
-        p = base;                                                  // xr = conv_res(stretch(a))
-        p.x = a; p.x_b = (long)u.C * Tin; p.x_T = (int)Tin;
-        p.mode = MODE_STRETCH; p.s = u.scale;
-        p.y = xr; p.y_b = cb; p.T = (int)Tout;
-        p.amax_in = am_x; p.bnd_path[0] = blob + u.first.bnd_off;  // |a| <= l1 |x| + bmax  (xr is only ever a residual: not tracked)
-        if (!d3_fused) {
-        HIP_TRY(order_after(stream, s_side));                      // a is ready
-        HIP_TRY(run_conv(cc, u.res, blob, p, 1, 0, 0, s_side, prof, ("up." + s + ".res_stretch").c_str()));
-        }
+            p = base;                                                  // xr = conv_res(stretch(a))
+            p.x = a; p.x_b = (long)u.C * Tin; p.x_T = (int)Tin;
+            p.mode = MODE_STRETCH; p.s = u.scale;
+            p.y = xr; p.y_b = cb; p.T = (int)Tout;
+            p.amax_in = am_x; p.bnd_path[0] = blob + u.first.bnd_off;  // |a| <= l1 |x| + bmax  (xr is only ever a residual: not tracked)
+            if (!d3_fused) {
+                HIP_TRY(order_after(stream, s_side));                      // a is ready
+                HIP_TRY(run_conv(cc, &u.res, blob, p, 1, s_side, prof, ("up." + s + ".res_stretch").c_str()));
+            }
 
-        p.flags = F_PRE_LRELU | F_POST_LRELU | aff_out;            // u1 = aff(lrelu(conv_up(stretch(lrelu(a)))))
-        p.y = nullptr; p.y2 = u1; p.y2_b = cb;
-        p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st;
-        HIP_TRY(run_conv(cc, u.up, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".up_stretch").c_str()));
+            p.flags = F_PRE_LRELU | F_POST_LRELU | aff_out;            // u1 = aff(lrelu(conv_up(stretch(lrelu(a)))))
+            p.y = nullptr; p.y2 = u1; p.y2_b = cb;
+            p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st;
+            HIP_TRY(run_conv(cc, &u.up, blob, p, 1, stream, prof, ("up." + s + ".up_stretch").c_str()));
         }
 
         // tiny batches: the sums the epilogue accumulated are replaced by exact ones (see stats_exact_kernel)
@@ -3396,28 +3482,28 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
             // unwritten: ADVICE r5)
             if (!ran) return fail(FASTSVC_E_INVALID, "up." + s + ".d3x: the launch table changed between the route decision and the launch");
         } else {
-        HIP_TRY(order_after(s_side, stream));                      // xr is ready
-        HIP_TRY(run_conv(cc, u.d3, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d3").c_str()));
-        if (cc.tuning && !prof && !head_fused) {
-            // tuning pass: the two separate launches again, timed, then the fused shapes against them
-            ConvParams pr = base;
-            pr.x = a; pr.x_b = (long)u.C * Tin; pr.x_T = (int)Tin;
-            pr.mode = MODE_STRETCH; pr.s = u.scale;
-            pr.y = xr; pr.y_b = cb; pr.T = (int)Tout;
-            pr.amax_in = am_x; pr.bnd_path[0] = blob + u.first.bnd_off;
-            ConvParams pq = p;
-            pq.flags &= ~F_STATS;                                  // (the InstanceNorm sums are accumulated once)
-            double sep_ms = 0.0;
-            const int rc = time_separate(stream, false, [&]() {
-                if (run_conv(cc, u.res, blob, pr, 1, 0, 0, stream, nullptr, ("up." + s + ".res_stretch").c_str()) != hipSuccess ||
-                    run_conv(cc, u.d3, blob, pq, 1, 0, 0, stream, nullptr, ("up." + s + ".d3").c_str()) != hipSuccess)
-                    return fail(FASTSVC_E_HIP, "timing the separate residual / d3 launches");
-                return (int)FASTSVC_OK;
-            }, sep_ms);
-            if (rc != FASTSVC_OK) return rc;
-            bool dummy = false;
-            HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 2, sep_ms, dummy));
-        }
+            HIP_TRY(order_after(s_side, stream));                      // xr is ready
+            HIP_TRY(run_conv(cc, &u.d3, blob, p, 1, stream, prof, ("up." + s + ".d3").c_str()));
+            if (cc.tuning && !prof && !head_fused) {
+                // tuning pass: the two separate launches again, timed, then the fused shapes against them
+                ConvParams pr = base;
+                pr.x = a; pr.x_b = (long)u.C * Tin; pr.x_T = (int)Tin;
+                pr.mode = MODE_STRETCH; pr.s = u.scale;
+                pr.y = xr; pr.y_b = cb; pr.T = (int)Tout;
+                pr.amax_in = am_x; pr.bnd_path[0] = blob + u.first.bnd_off;
+                ConvParams pq = p;
+                pq.flags &= ~F_STATS;                                  // (the InstanceNorm sums are accumulated once)
+                double sep_ms = 0.0;
+                const int rc = time_separate(stream, false, [&]() {
+                    if (run_conv(cc, &u.res, blob, pr, 1, stream, nullptr, ("up." + s + ".res_stretch").c_str()) != hipSuccess ||
+                        run_conv(cc, &u.d3, blob, pq, 1, stream, nullptr, ("up." + s + ".d3").c_str()) != hipSuccess)
+                        return fail(FASTSVC_E_HIP, "timing the separate residual / d3 launches");
+                    return (int)FASTSVC_OK;
+                }, sep_ms);
+                if (rc != FASTSVC_OK) return rc;
+                bool dummy = false;
+                HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 2, sep_ms, dummy));
+            }
         }
         HIP_TRY(exact_stats(u2, st + stn));
 
@@ -3425,7 +3511,7 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
         p.y = nullptr; p.y2 = u3;
         p.st_out = st + 2 * stn;
         
-        HIP_TRY(run_conv(cc, u.d9, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d9").c_str()));
+        HIP_TRY(run_conv(cc, &u.d9, blob, p, 1, stream, prof, ("up." + s + ".d9").c_str()));
         HIP_TRY(exact_stats(u3, st + 2 * stn));
 
         p.x = u3; p.st_in = st + 2 * stn;                          // out = conv_d27(lrelu(norm(u3))) + xmid
@@ -3441,7 +3527,7 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
             p.last_y = out; p.last_y_b = (long)P.cfg.out_channels * T;
             if (lengths) HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * T, stream));   // ragged batch: zero padding of the waveform
         }
-        HIP_TRY(run_conv(cc, u.d27, blob, p, 1, 0, 0, stream, prof, ("up." + s + ".d27").c_str(), &last_done));
+        HIP_TRY(run_conv(cc, &u.d27, blob, p, 1, stream, prof, ("up." + s + ".d27").c_str(), &last_done));
 
         x = xo; Cx = u.C; Tin = Tout;
     }
