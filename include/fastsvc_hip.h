@@ -201,6 +201,56 @@ int fastsvc_norm_group_stats(const void* u, int32_t storage, int32_t B, int32_t 
                              int32_t len_mul, const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
                              double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* fastsvc_forward with RUNNING InstanceNorm statistics, carried on the device from one forward to the next: what
+ * decode.StreamSession(norm="running") runs the windows of live streams through.  Row b is a window of the stream in
+ * slot[b]; window k of a stream is normalised at every norm point by the mean and biased variance of ALL frames of the
+ * stream up to the window's right edge, each counted once.  Arguments as fastsvc_forward, and
+ *   slot     DEVICE, B int32: the carry slot of row b's stream.  Rows of one slot are ASCENDING in b (window order).
+ *            slot[] is followed, not clamped: 0 <= slot[b] < the number of records `carry` holds is the caller's duty
+ *   own_lo, own_hi   DEVICE, B int32 each, in frames: the row's CORE [own_lo[b], own_hi[b]) of its lengths[b] valid
+ *            frames, 0 <= own_lo < own_hi <= lengths[b]; the frames [own_hi[b], lengths[b]) are its look-ahead
+ *   prior    DEVICE, B int32: frames of the stream in front of the core (all inside earlier cores), own_lo <= prior
+ *   reset    DEVICE, B int32: nonzero on the first window a stream runs in this slot - for it and the slot's rows behind
+ *            it in the batch the carry is taken as zero and NOT read, so opening a slot needs no memset.  Only on the
+ *            first row of a slot in the batch; prior == own_lo
+ *   parity   DEVICE, B int32, 0 / 1: which entry of the slot's record holds its carry; the same for all rows of a slot
+ *   carry    DEVICE: record s at carry + s * carry_bytes; carry_bytes >= fastsvc_norm_carry_bytes(plan), a multiple of
+ *            8.  A record is two ENTRIES (parity 0, 1) of, per up block in order, its three norm points' C x 2 doubles
+ *   scratch  DEVICE, >= fastsvc_norm_running_scratch_bytes(plan, B, F) bytes: the partial sums
+ * At each norm point, behind the launch that produced the tensor, per (row, channel) and all in float64, in this order:
+ * the carry; the core chunks of earlier rows of the slot in this batch, ascending (row, chunk); the row's own core chunks
+ * - the slot's new carry; the row's look-ahead chunks - the statistics, written as S * len_b / N with N = (prior[b] +
+ * lengths[b] - own_lo[b]) columns' worth of frames.  Chunks are 2048 columns from the start of each range.  The LAST row
+ * of a slot in the batch writes the new carry into entry parity ^ 1: a launch reads one entry of a record and writes the
+ * other, so its workgroups need no order; the CALLER flips the slot's parity after every call that had a row of it.
+ * No floating-point atomics: two runs give the same bits, and a stream's windows give the same carry and statistics
+ * bits however they fall into calls.  Two extra launches per norm point.  A reset row with own_lo == 0 (window 0 of a
+ * stream, which owns its whole row) is a PASS-THROUGH row: its statistics are left as the producer wrote them and only
+ * its carry is written - a batch of such rows gives fastsvc_forward's output bit for bit.  float32 storage: the bound
+ * behind the split-binary16 staging scale grows from sqrt(len_b) to sqrt(N), as in fastsvc_forward_grouped.
+ * spk_emb == NULL: there is no norm; the extra arguments are ignored (may be NULL), the carry is untouched and the
+ * launches and bytes are fastsvc_forward's.  Not together with the grouped route.  The device arrays cannot be checked
+ * here; the Python layer validates them on the host (engine.check_norm_running). */
+size_t fastsvc_norm_carry_bytes(const fastsvc_plan* plan);
+size_t fastsvc_norm_running_scratch_bytes(const fastsvc_plan* plan, int32_t B, int32_t F);
+int fastsvc_forward_running(const fastsvc_plan* plan, const void* dev_blob,
+                            const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                            float* out, int32_t B, int32_t F, const int32_t* lengths,
+                            const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                            const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                            void* carry, size_t carry_bytes,
+                            void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream);
+
+/* The same two launches for ONE tensor u (B, C, ld) of `storage` and one norm point's carry: record s is the 2 x C x 2
+ * doubles (entry, channel, sum u / sum u^2) at carry + s * 4 * C.  stats_out (B, C, 2) receives the statistics of every
+ * row that is not a pass-through row.  No column at or beyond a row's valid length or in front of own_lo * len_mul is
+ * read.  scratch: DEVICE, >= B * C * ceil(ld / 2048) * 32 bytes.  All pointers DEVICE; asynchronous on `stream`. */
+int fastsvc_norm_running_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                               int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                               const int32_t* prior, const int32_t* reset, const int32_t* parity, double* carry,
+                               double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Creates (and calibrates, see the conventions above: synchronises `stream`) the helper streams / events
  * fastsvc_forward may use for `stream` on the current device, so that the forward itself allocates nothing and
  * never synchronises (call once per stream, e.g. before graph capture or a latency-critical first call).

@@ -381,6 +381,33 @@ hipError_t launch_norm_group_partials(const float* u, double* part, int B, int C
 hipError_t launch_norm_group_pool(const double* part, double* st, int B, int C, int ld, const int* lens, int len_mul,
                                   const int* group, const int* own_lo, const int* own_hi, float* amax_raise, hipStream_t stream);
 
+// ---- RUNNING InstanceNorm sums of live streams (fastsvc_normgroup.hip; fastsvc_forward_running) ----
+// Row b is a window of the stream in slot[b]: its core is the columns [own_lo[b], own_hi[b]) * len_mul, its look-ahead
+// [own_hi[b], lens[b]) * len_mul (may be empty), and prior[b] frames of the stream lie in front of the core - all of
+// them inside earlier cores, so inside the slot's carry.  Rows of a slot ascend in b.  Two launches:
+//   partials: the group kernel's wave per (row, channel, chunk) over TWO ranges a row, each cut into chunks from its own
+//             start -> part[((b * 2 + range) * chunks + k) * C + c][2], range 0 the core, 1 the look-ahead.
+//   pool:     per (row b, channel), in this order: the slot's carry (entry parity[b]; zero, and not read, when the slot's
+//             first row of the batch has reset set - a stream that starts in this batch starts from nothing);
+//             the core chunks of the rows q < b of the slot, ascending (row, chunk); b's own core chunks - this is the
+//             slot's new carry, which the LAST row of the slot in the batch writes to entry parity[b] ^ 1; b's look-ahead
+//             chunks.  st[b][c] = that sum * (lens[b] * len_mul) / N, N = (prior[b] + lens[b] - own_lo[b]) * len_mul:
+//             every frame of the stream up to the row's right edge, once.  amax_raise as in the group pool.
+// carry: entry e of slot s is the C x 2 doubles at carry + s * slot_stride + e * parity_stride.  All rows of a slot must
+// carry ONE parity: the launch then reads entry `parity` and writes entry `parity ^ 1` of a slot, never one entry both
+// ways, whatever the order of its workgroups; the host flips the slot's parity after the launch is enqueued.
+// A row with reset[b] and own_lo[b] == 0 - the first window of a stream - is a PASS-THROUGH row: its st entries are left
+// as they are, only the carry is written (a reset row must be the first of its slot in the batch).
+// The six int arrays hold B entries; own_lo / own_hi / prior are clamped to the row, but slot[] IS followed: the caller
+// guarantees 0 <= slot[b] < the slots the carry holds (engine.check_norm_running).
+hipError_t launch_norm_running_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul,
+                                        const int* own_lo, const int* own_hi, const int* prior, const int* reset,
+                                        hipStream_t stream);
+hipError_t launch_norm_running_pool(const double* part, double* st, int B, int C, int ld, const int* lens, int len_mul,
+                                    const int* slot, const int* own_lo, const int* own_hi, const int* prior,
+                                    const int* reset, const int* parity, double* carry, long slot_stride,
+                                    long parity_stride, float* amax_raise, hipStream_t stream);
+
 // conv_last: 1x1, y[b][o][t] = bias[o] + sum_c w[o][c] * x[b][c][t]
 hipError_t launch_pointwise_out(const float* x, const float* w, const float* bias, float* y,
                                 int B, int C, int O, int T, const int* lens, int len_mul, hipStream_t stream);
@@ -418,6 +445,9 @@ hipError_t launch_cond_stage0(const CondStage0Params& p, hipStream_t stream); \
 hipError_t launch_cond_stage1(const CondStage1Params& p, hipStream_t stream); \
 hipError_t launch_norm_group_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul, \
                                       const int* group, const int* own_lo, const int* own_hi, hipStream_t stream); \
+hipError_t launch_norm_running_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul, \
+                                        const int* own_lo, const int* own_hi, const int* prior, const int* reset, \
+                                        hipStream_t stream); \
 
 namespace bf16 { FASTSVC_ACT_LAUNCHERS }
 namespace f16 { FASTSVC_ACT_LAUNCHERS }

@@ -1861,7 +1861,23 @@ struct CallCtx {
     const int32_t* ng_lo = nullptr;
     const int32_t* ng_hi = nullptr;
     double* ng_part = nullptr;
+    // fastsvc_forward_running: the rows are windows of live streams whose sums are carried from forward to forward.
+    // Device arrays of B entries, the slots' carry records (nr_stride doubles apart, both parity entries of
+    // norm_carry_doubles each) and the scratch in ng_part; never together with ng_group.
+    const int32_t* nr_slot = nullptr;
+    const int32_t* nr_prior = nullptr;
+    const int32_t* nr_reset = nullptr;
+    const int32_t* nr_parity = nullptr;
+    double* nr_carry = nullptr;
+    long nr_stride = 0;
 };
+
+// doubles of ONE parity entry of a slot's carry record: per up block its three norm points, C x 2 each, in dataflow order
+static long norm_carry_doubles(const fastsvc_plan& P, int blocks) {
+    long n = 0;
+    for (int i = 0; i < blocks; ++i) n += 3L * P.up[i].C * 2;
+    return n;
+}
 
 #ifdef FASTSVC_TIMELINE
 // diagnostic build (python -m svcc23_fastsvc_amd.build --timeline; tools/timeline.py): per-wave cycle stamps
@@ -3459,6 +3475,19 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
                     e = launch_norm_group_pool(cc.ng_part, stp, B, u.C, (int)Tout, lengths, m, cc.ng_group, cc.ng_lo, cc.ng_hi,
                                                (P.storage == 0 && stp == st) ? am_p : nullptr, stream);
             }
+            // Rows of live streams (fastsvc_forward_running): the same two launches with the slot's carry in front of the
+            // sums - this norm point's C x 2 doubles of the record, (stp - st) / stn the point of the block.
+            if (e == hipSuccess && cc.nr_slot) {
+                const int m = (int)(Tout / F);
+                const long entry = norm_carry_doubles(P, n);
+                double* carry = cc.nr_carry + norm_carry_doubles(P, i) + (stp - st) / stn * (long)u.C * 2;
+                e = FASTSVC_BY_STORAGE(P.storage, launch_norm_running_partials)(ut, cc.ng_part, B, u.C, (int)Tout, lengths, m,
+                                                                                cc.ng_lo, cc.ng_hi, cc.nr_prior, cc.nr_reset, stream);
+                if (e == hipSuccess)
+                    e = launch_norm_running_pool(cc.ng_part, stp, B, u.C, (int)Tout, lengths, m, cc.nr_slot, cc.ng_lo, cc.ng_hi,
+                                                 cc.nr_prior, cc.nr_reset, cc.nr_parity, carry, cc.nr_stride, entry,
+                                                 (P.storage == 0 && stp == st) ? am_p : nullptr, stream);
+            }
             return e;
         };
         HIP_TRY(exact_stats(u1, st));
@@ -3650,6 +3679,66 @@ int fastsvc_norm_group_stats(const void* u, int32_t storage, int32_t B, int32_t 
     HIP_TRY(FASTSVC_BY_STORAGE(storage, launch_norm_group_partials)(static_cast<const float*>(u), part, B, C, ld, lengths, len_mul,
                                                                     group, own_lo, own_hi, s));
     HIP_TRY(launch_norm_group_pool(part, stats_out, B, C, ld, lengths, len_mul, group, own_lo, own_hi, nullptr, s));
+    return FASTSVC_OK;
+}
+
+size_t fastsvc_norm_carry_bytes(const fastsvc_plan* plan) {
+    return plan ? 2 * (size_t)norm_carry_doubles(*plan, plan->n) * sizeof(double) : 0;
+}
+
+size_t fastsvc_norm_running_scratch_bytes(const fastsvc_plan* plan, int32_t B, int32_t F) {
+    return 2 * fastsvc_norm_group_scratch_bytes(plan, B, F);       // (two ranges a row)
+}
+
+int fastsvc_forward_running(const fastsvc_plan* plan, const void* dev_blob,
+                            const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                            float* out, int32_t B, int32_t F, const int32_t* lengths,
+                            const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                            const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                            void* carry, size_t carry_bytes,
+                            void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+    CallCtx cc;
+    if (spk_emb) {                                     // (without an embedding there is no norm: fastsvc_forward's launches and bytes)
+        if (!slot || !own_lo || !own_hi || !prior || !reset || !parity || !carry || !scratch)
+            return fail(FASTSVC_E_INVALID, "null argument");
+        if (!plan || B < 1 || B > 65535 || F < 1) return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535 and F >= 1");
+        if (carry_bytes < fastsvc_norm_carry_bytes(plan) || carry_bytes % sizeof(double) != 0 ||
+            reinterpret_cast<uintptr_t>(carry) % sizeof(double) != 0)
+            return fail(FASTSVC_E_INVALID, "carry_bytes, the bytes from one slot's record to the next, must be a multiple of 8 "
+                                           "and at least fastsvc_norm_carry_bytes; the carry 8-byte aligned");
+        if (scratch_bytes < fastsvc_norm_running_scratch_bytes(plan, B, F))
+            return fail(FASTSVC_E_WORKSPACE, "running-norm scratch too small (fastsvc_norm_running_scratch_bytes)");
+        cc.nr_slot = slot; cc.ng_lo = own_lo; cc.ng_hi = own_hi;
+        cc.nr_prior = prior; cc.nr_reset = reset; cc.nr_parity = parity;
+        cc.nr_carry = static_cast<double*>(carry);
+        cc.nr_stride = (long)(carry_bytes / sizeof(double));
+        cc.ng_part = static_cast<double*>(scratch);
+    }
+    return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
+                        workspace_bytes, stream, nullptr);
+}
+
+int fastsvc_norm_running_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                               int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                               const int32_t* prior, const int32_t* reset, const int32_t* parity, double* carry,
+                               double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!u || !slot || !own_lo || !own_hi || !prior || !reset || !parity || !carry || !stats_out || !scratch)
+        return fail(FASTSVC_E_INVALID, "null argument");
+    if (storage != 0 && storage != 1 && storage != 2)
+        return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
+    if (B < 1 || B > 65535 || C < 1 || ld < 1 || len_mul < 1 || ld % len_mul != 0)
+        return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535, C >= 1 and a pitch ld that is a positive multiple of len_mul");
+    if ((long)C * norm_group_chunks(ld) > 0x7fffffffL / 2)
+        return fail(FASTSVC_E_UNSUPPORTED, "too many (channel, chunk) items for one launch");
+    if (scratch_bytes < (size_t)B * C * norm_group_chunks(ld) * 4 * sizeof(double))
+        return fail(FASTSVC_E_WORKSPACE, "running-norm scratch too small: B * C * ceil(ld / 2048) * 32 bytes");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(scratch);
+    HIP_TRY(FASTSVC_BY_STORAGE(storage, launch_norm_running_partials)(static_cast<const float*>(u), part, B, C, ld, lengths,
+                                                                      len_mul, own_lo, own_hi, prior, reset, s));
+    HIP_TRY(launch_norm_running_pool(part, stats_out, B, C, ld, lengths, len_mul, slot, own_lo, own_hi, prior, reset, parity,
+                                     carry, 4L * C, 2L * C, nullptr, s));
     return FASTSVC_OK;
 }
 

@@ -21,7 +21,8 @@ batches whose output is not finite, and ``--storage auto`` is float16 storage wi
 ``--window CORE[,CONTEXT[,FADE]]`` decodes every utterance as overlapping windows (``convert_windowed``): recordings longer
 than one forward takes, in buffers sized by the window.  ``--stream PUSH[,CORE[,CONTEXT[,FADE]]] [--streams N]`` feeds the
 dumps as N concurrent simulated LIVE streams, PUSH frames per call (``StreamSession``: features arrive chunk by chunk,
-samples come back as soon as their window has its context).
+samples come back as soon as their window has its context); ``--stream-norm running`` normalises every window by the
+statistics of all frames its stream has delivered so far, carried on the GPU, instead of by the window's own.
 """
 from __future__ import annotations
 
@@ -335,6 +336,58 @@ def pool_norm_sums(s1, s2, owned: Sequence[int], lens: Sequence[int], group: Seq
         q1[b] = t1 * float(lens[b]) / float(N)
         q2[b] = t2 * float(lens[b]) / float(N)
     return q1, q2
+
+
+NORM_CHUNK = 2048             # columns of one partial sum (NORMGROUP_CHUNK of csrc/fastsvc_kernels.h)
+
+
+def chunk_sums(u, lo: int, hi: int, chunk: int = NORM_CHUNK) -> np.ndarray:
+    """``(n_chunks, C, 2)`` float64: sum u and sum u^2 of the columns ``[lo, hi)`` of ``u`` (C, T), cut into chunks of
+    ``chunk`` columns from ``lo`` - the partial sums of csrc/fastsvc_normgroup.hip up to the order inside a chunk.  An empty
+    range has no chunks."""
+    u = np.asarray(u, dtype=np.float64)
+    parts = [np.stack([u[:, a: min(a + chunk, hi)].sum(axis=1), (u[:, a: min(a + chunk, hi)] ** 2).sum(axis=1)], axis=-1)
+             for a in range(int(lo), int(hi), int(chunk))]
+    return np.stack(parts) if parts else np.zeros((0, u.shape[0], 2))
+
+
+def pool_running_sums(core, look, lens: Sequence[int], slot: Sequence[int], own_lo: Sequence[int], prior: Sequence[int],
+                      reset: Sequence[int], carry: Dict[int, np.ndarray]):
+    """The numpy reference of the RUNNING pool of csrc/fastsvc_normgroup.hip (``StreamSession(norm="running")``), float64.
+    Row b of one forward is a window of the stream in carry slot ``slot[b]``; ``core[b]`` and ``look[b]`` are the chunk
+    sums ``(n_chunks, C, 2)`` of its core and of its look-ahead (``chunk_sums``; the look-ahead may have none), ``lens[b]``
+    its valid length, ``own_lo[b]`` where its core starts in it and ``prior[b]`` what the stream holds in front of the
+    core - the three in one unit, frames or columns.  ``carry[s]`` (C, 2) holds the sums of the cores of all earlier
+    windows of slot s; a ``reset`` row starts its stream: it and the slot's rows behind it in the batch take the carry as
+    zero without looking.  Per row, added in THIS order: the carry; the core chunks of the rows q < b of the slot,
+    ascending (row, chunk); b's own core chunks, which gives the slot's new carry; b's look-ahead chunks, which gives S.
+    The row's statistics are ``S * lens[b] / N`` with ``N = prior[b] + lens[b] - own_lo[b]``, every frame of the stream up
+    to the row's right edge: ``[..., 0] / lens[b]`` is their mean.  The left fold makes carry and statistics the same bits
+    however a stream's windows fall into forwards.
+
+    Returns ``(stats, new_carry)``: per row ``(C, 2)``, or ``None`` for a PASS-THROUGH row (reset, ``own_lo == 0``: window 0
+    of a stream, whose statistics stay the producer's own), and ``carry`` updated with every slot of the batch (a new
+    dict)."""
+    B = len(slot)
+    stats: List[Optional[np.ndarray]] = []
+    new_carry = dict(carry)
+    for b in range(B):
+        C = np.asarray(core[b]).shape[1]
+        first = min(q for q in range(B) if slot[q] == slot[b])          # (a stream that starts in this batch starts from zero)
+        s = np.zeros((C, 2)) if reset[first] else np.array(carry[slot[b]], dtype=np.float64)
+        for q in range(b + 1):
+            if slot[q] == slot[b]:
+                for part in np.asarray(core[q], dtype=np.float64):
+                    s = s + part
+        new_carry[slot[b]] = s                               # (the slot's last row of the batch has the last word)
+        if reset[b] and int(own_lo[b]) == 0:
+            stats.append(None)
+            continue
+        for part in np.asarray(look[b], dtype=np.float64):
+            s = s + part
+        N = int(prior[b]) + int(lens[b]) - int(own_lo[b])
+        stats.append(s * float(lens[b]) / float(N))
+    return stats, new_carry
 
 
 def _window_groups(rows):
@@ -1456,12 +1509,21 @@ class StreamSession:
     windows are cross-faded by ``stitch_windows``' rule: everything a stream returned, concatenated, is samples ``[0, F
     hop)``, each exactly once, and equals ``stitch_windows`` of its windows.  WITHOUT a speaker embedding that is the
     whole-utterance result (to float32 kernel arithmetic); WITH one it is ``convert_windowed(norm="window")``'s function:
-    InstanceNorm normalises every window by its own statistics (whole-utterance or running statistics are out of scope
-    here: they need frames that have not arrived).
+    InstanceNorm normalises every window by its own statistics.  Whole-utterance statistics need frames that have not
+    arrived; ``norm="running"`` uses every frame that HAS: window k is normalised, at all norm points, by the mean and
+    variance of the stream's frames ``[0, in_hi_k)`` - the float64 sums of the cores of windows 0..k-1, carried on the
+    device from forward to forward (``Generator.forward(norm_running=...)``, csrc/fastsvc_normgroup.hip), plus the
+    window's own core and look-ahead.  Window 0 is ``norm="window"``'s, bit for bit, so a stream that ends inside it
+    returns the same bytes; later windows approach ``convert_windowed(norm="utterance")`` as the stream grows, and the
+    result does not depend on how windows fall into forwards beyond the forward's batching invariance (DESIGN.md 4.10
+    has the rule, its reference and its caveats).  It needs a model that takes an embedding; streams opened without
+    one run as under ``"window"`` and carry nothing.
 
     State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
     ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
-    upload buffer with a page-locked twin and one page-locked download buffer.  Per ``push``: one upload, one
+    upload buffer with a page-locked twin and one page-locked download buffer; with ``norm="running"`` per stream one
+    carry record (``plan.norm_carry_bytes()``: two parity entries of every norm point's sums, never zeroed - a stream's
+    first window resets it) and one scratch for the partial sums of a forward.  Per ``push``: one upload, one
     ``stream_push`` launch (appends to the rings and synthesises the chunk's excitation, csrc/fastsvc_stream.hip) and, if
     any window became ready, per ``max_batch`` rows one ``stream_assemble``, one forward with ``lengths``, one
     ``window_stitch`` and one download.  A push that completes no window runs no forward (``forwards`` counts them).
@@ -1483,7 +1545,7 @@ class StreamSession:
     fallback reports, graph capture of the per-push chain, several GPUs."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
-                 fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32):
+                 fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window"):
         from .engine import FastSVCError, STREAM_MAX_PUSH
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
@@ -1509,6 +1571,11 @@ class StreamSession:
             raise ValueError(f"max_push must be in [1, {STREAM_MAX_PUSH}], got {max_push}")
         self.channels = C = int(cfg.in_channels)
         self._takes_emb = bool(cfg.use_spk_emb)
+        if norm not in ("window", "running"):
+            raise ValueError(f"norm must be \"window\" or \"running\", got {norm!r}")
+        if norm == "running" and not self._takes_emb:
+            raise ValueError("norm=\"running\" needs a model that takes a speaker embedding: without one nothing is normalised")
+        self.norm = norm
         self.cap = cap = stream_ring_frames(core, context, max_push)
         dev, n = self.device, self.n_streams
         self._ppg = torch.empty((n, cap, C), dtype=torch.float32, device=dev)
@@ -1525,6 +1592,12 @@ class StreamSession:
         self._h_down = _PinnedSet()
         self._h_down.get("w", (n * (cap * hop + 8 * (cap // core + 2)),))
         self._up_done: Optional[torch.cuda.Event] = None
+        self._carry = self._norm_scratch = None
+        if norm == "running":
+            plan = model.plan
+            self._carry = torch.empty((n, plan.norm_carry_bytes() // 8), dtype=torch.float64, device=dev)
+            self._norm_scratch = torch.empty(max(plan.norm_running_scratch_bytes(self.max_batch, plan.padded_frames(core + 2 * context)), 1),
+                                             dtype=torch.uint8, device=dev)
         self._emb_rows: Dict[tuple, torch.Tensor] = {}                       # row slots of a forward -> their index tensor
         self._slots: List[Optional[Dict[str, object]]] = [None] * n          # per slot: the open stream's host state
         self._ids: Dict[int, int] = {}                                       # open id -> slot
@@ -1551,7 +1624,7 @@ class StreamSession:
             return
         self._closed = True
         torch.cuda.current_stream(self.device).synchronize()
-        self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = None
+        self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = self._carry = self._norm_scratch = None
         self._h_up = self._d_up = self._h_down = self._up_done = None
         self._slots, self._ids = [None] * self.n_streams, {}
 
@@ -1581,7 +1654,7 @@ class StreamSession:
         sid = self._next_id
         self._next_id += 1
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
-        self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, seed=key,
+        self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, norm_parity=0, seed=key,
                               stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
         self._ids[sid] = s
         self._layout.reset(s)
@@ -1697,7 +1770,18 @@ class StreamSession:
                         self._emb_rows.clear()
                     self._emb_rows[slots] = torch.as_tensor(slots, dtype=torch.int64, device=dev)
                 emb = self._emb.index_select(0, self._emb_rows[slots])
-            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+            if emb is not None and self.norm == "running":
+                # window k of a stream: its core starts own_lo frames into the row, core_lo frames of the stream lie in
+                # front of it, window 0 resets the slot's carry; the slot's parity says which entry of its record is current
+                running = ([r[0] for r in chunk], [r[4] - r[2] for r in chunk], [r[5] - r[2] for r in chunk],
+                           [r[4] for r in chunk], [int(r[1] == 0) for r in chunk],
+                           [self._slots[r[0]]["norm_parity"] for r in chunk])
+                y = self.model(ppg, sine, lft, emb, lengths=lens, norm_running=running, norm_carry=self._carry,
+                               norm_scratch=self._norm_scratch).to(torch.float32)
+                for s in dict.fromkeys(r[0] for r in chunk):         # (enqueued: the other entry is the slot's carry now)
+                    self._slots[s]["norm_parity"] ^= 1
+            else:
+                y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
             self.forwards += 1
             host, off = _stitch_to_host(y, lay, self._stage, self.pcm16, self._h_down, at=off)
             down.append((host, lay))
@@ -1769,7 +1853,11 @@ def main(argv=None) -> None:                                  # pragma: no cover
                     help="with --resident: feed the dumps as simulated LIVE streams, PUSH frames per stream and call "
                          "(StreamSession: windows of CORE frames, default 32, run as soon as their CONTEXT has arrived, "
                          "default the generator's receptive field; cross-fade over FADE frames, default 8); same file names; "
-                         "with a speaker embedding InstanceNorm normalises per window, as with --window")
+                         "with a speaker embedding InstanceNorm normalises per window, as with --window (see --stream-norm)")
+    ap.add_argument("--stream-norm", default="window", choices=["window", "running"],
+                    help="with --stream and a speaker embedding: InstanceNorm statistics of each window alone (default) or "
+                         "running - of every frame the stream has delivered up to the window's right edge, carried on the GPU "
+                         "from push to push; approaches the whole-utterance result as the stream grows")
     ap.add_argument("--streams", type=int, default=1, help="with --stream: dumps converted side by side (default 1)")
     args = ap.parse_args(argv)
     if args.stream is not None:
@@ -1782,9 +1870,9 @@ def main(argv=None) -> None:                                  # pragma: no cover
                 raise ValueError
         except ValueError:
             ap.error("--stream takes PUSH[,CORE[,CONTEXT[,FADE]]] in frames, --streams a count of at least 1")
-        args.stream = dict(zip(("max_push", "core", "context", "fade"), parts), n_streams=args.streams)
-    elif args.streams != 1:
-        ap.error("--streams needs --stream")
+        args.stream = dict(zip(("max_push", "core", "context", "fade"), parts), n_streams=args.streams, norm=args.stream_norm)
+    elif args.streams != 1 or args.stream_norm != "window":
+        ap.error("--streams and --stream-norm need --stream")
     if args.window is not None:
         if not args.resident or args.fanout > 1:
             ap.error("--window works on the --resident route, without --fanout")

@@ -35,7 +35,9 @@ ABI_SYMBOLS = (
     "fastsvc_plan_set_storage", "fastsvc_plan_get_storage",
     "fastsvc_weight_blob_bytes", "fastsvc_pack_weights", "fastsvc_workspace_bytes",
     "fastsvc_pack_device_scratch_bytes", "fastsvc_pack_device_launch_count", "fastsvc_pack_weights_device",
-    "fastsvc_forward", "fastsvc_forward_grouped", "fastsvc_norm_group_scratch_bytes", "fastsvc_norm_group_stats", "fastsvc_autotune", "fastsvc_tuned_count", "fastsvc_tuned_get", "fastsvc_tuned_set",
+    "fastsvc_forward", "fastsvc_forward_grouped", "fastsvc_norm_group_scratch_bytes", "fastsvc_norm_group_stats",
+    "fastsvc_forward_running", "fastsvc_norm_carry_bytes", "fastsvc_norm_running_scratch_bytes", "fastsvc_norm_running_stats",
+    "fastsvc_autotune", "fastsvc_tuned_count", "fastsvc_tuned_get", "fastsvc_tuned_set",
     "fastsvc_forward_profile", "fastsvc_workspace_tap", "fastsvc_forward_launch_count",
     "fastsvc_flops_per_sample", "fastsvc_signal_scratch_bytes", "fastsvc_signal_generate",
     "fastsvc_stream_prepare", "fastsvc_stream_release", "fastsvc_split_half", "fastsvc_plan_set_workspace_mode",
@@ -124,6 +126,14 @@ def load_library():
     lib.fastsvc_forward_grouped.restype = ctypes.c_int
     lib.fastsvc_norm_group_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.fastsvc_norm_group_stats.restype = ctypes.c_int
+    lib.fastsvc_norm_carry_bytes.argtypes = [vp]
+    lib.fastsvc_norm_carry_bytes.restype = sz
+    lib.fastsvc_norm_running_scratch_bytes.argtypes = [vp, i32, i32]
+    lib.fastsvc_norm_running_scratch_bytes.restype = sz
+    lib.fastsvc_forward_running.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp] + [vp] * 6 + [vp, sz, vp, sz, vp, sz, vp]
+    lib.fastsvc_forward_running.restype = ctypes.c_int
+    lib.fastsvc_norm_running_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32] + [vp] * 6 + [vp, vp, vp, sz, vp]
+    lib.fastsvc_norm_running_stats.restype = ctypes.c_int
     lib.fastsvc_loudness_frames.argtypes = [i32, i32]
     lib.fastsvc_loudness_frames.restype = i32
     lib.fastsvc_loudness_scratch_bytes.argtypes = [i32, i32, i32]
@@ -836,6 +846,92 @@ def norm_group_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: in
     return stats
 
 
+def check_norm_running(norm_running, lens: Sequence[int], n_slots: Optional[int] = None):
+    """Validate ``norm_running = (slot, own_lo, own_hi, prior, reset, parity)`` - six sequences of B ints, as
+    ``fastsvc_forward_running`` takes them - against the rows' frame counts ``lens``, on the host (the library gets device
+    arrays it cannot check, and it FOLLOWS ``slot``).  Row b is a window of the stream in carry slot ``slot[b]`` with the
+    core ``[own_lo[b], own_hi[b])``, ``0 <= own_lo < own_hi <= lens[b]``, and ``prior[b] >= own_lo[b]`` frames of the
+    stream in front of the core; a ``reset`` row (the first window a stream runs in its slot) has ``prior == own_lo`` and
+    is the first row of its slot in the batch.  Slots ascend through the batch (``slot[b] <= slot[b + 1]``, ``0 <= slot <
+    n_slots``), so a slot's rows are neighbours; they are in window order - ``prior[b + 1] == prior[b] + own_hi[b] -
+    own_lo[b]`` - and carry one ``parity`` (0 or 1).  Returns the six as lists of ints; ``ValueError`` names the first row
+    that breaks a rule."""
+    try:
+        slot, own_lo, own_hi, prior, reset, parity = ([int(v) for v in seq] for seq in norm_running)
+    except (TypeError, ValueError):
+        raise ValueError("norm_running must be (slot, own_lo, own_hi, prior, reset, parity), six sequences of ints") from None
+    B = len(lens)
+    if any(len(a) != B for a in (slot, own_lo, own_hi, prior, reset, parity)):
+        raise ValueError(f"norm_running must hold {B} entries each, got " +
+                         ", ".join(str(len(a)) for a in (slot, own_lo, own_hi, prior, reset, parity)))
+    for b in range(B):
+        if not 0 <= own_lo[b] < own_hi[b] <= int(lens[b]):
+            raise ValueError(f"row {b}: core frames [{own_lo[b]}, {own_hi[b]}) must satisfy 0 <= own_lo < own_hi <= "
+                             f"{int(lens[b])}, the row's frame count")
+        if slot[b] < 0 or (n_slots is not None and slot[b] >= int(n_slots)):
+            raise ValueError(f"row {b}: slot {slot[b]} is not one of the carry's" + ("" if n_slots is None else f" {int(n_slots)}"))
+        if prior[b] < own_lo[b]:
+            raise ValueError(f"row {b}: prior {prior[b]} must be at least own_lo {own_lo[b]} (the left context lies in earlier cores)")
+        if prior[b] + int(lens[b]) - own_lo[b] >= 2 ** 31:
+            raise ValueError(f"row {b}: prior {prior[b]} is out of range")
+        if parity[b] not in (0, 1):
+            raise ValueError(f"row {b}: parity must be 0 or 1, got {parity[b]}")
+        if reset[b] and prior[b] != own_lo[b]:
+            raise ValueError(f"row {b}: a reset row starts its stream, so prior must equal own_lo {own_lo[b]}, got {prior[b]}")
+        if b and slot[b] < slot[b - 1]:
+            raise ValueError(f"row {b}: slots must ascend through the batch, {slot[b]} follows {slot[b - 1]}")
+        if b and slot[b] == slot[b - 1]:
+            if reset[b]:
+                raise ValueError(f"row {b}: only the first row of slot {slot[b]} in the batch may be a reset row")
+            if parity[b] != parity[b - 1]:
+                raise ValueError(f"row {b}: the rows of slot {slot[b]} must carry one parity")
+            if prior[b] != prior[b - 1] + own_hi[b - 1] - own_lo[b - 1]:
+                raise ValueError(f"row {b}: the rows of slot {slot[b]} must be in window order: prior {prior[b]} should be "
+                                 f"{prior[b - 1] + own_hi[b - 1] - own_lo[b - 1]}, the frames up to the end of row {b - 1}'s core")
+    return slot, own_lo, own_hi, prior, [1 if v else 0 for v in reset], parity
+
+
+def norm_running_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: int, norm_running, carry: torch.Tensor,
+                       stats: torch.Tensor) -> torch.Tensor:
+    """Running InstanceNorm sums of one tensor with one norm point's carry (``fastsvc_norm_running_stats``,
+    csrc/fastsvc_normgroup.hip): ``u`` (B, C, ld) float32, bfloat16 or float16 on the device, row b valid for ``lens[b] *
+    len_mul`` columns (``None``: ``ld``), ``norm_running = (slot, own_lo, own_hi, prior, reset, parity)`` in frames
+    (``check_norm_running``).  ``carry`` (n_slots, 2, C, 2) float64: entry ``parity`` of a slot's record is read (not for a
+    reset row), entry ``parity ^ 1`` receives the slot's new carry - the caller flips its parity.  ``stats`` (B, C, 2)
+    float64 receives ``decode.pool_running_sums``' values for every row that is not a pass-through row (reset, ``own_lo ==
+    0``); those rows' entries are left untouched.  Two launches on the current stream.  Returns ``stats``."""
+    lib = load_library()
+    if not isinstance(u, torch.Tensor) or not u.is_cuda:
+        raise FastSVCError("norm_running_stats needs GPU tensors (no CPU fallback); got " + str(getattr(u, "device", type(u))))
+    codes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+    if u.dim() != 3 or u.dtype not in codes or not u.is_contiguous():
+        raise ValueError(f"u must be a contiguous (B, C, ld) float32 / bfloat16 / float16 tensor; got {tuple(u.shape)} {u.dtype}")
+    B, C, ld = u.shape
+    len_mul = int(len_mul)
+    if len_mul < 1 or ld % len_mul:
+        raise ValueError(f"the pitch {ld} must be a multiple of len_mul {len_mul}")
+    if lens is not None and (len(lens) != B or min(lens) < 1 or max(lens) * len_mul > ld):
+        raise ValueError(f"lens must hold {B} frame counts in [1, {ld // len_mul}]")
+    if not isinstance(stats, torch.Tensor) or stats.device != u.device or stats.dtype != torch.float64 or \
+            tuple(stats.shape) != (B, C, 2) or not stats.is_contiguous():
+        raise ValueError(f"stats must be a contiguous float64 {(B, C, 2)} tensor on {u.device}")
+    if not isinstance(carry, torch.Tensor) or carry.device != u.device or carry.dtype != torch.float64 or carry.dim() != 4 or \
+            tuple(carry.shape[1:]) != (2, C, 2) or carry.shape[0] < 1 or not carry.is_contiguous():
+        raise ValueError(f"carry must be a contiguous float64 (n_slots, 2, {C}, 2) tensor on {u.device}")
+    arrays = check_norm_running(norm_running, lens if lens is not None else [ld // len_mul] * B, carry.shape[0])
+    dev = u.device
+    ints = torch.tensor(list(arrays) + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
+    scratch = torch.empty(B * C * (-(-ld // 2048)) * 32, dtype=torch.uint8, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib, lib.fastsvc_norm_running_stats(ptr(u), codes[u.dtype], B, C, ld, ptr(ints[6]) if lens is not None else None,
+                                                   len_mul, *[ptr(ints[i]) for i in range(6)], ptr(carry), ptr(stats),
+                                                   ptr(scratch), scratch.numel(), ctypes.c_void_p(stream)),
+               "fastsvc_norm_running_stats")
+    return stats
+
+
 def _check(lib, rc: int, what: str):
     if rc != 0:
         msg = lib.fastsvc_last_error().decode("utf-8", "replace")
@@ -1020,6 +1116,14 @@ class Plan:
     def norm_group_scratch_bytes(self, B: int, F: int) -> int:
         """Bytes of device scratch one forward with ``norm_groups`` needs for its partial sums."""
         return int(self.lib.fastsvc_norm_group_scratch_bytes(self._h, B, F))
+
+    def norm_carry_bytes(self) -> int:
+        """Bytes of ONE slot's carry record for ``norm_running``: both parity entries of every norm point's C x 2 doubles."""
+        return int(self.lib.fastsvc_norm_carry_bytes(self._h))
+
+    def norm_running_scratch_bytes(self, B: int, F: int) -> int:
+        """Bytes of device scratch one forward with ``norm_running`` needs for its partial sums."""
+        return int(self.lib.fastsvc_norm_running_scratch_bytes(self._h, B, F))
 
     def padded_frames(self, F: int) -> int:
         """Frame count the library actually runs for an F-frame batch: the next multiple of 4 (the padded batch is run
@@ -1213,7 +1317,8 @@ class Plan:
                 spk_emb: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None, profile: Optional[list] = None,
                 autotune: bool = False, lengths=None, norm_groups=None,
-                norm_scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+                norm_scratch: Optional[torch.Tensor] = None, norm_running=None,
+                norm_carry: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Enqueue one forward on the current HIP stream of ``ppg.device``; returns (B, O, T).
 
         ``lengths`` (B frame counts, 1 <= n <= F; sequence or int tensor) makes the batch ragged:
@@ -1226,6 +1331,15 @@ class Plan:
         in their group that own all their frames run exactly as without it.  Not with ``profile`` or ``autotune``.
         ``norm_scratch``: a uint8 device tensor of at least ``norm_group_scratch_bytes(B, padded_frames(F))`` bytes for the
         partial sums (allocated per call when missing).
+
+        ``norm_running = (slot, own_lo, own_hi, prior, reset, parity)`` (six sequences of B ints, ``check_norm_running``)
+        with ``norm_carry``, a contiguous 2-D device tensor of one record per slot (``norm_carry_bytes()`` bytes a row, or
+        more), makes the rows windows of live streams (``fastsvc_forward_running``): each is normalised by the statistics
+        of every frame of its stream up to its right edge, the sums of earlier windows read from the slot's record, entry
+        ``parity``, and the new ones written to entry ``parity ^ 1`` - the CALLER flips a slot's parity after the call.
+        Not with ``norm_groups``, ``profile`` or ``autotune``; ``norm_scratch`` then needs
+        ``norm_running_scratch_bytes(B, padded_frames(F))`` bytes.  Without ``spk_emb`` nothing is normalised and nothing
+        carried.
 
         With ``profile`` (a list) the launches are bracketed by hipEvents on that stream, the
         stream is synchronised and one dict per kernel launch is appended to the list.
@@ -1256,6 +1370,21 @@ class Plan:
             if isinstance(lengths, torch.Tensor):
                 raise ValueError("norm_groups needs lengths on the host (the owned ranges are checked against them)")
             norm_groups = check_norm_groups(norm_groups, [F] * B if lengths is None else [int(v) for v in lengths])
+        if norm_running is not None:
+            if norm_groups is not None:
+                raise ValueError("norm_running and norm_groups exclude each other")
+            if profile is not None or autotune:
+                raise ValueError("norm_running runs neither profiled nor under autotune")
+            if isinstance(lengths, torch.Tensor):
+                raise ValueError("norm_running needs lengths on the host (the cores are checked against them)")
+            row = 0 if not isinstance(norm_carry, torch.Tensor) or norm_carry.dim() != 2 else norm_carry.shape[1] * norm_carry.element_size()
+            if row < self.norm_carry_bytes() or row % 8 or norm_carry.device != dev or not norm_carry.is_contiguous():
+                raise ValueError(f"norm_running needs norm_carry: a contiguous (n_slots, k) tensor on {dev} with rows of at least "
+                                 f"norm_carry_bytes() = {self.norm_carry_bytes()} bytes, a multiple of 8")
+            norm_running = check_norm_running(norm_running, [F] * B if lengths is None else [int(v) for v in lengths],
+                                              norm_carry.shape[0])
+        elif norm_carry is not None:
+            raise ValueError("norm_carry goes with norm_running")
         if F % 4 != 0 and profile is None and (self.storage != "float32" or self.pad_odd_lengths):
             # bfloat16 / float16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0
             # (three of four real utterances are not); float32 storage runs such rows on its slower kernels.  Pad to
@@ -1292,7 +1421,8 @@ class Plan:
                     raise ValueError("autotune times full-length batches: call it without lengths")
                 self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None, autotune=True)
             self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None,
-                         lengths=[F] * B if lengths is None else lengths, norm_groups=norm_groups, norm_scratch=norm_scratch)
+                         lengths=[F] * B if lengths is None else lengths, norm_groups=norm_groups, norm_scratch=norm_scratch,
+                         norm_running=norm_running, norm_carry=norm_carry)
             if out is None:
                 return py[..., :T].contiguous()
             out.copy_(py[..., :T])
@@ -1345,6 +1475,17 @@ class Plan:
                                                       common[10], common[11], ctypes.c_void_p(norm_scratch.data_ptr()),
                                                       norm_scratch.numel() * norm_scratch.element_size(), common[12])
                 workspace = (workspace, ng, norm_scratch)
+            elif norm_running is not None and spk_emb is not None:
+                need = self.norm_running_scratch_bytes(B, F)
+                if norm_scratch is None or norm_scratch.numel() * norm_scratch.element_size() < need or norm_scratch.device != dev:
+                    norm_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+                nr = self._stage_lengths(torch.tensor(norm_running, dtype=torch.int32).reshape(-1), 6 * B, dev)
+                rc = self.lib.fastsvc_forward_running(*common[:10], *[ctypes.c_void_p(nr[i * B:].data_ptr()) for i in range(6)],
+                                                      ctypes.c_void_p(norm_carry.data_ptr()),
+                                                      norm_carry.shape[1] * norm_carry.element_size(), common[10], common[11],
+                                                      ctypes.c_void_p(norm_scratch.data_ptr()),
+                                                      norm_scratch.numel() * norm_scratch.element_size(), common[12])
+                workspace = (workspace, nr, norm_scratch, norm_carry)
             elif profile is None:
                 rc = self.lib.fastsvc_forward(*common)
             else:

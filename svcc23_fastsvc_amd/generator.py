@@ -315,7 +315,8 @@ class FastSVCGenerator(nn.Module):
             self.invalidate_packed_weights()         # (never for today's plans: the packer ignores the storage)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, s, l, spk_emb=None, *, lengths=None, out=None, norm_groups=None, norm_scratch=None):
+    def forward(self, x, s, l, spk_emb=None, *, lengths=None, out=None, norm_groups=None, norm_scratch=None,
+                norm_running=None, norm_carry=None):
         """x (B, in_channels, F) PPG - s (B, 1, T) sine - l (B, 1, T) loudness -
         spk_emb (B, spk_emb_size) or None  ->  (B, out_channels, T), T = F * prod(scales).
         Same contract as fastsvc.py:305-332 (raw conv_last output, no tanh).
@@ -328,7 +329,10 @@ class FastSVCGenerator(nn.Module):
         frames ``[own_lo[b], own_hi[b])`` of its own and is normalised by the mean and variance of the owned frames of every
         row r with ``group[r] == group[b]`` (``group[b]`` = index of the group's first row).  The windows of one utterance
         are such a group (``DecodeSession.convert_windowed(norm="utterance")``).  ``None`` is the plain forward;
-        ``norm_scratch``: see ``Plan.forward``.
+        ``norm_scratch``: see ``Plan.forward``.  ``norm_running = (slot, own_lo, own_hi, prior, reset, parity)`` with
+        ``norm_carry`` (inference only, not with ``norm_groups``): the rows are windows of live streams, each normalised by
+        the statistics of every frame of its stream so far, carried on the device between forwards in ``norm_carry``
+        (``StreamSession(norm="running")``; ``Plan.forward`` has the contract).
 
         Autograd: whenever grad mode is enabled and a parameter or an input requires grad, the output carries a graph
         (``train()`` and ``eval()`` alike, as for any ``nn.Module``).  The plain HIP forward runs under
@@ -350,7 +354,8 @@ class FastSVCGenerator(nn.Module):
         needs_grad = torch.is_grad_enabled() and not self.inference_only and (
             any(p.requires_grad for p in self.parameters()) or
             any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, s, l, spk_emb)))
-        if needs_grad and not self.training and (lengths is not None or out is not None or norm_groups is not None):
+        if needs_grad and not self.training and (lengths is not None or out is not None or norm_groups is not None or
+                                                   norm_running is not None):
             needs_grad = False
         if needs_grad:
             # training (train_fastsvc.py:157-240 calls the module under autograd): HIP forward, PyTorch-ROCm
@@ -361,11 +366,14 @@ class FastSVCGenerator(nn.Module):
                 raise ValueError("`out=` is an inference extension: no backward through it")
             if norm_groups is not None:
                 raise NotImplementedError("`norm_groups` is an inference extension: no backward")
+            if norm_running is not None:
+                raise NotImplementedError("`norm_running` is an inference extension: no backward")
             from .autograd import forward_with_grad
             return forward_with_grad(self, x, s, l, spk_emb)
-        return self._forward_device(x, s, l, spk_emb, lengths, out, norm_groups, norm_scratch)
+        return self._forward_device(x, s, l, spk_emb, lengths, out, norm_groups, norm_scratch, norm_running, norm_carry)
 
-    def _forward_device(self, x, s, l, spk_emb, lengths, out=None, norm_groups=None, norm_scratch=None):
+    def _forward_device(self, x, s, l, spk_emb, lengths, out=None, norm_groups=None, norm_scratch=None, norm_running=None,
+                        norm_carry=None):
         """The HIP forward proper (no autograd): packed weights, workspace sub-batching, C-ABI call."""
         hop = self._cfg.hop
         B, _, F = x.shape
@@ -378,13 +386,14 @@ class FastSVCGenerator(nn.Module):
         Fw = plan.padded_frames(F)                 # (frame counts are run padded to a multiple of 4, as a ragged batch)
         while step > 1 and plan.workspace_bytes(step, Fw) > self.max_workspace_bytes:
             step = (step + 1) // 2
-        if norm_groups is not None and step != B:
-            raise FastSVCError(f"a batch with norm_groups runs as one forward: {B} rows of {F} frames need "
+        if (norm_groups is not None or norm_running is not None) and step != B:
+            raise FastSVCError(f"a batch with norm_groups or norm_running runs as one forward: {B} rows of {F} frames need "
                                f"{plan.workspace_bytes(B, Fw)} bytes of workspace, max_workspace_bytes is {self.max_workspace_bytes}")
         if step == B:
-            tune = bool(self.autotune) and lengths is None and norm_groups is None and (B, F, str(x.device)) not in self._tuned_shapes
+            tune = bool(self.autotune) and lengths is None and norm_groups is None and norm_running is None and \
+                (B, F, str(x.device)) not in self._tuned_shapes
             y = plan.forward(blob, x, s, l, spk_emb, autotune=tune, lengths=lengths, out=out, norm_groups=norm_groups,
-                             norm_scratch=norm_scratch)
+                             norm_scratch=norm_scratch, norm_running=norm_running, norm_carry=norm_carry)
             if tune:
                 self._tuned_shapes.add((B, F, str(x.device)))
         else:

@@ -14,7 +14,12 @@ the same number of yardstick batches; the two legs alternate, STREAM_REPS (defau
 the repetitions' means are reported with their spread.  Real-time factor: seconds of audio a push delivers (streams x
 core x hop / sample rate) over the push time.  The figures go to profiles/decode_stream.txt.
 
-    python tools/stream_latency.py"""
+--norm times another pair of legs instead: the same steady-state push in a StreamSession(norm="running") against a
+StreamSession(norm="window") fed the same chunks - two sessions alive in one process, alternated repetition by repetition.
+The running session carries its InstanceNorm sums on the device: one more read of the three FiLM-affined tensors of every
+up block and 24 small launches per forward.  Its figures go to profiles/decode_stream_norm.txt.
+
+    python tools/stream_latency.py [--norm]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -150,5 +155,52 @@ def main():
         f.write("\n".join(out) + "\n")
 
 
+def main_norm():
+    out = [f"stream norm: one StreamSession.push that completes one window per stream (every stream delivers `core` frames), host "
+           f"to host, norm=\"running\" against norm=\"window\" on the same chunks, two sessions in one process; context {ctx}, fade "
+           f"{FADE}, speaker embedding, F0 shift on, int16 out; {pushes} pushes per repetition, {reps} repetitions, legs alternated, "
+           f"median of the repetitions' means (min, max); {torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for core in (32, 100):
+            for N in (1, 8, 32):
+                src = [features(core * 8) for _ in range(N)]
+                legs = {}
+                for norm in ("window", "running"):
+                    s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, norm=norm)
+                    legs[norm] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[])
+
+                def push(leg):
+                    a = (leg["step"] % 8) * core
+                    leg["step"] += 1
+                    return leg["s"].push({i: dict(ppg=f["ppg"][a: a + core], f0=f["f0"][a: a + core], lft=f["lft"][a * hop: (a + core) * hop])
+                                          for i, f in zip(leg["ids"], src)})
+                for leg in legs.values():
+                    for _ in range(6):                   # (fill the context, warm every shape)
+                        push(leg)
+                    before = leg["s"].forwards
+                    got = push(leg)
+                    assert leg["s"].forwards == before + 1 and all(v.size == core * hop for v in got.values())
+                for _ in range(reps):
+                    for leg in legs.values():
+                        t0 = time.perf_counter()
+                        for _ in range(pushes):
+                            push(leg)
+                        leg["t"].append((time.perf_counter() - t0) / pushes)
+                for leg in legs.values():
+                    leg["s"].end(leg["ids"])
+                    leg["s"].close()
+                audio = N * core * hop / SR
+                mw, line_w = spread(f"{N:2d} streams, core {core:3d}: push, norm=window", legs["window"]["t"], audio)
+                mr, line_r = spread(f"{N:2d} streams, core {core:3d}: push, norm=running", legs["running"]["t"], audio)
+                out += [line_w, line_r, f"    running / window {mr / mw:.3f} (+{(mr - mw) * 1e3:.0f} us a push)"]
+                print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream_norm.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 if __name__ == "__main__":
-    main()
+    main_norm() if "--norm" in sys.argv[1:] else main()
