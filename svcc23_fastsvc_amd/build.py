@@ -80,9 +80,10 @@ UNITS = [
 
 
 def build(force: bool = False, verbose: bool = False, timeline: bool = False) -> str:
-    """timeline=True: diagnostic build with per-wave cycle stamps in the pipelined kernel
-    (-DFASTSVC_TIMELINE, tools/timeline.py) written to libfastsvc_hip_timeline.so, which only
-    tools/timeline.py loads (FASTSVC_HIP_LIB); the product library is left untouched."""
+    """timeline=True: diagnostic build with per-wave cycle stamps in the pipelined kernel and in the
+    conditioning pipelines (-DFASTSVC_TIMELINE; tools/timeline.py, tools/cond_timeline.py) written to
+    libfastsvc_hip_timeline.so, which only those tools load (FASTSVC_HIP_LIB); the product library
+    is left untouched."""
     if not force and not timeline and not os.environ.get("FASTSVC_BUILD_OUT") and not needs_build():
         return LIB_PATH
     import hashlib

@@ -645,6 +645,44 @@ __device__ __forceinline__ void p0_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// FASTSVC_TIMELINE builds only (tools/cond_timeline.py; 2-byte storage): where the cycles of a pipeline STEP go inside a
+// wave.  One c1 wave (0), one layer wave (4: c3) and one heads wave (8) - the three share a SIMD - stamp the cycle counter at
+// five points of every step: 0 step start (past the barrier), 1 every fragment of the step arrived (an explicit lgkmcnt(0):
+// the product build waits fragment by fragment), 2 last product issued, 3 first accumulator read by the epilogue (a
+// v_readfirstlane of it: issued when the matrix pipe has delivered), 4 last LDS store done.  Every workgroup runs the stamps
+// (the same disturbance everywhere); lane 0 of workgroup (1, 0) writes steps CS_TL_STEP0 .. + CS_TL_STEPS to the buffer the
+// host passes in amax_hd, which the 2-byte instances do not use otherwise: [role][step][CS_TL_WORDS].  A sched_barrier on
+// both sides of a stamp keeps hipcc from moving work across it.  The product build has none of this: CsTl is empty.
+#if defined(FASTSVC_TIMELINE) && defined(FASTSVC_ACT_2B)
+constexpr int CS_TL_STEP0 = 32, CS_TL_STEPS = 256, CS_TL_WORDS = 8;
+struct CsTl {
+    unsigned long long* rows = nullptr;
+    unsigned long long t[5] = {0, 0, 0, 0, 0};
+    int probe = 0;
+};
+#define CS_TL_MARK(tl, i) do { __builtin_amdgcn_sched_barrier(0); (tl).t[i] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define CS_TL_LDS_DONE() __builtin_amdgcn_s_waitcnt(0xc07f)     /* lgkmcnt(0), vmcnt / expcnt untouched */
+#define CS_TL_PROBE(tl, v) do { (tl).probe = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (v))); } while (0)
+__device__ __forceinline__ void cs_tl_open(CsTl& tl, float* buf, int role) {
+    if (buf && blockIdx.x == 1 && blockIdx.z == 0) tl.rows = reinterpret_cast<unsigned long long*>(buf) + (long)role * CS_TL_STEPS * CS_TL_WORDS;
+}
+__device__ __forceinline__ void cs_tl_flush(const CsTl& tl, int s, int lane) {
+    if (tl.rows && lane == 0 && (unsigned)(s - CS_TL_STEP0) < (unsigned)CS_TL_STEPS) {
+        unsigned long long* row = tl.rows + (s - CS_TL_STEP0) * CS_TL_WORDS;
+        #pragma unroll
+        for (int i = 0; i < 5; ++i) row[i] = tl.t[i];
+        row[5] = (unsigned)tl.probe;
+    }
+}
+#else
+struct CsTl {};
+#define CS_TL_MARK(tl, i) do {} while (0)
+#define CS_TL_LDS_DONE() do {} while (0)
+#define CS_TL_PROBE(tl, v) do {} while (0)
+__device__ __forceinline__ void cs_tl_open(CsTl&, float*, int) {}
+__device__ __forceinline__ void cs_tl_flush(const CsTl&, int, int) {}
+#endif
+
 // packed tile values, computed once and stored twice where a tile also feeds guard rows: the copy goes through a SELECT of
 // the destination (lanes outside the mirrored rows store into a dummy slot nobody reads) instead of a divergent branch
 struct CsPk4 { cs_u2 h, l; };
@@ -698,7 +736,7 @@ template <int N, int POS, int KIND>
 __device__ __forceinline__ void p0_layer_chunk(const unsigned char* in_plane, unsigned char* out_base, const CsW (&W)[3][2],
                                                const int (&rd)[3], const int (&wr)[2], const f32x4 (&kbv)[2], const f32x4 (&kivv)[2],
                                                const f32x4 (&r1wv)[2], const float (&xv)[N], int tstart, int Tv, int lane,
-                                               unsigned char* dummy /* this lane's 32 bytes nobody reads */) {
+                                               unsigned char* dummy /* this lane's 32 bytes nobody reads */, CsTl& tl) {
     using GEO = P0Geom<N>;
     constexpr int lo_off = GEO::PLANE_P;
     constexpr int NTL3 = 3 * N;
@@ -713,6 +751,8 @@ __device__ __forceinline__ void p0_layer_chunk(const unsigned char* in_plane, un
         #pragma unroll
         for (int tap = 0; tap < 3; ++tap) a[i][tap] = cs_read(in_plane, rd[tap] + PIN * 16 * CS_ROW, lo_off);
     }
+    CS_TL_LDS_DONE();
+    CS_TL_MARK(tl, 1);
     f32x4 acc[N][2];
     #pragma unroll
     for (int i = 0; i < N; ++i)
@@ -733,6 +773,7 @@ __device__ __forceinline__ void p0_layer_chunk(const unsigned char* in_plane, un
         for (int i = 0; i < N; ++i)
             #pragma unroll
             for (int m = 0; m < 2; ++m) acc[i][m] = cs_prod<true>(W[tap][m], a[i][tap], acc[i][m]);
+    CS_TL_MARK(tl, 2); CS_TL_PROBE(tl, acc[0][0].x); CS_TL_MARK(tl, 3);
     #pragma unroll
     for (int i = 0; i < N; ++i) {
         const int P = POS * N + i;                     // (compile-time after unrolling)
@@ -754,6 +795,8 @@ __device__ __forceinline__ void p0_layer_chunk(const unsigned char* in_plane, un
             if (P == NTL3 - 1) { unsigned char* g2 = l15 >= 8 ? dst - GEO::RING * CS_ROW : dummy; cs_put4(g2, g2 + (l15 >= 8 ? lo_off : 16), pk); }
         }
     }
+    CS_TL_LDS_DONE();
+    CS_TL_MARK(tl, 4);
 }
 
 template <int N>
@@ -882,13 +925,18 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
         for (int j = 0; j < 3; ++j) { xrequest(j); xcommit(j); }
         xrequest(3);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");       // (the wave's own reads below follow its writes in order)
+        CsTl tl;                                               // (a VALU role: no product phase - stamps 1, 2, 3 coincide)
+        if (wave == 0) cs_tl_open(tl, p.amax_hd, 0);
         p0_steps(nsteps, [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
+            CS_TL_MARK(tl, 0);
             if (s < Ktot && !(dbg & 8)) {
                 constexpr int POS = J;
                 const int tc0 = T0 - 64 + s * NT;
                 const int u = BLK + s * NT + col;              // ring index of this lane's column
                 float xa = xs[(u - 1) & (XR - 1)], xb = xs[u & (XR - 1)], xc = xs[(u + 1) & (XR - 1)];
+                CS_TL_LDS_DONE();
+                CS_TL_MARK(tl, 1); CS_TL_MARK(tl, 2); CS_TL_MARK(tl, 3);
                 xa = fmaxf(xa, xa * LRELU_SLOPE); xb = fmaxf(xb, xb * LRELU_SLOPE); xc = fmaxf(xc, xc * LRELU_SLOPE);
                 const f32x2 xa2 = {xa, xa}, xb2 = {xb, xb}, xc2 = {xc, xc};
                 const bool edge = tc0 < 0 || tc0 + NT > Tv;
@@ -916,6 +964,8 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
                     if (POS == 0) { unsigned char* g2 = col < 8 ? dst + RING * CS_ROW : dummy; cs_put8(g2, g2 + (col < 8 ? lo_off : 16), pk); }
                     if (POS == 2) { unsigned char* g2 = col >= NT - 8 ? dst - RING * CS_ROW : dummy; cs_put8(g2, g2 + (col >= NT - 8 ? lo_off : 16), pk); }
                 }
+                CS_TL_LDS_DONE();
+                CS_TL_MARK(tl, 4);
             }
             // block turn-over every XB steps: commit block m + 2 (requested XB steps ago; first needed by the last chunk of
             // this block of steps), request block m + 3 - into the slot of block m - 1, whose last reader (c3, two steps
@@ -925,6 +975,7 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
                 xcommit(m + 2);
                 xrequest(m + 3);
             }
+            cs_tl_flush(tl, s, lane);
         });
     } else if (wave < 8) {
         // ================= c2 / c3 / film.conv of one signal: both 16-channel output tiles per fragment =================
@@ -960,19 +1011,23 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
         float xv[N];
         #pragma unroll
         for (int i = 0; i < N; ++i) xv[i] = 0.f;
+        CsTl tl;
+        if (wave == 4) cs_tl_open(tl, p.amax_hd, 1);
         p0_steps(nsteps, [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
             const int k = s - L;
+            CS_TL_MARK(tl, 0);
             if (k >= 0 && k < Ktot && !(dbg & 16)) {
                 constexpr int P1 = (J + 2) % 3, P2 = (J + 1) % 3, P3 = J;       // (J - L) mod 3
                 const int tstart = T0 - 64 + 16 * (k * N - L);
-                if (L == 1) p0_layer_chunk<N, P1, 0>(in_plane, out_base, W, rd, wr, kbv, kivv, r1wv, xv, tstart, Tv, lane, dummy);
+                if (L == 1) p0_layer_chunk<N, P1, 0>(in_plane, out_base, W, rd, wr, kbv, kivv, r1wv, xv, tstart, Tv, lane, dummy, tl);
                 else if (L == 2) {
                     #pragma unroll
                     for (int i = 0; i < N; ++i) xv[i] = xs[(GEO::BLK + 16 * (k * N - 2) + 16 * i + l15) & (GEO::XR - 1)];   // the raw signal at c3's columns
-                    p0_layer_chunk<N, P2, 1>(in_plane, out_base, W, rd, wr, kbv, kivv, r1wv, xv, tstart, Tv, lane, dummy);
-                } else p0_layer_chunk<N, P3, 2>(in_plane, out_base, W, rd, wr, kbv, kivv, r1wv, xv, tstart, Tv, lane, dummy);
+                    p0_layer_chunk<N, P2, 1>(in_plane, out_base, W, rd, wr, kbv, kivv, r1wv, xv, tstart, Tv, lane, dummy, tl);
+                } else p0_layer_chunk<N, P3, 2>(in_plane, out_base, W, rd, wr, kbv, kivv, r1wv, xv, tstart, Tv, lane, dummy, tl);
             }
+            cs_tl_flush(tl, s, lane);
         });
     } else if (wave < 11) {
         // ================= heads: [scale ; shift] = conv3([u_lft ; u_sine]) + b5, one 16-channel output tile per wave =================
@@ -991,9 +1046,12 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
         if constexpr (CS_NP == 2) oinv = k5inv[m5 * 16 + l15];
         const unsigned char* upl = planes + 6 * PLANE;
         const int srow = (m5 * 16 + l15) * GEO::SP + 4 * g * (int)sizeof(act_t);
+        CsTl tl;
+        if (wave == 8) cs_tl_open(tl, p.amax_hd, 2);
         p0_steps(nsteps, [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
             const int k = s - 4;
+            CS_TL_MARK(tl, 0);
             if (k >= LAG && k < Ktot && !(dbg & 32)) {
                 constexpr int POS = (J + 2) % 3;               // (J - 4) mod 3
                 unsigned char* sb = stg + (s & 1) * GEO::STG + srow;
@@ -1010,11 +1068,13 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
                             #pragma unroll
                             for (int tap = 0; tap < 3; ++tap) a[ii][tap] = cs_read(upl + ch * PLANE, rd[tap] + PIN * 16 * CS_ROW, lo_off);
                         }
+                        if (i0 == 0 && ch == 0) { CS_TL_LDS_DONE(); CS_TL_MARK(tl, 1); }
                         #pragma unroll
                         for (int tap = 0; tap < 3; ++tap)
                             #pragma unroll
                             for (int ii = 0; ii < 2; ++ii) acc[ii] = cs_prod<false>(W5[ch][tap], a[ii][tap], acc[ii]);
                     }
+                    if (i0 == N - 2) { CS_TL_MARK(tl, 2); CS_TL_PROBE(tl, acc[0].x); CS_TL_MARK(tl, 3); }
 #ifdef FASTSVC_ACT_2B
                     cs_u2 outv[2];
 #else
@@ -1034,7 +1094,10 @@ void cond_stage0_pipe_kernel(const CondStage0Params p) {
 #endif
                     }
                 }
+                CS_TL_LDS_DONE();
+                CS_TL_MARK(tl, 4);
             }
+            cs_tl_flush(tl, s, lane);
         });
     } else {
         // ================= copy-out: staged [scale ; shift] rows -> ss (16 bytes per lane), h[::s'] -> hd =================
@@ -1653,7 +1716,7 @@ template <int POS, int NC, bool IN96, int KIND>
 __device__ __forceinline__ void q1_layer_chunk(const unsigned char* in_plane, unsigned char* out_base, const CsW* W /* [NC][3][3] */,
                                                const CsW* W1 /* [3], KIND 1 */, const unsigned char* xraw_tile0, const unsigned char* xraw_tile1,
                                                const int (&rd)[3], const int (&wr)[3], const f32x4 (&kbv)[3], int tstart, int Tv, int lane,
-                                               unsigned char* dummy) {
+                                               unsigned char* dummy, CsTl& tl) {
     using GEO = Q1Geom;
     constexpr int N = GEO::N, NTL3 = 3 * N;
     constexpr int TS_IN = 16 * (IN96 ? 96 : 64), TS_OUT = 16 * (KIND == 2 ? 64 : 96), GOFF = GEO::RING * (KIND == 2 ? 64 : 96);
@@ -1681,6 +1744,7 @@ __device__ __forceinline__ void q1_layer_chunk(const unsigned char* in_plane, un
             #pragma unroll
             for (int tap = 0; tap < 3; ++tap) a[i][tap].p[0] = *reinterpret_cast<const cs8*>(in_plane + rd[tap] + ch * 64 + PIN * TS_IN);
         }
+        if (ch == 0) { CS_TL_LDS_DONE(); CS_TL_MARK(tl, 1); }
         #pragma unroll
         for (int tap = 0; tap < 3; ++tap)
             #pragma unroll
@@ -1688,6 +1752,7 @@ __device__ __forceinline__ void q1_layer_chunk(const unsigned char* in_plane, un
                 #pragma unroll
                 for (int m = 0; m < 3; ++m) acc[i][m] = cs_prod<true>(W[(ch * 3 + tap) * 3 + m], a[i][tap], acc[i][m]);
     }
+    CS_TL_MARK(tl, 2); CS_TL_PROBE(tl, acc[0][0].x); CS_TL_MARK(tl, 3);
     #pragma unroll
     for (int i = 0; i < N; ++i) {
         const int P = POS * N + i;
@@ -1706,6 +1771,8 @@ __device__ __forceinline__ void q1_layer_chunk(const unsigned char* in_plane, un
             if (P == NTL3 - 1) { unsigned char* g2 = l15 >= 8 ? dst - GOFF : dummy; cs_put4(g2, g2, pk); }
         }
     }
+    CS_TL_LDS_DONE();
+    CS_TL_MARK(tl, 4);
 }
 
 __global__ __launch_bounds__(Q1_NTHREADS, 1)
@@ -1747,17 +1814,26 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
         // ================= stage-in of this signal's input + c1 = lrelu(conv3(lrelu(x)) + b1) =================
         const int sig = wave;
         const __amdgpu_buffer_rsrc_t xr = act_rsrc(reinterpret_cast<const float*>(p.x), sig * p.x_sig + (long)b * p.x_b, (long)C1_CIN * p.ldx);
-        const bool has_item = lane < 24;
-        const int it_q = lane / 3, it_o = lane - it_q * 3;     // rows 4 q .. 4 q + 3 of the chunk, octet o
+        // item = (two rows of the chunk, octet of 8 channels): 48 lanes, one 4-byte load per channel.  (As 24 items of four
+        // rows - 8-byte loads, three sets of 16 registers in flight - this role was over the register budget: hipcc kept an LDS
+        // address in scratch, and the reload's `s_waitcnt vmcnt(0)` - scratch loads return through the same in-order counter -
+        // also waited for the rows requested a moment before for two steps ahead: a memory latency per step, the pace of the
+        // whole pipeline, tools/cond_timeline.py.)
+        constexpr int RPI = 2;                                 // rows per item
+        const bool has_item = lane < 3 * (NT / RPI);
+        const int it_q = lane / 3, it_o = lane - it_q * 3;     // rows 2 q, 2 q + 1 of the chunk, octet o
         unsigned char* xact = L + GEO::O_XACT + sig * GEO::P64;
         unsigned char* xraw = L + GEO::O_XRAW + sig * GEO::XRAW;
-        cs_u2 px[3][8];                                        // three chunks in flight: requested two steps before their commit
-        auto request = [&](cs_u2 (&set)[8], int k0) {
-            const int t = torg + k0 * NT + 4 * it_q;
-            const bool tok = has_item && (unsigned)t < (unsigned)Tv && k0 < Ktot;
+        unsigned px[3][8];                                     // three chunks in flight: requested two steps before their commit
+        auto request = [&](unsigned (&set)[8], int k0) {
+            const int t = torg + k0 * NT + RPI * it_q;
+            // (the choice between a row's offset and the out-of-range one as a bit mask hipcc cannot see through: as a select of the
+            // offsets it became two branches with a load each - and a vmcnt(0) where they join)
+            int ok = (has_item && (unsigned)t < (unsigned)Tv && k0 < Ktot) ? -1 : 0;
+            asm("" : "+v"(ok));
             #pragma unroll
             for (int c = 0; c < 8; ++c)
-                set[c] = __builtin_amdgcn_raw_buffer_load_b64(xr, tok ? ((it_o * 8 + c) * p.ldx + t) * 2 : OOB_OFF, 0, 0);
+                set[c] = __builtin_amdgcn_raw_buffer_load_b32(xr, ((((it_o * 8 + c) * p.ldx + t) * 2) & ok) | (OOB_OFF & ~ok), 0, 0);
         };
         CsW W[9];
         #pragma unroll
@@ -1774,23 +1850,30 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
             wr[m] = (GUARD + l15) * 96 + (16 * m + 4 * g) * 2;
             kbv[m] = *reinterpret_cast<const f32x4*>(k1b + sig * 64 + 16 * m + 4 * g);
         }
+        // (the weights have landed before the first rows are requested: a wait for them inside the step loop, counted from this
+        // prologue, would also wait for rows requested a step before)
+        __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0)
         request(px[0], 0);
         request(px[1], 1);
         int xrt = 0;                                           // tile of the raw ring the next chunk goes to
+        CsTl tl;
+        if (wave == 0) cs_tl_open(tl, p.amax_hd, 0);
         p0_steps(nsteps, [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
+            CS_TL_MARK(tl, 0);
+            // the rows of chunk s + 2 are requested in EVERY step (past the last chunk: out of range, nothing is fetched).  Under
+            // `s < Ktot` hipcc could not count the loads issued between a set's request and its use - a path that skips a request
+            // has eight fewer - and waited with vmcnt(8) instead of vmcnt(16), i.e. also for the set requested ONE step before:
+            // the stage-in then waited a memory latency in every step.
+            request(px[(J + 2) % 3], s + 2);
             if (s < Ktot) {
                 // ---- stage-in of chunk s: raw -> the 12-tile ring, LeakyReLU'd -> position J of the 3-chunk ring ----
-                request(px[(J + 2) % 3], s + 2);
                 if (has_item) {
                     #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
+                    for (int j = 0; j < RPI; ++j) {
                         unsigned short e[8];
                         #pragma unroll
-                        for (int c = 0; c < 8; ++c) {
-                            const unsigned w = j < 2 ? px[J][c].x : px[J][c].y;
-                            e[c] = (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu));
-                        }
+                        for (int c = 0; c < 8; ++c) e[c] = (unsigned short)(j ? (px[J][c] >> 16) : (px[J][c] & 0xffffu));
                         const u32x4 raw = {(unsigned)e[0] | ((unsigned)e[1] << 16), (unsigned)e[2] | ((unsigned)e[3] << 16),
                                            (unsigned)e[4] | ((unsigned)e[5] << 16), (unsigned)e[6] | ((unsigned)e[7] << 16)};
                         f32x4 lo4, hi4;
@@ -1800,7 +1883,7 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
                             hi4[c] = a16_lo((unsigned)e[4 + c]);
                         }
                         const CsPk8 act = cs_pack8(cs_lrelu4(lo4), cs_lrelu4(hi4), 0xffffffffu);
-                        const int rr = 4 * it_q + j;
+                        const int rr = RPI * it_q + j;
                         *reinterpret_cast<u32x4*>(xraw + cs_off(xrt * 16 + rr, it_o)) = raw;
                         unsigned char* dst = xact + cs_off(GUARD + J * NT + rr, it_o);
                         cs_put8(dst, dst, act);
@@ -1813,7 +1896,8 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
             const int k = s - 1;
             if (k >= 0 && k < Ktot)
                 q1_layer_chunk<(J + 2) % 3, 1, false, 0>(xact, L + GEO::O_C1 + sig * GEO::P96, W, nullptr, nullptr, nullptr, rd, wr, kbv,
-                                                         torg + 16 * (k * N - 1), Tv, lane, dummy);
+                                                         torg + 16 * (k * N - 1), Tv, lane, dummy, tl);
+            cs_tl_flush(tl, s, lane);
         });
     } else if (wave < 8) {
         // ================= c2 / c3 / film.conv of one signal =================
@@ -1846,18 +1930,22 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
         unsigned char* out_base = L + (Lr == 2 ? GEO::O_C2 + sig * GEO::P96 : Lr == 3 ? GEO::O_H + sig * GEO::P96 : GEO::O_U);
         const unsigned char* xraw = L + GEO::O_XRAW + sig * GEO::XRAW;
         int xrt = GEO::XRT - 3;                                // c3's chunk 0 starts 3 tiles in front of the raw ring's tile 0
+        CsTl tl;
+        if (wave == 4) cs_tl_open(tl, p.amax_hd, 1);
         p0_steps(nsteps, [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
             const int k = s - Lr;
+            CS_TL_MARK(tl, 0);
             if (k >= 0 && k < Ktot) {
                 const int tstart = torg + 16 * (k * N - Lr);
-                if (Lr == 2) q1_layer_chunk<(J + 1) % 3, 2, true, 0>(in_plane, out_base, W, W1, nullptr, nullptr, rd, wr, kbv, tstart, Tv, lane, dummy);
+                if (Lr == 2) q1_layer_chunk<(J + 1) % 3, 2, true, 0>(in_plane, out_base, W, W1, nullptr, nullptr, rd, wr, kbv, tstart, Tv, lane, dummy, tl);
                 else if (Lr == 3) {
                     const int t1 = xrt + 1 >= GEO::XRT ? 0 : xrt + 1;
-                    q1_layer_chunk<J, 2, true, 1>(in_plane, out_base, W, W1, xraw + xrt * 1024, xraw + t1 * 1024, rd, wr, kbv, tstart, Tv, lane, dummy);
+                    q1_layer_chunk<J, 2, true, 1>(in_plane, out_base, W, W1, xraw + xrt * 1024, xraw + t1 * 1024, rd, wr, kbv, tstart, Tv, lane, dummy, tl);
                     xrt = t1 + 1 >= GEO::XRT ? 0 : t1 + 1;
-                } else q1_layer_chunk<(J + 2) % 3, 2, true, 2>(in_plane, out_base, W, W1, nullptr, nullptr, rd, wr, kbv, tstart, Tv, lane, dummy);
+                } else q1_layer_chunk<(J + 2) % 3, 2, true, 2>(in_plane, out_base, W, W1, nullptr, nullptr, rd, wr, kbv, tstart, Tv, lane, dummy, tl);
             }
+            cs_tl_flush(tl, s, lane);
         });
     } else if (wave < 11) {
         // ================= heads: two of the six 16-channel output tiles per wave, both from one fragment =================
@@ -1876,9 +1964,12 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
         const float bias0 = k5b[(2 * hw) * 16 + l15], bias1 = k5b[(2 * hw + 1) * 16 + l15];
         const unsigned char* upl = L + GEO::O_U;
         const int srow = ((2 * hw) * 16 + l15) * GEO::SP + 4 * g * 2;
+        CsTl tl;
+        if (wave == 8) cs_tl_open(tl, p.amax_hd, 2);
         p0_steps(nsteps, [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
             const int k = s - 5;
+            CS_TL_MARK(tl, 0);
             if (k >= LAG && k < Ktot) {
                 constexpr int POS = (J + 1) % 3;               // (J - 5) mod 3
                 unsigned char* sb = L + GEO::O_STG + (s & 1) * GEO::STG + srow;
@@ -1894,6 +1985,7 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
                         #pragma unroll
                         for (int tap = 0; tap < 3; ++tap) a[i][tap].p[0] = *reinterpret_cast<const cs8*>(upl + ch * GEO::P64 + rd[tap] + PIN * 1024);
                     }
+                    if (ch == 0) { CS_TL_LDS_DONE(); CS_TL_MARK(tl, 1); }
                     #pragma unroll
                     for (int tap = 0; tap < 3; ++tap)
                         #pragma unroll
@@ -1901,12 +1993,16 @@ void cond_stage1_pipe_kernel(const CondStage1Params p) {
                             #pragma unroll
                             for (int mm = 0; mm < 2; ++mm) acc[i][mm] = cs_prod<false>(W5[mm][ch * 3 + tap], a[i][tap], acc[i][mm]);
                 }
+                CS_TL_MARK(tl, 2); CS_TL_PROBE(tl, acc[0][0].x); CS_TL_MARK(tl, 3);
                 #pragma unroll
                 for (int i = 0; i < N; ++i)
                     #pragma unroll
                     for (int mm = 0; mm < 2; ++mm)
                         *reinterpret_cast<cs_u2*>(sb + mm * 16 * GEO::SP + i * 32) = __builtin_bit_cast(cs_u2, __builtin_convertvector(acc[i][mm], cs4));
+                CS_TL_LDS_DONE();
+                CS_TL_MARK(tl, 4);
             }
+            cs_tl_flush(tl, s, lane);
         });
     } else {
         // ================= copy-out: staged [scale ; shift] rows -> ss, h[::s'] -> hd =================

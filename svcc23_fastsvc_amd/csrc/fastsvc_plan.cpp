@@ -1908,6 +1908,35 @@ bool timeline_launch(const char* layer, ConvParams& p, long wgs, int nchunks, co
     }
     return true;
 }
+
+// The conditioning pipelines' step timeline (fastsvc_cond.hip, CsTl; tools/cond_timeline.py): FASTSVC_TIMELINE_LAYER =
+// cond.0 / cond.1, 2-byte storage.  The stamp buffer [role][step][word] rides in amax_hd, which those instances do not use.
+template <class Params, class LaunchFn>
+bool cond_timeline_launch(const char* layer, Params& q, hipStream_t stream, LaunchFn&& fn, hipError_t& err) {
+    const char* want = std::getenv("FASTSVC_TIMELINE_LAYER");
+    const char* out = std::getenv("FASTSVC_TIMELINE_OUT");
+    if (!want || !out || std::strcmp(want, layer) != 0 || q.small != 2) return false;
+    constexpr long ROLES = 3, STEPS = 256, WORDS = 8;     // (CS_TL_STEPS, CS_TL_WORDS)
+    unsigned long long* dbuf = nullptr;
+    const size_t bytes = (size_t)(ROLES * STEPS * WORDS) * sizeof(unsigned long long);
+    if (hipMalloc(&dbuf, bytes) != hipSuccess) { err = hipErrorOutOfMemory; return true; }
+    hipMemsetAsync(dbuf, 0, bytes, stream);
+    q.amax_hd = reinterpret_cast<float*>(dbuf);
+    err = fn();
+    q.amax_hd = nullptr;
+    if (err != hipSuccess) { hipFree(dbuf); return true; }
+    hipStreamSynchronize(stream);
+    std::vector<unsigned long long> host((size_t)(ROLES * STEPS * WORDS));
+    hipMemcpy(host.data(), dbuf, bytes, hipMemcpyDeviceToHost);
+    hipFree(dbuf);
+    if (FILE* f = std::fopen(out, "wb")) {
+        const long hdr[8] = {ROLES, STEPS, WORDS, q.tpw & 0xffff, q.B, q.T, 0, 0};
+        std::fwrite(hdr, sizeof(long), 8, f);
+        std::fwrite(host.data(), sizeof(unsigned long long), host.size(), f);
+        std::fclose(f);
+    }
+    return true;
+}
 #endif
 
 // Launch-table keys end in nothing (float32 storage), "|b" (bfloat16) or "|h" (float16).  The float16 objects have
@@ -2499,6 +2528,12 @@ hipError_t run_cond_stage0(const CallCtx& cc, const float* blob, const float* si
                 4.0 * (double)(2 * (d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
         kname = std::string(q.small == 2 ? "cond_stage0_pipe<" : "cond_stage0<") + prod_tag(P.storage) + ">";
     }
+#ifdef FASTSVC_TIMELINE
+    if (!prof && P.storage != 0) {
+        hipError_t te = hipSuccess;
+        if (cond_timeline_launch("cond.0", q, stream, [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage0)(q, stream); }, te)) return te;
+    }
+#endif
     const hipError_t e = launch_tail(prof, stream, "cond.0", kname.c_str(), q.tpw & 0xffff, q.small, flops, bytes,
                                      [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage0)(q, stream); });
     if (e == hipSuccess && prof && trace_env && trace_buf) {
@@ -2564,6 +2599,12 @@ hipError_t run_cond_stage1(const CallCtx& cc, const float* blob, const float* x,
                 4.0 * (double)(2 * (d.rc1[0].w_floats + d.c2[0].w_floats + d.c3[0].w_floats + d.film[0].w_floats) + d.heads.w_floats);
         kname = std::string(q.small == 2 ? "cond_stage1_pipe<" : "cond_stage1<") + prod_tag(P.storage) + ">";
     }
+#ifdef FASTSVC_TIMELINE
+    if (!prof && P.storage != 0) {
+        hipError_t te = hipSuccess;
+        if (cond_timeline_launch("cond.1", q, stream, [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage1)(q, stream); }, te)) return te;
+    }
+#endif
     return launch_tail(prof, stream, "cond.1", kname.c_str(), q.tpw & 0xffff, q.small, flops, bytes,
                        [&]() { return FASTSVC_BY_STORAGE(P.storage, launch_cond_stage1)(q, stream); });
 }
