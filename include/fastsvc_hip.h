@@ -251,6 +251,45 @@ int fastsvc_norm_running_stats(const void* u, int32_t storage, int32_t B, int32_
                                const int32_t* prior, const int32_t* reset, const int32_t* parity, double* carry,
                                double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* fastsvc_forward_running with a FORGETTING HORIZON: what decode.StreamSession(norm="running", horizon=H) runs its windows
+ * through.  The running sums are forgotten exponentially - a frame j cores back counts with the product of the decays of
+ * the cores since - so the population a window is normalised by, and with it the float32 headroom the statistics cost,
+ * is bounded however long the stream lives.  Arguments as fastsvc_forward_running, and
+ *   decay    DEVICE, B doubles, 8-byte aligned, 0 < decay[b] <= 1: what the slot's running sum is multiplied by in front
+ *            of row b's core (exp(-core frames / H), computed by the caller; any value on a stream's first window)
+ *   weight   DEVICE, B doubles: the weighted frames row b is normalised over - the decayed frame count of the cores up
+ *            to its own plus its look-ahead frames, weight[b] >= lengths[b] - own_lo[b]
+ *   bound    DEVICE, B doubles, bound[b] >= weight[b]: weight[b] over the smallest weight a column of the row has
+ * The fold is fastsvc_forward_running's with ONE multiplication per row at a fixed place: the carry (or zero behind a
+ * reset row); then for each row q <= b of the slot, ascending, the sum times decay[q] - rounded once, not fused into the
+ * next addition - plus q's core chunks; behind row b's core the slot's new carry; plus b's look-ahead chunks - the
+ * statistics, written as S * len_b / N with N = weight[b] * columns per frame, a double.  Carry and statistics are the
+ * same bits however a stream's windows fall into calls.  prior[] is validated by the caller but counts nothing here.
+ * float32 storage: a column of weight w is bounded by sqrt(N / w), so the staging scale's bound becomes sqrt(bound[b] *
+ * columns per frame) where that exceeds sqrt(len_b).  Same launches as fastsvc_forward_running (the pool kernel is
+ * norm_running_decay_pool_kernel), same carry record, scratch and pass-through rule.  With every decay 1, weight[b] =
+ * prior[b] + lengths[b] - own_lo[b] and bound = weight the statistics and the carry are fastsvc_forward_running's bits.
+ * spk_emb == NULL: there is no norm; the extra arguments are ignored (may be NULL), the carry is untouched and the
+ * launches and bytes are fastsvc_forward's.  The arrays cannot be checked here; the Python layer validates them on the
+ * host (engine.check_norm_decay). */
+int fastsvc_forward_running_decay(const fastsvc_plan* plan, const void* dev_blob,
+                                  const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                                  float* out, int32_t B, int32_t F, const int32_t* lengths,
+                                  const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                                  const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                                  const double* decay, const double* weight, const double* bound,
+                                  void* carry, size_t carry_bytes,
+                                  void* workspace, size_t workspace_bytes,
+                                  void* scratch, size_t scratch_bytes, void* stream);
+
+/* The same two launches for ONE tensor and one norm point's carry: fastsvc_norm_running_stats with the three arrays
+ * above (bound is read by nobody here: there is no staging scale to raise).  Scratch and carry as there. */
+int fastsvc_norm_running_stats_decay(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                                     int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                                     const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                                     const double* decay, const double* weight, const double* bound, double* carry,
+                                     double* stats_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Creates (and calibrates, see the conventions above: synchronises `stream`) the helper streams / events
  * fastsvc_forward may use for `stream` on the current device, so that the forward itself allocates nothing and
  * never synchronises (call once per stream, e.g. before graph capture or a latency-critical first call).

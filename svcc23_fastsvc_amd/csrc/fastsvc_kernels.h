@@ -400,13 +400,21 @@ hipError_t launch_norm_group_pool(const double* part, double* st, int B, int C, 
 // as they are, only the carry is written (a reset row must be the first of its slot in the batch).
 // The six int arrays hold B entries; own_lo / own_hi / prior are clamped to the row, but slot[] IS followed: the caller
 // guarantees 0 <= slot[b] < the slots the carry holds (engine.check_norm_running).
+// With a FORGETTING HORIZON (fastsvc_forward_running_decay; decay, weight and bound non-null, B doubles each on the device,
+// all three or none) the pool is norm_running_decay_pool_kernel: the same fold with the running sum multiplied by decay[q]
+// in front of every row q's core chunks (the carry's row included: one rounding at a fixed place, so the bits still do
+// not depend on how windows fall into launches), N = weight[b] * len_mul as a double, and the amax raise taken from
+// bound[b] * len_mul columns instead of N - a column of the left context weighs less than one.  prior[]
+// then counts nothing.  Null pointers: the launch, its kernel's name and its bits are as before.
 hipError_t launch_norm_running_partials(const float* u, double* part, int B, int C, int ld, const int* lens, int len_mul,
                                         const int* own_lo, const int* own_hi, const int* prior, const int* reset,
                                         hipStream_t stream);
 hipError_t launch_norm_running_pool(const double* part, double* st, int B, int C, int ld, const int* lens, int len_mul,
                                     const int* slot, const int* own_lo, const int* own_hi, const int* prior,
                                     const int* reset, const int* parity, double* carry, long slot_stride,
-                                    long parity_stride, float* amax_raise, hipStream_t stream);
+                                    long parity_stride, float* amax_raise, hipStream_t stream,
+                                    const double* decay = nullptr, const double* weight = nullptr,
+                                    const double* bound = nullptr);
 
 // conv_last: 1x1, y[b][o][t] = bias[o] + sum_c w[o][c] * x[b][c][t]
 hipError_t launch_pointwise_out(const float* x, const float* w, const float* bias, float* y,

@@ -20,7 +20,8 @@
 // chunk over two ranges a row, core and look-ahead, and a PREFIX pool in place of the group pool: carry, earlier cores of
 // the slot in the batch, own core (the new carry), look-ahead (the statistics) - one left fold in float64, so the bits do
 // not depend on how windows fall into forwards.  The carry is a pair of entries per slot: a launch reads entry `parity` and
-// writes entry `parity ^ 1`, no workgroup reads what another writes (fastsvc_kernels.h).
+// writes entry `parity ^ 1`, no workgroup reads what another writes (fastsvc_kernels.h).  With a forgetting
+// horizon (fastsvc_forward_running_decay) the fold multiplies the running sum by a per-row decay in front of every core.
 // Compiled three times (build.py): float32, bfloat16 and binary16 activation storage; the pools are defined once.
 #include "fastsvc_kernels.h"
 
@@ -217,18 +218,29 @@ void norm_group_pool_kernel(const double* __restrict__ part, double* __restrict_
 // one thread per (row, channel), as the group pool.  carry: entry e (0 / 1) of slot s at carry + s * slot_stride + e *
 // parity_stride, C x 2 doubles.  A launch READS entry parity[b] and WRITES entry parity[b] ^ 1 of the slots it touches;
 // all rows of a slot carry the same parity, so no workgroup of the launch reads what another writes.
-__global__ __launch_bounds__(64)
-void norm_running_pool_kernel(const double* __restrict__ part, double* __restrict__ st, int B, int C, int ld,
-                              const int* __restrict__ lens, int len_mul, const int* __restrict__ slot,
-                              const int* __restrict__ own_lo, const int* __restrict__ own_hi,
-                              const int* __restrict__ prior, const int* __restrict__ reset,
-                              const int* __restrict__ parity, double* carry, long slot_stride, long parity_stride,
-                              int chunks, float* __restrict__ amax_raise) {
+// DECAY (fastsvc_forward_running_decay): the running sum is multiplied by decay[q] in front of every row q's core - one
+// rounding at a fixed place of the fold (__dmul_rn: never contracted into the addition behind it) - the population is
+// weight[b] frames, a double, and the raise comes from bound[b] frames (fastsvc_kernels.h).
+template <bool DECAY>
+__device__ __forceinline__ void nr_pool(const double* __restrict__ part, double* __restrict__ st, int B, int C, int ld,
+                                        const int* __restrict__ lens, int len_mul, const int* __restrict__ slot,
+                                        const int* __restrict__ own_lo, const int* __restrict__ own_hi,
+                                        const int* __restrict__ prior, const int* __restrict__ reset,
+                                        const int* __restrict__ parity, double* carry, long slot_stride, long parity_stride,
+                                        int chunks, float* __restrict__ amax_raise, const double* __restrict__ decay,
+                                        const double* __restrict__ weight, const double* __restrict__ bound) {
     const int c = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y;
     const NrRow me = nr_row(b, ld, lens, len_mul, own_lo, own_hi, prior, reset);
     const int sl = slot[b], par = parity[b] & 1;
     const double L = (double)((long)me.len * len_mul);
-    const long N = (me.prior + me.len - me.lo) * len_mul;
+    double N, NB;                                                    // columns of the population; of the row's bound
+    if constexpr (DECAY) {
+        N = weight[b] * (double)len_mul;
+        NB = bound[b] * (double)len_mul;
+    } else {
+        N = (double)((me.prior + me.len - me.lo) * len_mul);
+        NB = N;
+    }
     if (c < C) {
         double* rec = carry + (long)sl * slot_stride + (long)c * 2;
         double s1 = 0.0, s2 = 0.0;
@@ -238,6 +250,10 @@ void norm_running_pool_kernel(const double* __restrict__ part, double* __restric
             // (in front of them the carry - unless the slot's first row of the batch starts a stream: zero, nothing read)
             if (first && !reset[q]) { s1 = rec[par * parity_stride]; s2 = rec[par * parity_stride + 1]; }
             first = false;
+            if constexpr (DECAY) {
+                const double d = decay[q];
+                s1 = __dmul_rn(s1, d); s2 = __dmul_rn(s2, d);
+            }
             const NrRow r = nr_row(q, ld, lens, len_mul, own_lo, own_hi, prior, reset);
             const int nk = (int)(((long)(r.hi - r.lo) * len_mul + NORMGROUP_CHUNK - 1) / NORMGROUP_CHUNK);
             for (int k = 0; k < nk; ++k) {
@@ -255,20 +271,42 @@ void norm_running_pool_kernel(const double* __restrict__ part, double* __restric
                 s1 += o[0]; s2 += o[1];
             }
             if (N > 0) {
-                st[((long)b * C + c) * 2 + 0] = s1 * L / (double)N;
-                st[((long)b * C + c) * 2 + 1] = s2 * L / (double)N;
+                st[((long)b * C + c) * 2 + 0] = s1 * L / N;
+                st[((long)b * C + c) * 2 + 1] = s2 * L / N;
             }
         }
     }
-    // (the group pool's raise: the bound of a normalised row is sqrt(N) here too - every column of the row is a member)
-    if (amax_raise && c == 0 && !me.pass && (double)N > L) {
+    // (the group pool's raise: the bound of a normalised row is sqrt(N) here too - every column of the row is a member;
+    // under a horizon a column of the left context weighs less than one, and the bound is sqrt(bound[b] * len_mul))
+    if (amax_raise && c == 0 && !me.pass && NB > L) {
         float* e = amax_raise + (long)b * AMAX_ENTRY;
         float m = 0.f;
         #pragma unroll
         for (int s = 0; s < AMAX_W; ++s) m = fmaxf(m, e[s * AMAX_STRIDE]);
-        const float d = (float)(sqrt((double)N) - sqrt(L));
+        const float d = (float)(sqrt(NB) - sqrt(L));
         e[0] = (m + d) * 1.00001f;
     }
+}
+__global__ __launch_bounds__(64)
+void norm_running_pool_kernel(const double* __restrict__ part, double* __restrict__ st, int B, int C, int ld,
+                              const int* __restrict__ lens, int len_mul, const int* __restrict__ slot,
+                              const int* __restrict__ own_lo, const int* __restrict__ own_hi,
+                              const int* __restrict__ prior, const int* __restrict__ reset,
+                              const int* __restrict__ parity, double* carry, long slot_stride, long parity_stride,
+                              int chunks, float* __restrict__ amax_raise) {
+    nr_pool<false>(part, st, B, C, ld, lens, len_mul, slot, own_lo, own_hi, prior, reset, parity, carry, slot_stride,
+                   parity_stride, chunks, amax_raise, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64)
+void norm_running_decay_pool_kernel(const double* __restrict__ part, double* __restrict__ st, int B, int C, int ld,
+                                    const int* __restrict__ lens, int len_mul, const int* __restrict__ slot,
+                                    const int* __restrict__ own_lo, const int* __restrict__ own_hi,
+                                    const int* __restrict__ prior, const int* __restrict__ reset,
+                                    const int* __restrict__ parity, double* carry, long slot_stride, long parity_stride,
+                                    int chunks, float* __restrict__ amax_raise, const double* __restrict__ decay,
+                                    const double* __restrict__ weight, const double* __restrict__ bound) {
+    nr_pool<true>(part, st, B, C, ld, lens, len_mul, slot, own_lo, own_hi, prior, reset, parity, carry, slot_stride,
+                  parity_stride, chunks, amax_raise, decay, weight, bound);
 }
 #endif
 
@@ -303,10 +341,17 @@ hipError_t launch_norm_group_pool(const double* part, double* st, int B, int C, 
 hipError_t launch_norm_running_pool(const double* part, double* st, int B, int C, int ld, const int* lens, int len_mul,
                                     const int* slot, const int* own_lo, const int* own_hi, const int* prior,
                                     const int* reset, const int* parity, double* carry, long slot_stride,
-                                    long parity_stride, float* amax_raise, hipStream_t stream) {
-    hipLaunchKernelGGL(norm_running_pool_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)B), dim3(64), 0, stream,
-                       part, st, B, C, ld, lens, len_mul, slot, own_lo, own_hi, prior, reset, parity, carry, slot_stride,
-                       parity_stride, norm_group_chunks(ld), amax_raise);
+                                    long parity_stride, float* amax_raise, hipStream_t stream, const double* decay,
+                                    const double* weight, const double* bound) {
+    const dim3 grid((unsigned)((C + 63) / 64), (unsigned)B);
+    if (decay)
+        hipLaunchKernelGGL(norm_running_decay_pool_kernel, grid, dim3(64), 0, stream, part, st, B, C, ld, lens, len_mul, slot,
+                           own_lo, own_hi, prior, reset, parity, carry, slot_stride, parity_stride, norm_group_chunks(ld),
+                           amax_raise, decay, weight, bound);
+    else
+        hipLaunchKernelGGL(norm_running_pool_kernel, grid, dim3(64), 0, stream, part, st, B, C, ld, lens, len_mul, slot,
+                           own_lo, own_hi, prior, reset, parity, carry, slot_stride, parity_stride, norm_group_chunks(ld),
+                           amax_raise);
     return hipGetLastError();
 }
 #endif

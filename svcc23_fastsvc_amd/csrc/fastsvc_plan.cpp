@@ -1870,6 +1870,10 @@ struct CallCtx {
     const int32_t* nr_parity = nullptr;
     double* nr_carry = nullptr;
     long nr_stride = 0;
+    // fastsvc_forward_running_decay: the forgetting horizon's per-row doubles (device, B entries; all three or none)
+    const double* nr_decay = nullptr;
+    const double* nr_weight = nullptr;
+    const double* nr_bound = nullptr;
 };
 
 // doubles of ONE parity entry of a slot's carry record: per up block its three norm points, C x 2 each, in dataflow order
@@ -3527,7 +3531,8 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
                 if (e == hipSuccess)
                     e = launch_norm_running_pool(cc.ng_part, stp, B, u.C, (int)Tout, lengths, m, cc.nr_slot, cc.ng_lo, cc.ng_hi,
                                                  cc.nr_prior, cc.nr_reset, cc.nr_parity, carry, cc.nr_stride, entry,
-                                                 (P.storage == 0 && stp == st) ? am_p : nullptr, stream);
+                                                 (P.storage == 0 && stp == st) ? am_p : nullptr, stream, cc.nr_decay,
+                                                 cc.nr_weight, cc.nr_bound);
             }
             return e;
         };
@@ -3731,18 +3736,25 @@ size_t fastsvc_norm_running_scratch_bytes(const fastsvc_plan* plan, int32_t B, i
     return 2 * fastsvc_norm_group_scratch_bytes(plan, B, F);       // (two ranges a row)
 }
 
-int fastsvc_forward_running(const fastsvc_plan* plan, const void* dev_blob,
-                            const float* ppg, const float* sine, const float* lft, const float* spk_emb,
-                            float* out, int32_t B, int32_t F, const int32_t* lengths,
-                            const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
-                            const int32_t* prior, const int32_t* reset, const int32_t* parity,
-                            void* carry, size_t carry_bytes,
-                            void* workspace, size_t workspace_bytes,
-                            void* scratch, size_t scratch_bytes, void* stream) {
+// fastsvc_forward_running and fastsvc_forward_running_decay: `decayed` says whether the three double arrays are part of
+// the call (they must then be there; without them they are null)
+static int forward_running_impl(const fastsvc_plan* plan, const void* dev_blob,
+                                const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                                float* out, int32_t B, int32_t F, const int32_t* lengths,
+                                const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                                const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                                bool decayed, const double* decay, const double* weight, const double* bound,
+                                void* carry, size_t carry_bytes,
+                                void* workspace, size_t workspace_bytes,
+                                void* scratch, size_t scratch_bytes, void* stream) {
     CallCtx cc;
     if (spk_emb) {                                     // (without an embedding there is no norm: fastsvc_forward's launches and bytes)
         if (!slot || !own_lo || !own_hi || !prior || !reset || !parity || !carry || !scratch)
             return fail(FASTSVC_E_INVALID, "null argument");
+        if (decayed && (!decay || !weight || !bound)) return fail(FASTSVC_E_INVALID, "null argument");
+        if (decayed && (reinterpret_cast<uintptr_t>(decay) | reinterpret_cast<uintptr_t>(weight) |
+                        reinterpret_cast<uintptr_t>(bound)) % sizeof(double) != 0)
+            return fail(FASTSVC_E_INVALID, "decay, weight and bound must be 8-byte aligned");
         if (!plan || B < 1 || B > 65535 || F < 1) return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535 and F >= 1");
         if (carry_bytes < fastsvc_norm_carry_bytes(plan) || carry_bytes % sizeof(double) != 0 ||
             reinterpret_cast<uintptr_t>(carry) % sizeof(double) != 0)
@@ -3755,17 +3767,49 @@ int fastsvc_forward_running(const fastsvc_plan* plan, const void* dev_blob,
         cc.nr_carry = static_cast<double*>(carry);
         cc.nr_stride = (long)(carry_bytes / sizeof(double));
         cc.ng_part = static_cast<double*>(scratch);
+        if (decayed) { cc.nr_decay = decay; cc.nr_weight = weight; cc.nr_bound = bound; }
     }
     return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
                         workspace_bytes, stream, nullptr);
 }
 
-int fastsvc_norm_running_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
-                               int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
-                               const int32_t* prior, const int32_t* reset, const int32_t* parity, double* carry,
-                               double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
-    if (!u || !slot || !own_lo || !own_hi || !prior || !reset || !parity || !carry || !stats_out || !scratch)
+int fastsvc_forward_running(const fastsvc_plan* plan, const void* dev_blob,
+                            const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                            float* out, int32_t B, int32_t F, const int32_t* lengths,
+                            const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                            const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                            void* carry, size_t carry_bytes,
+                            void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+    return forward_running_impl(plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, slot, own_lo, own_hi, prior, reset,
+                                parity, false, nullptr, nullptr, nullptr, carry, carry_bytes, workspace, workspace_bytes,
+                                scratch, scratch_bytes, stream);
+}
+
+int fastsvc_forward_running_decay(const fastsvc_plan* plan, const void* dev_blob,
+                                  const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                                  float* out, int32_t B, int32_t F, const int32_t* lengths,
+                                  const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                                  const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                                  const double* decay, const double* weight, const double* bound,
+                                  void* carry, size_t carry_bytes,
+                                  void* workspace, size_t workspace_bytes,
+                                  void* scratch, size_t scratch_bytes, void* stream) {
+    return forward_running_impl(plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, slot, own_lo, own_hi, prior, reset,
+                                parity, true, decay, weight, bound, carry, carry_bytes, workspace, workspace_bytes,
+                                scratch, scratch_bytes, stream);
+}
+
+static int norm_running_stats_impl(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                                   int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                                   const int32_t* prior, const int32_t* reset, const int32_t* parity, bool decayed,
+                                   const double* decay, const double* weight, const double* bound, double* carry,
+                                   double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+    if ((decayed && (!decay || !weight || !bound)) || !u || !slot || !own_lo || !own_hi || !prior || !reset || !parity || !carry || !stats_out || !scratch)
         return fail(FASTSVC_E_INVALID, "null argument");
+    if (decayed && (reinterpret_cast<uintptr_t>(decay) | reinterpret_cast<uintptr_t>(weight) |
+                    reinterpret_cast<uintptr_t>(bound)) % sizeof(double) != 0)
+        return fail(FASTSVC_E_INVALID, "decay, weight and bound must be 8-byte aligned");
     if (storage != 0 && storage != 1 && storage != 2)
         return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
     if (B < 1 || B > 65535 || C < 1 || ld < 1 || len_mul < 1 || ld % len_mul != 0)
@@ -3779,8 +3823,26 @@ int fastsvc_norm_running_stats(const void* u, int32_t storage, int32_t B, int32_
     HIP_TRY(FASTSVC_BY_STORAGE(storage, launch_norm_running_partials)(static_cast<const float*>(u), part, B, C, ld, lengths,
                                                                       len_mul, own_lo, own_hi, prior, reset, s));
     HIP_TRY(launch_norm_running_pool(part, stats_out, B, C, ld, lengths, len_mul, slot, own_lo, own_hi, prior, reset, parity,
-                                     carry, 4L * C, 2L * C, nullptr, s));
+                                     carry, 4L * C, 2L * C, nullptr, s, decayed ? decay : nullptr, decayed ? weight : nullptr,
+                                     decayed ? bound : nullptr));
     return FASTSVC_OK;
+}
+
+int fastsvc_norm_running_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                               int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                               const int32_t* prior, const int32_t* reset, const int32_t* parity, double* carry,
+                               double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+    return norm_running_stats_impl(u, storage, B, C, ld, lengths, len_mul, slot, own_lo, own_hi, prior, reset, parity, false,
+                                   nullptr, nullptr, nullptr, carry, stats_out, scratch, scratch_bytes, stream);
+}
+
+int fastsvc_norm_running_stats_decay(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                                     int32_t len_mul, const int32_t* slot, const int32_t* own_lo, const int32_t* own_hi,
+                                     const int32_t* prior, const int32_t* reset, const int32_t* parity,
+                                     const double* decay, const double* weight, const double* bound, double* carry,
+                                     double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+    return norm_running_stats_impl(u, storage, B, C, ld, lengths, len_mul, slot, own_lo, own_hi, prior, reset, parity, true,
+                                   decay, weight, bound, carry, stats_out, scratch, scratch_bytes, stream);
 }
 
 int fastsvc_autotune(const fastsvc_plan* plan, const void* dev_blob,

@@ -22,7 +22,8 @@ batches whose output is not finite, and ``--storage auto`` is float16 storage wi
 than one forward takes, in buffers sized by the window.  ``--stream PUSH[,CORE[,CONTEXT[,FADE]]] [--streams N]`` feeds the
 dumps as N concurrent simulated LIVE streams, PUSH frames per call (``StreamSession``: features arrive chunk by chunk,
 samples come back as soon as their window has its context); ``--stream-norm running`` normalises every window by the
-statistics of all frames its stream has delivered so far, carried on the GPU, instead of by the window's own.
+statistics of all frames its stream has delivered so far, carried on the GPU, instead of by the window's own, and
+``--stream-horizon FRAMES`` forgets those statistics exponentially.
 """
 from __future__ import annotations
 
@@ -352,7 +353,8 @@ def chunk_sums(u, lo: int, hi: int, chunk: int = NORM_CHUNK) -> np.ndarray:
 
 
 def pool_running_sums(core, look, lens: Sequence[int], slot: Sequence[int], own_lo: Sequence[int], prior: Sequence[int],
-                      reset: Sequence[int], carry: Dict[int, np.ndarray]):
+                      reset: Sequence[int], carry: Dict[int, np.ndarray], decay: Optional[Sequence[float]] = None,
+                      weight: Optional[Sequence[float]] = None):
     """The numpy reference of the RUNNING pool of csrc/fastsvc_normgroup.hip (``StreamSession(norm="running")``), float64.
     Row b of one forward is a window of the stream in carry slot ``slot[b]``; ``core[b]`` and ``look[b]`` are the chunk
     sums ``(n_chunks, C, 2)`` of its core and of its look-ahead (``chunk_sums``; the look-ahead may have none), ``lens[b]``
@@ -365,10 +367,18 @@ def pool_running_sums(core, look, lens: Sequence[int], slot: Sequence[int], own_
     to the row's right edge: ``[..., 0] / lens[b]`` is their mean.  The left fold makes carry and statistics the same bits
     however a stream's windows fall into forwards.
 
+    With a FORGETTING HORIZON (``decay`` and ``weight``, one float per row, both or neither; ``running_horizon_rows`` makes
+    them): the running sum is multiplied by ``decay[q]`` in front of the core chunks of EVERY row q of the fold, b's own
+    included - one rounding at a fixed place, so the bits still do not depend on the forwards - and ``N = weight[b]``, in
+    the unit of ``lens``.  ``decay`` all 1 and ``weight[b] = prior[b] + lens[b] - own_lo[b]`` give the bits of the call
+    without them.
+
     Returns ``(stats, new_carry)``: per row ``(C, 2)``, or ``None`` for a PASS-THROUGH row (reset, ``own_lo == 0``: window 0
     of a stream, whose statistics stay the producer's own), and ``carry`` updated with every slot of the batch (a new
     dict)."""
     B = len(slot)
+    if (decay is None) != (weight is None):
+        raise ValueError("decay and weight go together")
     stats: List[Optional[np.ndarray]] = []
     new_carry = dict(carry)
     for b in range(B):
@@ -377,6 +387,8 @@ def pool_running_sums(core, look, lens: Sequence[int], slot: Sequence[int], own_
         s = np.zeros((C, 2)) if reset[first] else np.array(carry[slot[b]], dtype=np.float64)
         for q in range(b + 1):
             if slot[q] == slot[b]:
+                if decay is not None:
+                    s = s * float(decay[q])
                 for part in np.asarray(core[q], dtype=np.float64):
                     s = s + part
         new_carry[slot[b]] = s                               # (the slot's last row of the batch has the last word)
@@ -385,9 +397,63 @@ def pool_running_sums(core, look, lens: Sequence[int], slot: Sequence[int], own_
             continue
         for part in np.asarray(look[b], dtype=np.float64):
             s = s + part
-        N = int(prior[b]) + int(lens[b]) - int(own_lo[b])
+        N = int(prior[b]) + int(lens[b]) - int(own_lo[b]) if weight is None else float(weight[b])
         stats.append(s * float(lens[b]) / float(N))
     return stats, new_carry
+
+
+def check_horizon(horizon, core: int) -> Optional[float]:
+    """A forgetting horizon in frames: ``None``, or a positive finite float of at least ``core`` -> ``None`` or the float."""
+    if horizon is None:
+        return None
+    try:
+        h = float(horizon)
+    except (TypeError, ValueError):
+        raise ValueError(f"horizon must be None or a number of frames, got {horizon!r}") from None
+    if not math.isfinite(h) or h <= 0.0:
+        raise ValueError(f"horizon must be positive and finite, got {horizon!r}")
+    if h < int(core):
+        raise ValueError(f"horizon {h:g} is shorter than the core of {int(core)} frames")
+    return h
+
+
+def running_horizon_rows(windows: Sequence[Tuple[int, int, int, int]], horizon: Optional[float], w_prev: Optional[float],
+                         core: Optional[int] = None):
+    """The host side of a forgetting horizon, pure float64: for a stream's NEXT windows ``(in_lo, in_hi,
+    core_lo, core_hi)``, ascending and adjacent, and ``w_prev``, the stream's weighted frame count after the window in
+    front of them (ignored when the first one is window 0, ``core_lo == 0``), returns ``(decay, weight, bound, w_new)`` -
+    three lists of one float per window, as ``fastsvc_forward_running_decay`` takes them, and the count after the last.
+
+    With c = core_hi - core_lo, la = in_hi - core_hi and H = ``horizon``: ``decay = exp(-c / H)`` (one ``math.exp`` value:
+    the device multiplies by exactly this double), ``w = decay w_prev + c`` (window 0: ``w = c``, its decay is 1 and
+    multiplies nothing), ``weight = w + la`` - the weighted frames the window is normalised over - and ``bound = weight /
+    wmin`` with ``wmin = exp(-(core_hi - core_hi_j) / H)`` the weight of the window's lightest column: core j holds
+    ``in_lo``.  ``core``: the size of the stream's full cores (every core but a stream's last is full); ``None`` takes the
+    longest core of ``windows``, which is right unless they are a stream's short last window alone.  ``horizon=None`` is
+    the rule without forgetting: decay 1, ``w = core_hi``, ``weight = bound = in_hi``."""
+    H = None if horizon is None else float(horizon)
+    if core is None and windows:
+        core = max(int(w[3]) - int(w[2]) for w in windows)
+    decay, weight, bound = [], [], []
+    w = None if w_prev is None else float(w_prev)
+    for in_lo, in_hi, lo, hi in windows:
+        in_lo, in_hi, lo, hi = int(in_lo), int(in_hi), int(lo), int(hi)
+        c, la = hi - lo, in_hi - hi
+        if not (0 <= in_lo <= lo < hi <= in_hi and c <= core and lo % core == 0):
+            raise ValueError(f"window ({in_lo}, {in_hi}, {lo}, {hi}) is not a window of cores of {core} frames")
+        if lo == 0:
+            d, w = 1.0, float(c)
+        else:
+            if w is None:
+                raise ValueError("w_prev is needed in front of a window that is not a stream's first")
+            d = 1.0 if H is None else math.exp(-c / H)
+            w = d * w + c
+        hi_j = (in_lo // core + 1) * core                    # (the right edge of the core that holds in_lo)
+        wmin = 1.0 if H is None or hi_j >= hi else math.exp(-(hi - hi_j) / H)
+        decay.append(d)
+        weight.append(w + la)
+        bound.append(max((w + la) / wmin, w + la))
+    return decay, weight, bound, w
 
 
 def _window_groups(rows):
@@ -1519,6 +1585,15 @@ class StreamSession:
     has the rule, its reference and its caveats).  It needs a model that takes an embedding; streams opened without
     one run as under ``"window"`` and carry nothing.
 
+    ``horizon=H`` (frames, ``H >= core``; only with ``norm="running"``) makes the running statistics FORGET: the carried
+    sums are multiplied by ``exp(-c / H)`` in front of every core of c frames, so a frame j cores back counts with
+    ``exp(-j core / H)`` while the window's own core and look-ahead count in full.  The population a window is normalised
+    by stays below ``core / (1 - exp(-core / H)) + context`` frames for as long as the stream lives - and with it the
+    float32 headroom the mode costs - and a change of level is forgotten at that rate instead of never.
+    One ``math.exp`` per window on the host (``running_horizon_rows``) feeds the device, the per-stream frame count ``w``
+    (``norm_frames``) lives on the host; the same launches, one more multiplication per row in the pool.  ``None``: no
+    forgetting, the launches and bytes as before.
+
     State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
     ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
     upload buffer with a page-locked twin and one page-locked download buffer; with ``norm="running"`` per stream one
@@ -1545,7 +1620,8 @@ class StreamSession:
     fallback reports, graph capture of the per-push chain, several GPUs."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
-                 fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window"):
+                 fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
+                 horizon: Optional[float] = None):
         from .engine import FastSVCError, STREAM_MAX_PUSH
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
@@ -1575,7 +1651,9 @@ class StreamSession:
             raise ValueError(f"norm must be \"window\" or \"running\", got {norm!r}")
         if norm == "running" and not self._takes_emb:
             raise ValueError("norm=\"running\" needs a model that takes a speaker embedding: without one nothing is normalised")
-        self.norm = norm
+        if horizon is not None and norm != "running":
+            raise ValueError("horizon forgets running statistics: it needs norm=\"running\"")
+        self.norm, self.horizon = norm, check_horizon(horizon, core)
         self.cap = cap = stream_ring_frames(core, context, max_push)
         dev, n = self.device, self.n_streams
         self._ppg = torch.empty((n, cap, C), dtype=torch.float32, device=dev)
@@ -1654,11 +1732,21 @@ class StreamSession:
         sid = self._next_id
         self._next_id += 1
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
-        self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, norm_parity=0, seed=key,
+        self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, norm_parity=0, norm_w=0.0, seed=key,
                               stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
         self._ids[sid] = s
         self._layout.reset(s)
         return sid
+
+    def norm_frames(self, sid: int) -> float:
+        """The weighted frames ``norm="running"`` carries for stream ``sid``: the frames of the cores that ran, each core
+        multiplied by the decays of the cores behind it - without a ``horizon`` simply their count.  0.0 before the
+        stream's first window and for a stream without an embedding, which carries nothing."""
+        if self.norm != "running":
+            raise ValueError("norm_frames needs norm=\"running\"")
+        if sid not in self._ids:
+            raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
+        return float(self._slots[self._ids[sid]]["norm_w"])
 
     def end(self, ids) -> Dict[int, np.ndarray]:
         """``push({}, end=ids)``: flush these streams and free their slots."""
@@ -1740,14 +1828,23 @@ class StreamSession:
                 st["parity"] ^= 1
         # ---- the windows that are ready now, in slot order, a stream's ascending
         rows = []
+        forget = []              # norm="running": per row (decay, weight, bound, the stream's weighted frames behind its core)
         for sid in sorted(ids, key=lambda i: self._ids[i]):
             s = self._ids[sid]
             st = self._slots[s]
             ended = sid in end
             ready = stream_ready_rows(st["seen"], ended, core, context, st["done"])
+            w = st["norm_w"]
             for j, (in_lo, in_hi, lo, hi) in enumerate(ready):
                 k = st["done"] + j
                 rows.append((s, k, in_lo, in_hi, lo, hi, ended and hi == st["seen"]))
+                if self.norm == "running" and st["emb"]:
+                    if self.horizon is None:             # (nothing forgotten: the frames up to the core's end)
+                        w = float(hi)
+                        forget.append((1.0, float(in_hi), float(in_hi), w))
+                    else:
+                        (d,), (wt,), (bd,), w = running_horizon_rows([(in_lo, in_hi, lo, hi)], self.horizon, w, core)
+                        forget.append((d, wt, bd, w))
             st["done"] += len(ready)
         seen = [0 if st is None else st["seen"] for st in self._slots]
         pieces: Dict[int, list] = {self._ids[sid]: [] for sid in ids}
@@ -1776,10 +1873,14 @@ class StreamSession:
                 running = ([r[0] for r in chunk], [r[4] - r[2] for r in chunk], [r[5] - r[2] for r in chunk],
                            [r[4] for r in chunk], [int(r[1] == 0) for r in chunk],
                            [self._slots[r[0]]["norm_parity"] for r in chunk])
+                fg = forget[c0: c0 + self.max_batch]
+                decay = None if self.horizon is None else tuple([f[i] for f in fg] for i in range(3))
                 y = self.model(ppg, sine, lft, emb, lengths=lens, norm_running=running, norm_carry=self._carry,
-                               norm_scratch=self._norm_scratch).to(torch.float32)
+                               norm_scratch=self._norm_scratch, norm_decay=decay).to(torch.float32)
                 for s in dict.fromkeys(r[0] for r in chunk):         # (enqueued: the other entry is the slot's carry now)
                     self._slots[s]["norm_parity"] ^= 1
+                for r, f in zip(chunk, fg):                          # (... and it holds this many weighted frames)
+                    self._slots[r[0]]["norm_w"] = f[3]
             else:
                 y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
             self.forwards += 1
@@ -1858,6 +1959,11 @@ def main(argv=None) -> None:                                  # pragma: no cover
                     help="with --stream and a speaker embedding: InstanceNorm statistics of each window alone (default) or "
                          "running - of every frame the stream has delivered up to the window's right edge, carried on the GPU "
                          "from push to push; approaches the whole-utterance result as the stream grows")
+    ap.add_argument("--stream-horizon", type=float, default=None, metavar="FRAMES",
+                    help="with --stream-norm running: forget the running statistics exponentially with this horizon, in "
+                         "frames (at least CORE): a frame j cores back counts with exp(-j CORE / FRAMES), so a change of "
+                         "level is forgotten and the population stays bounded however long the stream lives (default: never "
+                         "forget)")
     ap.add_argument("--streams", type=int, default=1, help="with --stream: dumps converted side by side (default 1)")
     args = ap.parse_args(argv)
     if args.stream is not None:
@@ -1870,9 +1976,13 @@ def main(argv=None) -> None:                                  # pragma: no cover
                 raise ValueError
         except ValueError:
             ap.error("--stream takes PUSH[,CORE[,CONTEXT[,FADE]]] in frames, --streams a count of at least 1")
+        if args.stream_horizon is not None and args.stream_norm != "running":
+            ap.error("--stream-horizon needs --stream-norm running")
         args.stream = dict(zip(("max_push", "core", "context", "fade"), parts), n_streams=args.streams, norm=args.stream_norm)
-    elif args.streams != 1 or args.stream_norm != "window":
-        ap.error("--streams and --stream-norm need --stream")
+        if args.stream_horizon is not None:
+            args.stream["horizon"] = args.stream_horizon
+    elif args.streams != 1 or args.stream_norm != "window" or args.stream_horizon is not None:
+        ap.error("--streams, --stream-norm and --stream-horizon need --stream")
     if args.window is not None:
         if not args.resident or args.fanout > 1:
             ap.error("--window works on the --resident route, without --fanout")

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import json
+import math
 import os
 from typing import Dict, Mapping, Optional, Sequence, Tuple
 
@@ -37,6 +38,7 @@ ABI_SYMBOLS = (
     "fastsvc_pack_device_scratch_bytes", "fastsvc_pack_device_launch_count", "fastsvc_pack_weights_device",
     "fastsvc_forward", "fastsvc_forward_grouped", "fastsvc_norm_group_scratch_bytes", "fastsvc_norm_group_stats",
     "fastsvc_forward_running", "fastsvc_norm_carry_bytes", "fastsvc_norm_running_scratch_bytes", "fastsvc_norm_running_stats",
+    "fastsvc_forward_running_decay", "fastsvc_norm_running_stats_decay",
     "fastsvc_autotune", "fastsvc_tuned_count", "fastsvc_tuned_get", "fastsvc_tuned_set",
     "fastsvc_forward_profile", "fastsvc_workspace_tap", "fastsvc_forward_launch_count",
     "fastsvc_flops_per_sample", "fastsvc_signal_scratch_bytes", "fastsvc_signal_generate",
@@ -134,6 +136,10 @@ def load_library():
     lib.fastsvc_forward_running.restype = ctypes.c_int
     lib.fastsvc_norm_running_stats.argtypes = [vp, i32, i32, i32, i32, vp, i32] + [vp] * 6 + [vp, vp, vp, sz, vp]
     lib.fastsvc_norm_running_stats.restype = ctypes.c_int
+    lib.fastsvc_forward_running_decay.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp] + [vp] * 9 + [vp, sz, vp, sz, vp, sz, vp]
+    lib.fastsvc_forward_running_decay.restype = ctypes.c_int
+    lib.fastsvc_norm_running_stats_decay.argtypes = [vp, i32, i32, i32, i32, vp, i32] + [vp] * 9 + [vp, vp, vp, sz, vp]
+    lib.fastsvc_norm_running_stats_decay.restype = ctypes.c_int
     lib.fastsvc_loudness_frames.argtypes = [i32, i32]
     lib.fastsvc_loudness_frames.restype = i32
     lib.fastsvc_loudness_scratch_bytes.argtypes = [i32, i32, i32]
@@ -891,15 +897,46 @@ def check_norm_running(norm_running, lens: Sequence[int], n_slots: Optional[int]
     return slot, own_lo, own_hi, prior, [1 if v else 0 for v in reset], parity
 
 
+def check_norm_decay(decay, weight, bound, running, lengths: Sequence[int]):
+    """Validate the three per-row float arrays of a forgetting horizon (``fastsvc_forward_running_decay``) against the rows
+    ``running = (slot, own_lo, own_hi, prior, reset, parity)`` (``check_norm_running`` has passed them) and their frame
+    counts ``lengths``, on the host: B entries each, everything finite, ``0 < decay[b] <= 1``, ``weight[b] >= lengths[b] -
+    own_lo[b]`` (the row's own core and look-ahead count in full) and ``bound[b] >= weight[b]`` (no column weighs more
+    than one).  Returns the three as lists of floats; ``ValueError`` names the first row that breaks a rule."""
+    try:
+        decay, weight, bound = ([float(v) for v in seq] for seq in (decay, weight, bound))
+    except (TypeError, ValueError):
+        raise ValueError("norm_decay must be (decay, weight, bound), three sequences of floats") from None
+    own_lo = [int(v) for v in running[1]]
+    B = len(lengths)
+    if any(len(a) != B for a in (decay, weight, bound, own_lo)):
+        raise ValueError(f"norm_decay must hold {B} entries each, like the rows, got {len(decay)}, {len(weight)}, {len(bound)}")
+    isfinite = math.isfinite
+    for b, (d, w, bd) in enumerate(zip(decay, weight, bound)):
+        if not (isfinite(d) and isfinite(w) and isfinite(bd)):
+            raise ValueError(f"row {b}: decay, weight and bound must be finite, got {d}, {w}, {bd}")
+        if not 0.0 < d <= 1.0:
+            raise ValueError(f"row {b}: decay must be in (0, 1], got {d}")
+        if w < int(lengths[b]) - own_lo[b]:
+            raise ValueError(f"row {b}: weight {w} is less than the {int(lengths[b]) - own_lo[b]} frames of the row's own core "
+                             f"and look-ahead")
+        if bd < w:
+            raise ValueError(f"row {b}: bound {bd} must be at least weight {w}")
+    return decay, weight, bound
+
+
 def norm_running_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: int, norm_running, carry: torch.Tensor,
-                       stats: torch.Tensor) -> torch.Tensor:
+                       stats: torch.Tensor, decay=None) -> torch.Tensor:
     """Running InstanceNorm sums of one tensor with one norm point's carry (``fastsvc_norm_running_stats``,
     csrc/fastsvc_normgroup.hip): ``u`` (B, C, ld) float32, bfloat16 or float16 on the device, row b valid for ``lens[b] *
     len_mul`` columns (``None``: ``ld``), ``norm_running = (slot, own_lo, own_hi, prior, reset, parity)`` in frames
     (``check_norm_running``).  ``carry`` (n_slots, 2, C, 2) float64: entry ``parity`` of a slot's record is read (not for a
     reset row), entry ``parity ^ 1`` receives the slot's new carry - the caller flips its parity.  ``stats`` (B, C, 2)
     float64 receives ``decode.pool_running_sums``' values for every row that is not a pass-through row (reset, ``own_lo ==
-    0``); those rows' entries are left untouched.  Two launches on the current stream.  Returns ``stats``."""
+    0``); those rows' entries are left untouched.  ``decay = (decay, weight, bound)``, three sequences of B floats
+    (``check_norm_decay``): the fold of a forgetting horizon, ``fastsvc_norm_running_stats_decay`` - the sum is multiplied
+    by ``decay[q]`` in front of every row's core and ``N = weight[b] * len_mul``.  Two launches on the current stream.
+    Returns ``stats``."""
     lib = load_library()
     if not isinstance(u, torch.Tensor) or not u.is_cuda:
         raise FastSVCError("norm_running_stats needs GPU tensors (no CPU fallback); got " + str(getattr(u, "device", type(u))))
@@ -923,9 +960,20 @@ def norm_running_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: 
     ints = torch.tensor(list(arrays) + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
     scratch = torch.empty(B * C * (-(-ld // 2048)) * 32, dtype=torch.uint8, device=dev)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    lens_ptr = ptr(ints[6]) if lens is not None else None
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib, lib.fastsvc_norm_running_stats(ptr(u), codes[u.dtype], B, C, ld, ptr(ints[6]) if lens is not None else None,
+        if decay is not None:
+            if len(decay) != 3:
+                raise ValueError("decay must be (decay, weight, bound), three sequences of floats")
+            dbl = torch.tensor(check_norm_decay(*decay, arrays, lens if lens is not None else [ld // len_mul] * B),
+                               dtype=torch.float64).to(dev)
+            _check(lib, lib.fastsvc_norm_running_stats_decay(ptr(u), codes[u.dtype], B, C, ld, lens_ptr, len_mul,
+                                                             *[ptr(ints[i]) for i in range(6)], *[ptr(dbl[i]) for i in range(3)],
+                                                             ptr(carry), ptr(stats), ptr(scratch), scratch.numel(),
+                                                             ctypes.c_void_p(stream)), "fastsvc_norm_running_stats_decay")
+            return stats
+        _check(lib, lib.fastsvc_norm_running_stats(ptr(u), codes[u.dtype], B, C, ld, lens_ptr,
                                                    len_mul, *[ptr(ints[i]) for i in range(6)], ptr(carry), ptr(stats),
                                                    ptr(scratch), scratch.numel(), ctypes.c_void_p(stream)),
                "fastsvc_norm_running_stats")
@@ -1318,7 +1366,7 @@ class Plan:
                 workspace: Optional[torch.Tensor] = None, profile: Optional[list] = None,
                 autotune: bool = False, lengths=None, norm_groups=None,
                 norm_scratch: Optional[torch.Tensor] = None, norm_running=None,
-                norm_carry: Optional[torch.Tensor] = None) -> torch.Tensor:
+                norm_carry: Optional[torch.Tensor] = None, norm_decay=None) -> torch.Tensor:
         """Enqueue one forward on the current HIP stream of ``ppg.device``; returns (B, O, T).
 
         ``lengths`` (B frame counts, 1 <= n <= F; sequence or int tensor) makes the batch ragged:
@@ -1339,7 +1387,10 @@ class Plan:
         ``parity``, and the new ones written to entry ``parity ^ 1`` - the CALLER flips a slot's parity after the call.
         Not with ``norm_groups``, ``profile`` or ``autotune``; ``norm_scratch`` then needs
         ``norm_running_scratch_bytes(B, padded_frames(F))`` bytes.  Without ``spk_emb`` nothing is normalised and nothing
-        carried.
+        carried.  ``norm_decay = (decay, weight, bound)`` (three sequences of B floats, ``check_norm_decay``; only with
+        ``norm_running``) forgets the carried sums exponentially (``fastsvc_forward_running_decay``): the slot's sums are
+        multiplied by ``decay[b]`` in front of row b's core and the row is normalised over ``weight[b]`` frames; the six
+        int arrays and these three travel to the device in one upload.
 
         With ``profile`` (a list) the launches are bracketed by hipEvents on that stream, the
         stream is synchronised and one dict per kernel launch is appended to the list.
@@ -1383,8 +1434,14 @@ class Plan:
                                  f"norm_carry_bytes() = {self.norm_carry_bytes()} bytes, a multiple of 8")
             norm_running = check_norm_running(norm_running, [F] * B if lengths is None else [int(v) for v in lengths],
                                               norm_carry.shape[0])
+            if norm_decay is not None:
+                if len(norm_decay) != 3:
+                    raise ValueError("norm_decay must be (decay, weight, bound), three sequences of floats")
+                norm_decay = check_norm_decay(*norm_decay, norm_running, [F] * B if lengths is None else [int(v) for v in lengths])
         elif norm_carry is not None:
             raise ValueError("norm_carry goes with norm_running")
+        elif norm_decay is not None:
+            raise ValueError("norm_decay goes with norm_running")
         if F % 4 != 0 and profile is None and (self.storage != "float32" or self.pad_odd_lengths):
             # bfloat16 / float16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0
             # (three of four real utterances are not); float32 storage runs such rows on its slower kernels.  Pad to
@@ -1422,7 +1479,7 @@ class Plan:
                 self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None, autotune=True)
             self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None,
                          lengths=[F] * B if lengths is None else lengths, norm_groups=norm_groups, norm_scratch=norm_scratch,
-                         norm_running=norm_running, norm_carry=norm_carry)
+                         norm_running=norm_running, norm_carry=norm_carry, norm_decay=norm_decay)
             if out is None:
                 return py[..., :T].contiguous()
             out.copy_(py[..., :T])
@@ -1479,12 +1536,20 @@ class Plan:
                 need = self.norm_running_scratch_bytes(B, F)
                 if norm_scratch is None or norm_scratch.numel() * norm_scratch.element_size() < need or norm_scratch.device != dev:
                     norm_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-                nr = self._stage_lengths(torch.tensor(norm_running, dtype=torch.int32).reshape(-1), 6 * B, dev)
-                rc = self.lib.fastsvc_forward_running(*common[:10], *[ctypes.c_void_p(nr[i * B:].data_ptr()) for i in range(6)],
-                                                      ctypes.c_void_p(norm_carry.data_ptr()),
-                                                      norm_carry.shape[1] * norm_carry.element_size(), common[10], common[11],
-                                                      ctypes.c_void_p(norm_scratch.data_ptr()),
-                                                      norm_scratch.numel() * norm_scratch.element_size(), common[12])
+                if norm_decay is None:
+                    host = torch.tensor(norm_running, dtype=torch.int32).reshape(-1)
+                else:                                    # (the doubles behind the 6 B ints - an even count, so 8-byte aligned)
+                    packed = np.empty(12 * B, dtype=np.int32)
+                    packed[:6 * B] = np.asarray(norm_running, dtype=np.int32).reshape(-1)
+                    packed[6 * B:].view(np.float64)[:] = np.asarray(norm_decay, dtype=np.float64).reshape(-1)
+                    host = torch.from_numpy(packed)
+                nr = self._stage_lengths(host, host.numel(), dev)
+                rc = getattr(self.lib, "fastsvc_forward_running" if norm_decay is None else "fastsvc_forward_running_decay")(
+                    *common[:10], *[ctypes.c_void_p(nr[i * B:].data_ptr()) for i in range(6)],
+                    *([] if norm_decay is None else [ctypes.c_void_p(nr[(6 + 2 * i) * B:].data_ptr()) for i in range(3)]),
+                    ctypes.c_void_p(norm_carry.data_ptr()), norm_carry.shape[1] * norm_carry.element_size(), common[10],
+                    common[11], ctypes.c_void_p(norm_scratch.data_ptr()),
+                    norm_scratch.numel() * norm_scratch.element_size(), common[12])
                 workspace = (workspace, nr, norm_scratch, norm_carry)
             elif profile is None:
                 rc = self.lib.fastsvc_forward(*common)

@@ -316,7 +316,7 @@ class FastSVCGenerator(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, s, l, spk_emb=None, *, lengths=None, out=None, norm_groups=None, norm_scratch=None,
-                norm_running=None, norm_carry=None):
+                norm_running=None, norm_carry=None, norm_decay=None):
         """x (B, in_channels, F) PPG - s (B, 1, T) sine - l (B, 1, T) loudness -
         spk_emb (B, spk_emb_size) or None  ->  (B, out_channels, T), T = F * prod(scales).
         Same contract as fastsvc.py:305-332 (raw conv_last output, no tanh).
@@ -332,7 +332,9 @@ class FastSVCGenerator(nn.Module):
         ``norm_scratch``: see ``Plan.forward``.  ``norm_running = (slot, own_lo, own_hi, prior, reset, parity)`` with
         ``norm_carry`` (inference only, not with ``norm_groups``): the rows are windows of live streams, each normalised by
         the statistics of every frame of its stream so far, carried on the device between forwards in ``norm_carry``
-        (``StreamSession(norm="running")``; ``Plan.forward`` has the contract).
+        (``StreamSession(norm="running")``; ``Plan.forward`` has the contract).  ``norm_decay = (decay, weight, bound)``,
+        three sequences of B floats (inference only, only with ``norm_running``): the carried sums are forgotten
+        exponentially - ``StreamSession(norm="running", horizon=H)``; ``decode.running_horizon_rows`` makes the three.
 
         Autograd: whenever grad mode is enabled and a parameter or an input requires grad, the output carries a graph
         (``train()`` and ``eval()`` alike, as for any ``nn.Module``).  The plain HIP forward runs under
@@ -347,6 +349,8 @@ class FastSVCGenerator(nn.Module):
                              f"{s.shape[-1]} / loudness {l.shape[-1]} samples")
         if spk_emb is not None and not self.use_spk_emb:
             raise ValueError("spk_emb given but the generator was built with use_spk_emb=False")
+        if norm_decay is not None and norm_running is None:
+            raise ValueError("norm_decay goes with norm_running")
         # nn.Module semantics (and the reference's): eval() does not detach - with grad enabled and parameters that
         # require grad the output carries a graph in either mode, so that a loss computed through a discriminator in
         # eval() still reaches the generator's parameters.  Only the inference extensions (`lengths`, `out=`) and the
@@ -368,12 +372,15 @@ class FastSVCGenerator(nn.Module):
                 raise NotImplementedError("`norm_groups` is an inference extension: no backward")
             if norm_running is not None:
                 raise NotImplementedError("`norm_running` is an inference extension: no backward")
+            if norm_decay is not None:
+                raise NotImplementedError("`norm_decay` is an inference extension: no backward")
             from .autograd import forward_with_grad
             return forward_with_grad(self, x, s, l, spk_emb)
-        return self._forward_device(x, s, l, spk_emb, lengths, out, norm_groups, norm_scratch, norm_running, norm_carry)
+        return self._forward_device(x, s, l, spk_emb, lengths, out, norm_groups, norm_scratch, norm_running, norm_carry,
+                                    norm_decay)
 
     def _forward_device(self, x, s, l, spk_emb, lengths, out=None, norm_groups=None, norm_scratch=None, norm_running=None,
-                        norm_carry=None):
+                        norm_carry=None, norm_decay=None):
         """The HIP forward proper (no autograd): packed weights, workspace sub-batching, C-ABI call."""
         hop = self._cfg.hop
         B, _, F = x.shape
@@ -393,7 +400,8 @@ class FastSVCGenerator(nn.Module):
             tune = bool(self.autotune) and lengths is None and norm_groups is None and norm_running is None and \
                 (B, F, str(x.device)) not in self._tuned_shapes
             y = plan.forward(blob, x, s, l, spk_emb, autotune=tune, lengths=lengths, out=out, norm_groups=norm_groups,
-                             norm_scratch=norm_scratch, norm_running=norm_running, norm_carry=norm_carry)
+                             norm_scratch=norm_scratch, norm_running=norm_running, norm_carry=norm_carry,
+                             norm_decay=norm_decay)
             if tune:
                 self._tuned_shapes.add((B, F, str(x.device)))
         else:

@@ -19,7 +19,11 @@ StreamSession(norm="window") fed the same chunks - two sessions alive in one pro
 The running session carries its InstanceNorm sums on the device: one more read of the three FiLM-affined tensors of every
 up block and 24 small launches per forward.  Its figures go to profiles/decode_stream_norm.txt.
 
-    python tools/stream_latency.py [--norm]"""
+--norm --horizon H: the pair is StreamSession(norm="running", horizon=H) against StreamSession(norm="running") - the same
+launches, one more multiplication per row in the pool and three double arrays in the per-forward upload.  Its figures go
+to profiles/decode_stream_horizon.txt.
+
+    python tools/stream_latency.py [--norm [--horizon H]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -155,9 +159,16 @@ def main():
         f.write("\n".join(out) + "\n")
 
 
-def main_norm():
+def main_norm(horizon=None):
+    # the two legs: (its name in the report, StreamSession's arguments), the yardstick first
+    if horizon is None:
+        pair = [("norm=window", dict(norm="window")), ("norm=running", dict(norm="running"))]
+    else:
+        pair = [("norm=running", dict(norm="running")), (f"horizon={horizon:g}", dict(norm="running", horizon=horizon))]
+    (base, _), (other, _) = pair
     out = [f"stream norm: one StreamSession.push that completes one window per stream (every stream delivers `core` frames), host "
-           f"to host, norm=\"running\" against norm=\"window\" on the same chunks, two sessions in one process; context {ctx}, fade "
+           f"to host, {other}{'' if horizon is None else ' (at least the core)'} against {base} on the same chunks, two sessions in "
+           f"one process; context {ctx}, fade "
            f"{FADE}, speaker embedding, F0 shift on, int16 out; {pushes} pushes per repetition, {reps} repetitions, legs alternated, "
            f"median of the repetitions' means (min, max); {torch.cuda.get_device_name(0)}"]
     print(out[0], flush=True)
@@ -168,9 +179,11 @@ def main_norm():
             for N in (1, 8, 32):
                 src = [features(core * 8) for _ in range(N)]
                 legs = {}
-                for norm in ("window", "running"):
-                    s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, norm=norm)
-                    legs[norm] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[])
+                for name, kw in pair:
+                    if kw.get("horizon") is not None and kw["horizon"] < core:
+                        kw = dict(kw, horizon=float(core))           # (a horizon is at least the core)
+                    s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, **kw)
+                    legs[name] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[])
 
                 def push(leg):
                     a = (leg["step"] % 8) * core
@@ -193,14 +206,22 @@ def main_norm():
                     leg["s"].end(leg["ids"])
                     leg["s"].close()
                 audio = N * core * hop / SR
-                mw, line_w = spread(f"{N:2d} streams, core {core:3d}: push, norm=window", legs["window"]["t"], audio)
-                mr, line_r = spread(f"{N:2d} streams, core {core:3d}: push, norm=running", legs["running"]["t"], audio)
-                out += [line_w, line_r, f"    running / window {mr / mw:.3f} (+{(mr - mw) * 1e3:.0f} us a push)"]
+                mw, line_w = spread(f"{N:2d} streams, core {core:3d}: push, {base}", legs[base]["t"], audio)
+                mr, line_r = spread(f"{N:2d} streams, core {core:3d}: push, {other}", legs[other]["t"], audio)
+                tail = "" if horizon is None else f"; spread of the {base} leg {(max(legs[base]['t']) - min(legs[base]['t'])) * 1e6:.0f} us"
+                out += [line_w, line_r, f"    {other.split('=')[0] if horizon is not None else 'running'} / "
+                                        f"{base.split('=')[1]} {mr / mw:.3f} ({(mr - mw) * 1e3:+.0f} us a push{tail})"]
                 print("\n".join(out[-3:]), flush=True)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "decode_stream_norm.txt"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", "decode_stream_norm.txt" if horizon is None else "decode_stream_horizon.txt"), "w") as f:
         f.write("\n".join(out) + "\n")
 
 
 if __name__ == "__main__":
-    main_norm() if "--norm" in sys.argv[1:] else main()
+    argv = sys.argv[1:]
+    if "--horizon" in argv:
+        if "--norm" not in argv or argv.index("--horizon") + 1 >= len(argv):
+            sys.exit("--horizon H goes with --norm")
+        main_norm(float(argv[argv.index("--horizon") + 1]))
+    else:
+        main_norm() if "--norm" in argv else main()
