@@ -1842,6 +1842,46 @@ int exec_ctx_release(hipStream_t stream) {
     return 1;
 }
 
+// doubles of ONE parity entry of a slot's carry record: per up block its three norm points, C x 2 each, in dataflow order
+static long norm_carry_doubles(const fastsvc_plan& P, int blocks) {
+    long n = 0;
+    for (int i = 0; i < blocks; ++i) n += 3L * P.up[i].C * 2;
+    return n;
+}
+
+// The InstanceNorm statistics a forward call replaces, behind every norm point's producer.  The
+// entry points fill it through check(); all arrays are device arrays of B entries.
+struct NormOverride {
+    // GROUPED (fastsvc_forward_grouped): sums pooled over groups of rows, `rows` the group of each (fastsvc_normgroup.hip).
+    // RUNNING (fastsvc_forward_running): the rows are windows of live streams whose sums are carried from forward to
+    // forward, `rows` the carry slot of each.
+    enum Kind { NONE, GROUPED, RUNNING } kind = NONE;
+    const fastsvc_plan* plan = nullptr;
+    int B = 0;
+    const int32_t *rows = nullptr, *lo = nullptr, *hi = nullptr;       // owned frames / core [lo, hi) of each row: both kinds
+    double* part = nullptr;            // the caller's scratch for the chunk partials: both kinds
+    // RUNNING: the slots' carry records (`stride` doubles apart, both parity entries of norm_carry_doubles each)
+    const int32_t *prior = nullptr, *reset = nullptr, *parity = nullptr;
+    double* carry = nullptr;
+    long stride = 0;
+    // fastsvc_forward_running_decay: the forgetting horizon's per-row doubles (all three or none)
+    const double *decay = nullptr, *weight = nullptr, *bound = nullptr;
+
+    // What the entry points of both kinds ask of a filled-in object: nothing null, the doubles aligned, the carry's
+    // stride and the scratch large enough for (B, F).  Sets plan, B and stride.
+    int check(const fastsvc_plan* P, int32_t B_, int32_t F, bool decayed, size_t carry_bytes, size_t scratch_bytes);
+
+    // Behind the producer of norm point `point` (0 / 1 / 2 in dataflow order) of up block i: the sums over the columns each
+    // row owns, pooled - over its group, or with its slot's carry in front - and scaled to the row's own length, overwrite
+    // whatever stands in the row's slots of `st`: the conv's sums or the exact ones, which stay those of the pass-through
+    // rows.  Two launches.  amax_raise (float32 storage, behind the block's FIRST producer; null otherwise): the pool also
+    // raises the rows' entries of the speaker biases' amax row - the bound of a normalised row is then sqrt(owned columns
+    // of the group), not sqrt(row length), and every consumer of the block that reads it runs behind this launch
+    // (DESIGN.md 4.9).
+    hipError_t apply(const float* ut, double* st, int i, int point, int C, int Tout, int m, const int32_t* lengths,
+                     float* amax_raise, hipStream_t stream) const;
+};
+
 // What one forward call carries to its launch routes: the entry point creates it, forward_impl fills in the plan's part.
 struct CallCtx {
     const fastsvc_plan* plan = nullptr;
@@ -1855,33 +1895,83 @@ struct CallCtx {
     // utterance sat at 3.4e-3 of the output's range where the float32 reference is 4e-5 from float64
     // (tools/stress_parity.py, seed 75).  Float32 storage only.  (fastsvc_kernels.hip speaks of it as g_exact_f32.)
     bool exact_f32 = false;
-    // fastsvc_forward_grouped: InstanceNorm sums pooled over groups of rows (fastsvc_normgroup.hip).  Device arrays of B
-    // entries and the caller's scratch for the chunk partials; all null in every other entry point.
-    const int32_t* ng_group = nullptr;
-    const int32_t* ng_lo = nullptr;
-    const int32_t* ng_hi = nullptr;
-    double* ng_part = nullptr;
-    // fastsvc_forward_running: the rows are windows of live streams whose sums are carried from forward to forward.
-    // Device arrays of B entries, the slots' carry records (nr_stride doubles apart, both parity entries of
-    // norm_carry_doubles each) and the scratch in ng_part; never together with ng_group.
-    const int32_t* nr_slot = nullptr;
-    const int32_t* nr_prior = nullptr;
-    const int32_t* nr_reset = nullptr;
-    const int32_t* nr_parity = nullptr;
-    double* nr_carry = nullptr;
-    long nr_stride = 0;
-    // fastsvc_forward_running_decay: the forgetting horizon's per-row doubles (device, B entries; all three or none)
-    const double* nr_decay = nullptr;
-    const double* nr_weight = nullptr;
-    const double* nr_bound = nullptr;
+    NormOverride norm;                 // fastsvc_forward_grouped / fastsvc_forward_running[_decay]; none in every other entry point
 };
 
-// doubles of ONE parity entry of a slot's carry record: per up block its three norm points, C x 2 each, in dataflow order
-static long norm_carry_doubles(const fastsvc_plan& P, int blocks) {
-    long n = 0;
-    for (int i = 0; i < blocks; ++i) n += 3L * P.up[i].C * 2;
-    return n;
+// Which stream each part of one forward runs on, and the events that order them (choose_schedule).
+struct Schedule {
+    // the caller's; FiLM nets of stages 0..n-2; 1x1 / stretch residual convs; speaker prologue
+    hipStream_t stream = nullptr, s_film = nullptr, s_side = nullptr, s_pre = nullptr;
+    ExecCtx* ctx = nullptr;            // null: everything on the caller's stream
+    std::unique_lock<std::mutex> lock; // ctx->busy, held for the duration of the enqueue
+    int evi = 0;                       // next event of the context's ring
+    hipEvent_t ss_ready[FASTSVC_MAX_STAGES] = {};     // FiLM output of stage k is complete
+
+    // `to` waits for everything enqueued on `from` so far
+    hipError_t order_after(hipStream_t from, hipStream_t to) {
+        if (from == to || !ctx) return hipSuccess;
+        hipEvent_t e = ctx->ev[evi++ % ctx->ev.size()];
+        hipError_t r = hipEventRecord(e, from);
+        if (r != hipSuccess) return r;
+        return hipStreamWaitEvent(to, e, 0);
+    }
+    // the scale / shift of stage k were enqueued on `on`: up block n-1-k waits for them
+    hipError_t record_ready(int k, hipStream_t on) {
+        if (on == stream || !ctx) return hipSuccess;
+        ss_ready[k] = ctx->ev[evi++ % ctx->ev.size()];
+        return hipEventRecord(ss_ready[k], on);
+    }
+};
+
+// Scheduling: the FiLM nets of stages 0..n-2 + the speaker projections can run on a lowest-priority
+// helper stream (mask bit 1; bit 0: the 1x1 / stretch residual convs, an experiment that never paid).  With the
+// fused launches that is worth ~2 % at cfg2 and nothing at cfg3 / cfg1 - and only where a fork + join through the
+// helper stream is as cheap as it should be, which ExecCtx measures once (measure_fork_join): with helper streams
+// created after an RCCL communicator the same schedule ran cfg2 in 2.54 ms instead of 1.43.  Default: bit 1 from
+// ~1.5e5 samples per call where the context says it pays, one stream otherwise; FASTSVC_STREAMS=<mask> forces a
+// mask (0: one stream), FASTSVC_SERIAL one stream.
+void choose_schedule(Schedule& sch, hipStream_t stream, int64_t samples, bool one_stream) {
+    int streams_mask = env().serial ? 0 : env().streams >= 0 ? (env().streams & 3) : (samples >= 150000 ? 2 : 0);
+    // per-launch profiling and autotuning run on ONE stream so that every kernel is timed alone
+    ExecCtx* ctx = (streams_mask == 0 || one_stream) ? nullptr : exec_ctx_for(stream);
+    if (ctx) {
+        sch.lock = std::unique_lock<std::mutex>(ctx->busy);
+        ensure_measured(stream, ctx);
+        if (env().streams < 0 && !ctx->pays) { sch.lock.unlock(); sch.lock = std::unique_lock<std::mutex>(); ctx = nullptr; streams_mask = 0; }
+    }
+    sch.ctx = ctx;
+    sch.stream = stream;
+    sch.s_film = (ctx && (streams_mask & 2)) ? ctx->aux[0] : stream;
+    sch.s_side = (ctx && (streams_mask & 1)) ? ctx->aux[1] : stream;
+    // the speaker prologue on the second helper stream - only where the helper streams pay at all: below ~1.5e5 samples
+    // per call the fork / join events cost more
+    sch.s_pre = (ctx && (streams_mask & 2)) ? ctx->aux[1] : stream;
 }
+
+// One forward call: what its steps share (forward_impl fills it in).
+struct Fwd {
+    const fastsvc_plan& P;
+    CallCtx& cc;
+    const float* blob;
+    const Workspace& ws;
+    unsigned char* wsb;                // the workspace's base
+    int B, F;
+    long hop, T;                       // samples per frame, samples per row
+    const int32_t* lengths;
+    bool spk;
+    Profiler* prof;
+    const float *ppg, *spk_emb;
+    float* out;
+    // raw signals: sig 0 = lft, sig 1 = sine, read in place (the dual-signal launches address signal `sig` as
+    // base + sig * stride; the stride between the caller's two tensors is whatever it is)
+    const float* sigbuf;
+    long sig_stride;
+    float *amax_inb, *amaxb;           // amax rows (float32 storage; see layout_workspace)
+
+    float* buf(const std::string& name) const { return reinterpret_cast<float*>(wsb + ws.find(name)->off_bytes); }
+    // amax row of a workspace tensor
+    float* am(const std::string& name) const { return amaxb + (size_t)(ws.find(name) - ws.bufs.data()) * 2 * B * 256; }
+};
 
 #ifdef FASTSVC_TIMELINE
 // diagnostic build (python -m svcc23_fastsvc_amd.build --timeline; tools/timeline.py): per-wave cycle stamps
@@ -3073,471 +3163,417 @@ int fastsvc_forward_launch_count(const fastsvc_plan* plan, int32_t with_spk_emb)
     return (with_spk_emb ? 1 : 0) + (plan->storage == 0 ? 1 : 0) + down + 2 * n + 6 * n + 1;     // (+ the input scan of float32 storage)
 }
 
+}  // extern "C"
+
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
         if (_e != hipSuccess)                                                                  \
             return fail(FASTSVC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));    \
     } while (0)
+#define FWD_STEP(expr)                                                                         \
+    do {                                                                                       \
+        const int _rc = (expr);                                                                \
+        if (_rc != FASTSVC_OK) return _rc;                                                     \
+    } while (0)
 
-static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_blob,
-                    const float* ppg, const float* sine, const float* lft, const float* spk_emb,
-                    float* out, int32_t B, int32_t F, const int32_t* lengths,
-                    void* workspace, size_t workspace_bytes, void* stream_, Profiler* prof) {
-    if (!plan || !dev_blob || !ppg || !sine || !lft || !out || !workspace)
+// ==========================================================================================
+// the forward: forward_impl drives the steps below
+// ==========================================================================================
+namespace {
+
+int NormOverride::check(const fastsvc_plan* P, int32_t B_, int32_t F, bool decayed, size_t carry_bytes, size_t scratch_bytes) {
+    const bool running = kind == RUNNING;
+    if (!rows || !lo || !hi || !part || (running && (!prior || !reset || !parity || !carry)))
         return fail(FASTSVC_E_INVALID, "null argument");
-    if (B < 1 || F < 1) return fail(FASTSVC_E_INVALID, "B and F must be >= 1");
-    const fastsvc_plan& P = *plan;
-    if (P.storage != 0) {
-        const std::string mode = P.storage == 2 ? "float16 storage" : "bfloat16 storage";
-        if (F % 4 != 0) return fail(FASTSVC_E_UNSUPPORTED, mode + " needs a frame count that is a multiple of 4");
-        for (int k = 0; k < P.n; ++k)
-            if (P.down[k].c2[0].KC != 24 || P.up[k].d3.KC != 24 || P.up[k].first.KC != 24)
-                return fail(FASTSVC_E_UNSUPPORTED, mode + " needs the pipelined kernels (24-channel K chunks)");
-        if (P.n > 1 && !P.down[1].rc1[0].dec2) return fail(FASTSVC_E_UNSUPPORTED, mode + " needs the fused decimating pair");
-    }
-    if (spk_emb && !P.cfg.use_spk_emb)
-        return fail(FASTSVC_E_INVALID, "spk_emb given but the generator was built with use_spk_emb=False");
-    const Workspace ws = layout_workspace(P, B, F);
-    if (workspace_bytes < ws.bytes) return fail(FASTSVC_E_WORKSPACE, "workspace too small");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    cc.plan = plan;
-    cc.storage = plan->storage;
-    cc.exact_f32 = plan->storage == 0 && F <= 4;
-    // Scheduling: the FiLM nets of stages 0..n-2 + the speaker projections can run on a lowest-priority
-    // helper stream (mask bit 1; bit 0: the 1x1 / stretch residual convs, an experiment that never paid).  With the
-    // fused launches that is worth ~2 % at cfg2 and nothing at cfg3 / cfg1 - and only where a fork + join through the
-    // helper stream is as cheap as it should be, which ExecCtx measures once (measure_fork_join): with helper streams
-    // created after an RCCL communicator the same schedule ran cfg2 in 2.54 ms instead of 1.43.  Default: bit 1 from
-    // ~1.5e5 samples per call where the context says it pays, one stream otherwise; FASTSVC_STREAMS=<mask> forces a
-    // mask (0: one stream), FASTSVC_SERIAL one stream.
-    int64_t hop = 1;                                       // samples per frame
-    for (int i = 0; i < plan->n; ++i) hop *= plan->cfg.upsampling_scales[i];
-    int streams_mask = env().serial ? 0 : env().streams >= 0 ? (env().streams & 3) : ((int64_t)B * F * hop >= 150000 ? 2 : 0);
-    // per-launch profiling and autotuning run on ONE stream so that every kernel is timed alone
-    ExecCtx* ctx = (streams_mask == 0 || cc.tuning || prof) ? nullptr : exec_ctx_for(stream);
-    std::unique_lock<std::mutex> ctx_lock;
-    if (ctx) {
-        ctx_lock = std::unique_lock<std::mutex>(ctx->busy);
-        ensure_measured(stream, ctx);
-        if (env().streams < 0 && !ctx->pays) { ctx_lock.unlock(); ctx_lock = std::unique_lock<std::mutex>(); ctx = nullptr; streams_mask = 0; }
-    }
-    hipStream_t s_film = (ctx && (streams_mask & 2)) ? ctx->aux[0] : stream;      // FiLM nets of stages 0..n-2
-    hipStream_t s_side = (ctx && (streams_mask & 1)) ? ctx->aux[1] : stream;      // 1x1 / stretch residual convs
-    int evi = 0;
-    // `to` waits for everything enqueued on `from` so far
-    auto order_after = [&](hipStream_t from, hipStream_t to) -> hipError_t {
-        if (from == to || !ctx) return hipSuccess;
-        hipEvent_t e = ctx->ev[evi++ % ctx->ev.size()];
-        hipError_t r = hipEventRecord(e, from);
-        if (r != hipSuccess) return r;
-        return hipStreamWaitEvent(to, e, 0);
-    };
-    std::vector<hipEvent_t> ss_ready(P.n, nullptr);       // FiLM output of stage k is complete
-    const float* blob = static_cast<const float*>(dev_blob);
-    unsigned char* wsb = static_cast<unsigned char*>(workspace);
-    auto buf = [&](const std::string& name) -> float* {
-        return reinterpret_cast<float*>(wsb + ws.find(name)->off_bytes);
-    };
-    const int n = P.n;
-    const long T = (long)hop * F;
-    {
-        // The kernels address every tensor of ONE utterance through a 32-bit buffer descriptor and
-        // 32-bit byte offsets ((row * pitch + t) * 4, 2*C rows for scale/shift): the largest of those
-        // spans must stay below 2 GiB.  (C = 24 at the full rate: ~11 M samples = 7.7 min at 24 kHz.)
-        // synth.max_forward_frames restates this computation in Python (Generator and DecodeSession.convert
-        // refuse before anything is allocated or launched): change the two together.
-        long worst = 4L * T;
-        long Tk = T;
-        for (int k = 0; k < P.n; ++k) { Tk /= P.down[k].scale; worst = std::max(worst, 2L * P.down[k].C * Tk * 4); }   // film_u / ss: 2C rows
-        long Ti = F;
-        for (int i = 0; i < P.n; ++i) { Ti *= P.up[i].scale; worst = std::max(worst, 2L * P.up[i].C * Ti * 4); }
-        worst = std::max(worst, (long)P.cfg.in_channels * F * 4);
-        if (worst >= 0x7fffffffL)
-            return fail(FASTSVC_E_UNSUPPORTED, "utterance too long for the 32-bit tensor descriptors of the kernels "
-                                                "(largest per-utterance tensor must stay below 2 GiB): split it");
-    }
-    const bool spk = spk_emb != nullptr;
-    // amax row of a workspace tensor (float32 storage; see layout_workspace)
-    float* amax_inb = buf("amax_in");
-    float* amaxb = buf("amax");
-    auto am = [&](const std::string& name) -> float* {
-        return amaxb + (size_t)(ws.find(name) - ws.bufs.data()) * 2 * B * 256;
-    };
+    if (decayed && (!decay || !weight || !bound)) return fail(FASTSVC_E_INVALID, "null argument");
+    if (decayed && (reinterpret_cast<uintptr_t>(decay) | reinterpret_cast<uintptr_t>(weight) |
+                    reinterpret_cast<uintptr_t>(bound)) % sizeof(double) != 0)
+        return fail(FASTSVC_E_INVALID, "decay, weight and bound must be 8-byte aligned");
+    if (!running && (!P || B_ < 1 || F < 1)) return fail(FASTSVC_E_INVALID, "B and F must be >= 1");
+    if (running && (!P || B_ < 1 || B_ > 65535 || F < 1)) return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535 and F >= 1");
+    if (running && (carry_bytes < fastsvc_norm_carry_bytes(P) || carry_bytes % sizeof(double) != 0 ||
+                    reinterpret_cast<uintptr_t>(carry) % sizeof(double) != 0))
+        return fail(FASTSVC_E_INVALID, "carry_bytes, the bytes from one slot's record to the next, must be a multiple of 8 "
+                                       "and at least fastsvc_norm_carry_bytes; the carry 8-byte aligned");
+    if (!running && scratch_bytes < fastsvc_norm_group_scratch_bytes(P, B_, F))
+        return fail(FASTSVC_E_WORKSPACE, "norm-group scratch too small (fastsvc_norm_group_scratch_bytes)");
+    if (running && scratch_bytes < fastsvc_norm_running_scratch_bytes(P, B_, F))
+        return fail(FASTSVC_E_WORKSPACE, "running-norm scratch too small (fastsvc_norm_running_scratch_bytes)");
+    plan = P; B = B_;
+    stride = (long)(carry_bytes / sizeof(double));
+    return FASTSVC_OK;
+}
 
-    // ---- raw signals: sig 0 = lft, sig 1 = sine, read in place (the dual-signal launches address signal
-    // `sig` as base + sig * stride; the stride between the caller's two tensors is whatever it is) ----
-    const float* sigbuf = lft;
-    const std::ptrdiff_t sig_bytes = reinterpret_cast<const char*>(sine) - reinterpret_cast<const char*>(lft);
-    if (sig_bytes % (std::ptrdiff_t)sizeof(float) != 0) return fail(FASTSVC_E_INVALID, "sine / lft must be 4-byte aligned");
-    const long sig_stride = (long)(sig_bytes / (std::ptrdiff_t)sizeof(float));
-    const bool no_scan = env().no_amax_scan;                     // A/B timing only: inputs then count as unit-scale
+hipError_t NormOverride::apply(const float* ut, double* st, int i, int point, int C, int Tout, int m, const int32_t* lengths,
+                               float* amax_raise, hipStream_t stream) const {
+    if (kind == NONE) return hipSuccess;
+    const fastsvc_plan& P = *plan;
+    if (kind == GROUPED) {
+        const hipError_t e = FASTSVC_BY_STORAGE(P.storage, launch_norm_group_partials)(ut, part, B, C, Tout, lengths, m, rows, lo, hi, stream);
+        return e != hipSuccess ? e : launch_norm_group_pool(part, st, B, C, Tout, lengths, m, rows, lo, hi, amax_raise, stream);
+    }
+    // the same two launches with the slot's carry in front of the sums - this norm point's C x 2 doubles of the record
+    double* at = carry + norm_carry_doubles(P, i) + point * (long)C * 2;
+    const hipError_t e = FASTSVC_BY_STORAGE(P.storage, launch_norm_running_partials)(ut, part, B, C, Tout, lengths, m, lo, hi, prior, reset, stream);
+    return e != hipSuccess ? e : launch_norm_running_pool(part, st, B, C, Tout, lengths, m, rows, lo, hi, prior, reset, parity, at, stride,
+                                                          norm_carry_doubles(P, P.n), amax_raise, stream, decay, weight, bound);
+}
+
+// what the 2-byte storages need of the plan and the frame count
+int check_storage_gates(const fastsvc_plan& P, int F) {
+    if (P.storage == 0) return FASTSVC_OK;
+    const std::string mode = P.storage == 2 ? "float16 storage" : "bfloat16 storage";
+    if (F % 4 != 0) return fail(FASTSVC_E_UNSUPPORTED, mode + " needs a frame count that is a multiple of 4");
+    for (int k = 0; k < P.n; ++k)
+        if (P.down[k].c2[0].KC != 24 || P.up[k].d3.KC != 24 || P.up[k].first.KC != 24)
+            return fail(FASTSVC_E_UNSUPPORTED, mode + " needs the pipelined kernels (24-channel K chunks)");
+    if (P.n > 1 && !P.down[1].rc1[0].dec2) return fail(FASTSVC_E_UNSUPPORTED, mode + " needs the fused decimating pair");
+    return FASTSVC_OK;
+}
+
+// The kernels address every tensor of ONE utterance through a 32-bit buffer descriptor and
+// 32-bit byte offsets ((row * pitch + t) * 4, 2*C rows for scale/shift): the largest of those
+// spans must stay below 2 GiB.  (C = 24 at the full rate: ~11 M samples = 7.7 min at 24 kHz.)
+// synth.max_forward_frames restates this computation in Python (Generator and DecodeSession.convert
+// refuse before anything is allocated or launched): change the two together.
+int check_descriptor_span(const fastsvc_plan& P, int F, long T) {
+    long worst = 4L * T;
+    long Tk = T;
+    for (int k = 0; k < P.n; ++k) { Tk /= P.down[k].scale; worst = std::max(worst, 2L * P.down[k].C * Tk * 4); }   // film_u / ss: 2C rows
+    long Ti = F;
+    for (int i = 0; i < P.n; ++i) { Ti *= P.up[i].scale; worst = std::max(worst, 2L * P.up[i].C * Ti * 4); }
+    worst = std::max(worst, (long)P.cfg.in_channels * F * 4);
+    if (worst >= 0x7fffffffL)
+        return fail(FASTSVC_E_UNSUPPORTED, "utterance too long for the 32-bit tensor descriptors of the kernels "
+                                            "(largest per-utterance tensor must stay below 2 GiB): split it");
+    return FASTSVC_OK;
+}
+
+// float32 storage: largest magnitudes of the inputs (scales of the split-binary16 staging) and zeroed amax
+// rows of the intermediates - ONE small launch, first thing on the caller's stream (everything else is
+// ordered behind it)
+int scan_input_amax(const Fwd& f, hipStream_t stream) {
+    const fastsvc_plan& P = f.P;
+    if (f.prof) HIP_TRY(f.prof->begin(stream, "amax_inputs", "amax_inputs", 0.0,
+                                      4.0 * ((double)P.cfg.in_channels * f.F + 2.0 * (double)f.hop * f.F) * f.B));
+    HIP_TRY(launch_amax_inputs(f.sigbuf, f.sig_stride, f.ppg, f.B, P.cfg.in_channels, f.F, (int)f.hop, f.lengths, f.amax_inb, f.amaxb,
+                               (int)f.ws.find("amax")->numel, stream));
+    if (f.prof) HIP_TRY(f.prof->end());
+    return FASTSVC_OK;
+}
+
+// ---- speaker bias for all blocks + zeroed InstanceNorm accumulators: first needed by up block 0, so
+// off the critical path (the down chains) on the second helper stream, joined before the up blocks ----
+int speaker_prologue(const Fwd& f, Schedule& sch) {
+    const fastsvc_plan& P = f.P;
+    const int n = P.n, B = f.B;
+    HIP_TRY(sch.order_after(sch.stream, sch.s_pre));       // after whatever the caller enqueued before us
+    const BufferSpec* s0 = f.ws.find("up.0.stats");
+    const BufferSpec* sl = f.ws.find("up." + std::to_string(n - 1) + ".stats");
+    const size_t span = sl->off_bytes + align_up((size_t)sl->numel * sizeof(double), 256) - s0->off_bytes;
+    HIP_TRY(hipMemsetAsync(f.wsb + s0->off_bytes, 0, span, sch.s_pre));
+    SpkBlock blocks[FASTSVC_MAX_STAGES];
+    for (int i = 0; i < n; ++i) {
+        blocks[i].w = f.blob + P.up[i].emb.w_off;
+        blocks[i].bias = f.blob + P.up[i].emb.b_off;
+        blocks[i].out = f.buf("up." + std::to_string(i) + ".spk");
+        blocks[i].C = P.up[i].C;
+        blocks[i].amax = P.storage == 0 ? f.am("up." + std::to_string(i) + ".spk") : nullptr;
+    }
+    double spk_c = 0; for (int i = 0; i < n; ++i) spk_c += P.up[i].C;
+    if (f.prof) HIP_TRY(f.prof->begin(sch.s_pre, "spk_proj", "spk_proj", 2.0 * spk_c * P.cfg.spk_emb_size * B,
+                                      4.0 * (spk_c * P.cfg.spk_emb_size + (double)B * P.cfg.spk_emb_size + spk_c * B)));
+    HIP_TRY(launch_spk_proj(f.spk_emb, blocks, n, B, P.cfg.spk_emb_size, sch.s_pre));
+    if (f.prof) HIP_TRY(f.prof->end());
+    return FASTSVC_OK;
+}
+
+// What the down loop carries from stage to stage: the input of stage k.
+struct CondCursor {
+    const float* h;                    // h_{k-1}; the raw signals in front of stage 0
+    int C;
+    long Th;                           // row length of `h` as stored
+    bool compact;                      // `h` already holds h_{k-1}[..., ::s_k] (run_cond_stage0 / run_cond_stage1)
+    long Tk;                           // row length of h_{k-1} at its own rate
+};
+
+// ---- one stage of the conditioning chains: both signals per launch (gridDim.z = 2B) ----
+struct CondStage {
+    const Fwd& f;
+    Schedule& sch;
+    const int k;
+    const DownStage& d;
+    const CondCursor in;
+    const std::string s;               // the stage's number in layer and buffer names
+    const long Tk;                     // row length of the stage's tensors
+    float *c1, *c2, *h;
+    const long tsig, tb;               // signal stride of the (2B, C, Tk) buffers; row stride
+    ConvParams base;
+    // MEASURED: the stage's input (raw signal scan / the previous stage's output) and its output h_k; the tensors
+    // in between are bounded from the input's maximum through the layers' (l1, bmax) - ConvParams::bnd_path
+    float *am_prev, *am_h;
+    const float* bnd_c1;
+    long bnd_c1_sig;
+
+    CondStage(const Fwd& f_, Schedule& sch_, int k_, const CondCursor& in_)
+        : f(f_), sch(sch_), k(k_), d(f_.P.down[k_]), in(in_), s(std::to_string(k_)), Tk(in_.Tk / d.scale),
+          c1(f_.buf("down_c1." + s)), c2(f_.buf("down_c2." + s)), h(f_.buf("down_h." + s)),
+          tsig((long)f_.B * d.C * Tk), tb((long)d.C * Tk) {
+        std::memset(&base, 0, sizeof(base));
+        base.B = f.B; base.T = (int)Tk; base.s = 1; base.mode = MODE_DIRECT;
+        base.lens = f.lengths; base.frames_ld = f.F;
+        base.amax_in_sig = f.B; base.amax_out_sig = f.B;           // (2B, C, T) tensors: one amax per (signal, utterance)
+        am_prev = k == 0 ? f.amax_inb : f.am("down_h." + std::to_string(k - 1));
+        am_h = f.am("down_h." + s);
+        bnd_c1 = f.blob + (k == 0 ? d.c1_raw[0].bnd_off : d.c1[0].bnd_off);
+        bnd_c1_sig = k == 0 ? (long)(d.c1_raw[1].bnd_off - d.c1_raw[0].bnd_off) : d.c1[0].bnd_pair;
+    }
+
     // the rank-1 residual of stage 0, r = conv1x1(raw signal), added by the launch that writes h_0
-    auto set_rank1_residual = [&](const DownStage& d, ConvParams& p) -> int {
-        p.r1x = sigbuf; p.r1x_sig = sig_stride; p.r1x_b = T;
-        p.r1w = blob + d.r_raw[0].w_off; p.r1b = blob + d.r_raw[0].b_off;
+    int set_rank1_residual(ConvParams& p) const {
+        p.r1x = f.sigbuf; p.r1x_sig = f.sig_stride; p.r1x_b = f.T;
+        p.r1w = f.blob + d.r_raw[0].w_off; p.r1b = f.blob + d.r_raw[0].b_off;
         p.r1_sig = (long)(d.r_raw[1].w_off - d.r_raw[0].w_off);
         if ((d.r_raw[1].b_off - d.r_raw[0].b_off) != (d.r_raw[1].w_off - d.r_raw[0].w_off))
             return fail(FASTSVC_E_INVALID, "internal: rank-1 pair strides");
         return FASTSVC_OK;
-    };
-    if (P.storage == 0 && !no_scan) {
-        // float32 storage: largest magnitudes of the inputs (scales of the split-binary16 staging) and zeroed amax
-        // rows of the intermediates - ONE small launch, first thing on the caller's stream (everything else is
-        // ordered behind it)
-        const BufferSpec* ab = ws.find("amax");
-        if (prof) HIP_TRY(prof->begin(stream, "amax_inputs", "amax_inputs", 0.0,
-                                      4.0 * ((double)P.cfg.in_channels * F + 2.0 * (double)hop * F) * B));
-        HIP_TRY(launch_amax_inputs(sigbuf, sig_stride, ppg, B, P.cfg.in_channels, F, (int)hop, lengths, amax_inb, amaxb,
-                                   (int)ab->numel, stream));
-        if (prof) HIP_TRY(prof->end());
     }
 
-    // ---- speaker bias for all blocks + zeroed InstanceNorm accumulators: first needed by up block 0, so
-    // off the critical path (the down chains) on the second helper stream, joined before the up blocks ----
-    // (only where the helper streams pay at all: below ~1.5e5 samples per call the fork / join events cost more)
-    hipStream_t s_pre = (ctx && (streams_mask & 2)) ? ctx->aux[1] : stream;
-    if (spk) {
-        HIP_TRY(order_after(stream, s_pre));               // after whatever the caller enqueued before us
-        const BufferSpec* s0 = ws.find("up.0.stats");
-        const BufferSpec* sl = ws.find("up." + std::to_string(n - 1) + ".stats");
-        const size_t span = sl->off_bytes + align_up((size_t)sl->numel * sizeof(double), 256) - s0->off_bytes;
-        HIP_TRY(hipMemsetAsync(wsb + s0->off_bytes, 0, span, s_pre));
-        SpkBlock blocks[FASTSVC_MAX_STAGES];
-        for (int i = 0; i < n; ++i) {
-            blocks[i].w = blob + P.up[i].emb.w_off;
-            blocks[i].bias = blob + P.up[i].emb.b_off;
-            blocks[i].out = buf("up." + std::to_string(i) + ".spk");
-            blocks[i].C = P.up[i].C;
-            blocks[i].amax = P.storage == 0 ? am("up." + std::to_string(i) + ".spk") : nullptr;
-        }
-        double spk_c = 0; for (int i = 0; i < n; ++i) spk_c += P.up[i].C;
-        if (prof) HIP_TRY(prof->begin(s_pre, "spk_proj", "spk_proj", 2.0 * spk_c * P.cfg.spk_emb_size * B,
-                                      4.0 * (spk_c * P.cfg.spk_emb_size + (double)B * P.cfg.spk_emb_size + spk_c * B)));
-        HIP_TRY(launch_spk_proj(spk_emb, blocks, n, B, P.cfg.spk_emb_size, s_pre));
-        if (prof) HIP_TRY(prof->end());
-    }
-
-    // ---- conditioning chains: both signals per launch (gridDim.z = 2B) ----
-    long Tk = T;
-    const float* hprev = sigbuf;
-    int Cprev = 1;
-    long Tprev = T;
-    bool hprev_compact = false;          // hprev already holds h_{k-1}[..., ::s_k] (run_cond_stage0)
-    for (int k = 0; k < n; ++k) {
-        const DownStage& d = P.down[k];
-        Tk = Tk / d.scale;
-        const std::string s = std::to_string(k);
-        float* c1 = buf("down_c1." + s);
-        float* c2 = buf("down_c2." + s);
-        float* h = buf("down_h." + s);
-        const long tsig = (long)B * d.C * Tk;     // signal stride of the (2B, C, Tk) buffers
-        const long tb = (long)d.C * Tk;
-        ConvParams base;
-        std::memset(&base, 0, sizeof(base));
-        base.B = B; base.T = (int)Tk; base.s = 1; base.mode = MODE_DIRECT;
-        base.lens = lengths; base.frames_ld = F;
-        base.amax_in_sig = B; base.amax_out_sig = B;               // (2B, C, T) tensors: one amax per (signal, utterance)
-        // MEASURED: the stage's input (raw signal scan / the previous stage's output) and its output h_k; the tensors
-        // in between are bounded from the input's maximum through the layers' (l1, bmax) - ConvParams::bnd_path
-        float* am_prev = k == 0 ? amax_inb : am("down_h." + std::to_string(k - 1));
-        float* am_h = am("down_h." + s);
-        const float* bnd_c1 = blob + (k == 0 ? d.c1_raw[0].bnd_off : d.c1[0].bnd_off);
-        const long bnd_c1_sig = k == 0 ? (long)(d.c1_raw[1].bnd_off - d.c1_raw[0].bnd_off) : d.c1[0].bnd_pair;
-        // the stage up to h_k without the whole-stage fusion below: first conv (+ 1x1 residual), then c2 -> c3
-        auto stage_unfused = [&](Profiler* pr) -> int {
-            if (k == 0) {
-                if (pr) HIP_TRY(pr->begin(stream, "down.0.c1", "in1_conv", 2.0 * 3 * d.C * (double)Tk * B * 2,
-                                              4.0 * (1.0 + d.C) * (double)Tk * B * 2));
-                HIP_TRY(FASTSVC_BY_STORAGE(P.storage, launch_in1_conv)(sigbuf, sig_stride, blob + d.c1_raw[0].w_off, blob + d.c1_raw[0].b_off,
-                                        (long)(d.c1_raw[1].w_off - d.c1_raw[0].w_off),
-                                        (long)(d.c1_raw[1].b_off - d.c1_raw[0].b_off), c1, 2, B, d.C, (int)Tk,
-                                        lengths, (int)(Tk / F), stream, nullptr));     // (c1 is bounded, not measured)
-                if (pr) HIP_TRY(pr->end());
-            } else {
-                float* r = buf("down_r." + s);
-                ConvParams p = base;                                   // r = conv1x1(h_{k-1}[::s])
-                p.x = hprev; p.x_sig = (long)B * Cprev * Tprev; p.x_b = (long)Cprev * Tprev; p.x_T = (int)Tprev;
-                p.mode = MODE_DECIMATE; p.s = hprev_compact ? 1 : d.scale;
-                p.amax_in = am_prev;
-                if (d.rc1[0].dec2 && !env().no_dec2) {
-                    // both convs of the decimated input in one launch: c1 -> y, r -> y2
-                    p.mode = MODE_DEC2;
-                    p.y = c1; p.y_sig = tsig; p.y_b = tb;
-                    p.y2 = r; p.y2_sig = tsig; p.y2_b = tb;
-                    HIP_TRY(run_conv(cc, d.rc1, blob, p, 2, stream, pr, ("down." + s + ".c1_res1x1").c_str()));
-                } else {
-                    p.y = r; p.y_sig = tsig; p.y_b = tb;
-                    HIP_TRY(order_after(stream, s_side));                  // h_{k-1} is ready
-                    HIP_TRY(run_conv(cc, d.r, blob, p, 2, s_side, pr, ("down." + s + ".res1x1").c_str()));
-                    p.flags = F_PRE_LRELU;                                 // c1 = conv3_d1(lrelu(h_{k-1}[::s]))
-                    p.y = c1;
-                    HIP_TRY(run_conv(cc, d.c1, blob, p, 2, stream, pr, ("down." + s + ".c1").c_str()));
-                }
-            }
-            {
-                ConvParams p = base;                                   // c2 = conv3_d2(lrelu(c1))
-                p.x = c1; p.x_sig = tsig; p.x_b = tb; p.x_T = (int)Tk;
-                p.flags = F_PRE_LRELU;
-                p.amax_in = am_prev; p.bnd_path[0] = bnd_c1; p.bnd_sig[0] = bnd_c1_sig;       // |c1| <= l1 |h_{k-1}| + bmax
-                ConvParams p3 = p;                                     // h = conv3_d4(lrelu(c2)) + r
-                p3.y = h; p3.y_sig = tsig; p3.y_b = tb; p3.amax_out = am_h;
-                if (k == 0) {
-                    const int rc = set_rank1_residual(d, p3);
-                    if (rc != FASTSVC_OK) return rc;
-                } else {
-                    p3.res = buf("down_r." + s); p3.res_sig = tsig; p3.res_b = tb;
-                    HIP_TRY(order_after(s_side, stream));              // r is ready
-                }
-                const std::string n2 = "down." + s + ".c2_d2", n3 = "down." + s + ".c3_d4", n23 = "down." + s + ".c23";
-                const long b3 = (long)(d.c3[1].b_off - d.c3[0].b_off);
-                auto separate = [&](Profiler* pr) -> int {
-                    p.y = c2; p.y_sig = tsig; p.y_b = tb;
-                    HIP_TRY(run_conv(cc, d.c2, blob, p, 2, stream, pr, n2.c_str()));
-                    ConvParams q = p3;
-                    q.x = c2; q.bnd_path[1] = blob + d.c2[0].bnd_off; q.bnd_sig[1] = d.c2[0].bnd_pair;   // ... and c2 behind it
-                    HIP_TRY(run_conv(cc, d.c3, blob, q, 2, stream, pr, n3.c_str()));
-                    return FASTSVC_OK;
-                };
-                // one launch for the pair where the stage has the fused variant (c2 then never reaches memory);
-                // a tuning pass times it against the two launches and the table keeps the winner
-                return fused_or_separate(stream, cc.tuning && !pr && d.c3[0].hxc_off[0], pr, n23.c_str(),
-                    [&](double sep_ms, bool& done) { return run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, b3, stream, pr, n23.c_str(), sep_ms, done); },
-                    separate);
-            }
-        };
-        // The WHOLE stage - chain and FiLM net of both signals - as one launch where it has the variant (compact
-        // workspace: h_0 itself is then not materialised, stage 1 reads the compact decimated copy)
+    // The WHOLE stage - chain and FiLM net of both signals - as one launch where it has the variant (compact
+    // workspace: h_k itself is then not materialised, stage k + 1 reads the compact decimated copy)
+    int whole_stage(bool& whole, CondCursor& next) const {
+        const fastsvc_plan& P = f.P;
         if (k == 0 && P.compact) {
-            bool whole = false;
-            HIP_TRY(run_cond_stage0(cc, blob, sigbuf, sig_stride, B, T, F, lengths, buf("ss.0"), buf("down_hd.1"),
-                                    (P.storage == 0 && !no_scan) ? amax_inb : nullptr, am("down_h.0"), stream, prof, whole));
-            if (whole) {
-                hprev = buf("down_hd.1"); Cprev = d.C; Tprev = Tk / P.down[1].scale; hprev_compact = true;
-                continue;
-            }
+            HIP_TRY(run_cond_stage0(f.cc, f.blob, f.sigbuf, f.sig_stride, f.B, f.T, f.F, f.lengths, f.buf("ss.0"), f.buf("down_hd.1"),
+                                    (P.storage == 0 && !env().no_amax_scan) ? f.amax_inb : nullptr, f.am("down_h.0"), sch.stream, f.prof, whole));
+            if (whole) { next = CondCursor{f.buf("down_hd.1"), d.C, Tk / P.down[1].scale, true, Tk}; return FASTSVC_OK; }
             // (the layout left this stage's buffers out: there is nothing to fall back into)
-            if (cond_stage_whole(P, 0, F)) return fail(FASTSVC_E_HIP, "whole-stage launch of stage 0 declined at run time");
+            if (cond_stage_whole(P, 0, f.F)) return fail(FASTSVC_E_HIP, "whole-stage launch of stage 0 declined at run time");
         }
-        if (k == 1 && P.compact && hprev_compact && n > 2) {
-            bool whole = false;
-            HIP_TRY(run_cond_stage1(cc, blob, hprev, B, Tk, F, lengths, buf("ss.1"), buf("down_hd.2"),
-                                    P.storage == 0 ? am("down_h.0") : nullptr, am("down_h.1"), stream, prof, whole));
-            if (whole) {
-                hprev = buf("down_hd.2"); Cprev = d.C; Tprev = Tk / P.down[2].scale; hprev_compact = true;
-                continue;
-            }
-            if (cond_stage_whole(P, 1, F)) return fail(FASTSVC_E_HIP, "whole-stage launch of stage 1 declined at run time");
+        if (k == 1 && P.compact && in.compact && P.n > 2) {
+            HIP_TRY(run_cond_stage1(f.cc, f.blob, in.h, f.B, Tk, f.F, f.lengths, f.buf("ss.1"), f.buf("down_hd.2"),
+                                    P.storage == 0 ? f.am("down_h.0") : nullptr, f.am("down_h.1"), sch.stream, f.prof, whole));
+            if (whole) { next = CondCursor{f.buf("down_hd.2"), d.C, Tk / P.down[2].scale, true, Tk}; return FASTSVC_OK; }
+            if (cond_stage_whole(P, 1, f.F)) return fail(FASTSVC_E_HIP, "whole-stage launch of stage 1 declined at run time");
         }
-        // Stage 0 as ONE launch where it has the variant (MODE_CHAIN1): the staging waves compute the 1 -> C conv
-        // from the raw signal, so neither c1 nor c2 reaches memory; a tuning pass times it against the other path
-        if (k == 0 && d.c3[0].hxc_off[0]) {
-            ConvParams p3 = base;
-            p3.x = sigbuf; p3.x_sig = sig_stride; p3.x_b = T; p3.x_T = (int)Tk;
-            p3.flags = F_PRE_LRELU;
-            p3.y = h; p3.y_sig = tsig; p3.y_b = tb;
-            p3.amax_in = amax_inb; p3.amax_out = am_h;
-            const int rc1 = set_rank1_residual(d, p3);
-            if (rc1 != FASTSVC_OK) return rc1;
-            const int rc = fused_or_separate(stream, cc.tuning && !prof, prof, "down.0.c123",
-                [&](double sep_ms, bool& done) {
-                    return run_chain(cc, d.c2[0], d.c3[0], blob, p3, 2, (long)(d.c3[1].b_off - d.c3[0].b_off), stream, prof,
-                                     "down.0.c123", sep_ms, done, d.c1_raw);
-                },
-                stage_unfused);
-            if (rc != FASTSVC_OK) return rc;
+        return FASTSVC_OK;
+    }
+
+    // c1 (+ the 1x1 residual r of stages >= 1) from the stage's input
+    int first_conv(Profiler* pr) {
+        const int B = f.B;
+        hipStream_t stream = sch.stream;
+        if (k == 0) {
+            if (pr) HIP_TRY(pr->begin(stream, "down.0.c1", "in1_conv", 2.0 * 3 * d.C * (double)Tk * B * 2,
+                                          4.0 * (1.0 + d.C) * (double)Tk * B * 2));
+            HIP_TRY(FASTSVC_BY_STORAGE(f.P.storage, launch_in1_conv)(f.sigbuf, f.sig_stride, f.blob + d.c1_raw[0].w_off, f.blob + d.c1_raw[0].b_off,
+                                    (long)(d.c1_raw[1].w_off - d.c1_raw[0].w_off),
+                                    (long)(d.c1_raw[1].b_off - d.c1_raw[0].b_off), c1, 2, B, d.C, (int)Tk,
+                                    f.lengths, (int)(Tk / f.F), stream, nullptr));     // (c1 is bounded, not measured)
+            if (pr) HIP_TRY(pr->end());
+            return FASTSVC_OK;
+        }
+        float* r = f.buf("down_r." + s);
+        ConvParams p = base;                                   // r = conv1x1(h_{k-1}[::s])
+        p.x = in.h; p.x_sig = (long)B * in.C * in.Th; p.x_b = (long)in.C * in.Th; p.x_T = (int)in.Th;
+        p.mode = MODE_DECIMATE; p.s = in.compact ? 1 : d.scale;
+        p.amax_in = am_prev;
+        if (d.rc1[0].dec2 && !env().no_dec2) {
+            // both convs of the decimated input in one launch: c1 -> y, r -> y2
+            p.mode = MODE_DEC2;
+            p.y = c1; p.y_sig = tsig; p.y_b = tb;
+            p.y2 = r; p.y2_sig = tsig; p.y2_b = tb;
+            HIP_TRY(run_conv(f.cc, d.rc1, f.blob, p, 2, stream, pr, ("down." + s + ".c1_res1x1").c_str()));
         } else {
-            const int rc = stage_unfused(prof);
-            if (rc != FASTSVC_OK) return rc;
+            p.y = r; p.y_sig = tsig; p.y_b = tb;
+            HIP_TRY(sch.order_after(stream, sch.s_side));          // h_{k-1} is ready
+            HIP_TRY(run_conv(f.cc, d.r, f.blob, p, 2, sch.s_side, pr, ("down." + s + ".res1x1").c_str()));
+            p.flags = F_PRE_LRELU;                                 // c1 = conv3_d1(lrelu(h_{k-1}[::s]))
+            p.y = c1;
+            HIP_TRY(run_conv(f.cc, d.c1, f.blob, p, 2, stream, pr, ("down." + s + ".c1").c_str()));
         }
-        {
-            // the FiLM net of the LAST stage feeds the first up block: critical path, caller's stream;
-            // the others are only needed by later up blocks: helper stream
-            hipStream_t sf = (k == n - 1) ? stream : s_film;
-            HIP_TRY(order_after(stream, sf));                      // h_k is ready
-            float* u = buf("film_u." + s);                         // (B, 2C, Tk): [lft ; sine] channels
-            float* ssb = buf("ss." + s);
-            const std::string nconv = "film." + s + ".conv", nheads = "film." + s + ".heads", nchain = "film." + s + ".chain";
-            auto film_separate = [&](Profiler* pr) -> int {
-                ConvParams p = base;
-                p.x = h; p.x_sig = tsig; p.x_b = tb; p.x_T = (int)Tk;
-                p.flags = F_POST_LRELU;
-                p.y = u; p.y_sig = tb; p.y_b = 2 * tb;
-                p.amax_in = am_h;
-                HIP_TRY(run_conv(cc, d.film, blob, p, 2, sf, pr, nconv.c_str()));
-                ConvParams q = base;                               // [scale ; shift] summed over both signals
-                q.x = u; q.x_sig = 0; q.x_b = 2 * tb; q.x_T = (int)Tk;
-                q.y = ssb; q.y_sig = 0; q.y_b = 2 * tb;
-                // u = [lrelu(conv_lft(h_lft)) ; lrelu(conv_sine(h_sine))]: the larger of the two halves' bounds
-                q.amax_in = am_h; q.amax_in_sig = 0; q.amax_in2 = B;
-                q.bnd_path[0] = blob + d.film[0].bnd_off; q.bnd_sig[0] = d.film[0].bnd_pair;
-                HIP_TRY(run_conv(cc, &d.heads, blob, q, 1, sf, pr, nheads.c_str()));
-                return FASTSVC_OK;
-            };
-            // the whole FiLM net of the stage in one launch where it has the variant: the 2C-channel intermediate
-            // stays in LDS (block-diagonal first conv over both chains' outputs, then the heads)
-            if (d.filmc.hxc_off[0] && ((long)tsig + (long)d.C * Tk) * 4 < (1L << 31)) {
-                ConvParams p3 = base;
-                p3.x = h; p3.x_sig = tsig; p3.x_b = tb; p3.x_T = (int)Tk; p3.xsplit = d.C;
-                p3.y = ssb; p3.y_sig = 0; p3.y_b = 2 * tb;
-                p3.amax_in = am_h; p3.amax_in2 = B;                 // channels [lft ; sine]: the larger of the two chains' maxima
-                const int rc = fused_or_separate(sf, cc.tuning && !prof, prof, nchain.c_str(),
-                    [&](double sep_ms, bool& done) { return run_chain(cc, d.filmc, d.filmc, blob, p3, 1, 0, sf, prof, nchain.c_str(), sep_ms, done); },
-                    film_separate);
-                if (rc != FASTSVC_OK) return rc;
-            } else {
-                const int rc = film_separate(prof);
-                if (rc != FASTSVC_OK) return rc;
-            }
-            if (sf != stream && ctx) {
-                ss_ready[k] = ctx->ev[evi++ % ctx->ev.size()];
-                HIP_TRY(hipEventRecord(ss_ready[k], sf));
-            }
-        }
-        hprev = h; Cprev = d.C; Tprev = Tk; hprev_compact = false;
+        return FASTSVC_OK;
     }
 
-    // ---- up blocks ----
-    if (spk) HIP_TRY(order_after(s_pre, stream));           // speaker biases and zeroed sums are ready
-    const float* x = ppg;
-    if (P.storage != 0) {                                          // external float32 input -> workspace bfloat16 / binary16
-        float* pa = buf("ppg_act");
-        HIP_TRY((P.storage == 2 ? f16::launch_act_convert : bf16::launch_act_convert)(ppg, pa, (long)B * P.cfg.in_channels * F, stream));
-        x = pa;
+    // the pair as two launches: p reads c1, p3 writes h
+    int pair_separate(ConvParams p, const ConvParams& p3, Profiler* pr) {
+        p.y = c2; p.y_sig = tsig; p.y_b = tb;
+        HIP_TRY(run_conv(f.cc, d.c2, f.blob, p, 2, sch.stream, pr, ("down." + s + ".c2_d2").c_str()));
+        ConvParams q = p3;
+        q.x = c2; q.bnd_path[1] = f.blob + d.c2[0].bnd_off; q.bnd_sig[1] = d.c2[0].bnd_pair;   // ... and c2 behind it
+        HIP_TRY(run_conv(f.cc, d.c3, f.blob, q, 2, sch.stream, pr, ("down." + s + ".c3_d4").c_str()));
+        return FASTSVC_OK;
     }
-    int Cx = P.cfg.in_channels;
-    long Tin = F;
-    bool last_done = false;
-    bool last_fusable = true;
-    {
-        char key[96];
-        std::snprintf(key, sizeof(key), "conv_last|%d|%ld%s", B, (long)T, key_suffix(P.storage));
-        fastsvc_plan::Choice ch;
-        if (env().no_fuse_last || (table_entry(P, key, ch) && ch.algo != 3)) last_fusable = false;
-    }
-    for (int i = 0; i < n; ++i) {
-        const UpStage& u = P.up[i];
-        const int k = n - 1 - i;
-        const long Tout = Tin * u.scale;
-        const std::string s = std::to_string(i);
-        float* a = buf("up." + s + ".a");
-        float* xr = buf("up." + s + ".xr");
-        float* u1 = buf("up." + s + ".u1");
-        float* xm = buf("up." + s + ".xmid");
-        float* u2 = buf("up." + s + ".u2");
-        float* u3 = buf("up." + s + ".u3");
-        float* xo = buf("up." + s + ".out");
-        float* pb = buf("up." + s + ".spk");
-        double* st = reinterpret_cast<double*>(buf("up." + s + ".stats"));
-        const float* ss = buf("ss." + std::to_string(k));
-        const long cb = (long)u.C * Tout;
-        const long stn = (long)B * u.C * 2;
-        ConvParams base;
-        std::memset(&base, 0, sizeof(base));
-        base.B = B; base.s = 1; base.mode = MODE_DIRECT;
-        base.lens = lengths; base.frames_ld = F;
-        // Every tensor that feeds a FiLM-affine is stored already affined (u = scale*t + shift,
-        // written by the producing epilogue, which also accumulates its InstanceNorm sums), so the
-        // consuming conv stages ONE tensor and applies (u - mean) * rstd + p, LeakyReLU on the fly.
-        const int aff_out = F_AFF_OUT | (spk ? F_STATS : 0);
-        const int pre = F_PRE_LRELU | (spk ? F_PRE_NORM : 0);
 
-        if (ss_ready[k]) HIP_TRY(hipStreamWaitEvent(stream, ss_ready[k], 0));   // scale/shift of stage k
-
-        // amax rows (float32 storage): every tensor a convolution stages WITHOUT an InstanceNorm in front
-        float* am_x = i == 0 ? amax_inb + 2 * B * 256 : am("up." + std::to_string(i - 1) + ".out");
-        float* am_p = am("up." + s + ".spk");                      // speaker biases: bound of a normalised row
-        // the block's head - conv_first and the two stretched convs behind it - as ONE launch where it has the variant
-        bool head_fused = false;
-        {
-            ConvParams ph = base;
-            ph.x = x; ph.x_b = (long)Cx * Tin; ph.x_T = (int)Tin;
-            ph.y = xr; ph.y_b = cb; ph.y2 = u1; ph.y2_b = cb;
-            ph.flags = F_POST_LRELU | aff_out;
-            ph.ss_out = ss; ph.ss_out_b = 2 * cb; ph.st_out = st;
-            ph.amax_in = am_x;
-            HIP_TRY(run_uphead(cc, u, blob, ph, stream, prof, ("up." + s + ".head").c_str(), head_fused));
+    // the stage up to h_k without the whole-stage fusion: first conv (+ 1x1 residual), then c2 -> c3
+    int unfused(Profiler* pr) {
+        FWD_STEP(first_conv(pr));
+        ConvParams p = base;                                   // c2 = conv3_d2(lrelu(c1))
+        p.x = c1; p.x_sig = tsig; p.x_b = tb; p.x_T = (int)Tk;
+        p.flags = F_PRE_LRELU;
+        p.amax_in = am_prev; p.bnd_path[0] = bnd_c1; p.bnd_sig[0] = bnd_c1_sig;       // |c1| <= l1 |h_{k-1}| + bmax
+        ConvParams p3 = p;                                     // h = conv3_d4(lrelu(c2)) + r
+        p3.y = h; p3.y_sig = tsig; p3.y_b = tb; p3.amax_out = am_h;
+        if (k == 0) {
+            FWD_STEP(set_rank1_residual(p3));
+        } else {
+            p3.res = f.buf("down_r." + s); p3.res_sig = tsig; p3.res_b = tb;
+            HIP_TRY(sch.order_after(sch.s_side, sch.stream));  // r is ready
         }
-        // xmid = conv_d3(lrelu(norm(u1))) + xr with xr computed INSIDE that launch from `a` (run_d3x) where the variant
-        // exists and the launch table does not say otherwise: the residual conv's launch and the tensor xr then go
-        ConvParams pd3 = base;
-        pd3.x = u1; pd3.x_b = cb; pd3.x_T = (int)Tout; pd3.T = (int)Tout;
-        pd3.flags = pre | aff_out; pd3.st_in = st; pd3.spk = pb;
-        pd3.amax_in = spk ? am_p : nullptr;
-        pd3.no_hx = (!spk && P.storage == 0) ? 1 : 0;
-        pd3.y = xm; pd3.y_b = cb; pd3.y2 = u2; pd3.y2_b = cb;
-        pd3.ss_out = ss; pd3.ss_out_b = 2 * cb; pd3.st_out = st + stn;
-        pd3.x2 = a; pd3.x2_b = (long)u.C * Tin; pd3.x2_T = (int)Tin; pd3.s2 = u.scale;
-        pd3.amax_x2 = am_x; pd3.bnd_x2 = blob + u.first.bnd_off;   // |a| <= l1 |x| + bmax
-        const std::string nd3x = "up." + s + ".d3x";
-        bool d3_fused = false;
-        if (!head_fused) HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 0, 0.0, d3_fused));
+        const std::string n23 = "down." + s + ".c23";
+        const long b3 = (long)(d.c3[1].b_off - d.c3[0].b_off);
+        // one launch for the pair where the stage has the fused variant (c2 then never reaches memory);
+        // a tuning pass times it against the two launches and the table keeps the winner
+        return fused_or_separate(sch.stream, f.cc.tuning && !pr && d.c3[0].hxc_off[0], pr, n23.c_str(),
+            [&](double sep_ms, bool& done) { return run_chain(f.cc, d.c2[0], d.c3[0], f.blob, p3, 2, b3, sch.stream, pr, n23.c_str(), sep_ms, done); },
+            [&](Profiler* q) { return pair_separate(p, p3, q); });
+    }
+
+    // Stage 0 as ONE launch where it has the variant (MODE_CHAIN1): the staging waves compute the 1 -> C conv
+    // from the raw signal, so neither c1 nor c2 reaches memory; a tuning pass times it against the other path
+    int chain1() {
+        ConvParams p3 = base;
+        p3.x = f.sigbuf; p3.x_sig = f.sig_stride; p3.x_b = f.T; p3.x_T = (int)Tk;
+        p3.flags = F_PRE_LRELU;
+        p3.y = h; p3.y_sig = tsig; p3.y_b = tb;
+        p3.amax_in = f.amax_inb; p3.amax_out = am_h;
+        FWD_STEP(set_rank1_residual(p3));
+        return fused_or_separate(sch.stream, f.cc.tuning && !f.prof, f.prof, "down.0.c123",
+            [&](double sep_ms, bool& done) {
+                return run_chain(f.cc, d.c2[0], d.c3[0], f.blob, p3, 2, (long)(d.c3[1].b_off - d.c3[0].b_off), sch.stream, f.prof,
+                                 "down.0.c123", sep_ms, done, d.c1_raw);
+            },
+            [&](Profiler* q) { return unfused(q); });
+    }
+
+    // the FiLM net as two launches on `sf`: u (B, 2C, Tk) = [lft ; sine] channels, then the heads
+    int film_separate(hipStream_t sf, float* u, float* ssb, Profiler* pr) {
         ConvParams p = base;
-        if (!head_fused) {
-            p = base;                                                  // a = conv_first(x)
-            p.x = x; p.x_b = (long)Cx * Tin; p.x_T = (int)Tin;
-            p.y = a; p.y_b = (long)u.C * Tin; p.T = (int)Tin;
-            p.amax_in = am_x;
-            HIP_TRY(run_conv(cc, &u.first, blob, p, 1, stream, prof, ("up." + s + ".conv_first").c_str()));
+        p.x = h; p.x_sig = tsig; p.x_b = tb; p.x_T = (int)Tk;
+        p.flags = F_POST_LRELU;
+        p.y = u; p.y_sig = tb; p.y_b = 2 * tb;
+        p.amax_in = am_h;
+        HIP_TRY(run_conv(f.cc, d.film, f.blob, p, 2, sf, pr, ("film." + s + ".conv").c_str()));
+        ConvParams q = base;                               // [scale ; shift] summed over both signals
+        q.x = u; q.x_sig = 0; q.x_b = 2 * tb; q.x_T = (int)Tk;
+        q.y = ssb; q.y_sig = 0; q.y_b = 2 * tb;
+        // u = [lrelu(conv_lft(h_lft)) ; lrelu(conv_sine(h_sine))]: the larger of the two halves' bounds
+        q.amax_in = am_h; q.amax_in_sig = 0; q.amax_in2 = f.B;
+        q.bnd_path[0] = f.blob + d.film[0].bnd_off; q.bnd_sig[0] = d.film[0].bnd_pair;
+        HIP_TRY(run_conv(f.cc, &d.heads, f.blob, q, 1, sf, pr, ("film." + s + ".heads").c_str()));
+        return FASTSVC_OK;
+    }
 
-            p = base;                                                  // xr = conv_res(stretch(a))
-            p.x = a; p.x_b = (long)u.C * Tin; p.x_T = (int)Tin;
-            p.mode = MODE_STRETCH; p.s = u.scale;
-            p.y = xr; p.y_b = cb; p.T = (int)Tout;
-            p.amax_in = am_x; p.bnd_path[0] = blob + u.first.bnd_off;  // |a| <= l1 |x| + bmax  (xr is only ever a residual: not tracked)
-            if (!d3_fused) {
-                HIP_TRY(order_after(stream, s_side));                      // a is ready
-                HIP_TRY(run_conv(cc, &u.res, blob, p, 1, s_side, prof, ("up." + s + ".res_stretch").c_str()));
-            }
-
-            p.flags = F_PRE_LRELU | F_POST_LRELU | aff_out;            // u1 = aff(lrelu(conv_up(stretch(lrelu(a)))))
-            p.y = nullptr; p.y2 = u1; p.y2_b = cb;
-            p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st;
-            HIP_TRY(run_conv(cc, &u.up, blob, p, 1, stream, prof, ("up." + s + ".up_stretch").c_str()));
+    // the stage's scale / shift from h_k
+    int film() {
+        // the FiLM net of the LAST stage feeds the first up block: critical path, caller's stream;
+        // the others are only needed by later up blocks: helper stream
+        hipStream_t sf = (k == f.P.n - 1) ? sch.stream : sch.s_film;
+        HIP_TRY(sch.order_after(sch.stream, sf));              // h_k is ready
+        float* u = f.buf("film_u." + s);
+        float* ssb = f.buf("ss." + s);
+        // the whole FiLM net of the stage in one launch where it has the variant: the 2C-channel intermediate
+        // stays in LDS (block-diagonal first conv over both chains' outputs, then the heads)
+        if (d.filmc.hxc_off[0] && ((long)tsig + (long)d.C * Tk) * 4 < (1L << 31)) {
+            const std::string nchain = "film." + s + ".chain";
+            ConvParams p3 = base;
+            p3.x = h; p3.x_sig = tsig; p3.x_b = tb; p3.x_T = (int)Tk; p3.xsplit = d.C;
+            p3.y = ssb; p3.y_sig = 0; p3.y_b = 2 * tb;
+            p3.amax_in = am_h; p3.amax_in2 = f.B;               // channels [lft ; sine]: the larger of the two chains' maxima
+            FWD_STEP(fused_or_separate(sf, f.cc.tuning && !f.prof, f.prof, nchain.c_str(),
+                [&](double sep_ms, bool& done) { return run_chain(f.cc, d.filmc, d.filmc, f.blob, p3, 1, 0, sf, f.prof, nchain.c_str(), sep_ms, done); },
+                [&](Profiler* q) { return film_separate(sf, u, ssb, q); }));
+        } else {
+            FWD_STEP(film_separate(sf, u, ssb, f.prof));
         }
+        HIP_TRY(sch.record_ready(k, sf));
+        return FASTSVC_OK;
+    }
+};
 
-        // tiny batches: the sums the epilogue accumulated are replaced by exact ones (see stats_exact_kernel)
-        auto exact_stats = [&](const float* ut, double* stp) -> hipError_t {
-            // ... and, in a small ragged batch of float32 storage, for its utterances of at most 4 frames (the launch is
-            // B x C one-wave workgroups that leave at once for the longer ones: not worth it on big batches, where a
-            // decode harness's length buckets never put a 1-frame utterance anyway)
-            const bool small_ragged = lengths && P.storage == 0 && F <= 64;
-            if (!spk) return hipSuccess;
-            hipError_t e = hipSuccess;
-            if (cc.exact_f32 || small_ragged)
-                e = launch_stats_exact(ut, stp, B, u.C, (int)Tout, lengths, (int)(Tout / F), 4, stream);
-            // Grouped rows (fastsvc_forward_grouped): the sums over the columns each row owns, pooled over its group and
-            // scaled to the row's own length, overwrite whatever stands in the row's slots - the conv's sums or the exact
-            // ones above, which stay those of the pass-through rows.  Two launches per norm point.  Behind the block's
-            // FIRST producer the pool also raises the rows' entries of the speaker biases' amax row (float32 storage):
-            // the bound of a normalised row is then sqrt(owned columns of the group), not sqrt(row length), and every
-            // consumer of the block that reads it runs behind this launch.
-            if (e == hipSuccess && cc.ng_group) {
-                const int m = (int)(Tout / F);
-                e = FASTSVC_BY_STORAGE(P.storage, launch_norm_group_partials)(ut, cc.ng_part, B, u.C, (int)Tout, lengths, m,
-                                                                              cc.ng_group, cc.ng_lo, cc.ng_hi, stream);
-                if (e == hipSuccess)
-                    e = launch_norm_group_pool(cc.ng_part, stp, B, u.C, (int)Tout, lengths, m, cc.ng_group, cc.ng_lo, cc.ng_hi,
-                                               (P.storage == 0 && stp == st) ? am_p : nullptr, stream);
-            }
-            // Rows of live streams (fastsvc_forward_running): the same two launches with the slot's carry in front of the
-            // sums - this norm point's C x 2 doubles of the record, (stp - st) / stn the point of the block.
-            if (e == hipSuccess && cc.nr_slot) {
-                const int m = (int)(Tout / F);
-                const long entry = norm_carry_doubles(P, n);
-                double* carry = cc.nr_carry + norm_carry_doubles(P, i) + (stp - st) / stn * (long)u.C * 2;
-                e = FASTSVC_BY_STORAGE(P.storage, launch_norm_running_partials)(ut, cc.ng_part, B, u.C, (int)Tout, lengths, m,
-                                                                                cc.ng_lo, cc.ng_hi, cc.nr_prior, cc.nr_reset, stream);
-                if (e == hipSuccess)
-                    e = launch_norm_running_pool(cc.ng_part, stp, B, u.C, (int)Tout, lengths, m, cc.nr_slot, cc.ng_lo, cc.ng_hi,
-                                                 cc.nr_prior, cc.nr_reset, cc.nr_parity, carry, cc.nr_stride, entry,
-                                                 (P.storage == 0 && stp == st) ? am_p : nullptr, stream, cc.nr_decay,
-                                                 cc.nr_weight, cc.nr_bound);
-            }
-            return e;
-        };
-        HIP_TRY(exact_stats(u1, st));
-        p = base;                                                  // xmid = conv_d3(lrelu(norm(u1))) + xr
+// stage k of the down loop: reads what `in` names, returns what stage k + 1 reads
+int cond_stage(const Fwd& f, Schedule& sch, int k, const CondCursor in, CondCursor& next) {
+    CondStage st(f, sch, k, in);
+    bool whole = false;
+    FWD_STEP(st.whole_stage(whole, next));
+    if (whole) return FASTSVC_OK;
+    FWD_STEP((k == 0 && st.d.c3[0].hxc_off[0]) ? st.chain1() : st.unfused(f.prof));
+    FWD_STEP(st.film());
+    next = CondCursor{st.h, st.d.C, st.Tk, false, st.Tk};
+    return FASTSVC_OK;
+}
+
+// What the up loop carries from block to block: the input of block i.
+struct UpCursor {
+    const float* x;
+    int C;
+    long T;
+};
+
+// ---- one up block ----
+struct UpBlock {
+    const Fwd& f;
+    Schedule& sch;
+    const int i, k;                    // the block; the conditioning stage whose scale / shift it applies
+    const UpStage& u;
+    const UpCursor in;
+    const std::string s;               // the block's number in layer and buffer names
+    const long Tin, Tout;
+    const long cb, stn;                // row stride of the block's (B, C, Tout) tensors; doubles of one norm point's sums
+    float *a, *xr, *u1, *xm, *u2, *u3, *xo, *pb;
+    double* st;
+    const float* ss;
+    ConvParams base;
+    // Every tensor that feeds a FiLM-affine is stored already affined (u = scale*t + shift,
+    // written by the producing epilogue, which also accumulates its InstanceNorm sums), so the
+    // consuming conv stages ONE tensor and applies (u - mean) * rstd + p, LeakyReLU on the fly.
+    int aff_out, pre;
+    // amax rows (float32 storage): every tensor a convolution stages WITHOUT an InstanceNorm in front
+    float* am_x;
+    float* am_p;                       // speaker biases: bound of a normalised row
+
+    UpBlock(const Fwd& f_, Schedule& sch_, int i_, const UpCursor& in_)
+        : f(f_), sch(sch_), i(i_), k(f_.P.n - 1 - i_), u(f_.P.up[i_]), in(in_), s(std::to_string(i_)), Tin(in_.T),
+          Tout(in_.T * u.scale), cb((long)u.C * Tout), stn((long)f_.B * u.C * 2),
+          a(f_.buf("up." + s + ".a")), xr(f_.buf("up." + s + ".xr")), u1(f_.buf("up." + s + ".u1")),
+          xm(f_.buf("up." + s + ".xmid")), u2(f_.buf("up." + s + ".u2")), u3(f_.buf("up." + s + ".u3")),
+          xo(f_.buf("up." + s + ".out")), pb(f_.buf("up." + s + ".spk")),
+          st(reinterpret_cast<double*>(f_.buf("up." + s + ".stats"))), ss(f_.buf("ss." + std::to_string(k))) {
+        std::memset(&base, 0, sizeof(base));
+        base.B = f.B; base.s = 1; base.mode = MODE_DIRECT;
+        base.lens = f.lengths; base.frames_ld = f.F;
+        aff_out = F_AFF_OUT | (f.spk ? F_STATS : 0);
+        pre = F_PRE_LRELU | (f.spk ? F_PRE_NORM : 0);
+        am_x = i == 0 ? f.amax_inb + 2 * f.B * 256 : f.am("up." + std::to_string(i - 1) + ".out");
+        am_p = f.am("up." + s + ".spk");
+    }
+
+    // the block's head - conv_first and the two stretched convs behind it - as ONE launch where it has the variant
+    int head(bool& fused) const {
+        ConvParams ph = base;
+        ph.x = in.x; ph.x_b = (long)in.C * Tin; ph.x_T = (int)Tin;
+        ph.y = xr; ph.y_b = cb; ph.y2 = u1; ph.y2_b = cb;
+        ph.flags = F_POST_LRELU | aff_out;
+        ph.ss_out = ss; ph.ss_out_b = 2 * cb; ph.st_out = st;
+        ph.amax_in = am_x;
+        HIP_TRY(run_uphead(f.cc, u, f.blob, ph, sch.stream, f.prof, ("up." + s + ".head").c_str(), fused));
+        return FASTSVC_OK;
+    }
+
+    // xr = conv_res(stretch(a))
+    ConvParams stretch_params() const {
+        ConvParams p = base;
+        p.x = a; p.x_b = (long)u.C * Tin; p.x_T = (int)Tin;
+        p.mode = MODE_STRETCH; p.s = u.scale;
+        p.y = xr; p.y_b = cb; p.T = (int)Tout;
+        p.amax_in = am_x; p.bnd_path[0] = f.blob + u.first.bnd_off;    // |a| <= l1 |x| + bmax  (xr is only ever a residual: not tracked)
+        return p;
+    }
+
+    // xmid = conv_d3(lrelu(norm(u1))) + xr, and u2 = aff(xmid)
+    ConvParams d3_params() const {
+        ConvParams p = base;
         p.x = u1; p.x_b = cb; p.x_T = (int)Tout; p.T = (int)Tout;
         p.flags = pre | aff_out; p.st_in = st; p.spk = pb;
         p.res = xr; p.res_b = cb;
@@ -3545,77 +3581,226 @@ static int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_b
         // (fastsvc.py:134-140): the three FiLM affines of a block multiply unnormalised activations, nothing bounds
         // them short of measuring every FiLM-affined tensor in the store-bound FiLM epilogues - that path keeps
         // these three convs on the exact f32-input MFMA kernels instead (float32 storage; bf16 has float32's range)
-        p.amax_in = spk ? am_p : nullptr;
-        p.no_hx = (!spk && P.storage == 0) ? 1 : 0;
-        p.y = xm; p.y_b = cb; p.y2 = u2; p.y2_b = cb;              // and u2 = aff(xmid)
+        p.amax_in = f.spk ? am_p : nullptr;
+        p.no_hx = (!f.spk && f.P.storage == 0) ? 1 : 0;
+        p.y = xm; p.y_b = cb; p.y2 = u2; p.y2_b = cb;
         p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st + stn;
+        return p;
+    }
+
+    // ... with xr computed INSIDE that launch from `a` (run_d3x) where the variant exists and the launch table does
+    // not say otherwise: the residual conv's launch and the tensor xr then go
+    ConvParams d3x_params() const {
+        ConvParams p = d3_params();
+        p.res = nullptr; p.res_b = 0;
+        p.x2 = a; p.x2_b = (long)u.C * Tin; p.x2_T = (int)Tin; p.s2 = u.scale;
+        p.amax_x2 = am_x; p.bnd_x2 = f.blob + u.first.bnd_off;     // |a| <= l1 |x| + bmax
+        return p;
+    }
+
+    // the head as separate launches: a, xr (not when the d3x route computes it) and u1
+    int first_res_up(bool d3_fused) {
+        hipStream_t stream = sch.stream;
+        ConvParams p = base;                                       // a = conv_first(x)
+        p.x = in.x; p.x_b = (long)in.C * Tin; p.x_T = (int)Tin;
+        p.y = a; p.y_b = (long)u.C * Tin; p.T = (int)Tin;
+        p.amax_in = am_x;
+        HIP_TRY(run_conv(f.cc, &u.first, f.blob, p, 1, stream, f.prof, ("up." + s + ".conv_first").c_str()));
+
+        p = stretch_params();
+        if (!d3_fused) {
+            HIP_TRY(sch.order_after(stream, sch.s_side));              // a is ready
+            HIP_TRY(run_conv(f.cc, &u.res, f.blob, p, 1, sch.s_side, f.prof, ("up." + s + ".res_stretch").c_str()));
+        }
+
+        p.flags = F_PRE_LRELU | F_POST_LRELU | aff_out;            // u1 = aff(lrelu(conv_up(stretch(lrelu(a)))))
+        p.y = nullptr; p.y2 = u1; p.y2_b = cb;
+        p.ss_out = ss; p.ss_out_b = 2 * cb; p.st_out = st;
+        HIP_TRY(run_conv(f.cc, &u.up, f.blob, p, 1, stream, f.prof, ("up." + s + ".up_stretch").c_str()));
+        return FASTSVC_OK;
+    }
+
+    // tiny batches: the sums the epilogue accumulated are replaced by exact ones (see stats_exact_kernel)
+    hipError_t exact_sums(const float* ut, double* stp) const {
+        // ... and, in a small ragged batch of float32 storage, for its utterances of at most 4 frames (the launch is
+        // B x C one-wave workgroups that leave at once for the longer ones: not worth it on big batches, where a
+        // decode harness's length buckets never put a 1-frame utterance anyway)
+        const bool small_ragged = f.lengths && f.P.storage == 0 && f.F <= 64;
+        if (!f.cc.exact_f32 && !small_ragged) return hipSuccess;
+        return launch_stats_exact(ut, stp, f.B, u.C, (int)Tout, f.lengths, (int)(Tout / f.F), 4, sch.stream);
+    }
+
+    // behind the producer of norm point `point` (0: u1, 1: u2, 2: u3): the exact sums, then the call's override
+    int norm_point(const float* ut, int point) const {
+        if (!f.spk) return FASTSVC_OK;
+        double* stp = st + point * stn;
+        HIP_TRY(exact_sums(ut, stp));
+        HIP_TRY(f.cc.norm.apply(ut, stp, i, point, u.C, (int)Tout, (int)(Tout / f.F), f.lengths,
+                                (f.P.storage == 0 && point == 0) ? am_p : nullptr, sch.stream));
+        return FASTSVC_OK;
+    }
+
+    // xmid and u2, on the route the query call in front of conv_first decided
+    int d3(const ConvParams& pd3, bool d3_fused, bool head_fused) {
         if (d3_fused) {
             bool ran = false;
-            HIP_TRY(run_d3x(cc, u, blob, pd3, stream, prof, nd3x.c_str(), 1, 0.0, ran));
+            HIP_TRY(run_d3x(f.cc, u, f.blob, pd3, sch.stream, f.prof, ("up." + s + ".d3x").c_str(), 1, 0.0, ran));
             // (the route was decided by the query call in front of conv_first - the separate residual launch was skipped on its
             // word; a launch table that changed in between - another thread's load_tuned on this plan - must not leave xmid / u2
             // unwritten: ADVICE r5)
             if (!ran) return fail(FASTSVC_E_INVALID, "up." + s + ".d3x: the launch table changed between the route decision and the launch");
-        } else {
-            HIP_TRY(order_after(s_side, stream));                      // xr is ready
-            HIP_TRY(run_conv(cc, &u.d3, blob, p, 1, stream, prof, ("up." + s + ".d3").c_str()));
-            if (cc.tuning && !prof && !head_fused) {
-                // tuning pass: the two separate launches again, timed, then the fused shapes against them
-                ConvParams pr = base;
-                pr.x = a; pr.x_b = (long)u.C * Tin; pr.x_T = (int)Tin;
-                pr.mode = MODE_STRETCH; pr.s = u.scale;
-                pr.y = xr; pr.y_b = cb; pr.T = (int)Tout;
-                pr.amax_in = am_x; pr.bnd_path[0] = blob + u.first.bnd_off;
-                ConvParams pq = p;
-                pq.flags &= ~F_STATS;                                  // (the InstanceNorm sums are accumulated once)
-                double sep_ms = 0.0;
-                const int rc = time_separate(stream, false, [&]() {
-                    if (run_conv(cc, &u.res, blob, pr, 1, stream, nullptr, ("up." + s + ".res_stretch").c_str()) != hipSuccess ||
-                        run_conv(cc, &u.d3, blob, pq, 1, stream, nullptr, ("up." + s + ".d3").c_str()) != hipSuccess)
-                        return fail(FASTSVC_E_HIP, "timing the separate residual / d3 launches");
-                    return (int)FASTSVC_OK;
-                }, sep_ms);
-                if (rc != FASTSVC_OK) return rc;
-                bool dummy = false;
-                HIP_TRY(run_d3x(cc, u, blob, pd3, stream, nullptr, nd3x.c_str(), 2, sep_ms, dummy));
-            }
+            return FASTSVC_OK;
         }
-        HIP_TRY(exact_stats(u2, st + stn));
+        HIP_TRY(sch.order_after(sch.s_side, sch.stream));              // xr is ready
+        HIP_TRY(run_conv(f.cc, &u.d3, f.blob, d3_params(), 1, sch.stream, f.prof, ("up." + s + ".d3").c_str()));
+        if (!f.cc.tuning || f.prof || head_fused) return FASTSVC_OK;
+        // tuning pass: the two separate launches again, timed, then the fused shapes against them
+        const ConvParams pr = stretch_params();
+        ConvParams pq = d3_params();
+        pq.flags &= ~F_STATS;                                  // (the InstanceNorm sums are accumulated once)
+        double sep_ms = 0.0;
+        FWD_STEP(time_separate(sch.stream, false, [&]() {
+            if (run_conv(f.cc, &u.res, f.blob, pr, 1, sch.stream, nullptr, ("up." + s + ".res_stretch").c_str()) != hipSuccess ||
+                run_conv(f.cc, &u.d3, f.blob, pq, 1, sch.stream, nullptr, ("up." + s + ".d3").c_str()) != hipSuccess)
+                return fail(FASTSVC_E_HIP, "timing the separate residual / d3 launches");
+            return (int)FASTSVC_OK;
+        }, sep_ms));
+        bool dummy = false;
+        HIP_TRY(run_d3x(f.cc, u, f.blob, pd3, sch.stream, nullptr, ("up." + s + ".d3x").c_str(), 2, sep_ms, dummy));
+        return FASTSVC_OK;
+    }
 
-        p.x = u2; p.st_in = st + stn; p.res = nullptr;             // u3 = aff(conv_d9(lrelu(norm(u2))))
+    // u3 = aff(conv_d9(lrelu(norm(u2))))
+    ConvParams d9_params() const {
+        ConvParams p = d3_params();
+        p.x = u2; p.st_in = st + stn; p.res = nullptr;
         p.y = nullptr; p.y2 = u3;
         p.st_out = st + 2 * stn;
-        
-        HIP_TRY(run_conv(cc, &u.d9, blob, p, 1, stream, prof, ("up." + s + ".d9").c_str()));
-        HIP_TRY(exact_stats(u3, st + 2 * stn));
+        return p;
+    }
 
-        p.x = u3; p.st_in = st + 2 * stn;                          // out = conv_d27(lrelu(norm(u3))) + xmid
+    // out = conv_d27(lrelu(norm(u3))) + xmid
+    int d27(bool last_fusable, bool& last_done) {
+        const fastsvc_plan& P = f.P;
+        ConvParams p = d9_params();
+        p.x = u3; p.st_in = st + 2 * stn;
         p.flags = pre; p.ss_out = nullptr; p.st_out = nullptr; p.y2 = nullptr;
         p.res = xm; p.res_b = cb;
         p.y = xo; p.y_b = cb;
-        p.amax_out = i + 1 < n ? am("up." + s + ".out") : nullptr;
-        if (i == n - 1 && P.cfg.out_channels == 1 && last_fusable) {
+        p.amax_out = i + 1 < P.n ? f.am("up." + s + ".out") : nullptr;
+        if (i == P.n - 1 && P.cfg.out_channels == 1 && last_fusable) {
             // conv_last in the same launch where the launch has the variant (run_conv decides; the block's
             // C-channel output is then not materialised - a launch table with algorithm 0 under "conv_last|B|T"
             // keeps the two launches, e.g. to read the `up.<n-1>.out` tap)
-            p.last_w = blob + P.last.w_off; p.last_b = blob + P.last.b_off;
-            p.last_y = out; p.last_y_b = (long)P.cfg.out_channels * T;
-            if (lengths) HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * T, stream));   // ragged batch: zero padding of the waveform
+            p.last_w = f.blob + P.last.w_off; p.last_b = f.blob + P.last.b_off;
+            p.last_y = f.out; p.last_y_b = (long)P.cfg.out_channels * f.T;
+            if (f.lengths) HIP_TRY(hipMemsetAsync(f.out, 0, sizeof(float) * (size_t)f.B * f.T, sch.stream));   // ragged batch: zero padding of the waveform
         }
-        HIP_TRY(run_conv(cc, &u.d27, blob, p, 1, stream, prof, ("up." + s + ".d27").c_str(), &last_done));
-
-        x = xo; Cx = u.C; Tin = Tout;
+        HIP_TRY(run_conv(f.cc, &u.d27, f.blob, p, 1, sch.stream, f.prof, ("up." + s + ".d27").c_str(), &last_done));
+        return FASTSVC_OK;
     }
+};
 
-    // ---- conv_last ----
-    if (last_done) return FASTSVC_OK;
-    if (prof) HIP_TRY(prof->begin(stream, "conv_last", "pointwise_out", 2.0 * Cx * P.cfg.out_channels * (double)T * B,
-                                  4.0 * (Cx + P.cfg.out_channels) * (double)T * B));
-    HIP_TRY(FASTSVC_BY_STORAGE(P.storage, launch_pointwise_out)(x, blob + P.last.w_off, blob + P.last.b_off, out, B, Cx,
-                                 P.cfg.out_channels, (int)T, lengths, (int)hop, stream));
-    if (prof) HIP_TRY(prof->end());
+// block i of the up loop: reads what `in` names, returns what block i + 1 (or conv_last) reads
+int up_block(const Fwd& f, Schedule& sch, int i, const UpCursor in, bool last_fusable, UpCursor& next, bool& last_done) {
+    UpBlock b(f, sch, i, in);
+    if (sch.ss_ready[b.k]) HIP_TRY(hipStreamWaitEvent(sch.stream, sch.ss_ready[b.k], 0));   // scale/shift of stage k
+    bool head_fused = false, d3_fused = false;
+    FWD_STEP(b.head(head_fused));
+    const ConvParams pd3 = b.d3x_params();
+    if (!head_fused) {
+        HIP_TRY(run_d3x(f.cc, b.u, f.blob, pd3, sch.stream, nullptr, ("up." + b.s + ".d3x").c_str(), 0, 0.0, d3_fused));
+        FWD_STEP(b.first_res_up(d3_fused));
+    }
+    FWD_STEP(b.norm_point(b.u1, 0));
+    FWD_STEP(b.d3(pd3, d3_fused, head_fused));
+    FWD_STEP(b.norm_point(b.u2, 1));
+    HIP_TRY(run_conv(f.cc, &b.u.d9, f.blob, b.d9_params(), 1, sch.stream, f.prof, ("up." + b.s + ".d9").c_str()));
+    FWD_STEP(b.norm_point(b.u3, 2));
+    FWD_STEP(b.d27(last_fusable, last_done));
+    next = UpCursor{b.xo, b.u.C, b.Tout};
     return FASTSVC_OK;
 }
+
+// conv_last rides in the last block's d27 launch unless the launch table keeps the two launches
+bool conv_last_fusable(const fastsvc_plan& P, int B, long T) {
+    char key[96];
+    std::snprintf(key, sizeof(key), "conv_last|%d|%ld%s", B, (long)T, key_suffix(P.storage));
+    fastsvc_plan::Choice ch;
+    return !(env().no_fuse_last || (table_entry(P, key, ch) && ch.algo != 3));
+}
+
+int conv_last(const Fwd& f, const UpCursor& in, hipStream_t stream) {
+    const fastsvc_plan& P = f.P;
+    if (f.prof) HIP_TRY(f.prof->begin(stream, "conv_last", "pointwise_out", 2.0 * in.C * P.cfg.out_channels * (double)f.T * f.B,
+                                      4.0 * (in.C + P.cfg.out_channels) * (double)f.T * f.B));
+    HIP_TRY(FASTSVC_BY_STORAGE(P.storage, launch_pointwise_out)(in.x, f.blob + P.last.w_off, f.blob + P.last.b_off, f.out, f.B, in.C,
+                                 P.cfg.out_channels, (int)f.T, f.lengths, (int)f.hop, stream));
+    if (f.prof) HIP_TRY(f.prof->end());
+    return FASTSVC_OK;
+}
+
+int forward_impl(CallCtx& cc, const fastsvc_plan* plan, const void* dev_blob,
+                 const float* ppg, const float* sine, const float* lft, const float* spk_emb,
+                 float* out, int32_t B, int32_t F, const int32_t* lengths,
+                 void* workspace, size_t workspace_bytes, void* stream_, Profiler* prof) {
+    // 1. arguments and storage gates
+    if (!plan || !dev_blob || !ppg || !sine || !lft || !out || !workspace)
+        return fail(FASTSVC_E_INVALID, "null argument");
+    if (B < 1 || F < 1) return fail(FASTSVC_E_INVALID, "B and F must be >= 1");
+    const fastsvc_plan& P = *plan;
+    FWD_STEP(check_storage_gates(P, F));
+    if (spk_emb && !P.cfg.use_spk_emb)
+        return fail(FASTSVC_E_INVALID, "spk_emb given but the generator was built with use_spk_emb=False");
+    // 2. the workspace
+    const Workspace ws = layout_workspace(P, B, F);
+    if (workspace_bytes < ws.bytes) return fail(FASTSVC_E_WORKSPACE, "workspace too small");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    cc.plan = plan;
+    cc.storage = plan->storage;
+    cc.exact_f32 = plan->storage == 0 && F <= 4;
+    // 3. the schedule
+    int64_t hop = 1;                                       // samples per frame
+    for (int i = 0; i < P.n; ++i) hop *= P.cfg.upsampling_scales[i];
+    Schedule sch;
+    choose_schedule(sch, stream, (int64_t)B * F * hop, cc.tuning || prof);
+    // 4. the 32-bit descriptor span
+    const long T = (long)hop * F;
+    FWD_STEP(check_descriptor_span(P, F, T));
+    const std::ptrdiff_t sig_bytes = reinterpret_cast<const char*>(sine) - reinterpret_cast<const char*>(lft);
+    if (sig_bytes % (std::ptrdiff_t)sizeof(float) != 0) return fail(FASTSVC_E_INVALID, "sine / lft must be 4-byte aligned");
+    unsigned char* wsb = static_cast<unsigned char*>(workspace);
+    Fwd f{P, cc, static_cast<const float*>(dev_blob), ws, wsb, B, F, (long)hop, T, lengths, spk_emb != nullptr, prof, ppg, spk_emb, out,
+          lft, (long)(sig_bytes / (std::ptrdiff_t)sizeof(float)), nullptr, nullptr};
+    f.amax_inb = f.buf("amax_in");
+    f.amaxb = f.buf("amax");
+    // 5. the inputs' amax  (no_amax_scan - A/B timing only: inputs then count as unit-scale)
+    if (P.storage == 0 && !env().no_amax_scan) FWD_STEP(scan_input_amax(f, stream));
+    // 6. the speaker prologue
+    if (f.spk) FWD_STEP(speaker_prologue(f, sch));
+    // 7. the conditioning chains
+    CondCursor hc{f.sigbuf, 1, T, false, T};
+    for (int k = 0; k < P.n; ++k) FWD_STEP(cond_stage(f, sch, k, hc, hc));
+    // 8. join; the ppg in the activation storage
+    if (f.spk) HIP_TRY(sch.order_after(sch.s_pre, stream));    // speaker biases and zeroed sums are ready
+    UpCursor xc{ppg, P.cfg.in_channels, F};
+    if (P.storage != 0) {                                          // external float32 input -> workspace bfloat16 / binary16
+        float* pa = f.buf("ppg_act");
+        HIP_TRY((P.storage == 2 ? f16::launch_act_convert : bf16::launch_act_convert)(ppg, pa, (long)B * P.cfg.in_channels * F, stream));
+        xc.x = pa;
+    }
+    // 9. the up blocks
+    const bool last_fusable = conv_last_fusable(P, B, T);
+    bool last_done = false;
+    for (int i = 0; i < P.n; ++i) FWD_STEP(up_block(f, sch, i, xc, last_fusable, xc, last_done));
+    // 10. conv_last, unless the last block's d27 launch ran it
+    return last_done ? (int)FASTSVC_OK : conv_last(f, xc, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
 
 void fastsvc_split_half(const float* x, int64_t n, uint16_t* f16_hi, uint16_t* f16_lo, uint16_t* bf16) {
     for (int64_t i = 0; i < n; ++i) {
@@ -3697,29 +3882,38 @@ int fastsvc_forward_grouped(const fastsvc_plan* plan, const void* dev_blob,
                             void* scratch, size_t scratch_bytes, void* stream) {
     CallCtx cc;
     if (spk_emb) {                                     // (without an embedding there is no norm: fastsvc_forward's launches and bytes)
-        if (!group || !own_lo || !own_hi || !scratch) return fail(FASTSVC_E_INVALID, "null argument");
-        if (!plan || B < 1 || F < 1) return fail(FASTSVC_E_INVALID, "B and F must be >= 1");
-        if (scratch_bytes < fastsvc_norm_group_scratch_bytes(plan, B, F))
-            return fail(FASTSVC_E_WORKSPACE, "norm-group scratch too small (fastsvc_norm_group_scratch_bytes)");
-        cc.ng_group = group; cc.ng_lo = own_lo; cc.ng_hi = own_hi;
-        cc.ng_part = static_cast<double*>(scratch);
+        NormOverride& o = cc.norm;
+        o.kind = NormOverride::GROUPED;
+        o.rows = group; o.lo = own_lo; o.hi = own_hi;
+        o.part = static_cast<double*>(scratch);
+        const int rc = o.check(plan, B, F, false, 0, scratch_bytes);
+        if (rc != FASTSVC_OK) return rc;
     }
     return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
                         workspace_bytes, stream, nullptr);
 }
 
-int fastsvc_norm_group_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
-                             int32_t len_mul, const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
-                             double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
-    if (!u || !group || !own_lo || !own_hi || !stats_out || !scratch) return fail(FASTSVC_E_INVALID, "null argument");
+// What fastsvc_norm_group_stats and fastsvc_norm_running_stats[_decay] ask of the tensor and the scratch; `ranges`: column
+// ranges a row sums separately (1 grouped, 2 running)
+static int norm_stats_check(int32_t storage, int32_t B, int32_t C, int32_t ld, int32_t len_mul, int ranges, size_t scratch_bytes) {
     if (storage != 0 && storage != 1 && storage != 2)
         return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
     if (B < 1 || B > 65535 || C < 1 || ld < 1 || len_mul < 1 || ld % len_mul != 0)
         return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535, C >= 1 and a pitch ld that is a positive multiple of len_mul");
     if ((long)C * norm_group_chunks(ld) > 0x7fffffffL / 2)
         return fail(FASTSVC_E_UNSUPPORTED, "too many (channel, chunk) items for one launch");
-    if (scratch_bytes < (size_t)B * C * norm_group_chunks(ld) * 2 * sizeof(double))
-        return fail(FASTSVC_E_WORKSPACE, "norm-group scratch too small: B * C * ceil(ld / 2048) * 16 bytes");
+    if (scratch_bytes < (size_t)B * C * norm_group_chunks(ld) * 2 * ranges * sizeof(double))
+        return fail(FASTSVC_E_WORKSPACE, ranges == 1 ? "norm-group scratch too small: B * C * ceil(ld / 2048) * 16 bytes"
+                                                     : "running-norm scratch too small: B * C * ceil(ld / 2048) * 32 bytes");
+    return FASTSVC_OK;
+}
+
+int fastsvc_norm_group_stats(const void* u, int32_t storage, int32_t B, int32_t C, int32_t ld, const int32_t* lengths,
+                             int32_t len_mul, const int32_t* group, const int32_t* own_lo, const int32_t* own_hi,
+                             double* stats_out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!u || !group || !own_lo || !own_hi || !stats_out || !scratch) return fail(FASTSVC_E_INVALID, "null argument");
+    const int rc = norm_stats_check(storage, B, C, ld, len_mul, 1, scratch_bytes);
+    if (rc != FASTSVC_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(scratch);
     HIP_TRY(FASTSVC_BY_STORAGE(storage, launch_norm_group_partials)(static_cast<const float*>(u), part, B, C, ld, lengths, len_mul,
@@ -3749,25 +3943,15 @@ static int forward_running_impl(const fastsvc_plan* plan, const void* dev_blob,
                                 void* scratch, size_t scratch_bytes, void* stream) {
     CallCtx cc;
     if (spk_emb) {                                     // (without an embedding there is no norm: fastsvc_forward's launches and bytes)
-        if (!slot || !own_lo || !own_hi || !prior || !reset || !parity || !carry || !scratch)
-            return fail(FASTSVC_E_INVALID, "null argument");
-        if (decayed && (!decay || !weight || !bound)) return fail(FASTSVC_E_INVALID, "null argument");
-        if (decayed && (reinterpret_cast<uintptr_t>(decay) | reinterpret_cast<uintptr_t>(weight) |
-                        reinterpret_cast<uintptr_t>(bound)) % sizeof(double) != 0)
-            return fail(FASTSVC_E_INVALID, "decay, weight and bound must be 8-byte aligned");
-        if (!plan || B < 1 || B > 65535 || F < 1) return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535 and F >= 1");
-        if (carry_bytes < fastsvc_norm_carry_bytes(plan) || carry_bytes % sizeof(double) != 0 ||
-            reinterpret_cast<uintptr_t>(carry) % sizeof(double) != 0)
-            return fail(FASTSVC_E_INVALID, "carry_bytes, the bytes from one slot's record to the next, must be a multiple of 8 "
-                                           "and at least fastsvc_norm_carry_bytes; the carry 8-byte aligned");
-        if (scratch_bytes < fastsvc_norm_running_scratch_bytes(plan, B, F))
-            return fail(FASTSVC_E_WORKSPACE, "running-norm scratch too small (fastsvc_norm_running_scratch_bytes)");
-        cc.nr_slot = slot; cc.ng_lo = own_lo; cc.ng_hi = own_hi;
-        cc.nr_prior = prior; cc.nr_reset = reset; cc.nr_parity = parity;
-        cc.nr_carry = static_cast<double*>(carry);
-        cc.nr_stride = (long)(carry_bytes / sizeof(double));
-        cc.ng_part = static_cast<double*>(scratch);
-        if (decayed) { cc.nr_decay = decay; cc.nr_weight = weight; cc.nr_bound = bound; }
+        NormOverride& o = cc.norm;
+        o.kind = NormOverride::RUNNING;
+        o.rows = slot; o.lo = own_lo; o.hi = own_hi;
+        o.prior = prior; o.reset = reset; o.parity = parity;
+        o.carry = static_cast<double*>(carry);
+        o.part = static_cast<double*>(scratch);
+        if (decayed) { o.decay = decay; o.weight = weight; o.bound = bound; }
+        const int rc = o.check(plan, B, F, decayed, carry_bytes, scratch_bytes);
+        if (rc != FASTSVC_OK) return rc;
     }
     return forward_impl(cc, plan, dev_blob, ppg, sine, lft, spk_emb, out, B, F, lengths, workspace,
                         workspace_bytes, stream, nullptr);
@@ -3810,14 +3994,8 @@ static int norm_running_stats_impl(const void* u, int32_t storage, int32_t B, in
     if (decayed && (reinterpret_cast<uintptr_t>(decay) | reinterpret_cast<uintptr_t>(weight) |
                     reinterpret_cast<uintptr_t>(bound)) % sizeof(double) != 0)
         return fail(FASTSVC_E_INVALID, "decay, weight and bound must be 8-byte aligned");
-    if (storage != 0 && storage != 1 && storage != 2)
-        return fail(FASTSVC_E_INVALID, "storage dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
-    if (B < 1 || B > 65535 || C < 1 || ld < 1 || len_mul < 1 || ld % len_mul != 0)
-        return fail(FASTSVC_E_INVALID, "need 1 <= B <= 65535, C >= 1 and a pitch ld that is a positive multiple of len_mul");
-    if ((long)C * norm_group_chunks(ld) > 0x7fffffffL / 2)
-        return fail(FASTSVC_E_UNSUPPORTED, "too many (channel, chunk) items for one launch");
-    if (scratch_bytes < (size_t)B * C * norm_group_chunks(ld) * 4 * sizeof(double))
-        return fail(FASTSVC_E_WORKSPACE, "running-norm scratch too small: B * C * ceil(ld / 2048) * 32 bytes");
+    const int rc = norm_stats_check(storage, B, C, ld, len_mul, 2, scratch_bytes);
+    if (rc != FASTSVC_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(scratch);
     HIP_TRY(FASTSVC_BY_STORAGE(storage, launch_norm_running_partials)(static_cast<const float*>(u), part, B, C, ld, lengths,

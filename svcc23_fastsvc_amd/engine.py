@@ -10,7 +10,7 @@ import ctypes
 import json
 import math
 import os
-from typing import Dict, Mapping, Optional, Sequence, Tuple
+from typing import Dict, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,6 +28,7 @@ MAX_STAGES = 8
 # activation storage of a plan: name -> fastsvc_plan_set_storage code / the dtype of the workspace taps
 STORAGE_CODES = {"float32": 0, "bfloat16": 1, "float16": 2}
 STORAGE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
+DTYPE_CODES = {dt: STORAGE_CODES[name] for name, dt in STORAGE_DTYPES.items()}       # the C side's storage code of a tensor
 TUNED_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_mi355x.json")
 
 # every symbol include/fastsvc_hip.h declares (checked by tests/test_boundary.py)
@@ -817,18 +818,18 @@ def check_norm_groups(norm_groups, lens: Sequence[int]):
     return group, own_lo, own_hi
 
 
-def norm_group_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: int, norm_groups, stats: torch.Tensor) -> torch.Tensor:
-    """InstanceNorm sums of one tensor pooled over groups of rows (``fastsvc_norm_group_stats``,
-    csrc/fastsvc_normgroup.hip): ``u`` (B, C, ld) float32, bfloat16 or float16 on the device, row b valid for ``lens[b] *
-    len_mul`` columns (``None``: ``ld``), ``norm_groups = (group, own_lo, own_hi)`` in frames.  ``stats`` (B, C, 2)
-    float64 receives, for every row that is not alone in its group owning all its frames, the group's sums over the owned
-    columns times ``lens[b] * len_mul / N`` - ``decode.pool_norm_sums``' values; the other rows' entries are left
-    untouched.  Two launches on the current stream.  Returns ``stats``."""
-    lib = load_library()
+class _NormOverride(NamedTuple):         # what replaces a forward's InstanceNorm statistics (Plan.forward), validated
+    kind: str                          # "grouped" (norm_groups) or "running" (norm_running)
+    rows: tuple                        # 3 (group, own_lo, own_hi) or 6 (slot, own_lo, own_hi, prior, reset, parity) lists of B ints
+    decay: Optional[tuple]             # running only: (decay, weight, bound), lists of B floats, or None
+
+
+def _norm_stats_args(who: str, u, lens, len_mul, stats):
+    """What ``norm_group_stats`` and ``norm_running_stats`` ask of ``u``, ``lens``, ``len_mul`` and ``stats``; returns
+    ``(B, C, ld, len_mul, frame counts)``, the frame counts ``lens`` or, without, the full ``ld // len_mul`` of every row."""
     if not isinstance(u, torch.Tensor) or not u.is_cuda:
-        raise FastSVCError("norm_group_stats needs GPU tensors (no CPU fallback); got " + str(getattr(u, "device", type(u))))
-    codes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-    if u.dim() != 3 or u.dtype not in codes or not u.is_contiguous():
+        raise FastSVCError(who + " needs GPU tensors (no CPU fallback); got " + str(getattr(u, "device", type(u))))
+    if u.dim() != 3 or u.dtype not in DTYPE_CODES or not u.is_contiguous():
         raise ValueError(f"u must be a contiguous (B, C, ld) float32 / bfloat16 / float16 tensor; got {tuple(u.shape)} {u.dtype}")
     B, C, ld = u.shape
     len_mul = int(len_mul)
@@ -839,14 +840,26 @@ def norm_group_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: in
     if not isinstance(stats, torch.Tensor) or stats.device != u.device or stats.dtype != torch.float64 or \
             tuple(stats.shape) != (B, C, 2) or not stats.is_contiguous():
         raise ValueError(f"stats must be a contiguous float64 {(B, C, 2)} tensor on {u.device}")
-    group, own_lo, own_hi = check_norm_groups(norm_groups, lens if lens is not None else [ld // len_mul] * B)
+    return B, C, ld, len_mul, lens if lens is not None else [ld // len_mul] * B
+
+
+def norm_group_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: int, norm_groups, stats: torch.Tensor) -> torch.Tensor:
+    """InstanceNorm sums of one tensor pooled over groups of rows (``fastsvc_norm_group_stats``,
+    csrc/fastsvc_normgroup.hip): ``u`` (B, C, ld) float32, bfloat16 or float16 on the device, row b valid for ``lens[b] *
+    len_mul`` columns (``None``: ``ld``), ``norm_groups = (group, own_lo, own_hi)`` in frames.  ``stats`` (B, C, 2)
+    float64 receives, for every row that is not alone in its group owning all its frames, the group's sums over the owned
+    columns times ``lens[b] * len_mul / N`` - ``decode.pool_norm_sums``' values; the other rows' entries are left
+    untouched.  Two launches on the current stream.  Returns ``stats``."""
+    lib = load_library()
+    B, C, ld, len_mul, lens_host = _norm_stats_args("norm_group_stats", u, lens, len_mul, stats)
+    group, own_lo, own_hi = check_norm_groups(norm_groups, lens_host)
     dev = u.device
     ints = torch.tensor([group, own_lo, own_hi] + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
     scratch = torch.empty(B * C * (-(-ld // 2048)) * 16, dtype=torch.uint8, device=dev)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib, lib.fastsvc_norm_group_stats(ptr(u), codes[u.dtype], B, C, ld, ptr(ints[3]) if lens is not None else None,
+        _check(lib, lib.fastsvc_norm_group_stats(ptr(u), DTYPE_CODES[u.dtype], B, C, ld, ptr(ints[3]) if lens is not None else None,
                                                  len_mul, ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(stats), ptr(scratch),
                                                  scratch.numel(), ctypes.c_void_p(stream)), "fastsvc_norm_group_stats")
     return stats
@@ -938,45 +951,26 @@ def norm_running_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: 
     by ``decay[q]`` in front of every row's core and ``N = weight[b] * len_mul``.  Two launches on the current stream.
     Returns ``stats``."""
     lib = load_library()
-    if not isinstance(u, torch.Tensor) or not u.is_cuda:
-        raise FastSVCError("norm_running_stats needs GPU tensors (no CPU fallback); got " + str(getattr(u, "device", type(u))))
-    codes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-    if u.dim() != 3 or u.dtype not in codes or not u.is_contiguous():
-        raise ValueError(f"u must be a contiguous (B, C, ld) float32 / bfloat16 / float16 tensor; got {tuple(u.shape)} {u.dtype}")
-    B, C, ld = u.shape
-    len_mul = int(len_mul)
-    if len_mul < 1 or ld % len_mul:
-        raise ValueError(f"the pitch {ld} must be a multiple of len_mul {len_mul}")
-    if lens is not None and (len(lens) != B or min(lens) < 1 or max(lens) * len_mul > ld):
-        raise ValueError(f"lens must hold {B} frame counts in [1, {ld // len_mul}]")
-    if not isinstance(stats, torch.Tensor) or stats.device != u.device or stats.dtype != torch.float64 or \
-            tuple(stats.shape) != (B, C, 2) or not stats.is_contiguous():
-        raise ValueError(f"stats must be a contiguous float64 {(B, C, 2)} tensor on {u.device}")
+    B, C, ld, len_mul, lens_host = _norm_stats_args("norm_running_stats", u, lens, len_mul, stats)
     if not isinstance(carry, torch.Tensor) or carry.device != u.device or carry.dtype != torch.float64 or carry.dim() != 4 or \
             tuple(carry.shape[1:]) != (2, C, 2) or carry.shape[0] < 1 or not carry.is_contiguous():
         raise ValueError(f"carry must be a contiguous float64 (n_slots, 2, {C}, 2) tensor on {u.device}")
-    arrays = check_norm_running(norm_running, lens if lens is not None else [ld // len_mul] * B, carry.shape[0])
+    arrays = check_norm_running(norm_running, lens_host, carry.shape[0])
     dev = u.device
     ints = torch.tensor(list(arrays) + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
     scratch = torch.empty(B * C * (-(-ld // 2048)) * 32, dtype=torch.uint8, device=dev)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
     lens_ptr = ptr(ints[6]) if lens is not None else None
+    name, dbl = "fastsvc_norm_running_stats", []
+    if decay is not None:
+        if len(decay) != 3:
+            raise ValueError("decay must be (decay, weight, bound), three sequences of floats")
+        name, dbl = name + "_decay", torch.tensor(check_norm_decay(*decay, arrays, lens_host), dtype=torch.float64).to(dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if decay is not None:
-            if len(decay) != 3:
-                raise ValueError("decay must be (decay, weight, bound), three sequences of floats")
-            dbl = torch.tensor(check_norm_decay(*decay, arrays, lens if lens is not None else [ld // len_mul] * B),
-                               dtype=torch.float64).to(dev)
-            _check(lib, lib.fastsvc_norm_running_stats_decay(ptr(u), codes[u.dtype], B, C, ld, lens_ptr, len_mul,
-                                                             *[ptr(ints[i]) for i in range(6)], *[ptr(dbl[i]) for i in range(3)],
-                                                             ptr(carry), ptr(stats), ptr(scratch), scratch.numel(),
-                                                             ctypes.c_void_p(stream)), "fastsvc_norm_running_stats_decay")
-            return stats
-        _check(lib, lib.fastsvc_norm_running_stats(ptr(u), codes[u.dtype], B, C, ld, lens_ptr,
-                                                   len_mul, *[ptr(ints[i]) for i in range(6)], ptr(carry), ptr(stats),
-                                                   ptr(scratch), scratch.numel(), ctypes.c_void_p(stream)),
-               "fastsvc_norm_running_stats")
+        _check(lib, getattr(lib, name)(ptr(u), DTYPE_CODES[u.dtype], B, C, ld, lens_ptr, len_mul, *[ptr(ints[i]) for i in range(6)],
+                                       *[ptr(d) for d in dbl], ptr(carry), ptr(stats), ptr(scratch), scratch.numel(),
+                                       ctypes.c_void_p(stream)), name)
     return stats
 
 
@@ -1397,93 +1391,14 @@ class Plan:
         With ``autotune`` every convolution first times its candidate launch shapes for this
         (B, F) and the plan remembers the fastest (cf. ``cudnn.benchmark``); synchronises."""
         cfg = self.cfg
-        if not ppg.is_cuda:
-            raise FastSVCError("FastSVC HIP path needs GPU tensors (no CPU fallback); got " + str(ppg.device))
-        dev = ppg.device
-        for name, t in (("sine", sine), ("lft", lft), ("spk_emb", spk_emb), ("blob", blob)):
-            if t is not None and t.device != dev:
-                raise ValueError(f"{name} is on {t.device}, expected {dev}")
-        if ppg.dim() != 3 or ppg.shape[1] != cfg.in_channels:
-            raise ValueError(f"ppg must be (B, {cfg.in_channels}, F), got {tuple(ppg.shape)}")
-        B, _, F = ppg.shape
+        ppg, sine, lft, spk_emb = self._check_inputs(blob, ppg, sine, lft, spk_emb)
+        dev, (B, _, F) = ppg.device, ppg.shape
         T = F * cfg.hop
-        for name, t in (("sine", sine), ("lft", lft)):
-            if tuple(t.shape) != (B, 1, T):
-                raise ValueError(f"{name} must be (B, 1, F*{cfg.hop}) = {(B, 1, T)}, got {tuple(t.shape)}")
-        if spk_emb is not None and tuple(spk_emb.shape) != (B, cfg.spk_emb_size):
-            raise ValueError(f"spk_emb must be {(B, cfg.spk_emb_size)}, got {tuple(spk_emb.shape)}")
-        ppg, sine, lft = (t.to(torch.float32).contiguous() for t in (ppg, sine, lft))
-        if spk_emb is not None:
-            spk_emb = spk_emb.to(torch.float32).contiguous()
-        if norm_groups is not None:
-            if profile is not None or autotune:
-                raise ValueError("norm_groups runs neither profiled nor under autotune")
-            if isinstance(lengths, torch.Tensor):
-                raise ValueError("norm_groups needs lengths on the host (the owned ranges are checked against them)")
-            norm_groups = check_norm_groups(norm_groups, [F] * B if lengths is None else [int(v) for v in lengths])
-        if norm_running is not None:
-            if norm_groups is not None:
-                raise ValueError("norm_running and norm_groups exclude each other")
-            if profile is not None or autotune:
-                raise ValueError("norm_running runs neither profiled nor under autotune")
-            if isinstance(lengths, torch.Tensor):
-                raise ValueError("norm_running needs lengths on the host (the cores are checked against them)")
-            row = 0 if not isinstance(norm_carry, torch.Tensor) or norm_carry.dim() != 2 else norm_carry.shape[1] * norm_carry.element_size()
-            if row < self.norm_carry_bytes() or row % 8 or norm_carry.device != dev or not norm_carry.is_contiguous():
-                raise ValueError(f"norm_running needs norm_carry: a contiguous (n_slots, k) tensor on {dev} with rows of at least "
-                                 f"norm_carry_bytes() = {self.norm_carry_bytes()} bytes, a multiple of 8")
-            norm_running = check_norm_running(norm_running, [F] * B if lengths is None else [int(v) for v in lengths],
-                                              norm_carry.shape[0])
-            if norm_decay is not None:
-                if len(norm_decay) != 3:
-                    raise ValueError("norm_decay must be (decay, weight, bound), three sequences of floats")
-                norm_decay = check_norm_decay(*norm_decay, norm_running, [F] * B if lengths is None else [int(v) for v in lengths])
-        elif norm_carry is not None:
-            raise ValueError("norm_carry goes with norm_running")
-        elif norm_decay is not None:
-            raise ValueError("norm_decay goes with norm_running")
+        override = self._norm_override(B, F, dev, lengths, profile is not None or autotune, norm_groups, norm_running,
+                                       norm_carry, norm_decay)
         if F % 4 != 0 and profile is None and (self.storage != "float32" or self.pad_odd_lengths):
-            # bfloat16 / float16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0
-            # (three of four real utterances are not); float32 storage runs such rows on its slower kernels.  Pad to
-            # the next multiple and run the padded batch as a ragged one - `lengths` makes every utterance exactly
-            # what it would be alone at its own length.  The caller's workspace is used when it holds the padded
-            # batch (size it with `workspace_bytes(B, padded_frames(F))`); the padded inputs live in one reused
-            # staging set.  Autotuning tunes the padded shape (launch shapes are keyed by the padded row lengths).
-            Fp = self.padded_frames(F)
-            hop = cfg.hop
-            if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
-                lh = torch.as_tensor(lengths, dtype=torch.int64, device="cpu").reshape(-1)
-                if lh.numel() != B or int(lh.min()) < 1 or int(lh.max()) > F:        # (against the caller's F, not the padded one)
-                    raise ValueError(f"lengths must hold {B} frame counts in [1, {F}]")
-            if workspace is not None and workspace.numel() < self.workspace_bytes(B, Fp):
-                raise ValueError(f"workspace too small for the padded batch: size it with workspace_bytes({B}, padded_frames({F}) = {Fp})")
-            # one staging set per (shape, device, STREAM): forwards of one plan on different streams must not share it
-            key = (B, Fp, str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
-            sets = self.__dict__.setdefault("_pad_sets", {})
-            if key not in sets:
-                if len(sets) >= 8:
-                    sets.pop(next(iter(sets)))
-                sets[key] = [torch.zeros((B, cfg.in_channels, Fp), dtype=torch.float32, device=dev),
-                             torch.zeros((B, 1, Fp * hop), dtype=torch.float32, device=dev),
-                             torch.zeros((B, 1, Fp * hop), dtype=torch.float32, device=dev),
-                             torch.empty((B, cfg.out_channels, Fp * hop), dtype=torch.float32, device=dev), F]
-            pp, ps, pl, py, lastF = sets[key]
-            pp[..., :F].copy_(ppg); ps[..., :T].copy_(sine); pl[..., :T].copy_(lft)
-            if lastF > F:                                    # a longer batch used this set: its tail is not padding
-                pp[..., F:lastF].zero_(); ps[..., T:lastF * hop].zero_(); pl[..., T:lastF * hop].zero_()
-            sets[key][4] = F
-            ok_ws = workspace is not None
-            if autotune:
-                if lengths is not None:
-                    raise ValueError("autotune times full-length batches: call it without lengths")
-                self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None, autotune=True)
-            self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace if ok_ws else None,
-                         lengths=[F] * B if lengths is None else lengths, norm_groups=norm_groups, norm_scratch=norm_scratch,
-                         norm_running=norm_running, norm_carry=norm_carry, norm_decay=norm_decay)
-            if out is None:
-                return py[..., :T].contiguous()
-            out.copy_(py[..., :T])
-            return out
+            return self._forward_padded(blob, ppg, sine, lft, spk_emb, out, workspace, autotune, lengths, override,
+                                        norm_scratch, norm_carry)
         lens_dev = None
         if lengths is not None:
             if autotune:
@@ -1509,54 +1424,46 @@ class Plan:
         elif out.dtype != torch.float32 or tuple(out.shape) != (B, cfg.out_channels, T) or out.device != dev or \
                 not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 {(B, cfg.out_channels, T)} tensor on {dev}")
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())      # noqa: E731
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            common = (
-                self._h, ctypes.c_void_p(blob.data_ptr()),
-                ctypes.c_void_p(ppg.data_ptr()), ctypes.c_void_p(sine.data_ptr()),
-                ctypes.c_void_p(lft.data_ptr()),
-                ctypes.c_void_p(spk_emb.data_ptr()) if spk_emb is not None else None,
-                ctypes.c_void_p(out.data_ptr()), B, F,
-                ctypes.c_void_p(lens_dev.data_ptr()) if lens_dev is not None else None,
-                ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(stream))
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            tensors = (self._h, ptr(blob), ptr(ppg), ptr(sine), ptr(lft), ptr(spk_emb), ptr(out), B, F)
+            lens_p, ws = ptr(lens_dev), (ptr(workspace), workspace.numel())
             if autotune:
                 ntr = ctypes.c_int32(0)
-                rc = self.lib.fastsvc_autotune(*common[:9], common[10], common[11], common[12], ctypes.byref(ntr))
+                rc = self.lib.fastsvc_autotune(*tensors, *ws, stream, ctypes.byref(ntr))
                 self.last_autotune_trials = int(ntr.value)
-            elif norm_groups is not None and spk_emb is not None:
-                need = self.norm_group_scratch_bytes(B, F)
+            elif override is not None and spk_emb is not None:
+                grouped = override.kind == "grouped"
+                need = self.norm_group_scratch_bytes(B, F) if grouped else self.norm_running_scratch_bytes(B, F)
                 if norm_scratch is None or norm_scratch.numel() * norm_scratch.element_size() < need or norm_scratch.device != dev:
                     norm_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-                ng = self._stage_lengths(torch.tensor(norm_groups, dtype=torch.int32).reshape(-1), 3 * B, dev)
-                rc = self.lib.fastsvc_forward_grouped(*common[:10], *[ctypes.c_void_p(ng[i * B:].data_ptr()) for i in range(3)],
-                                                      common[10], common[11], ctypes.c_void_p(norm_scratch.data_ptr()),
-                                                      norm_scratch.numel() * norm_scratch.element_size(), common[12])
-                workspace = (workspace, ng, norm_scratch)
-            elif norm_running is not None and spk_emb is not None:
-                need = self.norm_running_scratch_bytes(B, F)
-                if norm_scratch is None or norm_scratch.numel() * norm_scratch.element_size() < need or norm_scratch.device != dev:
-                    norm_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-                if norm_decay is None:
-                    host = torch.tensor(norm_running, dtype=torch.int32).reshape(-1)
-                else:                                    # (the doubles behind the 6 B ints - an even count, so 8-byte aligned)
+                scratch = (ptr(norm_scratch), norm_scratch.numel() * norm_scratch.element_size())
+                if override.decay is None:               # 3 (grouped) or 6 (running) arrays of B ints in one upload ...
+                    host = torch.tensor(override.rows, dtype=torch.int32).reshape(-1)
+                else:                                    # (... the doubles behind the 6 B ints - an even count, so 8-byte aligned)
                     packed = np.empty(12 * B, dtype=np.int32)
-                    packed[:6 * B] = np.asarray(norm_running, dtype=np.int32).reshape(-1)
-                    packed[6 * B:].view(np.float64)[:] = np.asarray(norm_decay, dtype=np.float64).reshape(-1)
+                    packed[:6 * B] = np.asarray(override.rows, dtype=np.int32).reshape(-1)
+                    packed[6 * B:].view(np.float64)[:] = np.asarray(override.decay, dtype=np.float64).reshape(-1)
                     host = torch.from_numpy(packed)
-                nr = self._stage_lengths(host, host.numel(), dev)
-                rc = getattr(self.lib, "fastsvc_forward_running" if norm_decay is None else "fastsvc_forward_running_decay")(
-                    *common[:10], *[ctypes.c_void_p(nr[i * B:].data_ptr()) for i in range(6)],
-                    *([] if norm_decay is None else [ctypes.c_void_p(nr[(6 + 2 * i) * B:].data_ptr()) for i in range(3)]),
-                    ctypes.c_void_p(norm_carry.data_ptr()), norm_carry.shape[1] * norm_carry.element_size(), common[10],
-                    common[11], ctypes.c_void_p(norm_scratch.data_ptr()),
-                    norm_scratch.numel() * norm_scratch.element_size(), common[12])
-                workspace = (workspace, nr, norm_scratch, norm_carry)
+                up = self._stage_lengths(host, host.numel(), dev)
+                rows_p = [ctypes.c_void_p(up[i * B:].data_ptr()) for i in range(len(override.rows))]
+                if grouped:
+                    rc = self.lib.fastsvc_forward_grouped(*tensors, lens_p, *rows_p, *ws, *scratch, stream)
+                else:
+                    carry = (ptr(norm_carry), norm_carry.shape[1] * norm_carry.element_size())
+                    if override.decay is None:
+                        rc = self.lib.fastsvc_forward_running(*tensors, lens_p, *rows_p, *carry, *ws, *scratch, stream)
+                    else:
+                        decay_p = [ctypes.c_void_p(up[(6 + 2 * i) * B:].data_ptr()) for i in range(3)]
+                        rc = self.lib.fastsvc_forward_running_decay(*tensors, lens_p, *rows_p, *decay_p, *carry, *ws, *scratch, stream)
+                workspace = (workspace, up, norm_scratch, norm_carry)
             elif profile is None:
-                rc = self.lib.fastsvc_forward(*common)
+                rc = self.lib.fastsvc_forward(*tensors, lens_p, *ws, stream)
             else:
                 recs = (_LaunchRecord * 256)()
                 n = ctypes.c_int32(0)
-                rc = self.lib.fastsvc_forward_profile(*common, recs, 256, ctypes.byref(n))
+                rc = self.lib.fastsvc_forward_profile(*tensors, lens_p, *ws, stream, recs, 256, ctypes.byref(n))
                 if rc == 0:
                     for i in range(n.value):
                         profile.append(dict(layer=recs[i].layer.decode(), kernel=recs[i].kernel.decode(),
@@ -1565,3 +1472,95 @@ class Plan:
         _check(self.lib, rc, "fastsvc_forward")
         self._last_workspace = (workspace, lens_dev)      # keep alive until the stream has consumed them
         return out
+
+    def _check_inputs(self, blob, ppg, sine, lft, spk_emb):
+        """The tensors of one forward against the plan's config and each other; returns the four inputs as contiguous float32."""
+        cfg = self.cfg
+        if not ppg.is_cuda:
+            raise FastSVCError("FastSVC HIP path needs GPU tensors (no CPU fallback); got " + str(ppg.device))
+        dev = ppg.device
+        for name, t in (("sine", sine), ("lft", lft), ("spk_emb", spk_emb), ("blob", blob)):
+            if t is not None and t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, expected {dev}")
+        if ppg.dim() != 3 or ppg.shape[1] != cfg.in_channels:
+            raise ValueError(f"ppg must be (B, {cfg.in_channels}, F), got {tuple(ppg.shape)}")
+        B, _, F = ppg.shape
+        T = F * cfg.hop
+        for name, t in (("sine", sine), ("lft", lft)):
+            if tuple(t.shape) != (B, 1, T):
+                raise ValueError(f"{name} must be (B, 1, F*{cfg.hop}) = {(B, 1, T)}, got {tuple(t.shape)}")
+        if spk_emb is not None and tuple(spk_emb.shape) != (B, cfg.spk_emb_size):
+            raise ValueError(f"spk_emb must be {(B, cfg.spk_emb_size)}, got {tuple(spk_emb.shape)}")
+        return tuple(None if t is None else t.to(torch.float32).contiguous() for t in (ppg, sine, lft, spk_emb))
+
+    def _norm_override(self, B: int, F: int, dev, lengths, timed: bool, norm_groups, norm_running, norm_carry, norm_decay):
+        """``norm_groups`` or ``norm_running`` (+ ``norm_carry``, ``norm_decay``) of one forward, validated on the host
+        against the rows' frame counts; a ``_NormOverride`` record, or None when the call has neither."""
+        def lens_host(name: str, what: str):
+            if timed:
+                raise ValueError(f"{name} runs neither profiled nor under autotune")
+            if isinstance(lengths, torch.Tensor):
+                raise ValueError(f"{name} needs lengths on the host (the {what} are checked against them)")
+            return [F] * B if lengths is None else [int(v) for v in lengths]
+        grouped = None
+        if norm_groups is not None:
+            grouped = _NormOverride("grouped", check_norm_groups(norm_groups, lens_host("norm_groups", "owned ranges")), None)
+        if norm_running is None:
+            if norm_carry is not None or norm_decay is not None:
+                raise ValueError(("norm_carry" if norm_carry is not None else "norm_decay") + " goes with norm_running")
+            return grouped
+        if grouped is not None:
+            raise ValueError("norm_running and norm_groups exclude each other")
+        lens = lens_host("norm_running", "cores")
+        row = 0 if not isinstance(norm_carry, torch.Tensor) or norm_carry.dim() != 2 else norm_carry.shape[1] * norm_carry.element_size()
+        if row < self.norm_carry_bytes() or row % 8 or norm_carry.device != dev or not norm_carry.is_contiguous():
+            raise ValueError(f"norm_running needs norm_carry: a contiguous (n_slots, k) tensor on {dev} with rows of at least "
+                             f"norm_carry_bytes() = {self.norm_carry_bytes()} bytes, a multiple of 8")
+        rows = check_norm_running(norm_running, lens, norm_carry.shape[0])
+        if norm_decay is not None:
+            if len(norm_decay) != 3:
+                raise ValueError("norm_decay must be (decay, weight, bound), three sequences of floats")
+            norm_decay = check_norm_decay(*norm_decay, rows, lens)
+        return _NormOverride("running", rows, norm_decay)
+
+    def _forward_padded(self, blob, ppg, sine, lft, spk_emb, out, workspace, autotune, lengths, override, norm_scratch,
+                        norm_carry) -> torch.Tensor:
+        """bfloat16 / float16 storage moves 4 time steps per access at the frame rate, so the library wants F % 4 == 0 (three
+        of four real utterances are not); float32 storage runs such rows on its slower kernels.  Pad to the next multiple and
+        run the padded batch as a ragged one - `lengths` makes every utterance exactly what it would be alone at its own
+        length.  The caller's workspace is used when it holds the padded batch (size it with `workspace_bytes(B,
+        padded_frames(F))`); the padded inputs live in one reused staging set.  Autotuning tunes the padded shape (launch
+        shapes are keyed by the padded row lengths)."""
+        cfg, dev, (B, _, F) = self.cfg, ppg.device, ppg.shape
+        Fp, hop = self.padded_frames(F), cfg.hop
+        T = F * hop
+        if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            lh = torch.as_tensor(lengths, dtype=torch.int64, device="cpu").reshape(-1)
+            if lh.numel() != B or int(lh.min()) < 1 or int(lh.max()) > F:        # (against the caller's F, not the padded one)
+                raise ValueError(f"lengths must hold {B} frame counts in [1, {F}]")
+        if workspace is not None and workspace.numel() < self.workspace_bytes(B, Fp):
+            raise ValueError(f"workspace too small for the padded batch: size it with workspace_bytes({B}, padded_frames({F}) = {Fp})")
+        # one staging set per (shape, device, STREAM): forwards of one plan on different streams must not share it
+        key = (B, Fp, str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
+        sets = self.__dict__.setdefault("_pad_sets", {})
+        if key not in sets:
+            if len(sets) >= 8:
+                sets.pop(next(iter(sets)))
+            sets[key] = [torch.zeros((B, cfg.in_channels, Fp), dtype=torch.float32, device=dev),
+                         torch.zeros((B, 1, Fp * hop), dtype=torch.float32, device=dev),
+                         torch.zeros((B, 1, Fp * hop), dtype=torch.float32, device=dev),
+                         torch.empty((B, cfg.out_channels, Fp * hop), dtype=torch.float32, device=dev), F]
+        pp, ps, pl, py, lastF = sets[key]
+        pp[..., :F].copy_(ppg); ps[..., :T].copy_(sine); pl[..., :T].copy_(lft)
+        if lastF > F:                                    # a longer batch used this set: its tail is not padding
+            pp[..., F:lastF].zero_(); ps[..., T:lastF * hop].zero_(); pl[..., T:lastF * hop].zero_()
+        sets[key][4] = F
+        if autotune:
+            if lengths is not None:
+                raise ValueError("autotune times full-length batches: call it without lengths")
+            self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace, autotune=True)
+        kind, rows, decay = override or (None, None, None)
+        self.forward(blob, pp, ps, pl, spk_emb, out=py, workspace=workspace, lengths=[F] * B if lengths is None else lengths,
+                     norm_groups=rows if kind == "grouped" else None, norm_running=rows if kind == "running" else None,
+                     norm_scratch=norm_scratch, norm_carry=norm_carry, norm_decay=decay)
+        return py[..., :T].contiguous() if out is None else out.copy_(py[..., :T])

@@ -178,7 +178,7 @@ def layer_table(cfg: GeneratorConfig) -> List[LayerSpec]:
 def max_forward_frames(cfg: GeneratorConfig) -> int:
     """The longest utterance, in frames, one forward takes: the kernels address every tensor of ONE utterance through
     32-bit byte offsets, so the largest of them - the full-rate waveform, the 2 C rows of a conditioning chain's scale /
-    shift or of an up block, the ppg - must stay below 2 GiB (``forward_impl`` in csrc/fastsvc_plan.cpp makes the same
+    shift or of an up block, the ppg - must stay below 2 GiB (``check_descriptor_span`` in csrc/fastsvc_plan.cpp makes the same
     computation and returns FASTSVC_E_UNSUPPORTED beyond it; 4 bytes an element in every storage).  69 905 frames for the
     recipe's generator at hop 160.  Longer utterances run as windows: ``DecodeSession.convert_windowed``."""
     per_frame = 4 * cfg.hop
