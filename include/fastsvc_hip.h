@@ -624,6 +624,38 @@ int fastsvc_stream_assemble(const float* ppg_ring, const float* lft_ring, const 
                             float* ppg_out, float* lft_out, float* sine_out,
                             int32_t R, int32_t C, int32_t hop, int32_t width, void* stream_);
 
+/* Loudness of live streams from their raw audio (csrc/fastsvc_stream_loudness.hip; decode.StreamSession(loudness="audio")).
+ * The stream's audio is appended to an AUDIO ring, (n_streams, cap * hop) float32 with sample p at index p % (cap * hop) -
+ * fastsvc_stream_push does that when it is handed the audio ring where it takes the lft ring - and this call turns the
+ * frames that have become FINAL into fastsvc_loudness_extract's value, hop samples per frame, written into lft_ring at
+ * frame index f % cap.  Frame f is the whole-file function's frame f of the stream's audio y[0, T), T = F hop (periodic
+ * Hann, 2048 samples centred on f hop, np.pad reflection at 0 and, once the stream has ended, at T), except for ONE
+ * thing: its 80 dB floor hangs under the running maximum M_f = max over frames g <= f and all bins of the power, not
+ * under the maximum of the whole utterance, which a live stream does not know.  A frame is final once
+ * its last sample f hop + 1023 has arrived, or the stream has ended.
+ *
+ * Entry i finalises the n[i] frames from first_frame[i] of stream stream[i] (every stream at most once per call; 0 <= n[i]
+ * <= max_frames <= min(cap, 2048); 0 changes nothing), of which seen[i] frames (seen[i] * hop samples) have arrived; with
+ * ended[i] these are the stream's last frames, first_frame[i] + n[i] == seen[i].  A stream's frames must be finalised in
+ * order, each once.
+ *   peak     (n_streams, 2) float32: the running maximum, in the entry the last call WROTE (a call reads entry parity[i]
+ *            and writes entry parity[i] ^ 1: the caller alternates it per stream and call that finalises at least one
+ *            frame).  first_frame[i] == 0 starts from 0 and reads nothing: opening a slot needs no clearing.
+ *   scratch  fastsvc_stream_loudness_scratch_bytes(n_streams, max_frames) DEVICE bytes: the power rows and maxima of one
+ *            call's frames.
+ * Two launches per 64 entries - the power rows, then maximum / floor / A-weighting / mean / log - none when every n[i] is
+ * 0; plain vector stores, no atomics; no load outside the stream's audio ring, its peak entry and the scratch, no store
+ * outside the scratch, the stream's lft ring rows and its peak pair.  Per-entry arrays are HOST arrays of S entries, read
+ * during the call.  Everything is checked on the host BEFORE anything is enqueued - null or misaligned pointers, sizes,
+ * n[i] > max_frames, a stream out of range or listed twice, frames that are not final or whose samples the ring no longer
+ * holds: FASTSVC_E_INVALID with the reason in fastsvc_last_error(); a failed launch is FASTSVC_E_HIP.  Asynchronous on
+ * `stream_`. */
+size_t fastsvc_stream_loudness_scratch_bytes(int32_t n_streams, int32_t max_frames);
+int fastsvc_stream_loudness(const float* audio_ring, float* lft_ring, float* peak, void* scratch, int32_t S,
+                            const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                            const int32_t* ended, const int32_t* parity, int32_t n_streams, int32_t cap, int32_t max_frames,
+                            int32_t hop, float sample_rate, void* stream_);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

@@ -640,6 +640,46 @@ def stream_ring_frames(core: int, context: int, max_push: int) -> int:
     return -(-(int(core) + 2 * int(context) + int(max_push)) // 4) * 4
 
 
+LOUDNESS_HALF_FRAME = 1024      # samples a loudness frame reads on either side of its centre (n_fft 2048)
+
+
+def stream_loudness_lag(hop: int) -> int:
+    """Frames a live stream's loudness runs behind its audio: ``ceil(1024 / hop) - 1`` (6 at hop 160).  Frame f is the
+    2048 samples centred on ``f hop``, so it reads samples up to ``f hop + 1023`` and is FINAL once ``seen hop >= f hop +
+    1024``: with ``seen`` frames of audio the frames ``[0, seen - lag)`` are."""
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError(f"hop must be >= 1, got {hop}")
+    return -(-LOUDNESS_HALF_FRAME // hop) - 1
+
+
+def stream_final_frames(seen: int, ended: bool, hop: int) -> int:
+    """Frames of a live stream whose loudness is final when ``seen`` frames of audio have arrived: ``max(0, seen - lag)``
+    before the end, and all ``seen`` of them once the stream has ended (the last ones read reflected samples)."""
+    seen = int(seen)
+    return seen if ended else max(0, seen - stream_loudness_lag(hop))
+
+
+def stream_loudness_ring_frames(core: int, context: int, max_push: int, hop: int) -> int:
+    """Frames a live stream retains on the device with ``loudness="audio"``, ``lag = stream_loudness_lag(hop)``: the larger
+    of two bounds, rounded up to a multiple of 4.
+
+    FRAMES.  After every push all windows whose frames are final have run, so the oldest window that has not run, k, lacks
+    a FINAL frame: ``final < (k + 1) core + context``, and ``seen <= final + lag``.  The next push brings at most
+    ``max_push`` frames and window k reads from ``k core - context``: the frames still needed plus the next chunk span
+    less than ``core + 2 context + max_push + lag`` - ``stream_ring_frames(core, context, max_push + lag)``.
+
+    SAMPLES.  The audio ring holds ``cap hop`` samples, sample p at ``p % (cap hop)``.  The oldest frame that is not
+    final, ``f0 >= seen - lag``, reads from sample ``f0 hop - 1024``; after the next push the ring ends at ``(seen +
+    max_push) hop``.  So ``cap hop >= (max_push + lag) hop + 1024`` keeps every sample a frame still reads - the binding
+    bound when ``core + 2 context`` is small."""
+    core, context, max_push, hop = int(core), int(context), int(max_push), int(hop)
+    lag = stream_loudness_lag(hop)
+    frames = stream_ring_frames(core, context, max_push + lag)
+    samples = -(-((max_push + lag) * hop + LOUDNESS_HALF_FRAME) // hop)
+    return -(-max(frames, samples) // 4) * 4
+
+
 class StreamStitchLayout:
     """``stitch_layout``, incrementally: the streams' rows arrive batch by batch (a ``StreamSession.push`` is one batch
     per forward) and nobody knows the final length yet.  ``batch(rows, seen)`` returns for these rows what
@@ -1594,12 +1634,32 @@ class StreamSession:
     (``norm_frames``) lives on the host; the same launches, one more multiplication per row in the pool.  ``None``: no
     forgetting, the launches and bytes as before.
 
+    ``loudness="audio"`` takes the stream's raw audio instead of its loudness: a chunk is ``dict(ppg, f0, audio=(n hop,))``,
+    and the A-weighted log loudness ``loudness_extract`` computes for whole files is made on the device, frame by frame, as
+    the audio arrives (csrc/fastsvc_stream_loudness.hip).  Frame f is the whole-file function's frame f of the stream's
+    audio ``y[0, F hop)`` - periodic Hann, 2048 samples centred on ``f hop``, reflection at both ends - with ONE departure:
+    its 80 dB floor hangs under the RUNNING maximum of the power over the frames ``<= f``, not under the maximum of the
+    whole utterance, which a live stream does not know.  That is a definition, not an approximation: it is causal and per
+    frame, so it cannot depend on how the stream was cut into pushes, and it equals the whole-file value wherever the
+    running maximum has reached the utterance's or no bin of the frame lies under either floor - for every frame of a
+    stream whose loudest frame is its first - but a quiet passage BEFORE the utterance's peak is floored lower than the
+    whole-file function floors it, and reads quieter (DESIGN.md 4.10 has figures).  A frame reads 1023 samples past its centre, so it is FINAL
+    ``lag = stream_loudness_lag(hop)`` frames after it arrived (6 at hop 160) or at the stream's end; window k is ready
+    when ``stream_ready_rows(final, ...)`` says so, ``final = stream_final_frames(seen, ended, hop)`` in ``seen``'s place,
+    so a stream's rows are still ``window_plan([F], core, context)`` and stitching, running norms and horizons are
+    untouched.  ppg and f0 still come from outside.  ``"given"`` (the default): launches, bytes and bits as before.
+
     State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
     ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
     upload buffer with a page-locked twin and one page-locked download buffer; with ``norm="running"`` per stream one
     carry record (``plan.norm_carry_bytes()``: two parity entries of every norm point's sums, never zeroed - a stream's
-    first window resets it) and one scratch for the partial sums of a forward.  Per ``push``: one upload, one
-    ``stream_push`` launch (appends to the rings and synthesises the chunk's excitation, csrc/fastsvc_stream.hip) and, if
+    first window resets it) and one scratch for the partial sums of a forward; with ``loudness="audio"`` the rings hold
+    ``stream_loudness_ring_frames(core, context, max_push, hop)`` frames, and per stream there is a fourth ring, the audio
+    (sample p at ``p % (cap hop)``), and the running maximum (a float32 parity pair, never zeroed - a stream's first frame
+    starts it), plus one scratch for the power rows of the ``max_push + lag`` frames a push can finalise per stream.  Per
+    ``push``: one upload, one ``stream_push`` launch (appends to the rings and synthesises the chunk's excitation,
+    csrc/fastsvc_stream.hip), with ``loudness="audio"`` two ``stream_loudness`` launches when any frame became final (power
+    rows; then maximum, floor, weighting, mean and log into the lft ring) and none otherwise, and, if
     any window became ready, per ``max_batch`` rows one ``stream_assemble``, one forward with ``lengths``, one
     ``window_stitch`` and one download.  A push that completes no window runs no forward (``forwards`` counts them).
 
@@ -1613,15 +1673,18 @@ class StreamSession:
     push that delivers frame ``(t // core + 1) core + context - 1`` - its window's last context frame; the last ``fade /
     2`` frames of every core wait for the next window as well and return with frame ``(t // core + 2) core + context -
     1``; ``end`` returns everything still held; ``fade=0`` holds nothing back.  So ``core + context`` is the typical and
-    ``2 core + context`` the worst delay.
+    ``2 core + context`` the worst delay.  With ``loudness="audio"`` every one of these is ``lag`` frames later: the push
+    that delivers frame ``(t // core + 1) core + context - 1 + lag``, ``core + context + lag`` typical, ``2 core + context
+    + lag`` worst.
 
     ``push`` validates everything before it uploads or enqueues anything: a ``ValueError`` leaves the session as it
     was.  Not thread-safe.  ``out_channels`` must be 1 and the signal generator's only signal "sine".  Not built: checked /
-    fallback reports, graph capture of the per-push chain, several GPUs."""
+    fallback reports, graph capture of the per-push chain, several GPUs; for ``loudness="audio"`` a preset peak for
+    calibration, a forgetting horizon for the maximum, ppg and f0 from audio."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
                  fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
-                 horizon: Optional[float] = None):
+                 horizon: Optional[float] = None, loudness: str = "given"):
         from .engine import FastSVCError, STREAM_MAX_PUSH
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
@@ -1654,12 +1717,25 @@ class StreamSession:
         if horizon is not None and norm != "running":
             raise ValueError("horizon forgets running statistics: it needs norm=\"running\"")
         self.norm, self.horizon = norm, check_horizon(horizon, core)
-        self.cap = cap = stream_ring_frames(core, context, max_push)
+        if loudness not in ("given", "audio"):
+            raise ValueError(f"loudness must be \"given\" or \"audio\", got {loudness!r}")
+        self.loudness = loudness
+        self.lag = stream_loudness_lag(hop) if loudness == "audio" else 0
+        self.cap = cap = stream_ring_frames(core, context, max_push) if loudness == "given" else \
+            stream_loudness_ring_frames(core, context, max_push, hop)
         dev, n = self.device, self.n_streams
         self._ppg = torch.empty((n, cap, C), dtype=torch.float32, device=dev)
         self._lft = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
         self._exc = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
         self._phase = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        self._audio = self._peak = self._loud_scratch = None
+        if loudness == "audio":
+            from .engine import stream_loudness_scratch_bytes
+            # the audio ring (sample p at p % (cap hop)), the running maximum's parity pair (never zeroed: a stream's
+            # first frame starts it) and the power rows of the most frames a push can finalise per stream
+            self._audio = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
+            self._peak = torch.empty((n, 2), dtype=torch.float32, device=dev)
+            self._loud_scratch = torch.empty(stream_loudness_scratch_bytes(n, max_push + self.lag), dtype=torch.uint8, device=dev)
         self._layout = StreamStitchLayout(n, hop, fade)
         self._stage = torch.empty(max(self._layout.stage_elems, 1), dtype=torch.float32, device=dev)
         self._emb = torch.zeros((n, max(int(cfg.spk_emb_size), 1)), dtype=torch.float32, device=dev)
@@ -1682,13 +1758,15 @@ class StreamSession:
         self._next_id = 0
         self.forwards = 0
         # set to a dict to have push leave what it made there (tests): "excitation", per stream id the device tensors of
-        # its chunks' excitation in order, and "forwards", per forward (its rows, the assembled excitation rows)
+        # its chunks' excitation in order, "forwards", per forward (its rows, the assembled excitation rows), and with
+        # loudness="audio" "lft", per stream id the device tensors of its newly final frames' loudness in order
         self._stream_trace: Optional[Dict[str, object]] = None
         self._closed = False
 
-    latency_frames = property(lambda self: self.core + self.context, doc="the typical delay, in frames of input: core + context")
-    latency_frames_max = property(lambda self: 2 * self.core + self.context,
-                                  doc="the worst delay (the last fade / 2 frames of a core): 2 core + context")
+    latency_frames = property(lambda self: self.core + self.context + self.lag,
+                              doc="the typical delay, in frames of input: core + context (+ the loudness lag with loudness=\"audio\")")
+    latency_frames_max = property(lambda self: 2 * self.core + self.context + self.lag,
+                                  doc="the worst delay (the last fade / 2 frames of a core): 2 core + context (+ the loudness lag)")
 
     def __enter__(self):
         return self
@@ -1703,6 +1781,7 @@ class StreamSession:
         self._closed = True
         torch.cuda.current_stream(self.device).synchronize()
         self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = self._carry = self._norm_scratch = None
+        self._audio = self._peak = self._loud_scratch = None
         self._h_up = self._d_up = self._h_down = self._up_done = None
         self._slots, self._ids = [None] * self.n_streams, {}
 
@@ -1733,6 +1812,7 @@ class StreamSession:
         self._next_id += 1
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
         self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, norm_parity=0, norm_w=0.0, seed=key,
+                              final=0, loud_parity=0,       # (loudness="audio": frames whose loudness is final; the peak entry to read)
                               stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
         self._ids[sid] = s
         self._layout.reset(s)
@@ -1755,14 +1835,17 @@ class StreamSession:
     @torch.no_grad()
     def push(self, chunks, end=()) -> Dict[int, np.ndarray]:
         """Append a chunk to every stream of ``chunks`` - ``{id: dict(ppg=(n, C), f0=(n,) | (n, 1), lft=(n hop,) | (n hop,
-        1))}``, ``0 <= n <= max_push`` - run every window that became ready, and return ``{id: samples}`` for every id of
+        1))}``, ``0 <= n <= max_push``; with ``loudness="audio"`` the chunk carries ``audio=(n hop,) | (n hop, 1)`` in place of
+        ``lft`` - run every window that became ready, and return ``{id: samples}`` for every id of
         ``chunks`` and ``end``: the stream's next samples, int16 (``pcm16``) or float32, a new array, empty when no
         window of the stream ran.  Streams in ``end`` end after their chunk: their remaining windows run in this call
         and their slots are free afterwards."""
         if self._closed:
             raise RuntimeError("StreamSession is closed")
-        from .engine import stream_assemble, stream_push
+        from .engine import stream_assemble, stream_loudness, stream_push
         hop, C, core, context = self.hop, self.channels, self.core, self.context
+        from_audio = self.loudness == "audio"
+        sig, other = ("audio", "lft") if from_audio else ("lft", "audio")     # (the chunk's third array, and the other mode's)
         end = [int(i) for i in end]
         # ---- validation: nothing is touched before every chunk has passed
         for sid in list(chunks) + end:
@@ -1773,9 +1856,12 @@ class StreamSession:
         parts = {}
         for sid, ch in chunks.items():
             try:
-                ppg, f0, lft = (np.asarray(ch[key]) for key in ("ppg", "f0", "lft"))
+                ppg, f0, lft = (np.asarray(ch[key]) for key in ("ppg", "f0", sig))
+                stray = other in ch
             except (KeyError, TypeError) as e:
-                raise ValueError(f"stream {sid}: a chunk is a dict with ppg, f0 and lft") from e
+                raise ValueError(f"stream {sid}: a chunk is a dict with ppg, f0 and {sig}") from e
+            if stray:
+                raise ValueError(f"stream {sid}: the session was built with loudness=\"{self.loudness}\": a chunk carries {sig}, not {other}")
             if ppg.ndim != 2 or ppg.shape[1] != C:
                 raise ValueError(f"stream {sid}: ppg must be (n, {C}), got {ppg.shape}")
             n = int(ppg.shape[0])
@@ -1784,7 +1870,7 @@ class StreamSession:
             if f0.shape not in ((n,), (n, 1)):
                 raise ValueError(f"stream {sid}: f0 must be ({n},) or ({n}, 1), got {f0.shape}")
             if lft.shape not in ((n * hop,), (n * hop, 1)):
-                raise ValueError(f"stream {sid}: lft must be ({n * hop},) or ({n * hop}, 1), got {lft.shape}")
+                raise ValueError(f"stream {sid}: {sig} must be ({n * hop},) or ({n * hop}, 1), got {lft.shape}")
             parts[sid] = (n, ppg, f0.reshape(-1), lft.reshape(-1))
         ids = list(dict.fromkeys(list(chunks) + end))
         dev = self.device
@@ -1813,9 +1899,10 @@ class StreamSession:
             self._up_done = torch.cuda.Event()
             self._up_done.record(stream)
             sg = self.signal_generator
+            # (with loudness="audio" the chunk's third array is audio: the same copy appends it to the audio ring)
             stream_push(self._d_up, args["streams"], args["n"], args["up_off"], args["pos"], args["first"], args["parity"],
-                        args["seed"], self._ppg, self._lft, self._exc, self._phase, self.max_push, float(sg.sample_rate),
-                        float(sg.sine_amp), float(sg.noise_amp))
+                        args["seed"], self._ppg, self._audio if from_audio else self._lft, self._exc, self._phase, self.max_push,
+                        float(sg.sample_rate), float(sg.sine_amp), float(sg.noise_amp))
             for sid in pushed:
                 st = self._slots[self._ids[sid]]
                 n = parts[sid][0]
@@ -1826,18 +1913,41 @@ class StreamSession:
                 st["seen"] += n
                 st["first"] = False
                 st["parity"] ^= 1
-        # ---- the windows that are ready now, in slot order, a stream's ascending
+        # ---- loudness="audio": the frames that became final - by their audio's arrival, or by the stream's end, with or
+        # without a chunk - go from the audio ring into the lft ring, two launches for all streams
+        if from_audio:
+            args = {key: [] for key in ("streams", "first_frame", "n", "seen", "ended", "parity")}
+            for sid in ids:
+                st = self._slots[self._ids[sid]]
+                final = stream_final_frames(st["seen"], sid in end, hop)
+                if final > st["final"]:
+                    for key, v in zip(args, (self._ids[sid], st["final"], final - st["final"], st["seen"], sid in end, st["loud_parity"])):
+                        args[key].append(v)
+            if args["streams"]:
+                stream_loudness(self._audio, self._lft, self._peak, self._loud_scratch, args["streams"], args["first_frame"], args["n"],
+                                args["seen"], args["ended"], args["parity"], self.cap, self.max_push + self.lag,
+                                float(self.signal_generator.sample_rate))
+                for s, f, n in zip(args["streams"], args["first_frame"], args["n"]):
+                    st = self._slots[s]
+                    if trace is not None:
+                        idx = (torch.arange(f, f + n, device=dev) % self.cap)
+                        trace.setdefault("lft", {}).setdefault(st["id"], []).append(self._lft[s].view(self.cap, hop)[idx].reshape(-1))
+                    st["final"] = f + n
+                    st["loud_parity"] ^= 1
+        # ---- the windows that are ready now, in slot order, a stream's ascending: ready by the frames whose features are
+        # complete (all that arrived - or, with loudness="audio", the final ones)
+        count = "final" if from_audio else "seen"
         rows = []
         forget = []              # norm="running": per row (decay, weight, bound, the stream's weighted frames behind its core)
         for sid in sorted(ids, key=lambda i: self._ids[i]):
             s = self._ids[sid]
             st = self._slots[s]
             ended = sid in end
-            ready = stream_ready_rows(st["seen"], ended, core, context, st["done"])
+            ready = stream_ready_rows(st[count], ended, core, context, st["done"])
             w = st["norm_w"]
             for j, (in_lo, in_hi, lo, hi) in enumerate(ready):
                 k = st["done"] + j
-                rows.append((s, k, in_lo, in_hi, lo, hi, ended and hi == st["seen"]))
+                rows.append((s, k, in_lo, in_hi, lo, hi, ended and hi == st[count]))
                 if self.norm == "running" and st["emb"]:
                     if self.horizon is None:             # (nothing forgotten: the frames up to the core's end)
                         w = float(hi)
@@ -1846,7 +1956,13 @@ class StreamSession:
                         (d,), (wt,), (bd,), w = running_horizon_rows([(in_lo, in_hi, lo, hi)], self.horizon, w, core)
                         forget.append((d, wt, bd, w))
             st["done"] += len(ready)
-        seen = [0 if st is None else st["seen"] for st in self._slots]
+        # per slot, the frames whose features are complete: what the stitch layout clips a zone by and what the assembly may
+        # cut rows from.  With loudness="audio" the ppg and excitation rings are `lag` frames ahead of that, and the ring
+        # is sized for it (stream_loudness_ring_frames): a row still lies inside the frames they retain
+        seen = [0 if st is None else st[count] for st in self._slots]
+        for s, _, in_lo, _, _, _, _ in rows if from_audio else ():
+            if in_lo < self._slots[s]["seen"] - self.cap:
+                raise RuntimeError(f"stream slot {s}: frame {in_lo} has left the ring of {self.cap} frames")
         pieces: Dict[int, list] = {self._ids[sid]: [] for sid in ids}
         down = []
         off = 0

@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "fastsvc_fanout_launch_count", "fastsvc_fanout_assemble",
     "fastsvc_window_launch_count", "fastsvc_window_assemble", "fastsvc_window_stitch",
     "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble",
+    "fastsvc_stream_loudness_scratch_bytes", "fastsvc_stream_loudness",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -220,6 +221,12 @@ def load_library():
     lib.fastsvc_stream_assemble.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i64),
                                             ctypes.POINTER(i32), vp, vp, vp, i32, i32, i32, i32, vp]
     lib.fastsvc_stream_assemble.restype = ctypes.c_int
+    lib.fastsvc_stream_loudness_scratch_bytes.argtypes = [i32, i32]
+    lib.fastsvc_stream_loudness_scratch_bytes.restype = sz
+    lib.fastsvc_stream_loudness.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                            ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, i32, i32, i32,
+                                            ctypes.c_float, vp]
+    lib.fastsvc_stream_loudness.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -791,6 +798,63 @@ def stream_assemble(ppg_ring: torch.Tensor, lft_ring: torch.Tensor, exc_ring: to
                                                 *[ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
                "fastsvc_stream_assemble")
     return tuple(outs)
+
+
+STREAM_LOUDNESS_MAX_FRAMES = 2048      # frames of one stream a stream_loudness call finalises
+
+
+def stream_loudness_scratch_bytes(n_streams: int, max_frames: int) -> int:
+    """Bytes of the scratch ``stream_loudness`` needs for ``n_streams`` slots that finalise at most ``max_frames`` frames
+    each per call: their power rows and maxima."""
+    return int(load_library().fastsvc_stream_loudness_scratch_bytes(int(n_streams), int(max_frames)))
+
+
+def stream_loudness(audio_ring: torch.Tensor, lft_ring: torch.Tensor, peak: torch.Tensor, scratch: torch.Tensor,
+                    streams: Sequence[int], first_frame: Sequence[int], n: Sequence[int], seen: Sequence[int],
+                    ended: Sequence[int], parity: Sequence[int], cap: int, max_frames: int, sample_rate: float) -> None:
+    """The A-weighted log loudness of the frames of live streams that have become final, from their audio rings into
+    their lft rings, by TWO HIP launches per 64 streams on the current stream (fastsvc_stream_loudness,
+    csrc/fastsvc_stream_loudness.hip; none when every ``n[i]`` is 0).
+
+    ``audio_ring`` and ``lft_ring`` are ``(n_streams, cap * hop)``: sample p of a stream's audio at index ``p % (cap *
+    hop)`` (``stream_push`` appends it, handed the audio ring as its lft ring), the loudness of frame f at frame index ``f
+    % cap``.  Entry i finalises the ``n[i]`` frames (``0 <= n[i] <= max_frames``) from ``first_frame[i]`` of stream
+    ``streams[i]`` (each at most once), of which ``seen[i]`` frames have arrived; ``ended[i]``: they are the stream's last,
+    with reflection at its end.  ``peak (n_streams, 2)`` float32 carries the running maximum the 80 dB floor hangs under:
+    the call reads entry ``parity[i]`` (or starts from 0 when ``first_frame[i] == 0``) and writes entry ``parity[i] ^ 1``.
+    ``scratch``: ``stream_loudness_scratch_bytes(n_streams, max_frames)`` bytes.  Anything out of range raises
+    ``ValueError`` before a launch and changes nothing; fails loudly off the GPU."""
+    lib = load_library()
+    for name, t, dtype, dim in (("audio_ring", audio_ring, torch.float32, 2), ("lft_ring", lft_ring, torch.float32, 2),
+                                ("peak", peak, torch.float32, 2), ("scratch", scratch, torch.uint8, 1)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"stream_loudness needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
+        if t.dtype != dtype or not t.is_contiguous() or t.device != audio_ring.device or t.dim() != dim:
+            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {audio_ring.device}")
+    n_streams, cap, max_frames = int(audio_ring.shape[0]), int(cap), int(max_frames)
+    if cap < 4 or cap % 4 or audio_ring.shape[1] == 0 or audio_ring.shape[1] % cap or lft_ring.shape != audio_ring.shape:
+        raise ValueError(f"the rings must both be (n_streams, cap * hop) with cap {cap} a multiple of 4, got "
+                         f"{tuple(audio_ring.shape)} and {tuple(lft_ring.shape)}")
+    hop = int(audio_ring.shape[1]) // cap
+    if tuple(peak.shape) != (n_streams, 2):
+        raise ValueError(f"peak must be ({n_streams}, 2), got {tuple(peak.shape)}")
+    if not 1 <= max_frames <= min(cap, STREAM_LOUDNESS_MAX_FRAMES):
+        raise ValueError(f"max_frames must be in [1, min(cap {cap}, {STREAM_LOUDNESS_MAX_FRAMES})], got {max_frames}")
+    if scratch.numel() < stream_loudness_scratch_bytes(n_streams, max_frames):
+        raise ValueError(f"scratch holds {scratch.numel()} bytes, {stream_loudness_scratch_bytes(n_streams, max_frames)} are needed")
+    S = len(streams)
+    if S == 0 or any(len(v) != S for v in (first_frame, n, seen, ended, parity)):
+        raise ValueError("stream_loudness needs at least one stream and one entry per stream in every array")
+    i32s = lambda v: (ctypes.c_int32 * S)(*[int(x) for x in v])      # noqa: E731
+    i64s = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])      # noqa: E731
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    with torch.cuda.device(audio_ring.device):
+        stream = torch.cuda.current_stream(audio_ring.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_loudness(ptr(audio_ring), ptr(lft_ring), ptr(peak), ptr(scratch), S, i32s(streams),
+                                                i64s(first_frame), i32s(n), i64s(seen), i32s([1 if v else 0 for v in ended]),
+                                                i32s([int(v) & 1 for v in parity]), n_streams, cap, max_frames, hop,
+                                                ctypes.c_float(float(sample_rate)), ctypes.c_void_p(stream)),
+               "fastsvc_stream_loudness")
 
 
 def check_norm_groups(norm_groups, lens: Sequence[int]):

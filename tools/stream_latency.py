@@ -23,7 +23,11 @@ up block and 24 small launches per forward.  Its figures go to profiles/decode_s
 launches, one more multiplication per row in the pool and three double arrays in the per-forward upload.  Its figures go
 to profiles/decode_stream_horizon.txt.
 
-    python tools/stream_latency.py [--norm [--horizon H]]"""
+--audio: the pair is StreamSession(loudness="audio") against StreamSession(loudness="given") on the same ppg and f0, 1, 8 and
+32 streams at core 32 in both storages: the audio session is pushed samples and makes the loudness on the device (two more
+launches per push, csrc/fastsvc_stream_loudness.hip).  Its figures go to profiles/decode_stream_loudness.txt.
+
+    python tools/stream_latency.py [--norm [--horizon H] | --audio]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -217,9 +221,66 @@ def main_norm(horizon=None):
         f.write("\n".join(out) + "\n")
 
 
+def main_audio():
+    core = 32
+    lag = Dc.stream_loudness_lag(hop)
+    out = [f"stream loudness: one StreamSession.push that completes one window per stream (every stream delivers {core} frames), host "
+           f"to host, loudness=audio (the chunk carries {core} x {hop} samples of audio; the push finalises {core} frames of loudness "
+           f"per stream on the device, {lag} frames behind the audio: two more launches) against loudness=given (the chunk carries "
+           f"the loudness) on the same ppg and f0, two sessions in one process; context {ctx}, fade {FADE}, speaker embedding, F0 "
+           f"shift on, int16 out; {pushes} pushes per repetition, {reps} repetitions, legs alternated, median of the repetitions' "
+           f"means (min, max); {torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for N in (1, 8, 32):
+            src = [features(core * 8) for _ in range(N)]
+            for f in src:
+                f["audio"] = (0.1 * rng.standard_normal((core * 8 * hop, 1))).astype(np.float32)
+            legs = {}
+            for name in ("given", "audio"):
+                s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, loudness=name)
+                legs[name] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[],
+                                  key="lft" if name == "given" else "audio")
+
+            def push(leg):
+                a = (leg["step"] % 8) * core
+                leg["step"] += 1
+                k = leg["key"]
+                return leg["s"].push({i: {"ppg": f["ppg"][a: a + core], "f0": f["f0"][a: a + core], k: f[k][a * hop: (a + core) * hop]}
+                                      for i, f in zip(leg["ids"], src)})
+            for leg in legs.values():
+                for _ in range(6):                       # (fill the context, warm every shape)
+                    push(leg)
+                before = leg["s"].forwards
+                got = push(leg)
+                assert leg["s"].forwards == before + 1 and all(v.size == core * hop for v in got.values())
+            for _ in range(reps):
+                for leg in legs.values():
+                    t0 = time.perf_counter()
+                    for _ in range(pushes):
+                        push(leg)
+                    leg["t"].append((time.perf_counter() - t0) / pushes)
+            for leg in legs.values():
+                leg["s"].end(leg["ids"])
+                leg["s"].close()
+            audio = N * core * hop / SR
+            mg, line_g = spread(f"{N:2d} streams, core {core:3d}: push, loudness=given", legs["given"]["t"], audio)
+            ma, line_a = spread(f"{N:2d} streams, core {core:3d}: push, loudness=audio", legs["audio"]["t"], audio)
+            out += [line_g, line_a, f"    audio / given {ma / mg:.3f} ({(ma - mg) * 1e3:+.0f} us a push; spread of the given leg "
+                                    f"{(max(legs['given']['t']) - min(legs['given']['t'])) * 1e6:.0f} us)"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream_loudness.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
-    if "--horizon" in argv:
+    if "--audio" in argv:
+        main_audio()
+    elif "--horizon" in argv:
         if "--norm" not in argv or argv.index("--horizon") + 1 >= len(argv):
             sys.exit("--horizon H goes with --norm")
         main_norm(float(argv[argv.index("--horizon") + 1]))
