@@ -33,7 +33,8 @@ import math
 import os
 import time
 import wave
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -680,6 +681,23 @@ def stream_loudness_ring_frames(core: int, context: int, max_push: int, hop: int
     return -(-max(frames, samples) // 4) * 4
 
 
+class StreamRow(NamedTuple):
+    """Window ``k`` of the live stream in slot ``stream`` as a row of a forward: it reads the stream's frames ``[in_lo,
+    in_hi)``, owns ``[core_lo, core_hi)`` of them, and is the stream's ``last`` window or not.  The row type of
+    ``stream_push_rows``, of ``StreamStitchLayout.batch`` (which also takes the plain 7-tuple) and of a session's trace."""
+    stream: int
+    k: int
+    in_lo: int
+    in_hi: int
+    core_lo: int
+    core_hi: int
+    last: bool
+
+    frames = property(lambda r: r.in_hi - r.in_lo, doc="frames the row holds")
+    own_lo = property(lambda r: r.core_lo - r.in_lo, doc="where its core starts, in frames of the row")
+    own_hi = property(lambda r: r.core_hi - r.in_lo, doc="where its core ends, in frames of the row")
+
+
 class StreamStitchLayout:
     """``stitch_layout``, incrementally: the streams' rows arrive batch by batch (a ``StreamSession.push`` is one batch
     per forward) and nobody knows the final length yet.  ``batch(rows, seen)`` returns for these rows what
@@ -692,9 +710,9 @@ class StreamStitchLayout:
     the slot a row of the same batch reads.  ``pending[s]`` is the window of stream s whose right zone is staged and
     waits for its neighbour, ``written[s]`` the slot (0 / 1) it is in.
 
-    A row is ``(stream, k, in_lo, in_hi, core_lo, core_hi, last)``: window k of the stream, and whether it is the
-    stream's last one.  Rows of a stream must come in window order; ``seen[stream]`` is the stream's frame count (its
-    final one when it has ended), which clips a zone the stream ends in."""
+    A row is a ``StreamRow``, or the plain tuple ``(stream, k, in_lo, in_hi, core_lo, core_hi, last)``: window k of the
+    stream, and whether it is the stream's last one.  Rows of a stream must come in window order; ``seen[stream]`` is
+    the stream's frame count (its final one when it has ended), which clips a zone the stream ends in."""
 
     def __init__(self, n_streams: int, hop: int, fade: int):
         fade = int(fade)
@@ -715,13 +733,15 @@ class StreamStitchLayout:
 
     def batch(self, rows, seen):
         hop, half = self.hop, self.half
-        where = {(r[0], r[1]): j for j, r in enumerate(rows)}
+        rows = [r if isinstance(r, StreamRow) else StreamRow(*r) for r in rows]
+        where = {(r.stream, r.k): j for j, r in enumerate(rows)}
         if len(where) != len(rows):
             raise ValueError("a window is in the batch twice")
-        width = max(r[3] - r[2] for r in rows) * hop
+        width = max(r.frames for r in rows) * hop
         pending, written = list(self.pending), list(self.written)
         specs = []
-        for s, k, in_lo, in_hi, lo, hi, last in rows:
+        for r in rows:
+            s, k = r.stream, r.k
             lm = rm = NONE
             ls = rs = 0
             if half and k > 0:
@@ -734,15 +754,15 @@ class StreamStitchLayout:
                     pending[s] = None
                 else:
                     raise ValueError(f"stream {s}: window {k} runs, but window {k - 1} has not staged its fade zone")
-            if half and not last:
+            if half and not r.last:
                 if (s, k + 1) in where:
-                    b = rows[where[(s, k + 1)]]
-                    rm, rs = FROM_Y, where[(s, k + 1)] * width + (hi * hop - half - b[2] * hop)
+                    j = where[(s, k + 1)]                # (the zone's other half is in the next window's row of this forward)
+                    rm, rs = FROM_Y, j * width + (r.core_hi * hop - half - rows[j].in_lo * hop)
                 else:
                     written[s] ^= 1                      # (not the slot the stream's first row of this batch may read)
                     rm, rs = STAGE, self.slot(s, written[s])
                     pending[s] = k
-            specs.append((s, int(seen[s]) * hop, in_lo, in_hi, lo, hi, lm, rm, ls, rs))
+            specs.append((s, int(seen[s]) * hop, r.in_lo, r.in_hi, r.core_lo, r.core_hi, lm, rm, ls, rs))
         # (a stream's windows run in order: the left zone is written only when blended from the stage, the right one only
         # when blended from the forward's output)
         d = _emit_rows(specs, hop, half, width, (FROM_STAGE,), (FROM_Y,))
@@ -751,6 +771,102 @@ class StreamStitchLayout:
 
 
 stream_stitch_layout = StreamStitchLayout           # (the incremental counterpart of ``stitch_layout``, under its name)
+
+
+@dataclass
+class _Stream:
+    """What the host knows of one open stream of a ``StreamSession``.  Three of the fields say which entry of a two-entry
+    record on the device is current: a launch reads entry p and writes entry ``p ^ 1``, and the field flips once that
+    launch is enqueued."""
+    id: int                          # what ``open`` returned
+    slot: int                        # its row of every per-stream device buffer
+    emb: bool                        # opened with a speaker embedding
+    seed: int                        # keys the excitation's noise
+    stats: Optional[tuple]           # ([mean, std] of the source's log F0, of the target's), or None: no F0 shift
+    from_audio: bool = False         # the session makes the loudness (loudness="audio")
+    seen: int = 0                    # frames that have arrived
+    first: bool = True               # nothing has arrived: the sine phase starts at 0
+    parity: int = 0                  # the phase record's current entry (flips with every stream_push)
+    final: int = 0                   # loudness="audio": frames whose loudness is final
+    loud_parity: int = 0             # the peak record's current entry (flips with every stream_loudness)
+    done: int = 0                    # windows that ran
+    norm_parity: int = 0             # norm="running": the carry record's current entry (flips with every forward)
+    norm_w: float = 0.0              # ... and the weighted frames it holds (``running_horizon_rows``' w)
+
+    @property
+    def complete(self) -> int:
+        """Frames whose features are complete - what a window is ready by: all that arrived or, when the session makes the
+        loudness, those whose loudness is final."""
+        return self.final if self.from_audio else self.seen
+
+
+def check_stream_chunks(chunks, end, open_ids, channels: int, hop: int, max_push: int, loudness: str = "given"):
+    """Everything ``StreamSession.push`` refuses, on the host alone: ``chunks = {id: dict(ppg, f0, lft | audio)}`` and the
+    ids in ``end`` against the open ids, the ppg channels, ``hop``, ``max_push`` and the session's ``loudness`` mode.
+    Returns ``(parts, ids, end)``: ``parts[id] = (n, ppg (n, C), f0 (n,), lft or audio (n hop,))`` as numpy arrays in the
+    order of ``chunks``, ``ids`` every id of ``chunks`` and ``end`` once, in that order, and ``end`` as a list of ints.
+    A ``ValueError`` names the first thing wrong; nothing is changed."""
+    C, hop = int(channels), int(hop)
+    sig, other = ("audio", "lft") if loudness == "audio" else ("lft", "audio")     # (the chunk's third array, and the other mode's)
+    end = [int(i) for i in end]
+    for sid in list(chunks) + end:
+        if sid not in open_ids:
+            raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
+    if len(set(end)) != len(end):
+        raise ValueError("a stream is listed twice in end")
+    parts = {}
+    for sid, ch in chunks.items():
+        try:
+            ppg, f0, lft = (np.asarray(ch[key]) for key in ("ppg", "f0", sig))
+            stray = other in ch
+        except (KeyError, TypeError) as e:
+            raise ValueError(f"stream {sid}: a chunk is a dict with ppg, f0 and {sig}") from e
+        if stray:
+            raise ValueError(f"stream {sid}: the session was built with loudness=\"{loudness}\": a chunk carries {sig}, not {other}")
+        if ppg.ndim != 2 or ppg.shape[1] != C:
+            raise ValueError(f"stream {sid}: ppg must be (n, {C}), got {ppg.shape}")
+        n = int(ppg.shape[0])
+        if n > max_push:
+            raise ValueError(f"stream {sid}: {n} frames in one push, max_push is {max_push}")
+        if f0.shape not in ((n,), (n, 1)):
+            raise ValueError(f"stream {sid}: f0 must be ({n},) or ({n}, 1), got {f0.shape}")
+        if lft.shape not in ((n * hop,), (n * hop, 1)):
+            raise ValueError(f"stream {sid}: {sig} must be ({n * hop},) or ({n * hop}, 1), got {lft.shape}")
+        parts[sid] = (n, ppg, f0.reshape(-1), lft.reshape(-1))
+    return parts, list(dict.fromkeys(list(chunks) + end)), end
+
+
+def stream_push_rows(streams: Sequence[_Stream], ended, core: int, context: int, running: bool = False,
+                     horizon: Optional[float] = None):
+    """The forwards' rows of one ``StreamSession.push``, planned on the host: ``streams`` are the records of the streams
+    the push names, in slot order, ``ended`` the ids that end with it.  Returns ``(rows, forget)``.
+
+    ``rows``: a ``StreamRow`` for every window that is ready now (``stream_ready_rows`` by the stream's ``complete``
+    frames), stream after stream and a stream's ascending from window ``done`` - the order the forwards take them in;
+    ``last`` is set on the window an ended stream stops in.
+
+    ``forget``, with ``running`` (``norm="running"``): per row of a stream with an embedding - they all have one, or none
+    has - ``(decay, weight, bound, w)``, ``running_horizon_rows``' three for the stream's ready windows behind its
+    ``norm_w`` (one call per stream; ``horizon=None`` forgets nothing) and the weighted frames ``w`` the stream carries
+    once the row has run.  Otherwise empty.
+
+    Reads the records and changes none: the caller sets ``done`` to ``k + 1`` of a stream's last row, and ``norm_w`` to a
+    row's ``w`` when its forward is enqueued."""
+    rows: List[StreamRow] = []
+    forget = []
+    for st in streams:
+        end, complete, k = st.id in ended, st.complete, st.done
+        ready = stream_ready_rows(complete, end, core, context, k)
+        for in_lo, in_hi, lo, hi in ready:
+            rows.append(StreamRow(st.slot, k, in_lo, in_hi, lo, hi, end and hi == complete))
+            k += 1
+        if ready and running and st.emb:
+            w = st.norm_w
+            decay, weight, bound, _ = running_horizon_rows(ready, horizon, w, core)
+            for (_, _, lo, hi), d, wt, bd in zip(ready, decay, weight, bound):
+                w = d * w + (hi - lo) if lo else float(hi)       # (``running_horizon_rows``' w, after every window)
+                forget.append((d, wt, bd, w))
+    return rows, forget
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
@@ -1656,12 +1772,11 @@ class StreamSession:
     first window resets it) and one scratch for the partial sums of a forward; with ``loudness="audio"`` the rings hold
     ``stream_loudness_ring_frames(core, context, max_push, hop)`` frames, and per stream there is a fourth ring, the audio
     (sample p at ``p % (cap hop)``), and the running maximum (a float32 parity pair, never zeroed - a stream's first frame
-    starts it), plus one scratch for the power rows of the ``max_push + lag`` frames a push can finalise per stream.  Per
-    ``push``: one upload, one ``stream_push`` launch (appends to the rings and synthesises the chunk's excitation,
-    csrc/fastsvc_stream.hip), with ``loudness="audio"`` two ``stream_loudness`` launches when any frame became final (power
-    rows; then maximum, floor, weighting, mean and log into the lft ring) and none otherwise, and, if
-    any window became ready, per ``max_batch`` rows one ``stream_assemble``, one forward with ``lengths``, one
-    ``window_stitch`` and one download.  A push that completes no window runs no forward (``forwards`` counts them).
+    starts it), plus one scratch for the power rows of the ``max_push + lag`` frames a push can finalise per stream.  A
+    ``push`` is a driver over named steps, whose docstrings say what each launches: ``check_stream_chunks``, ``_append``
+    (one upload, one ``stream_push``), with ``loudness="audio"`` ``_finalise_loudness`` (two ``stream_loudness`` launches, or
+    none), ``stream_push_rows`` and, per ``max_batch`` ready rows, ``_forward_rows``; ``_collect`` waits once.  A push that
+    completes no window runs no forward (``forwards`` counts them).
 
     Excitation: the phase is carried from push to push in float64 and equals the whole-utterance scan bit for bit, so
     with ``noise_amp == 0`` the streamed excitation IS ``signal_generator`` on the whole f0.  The noise is keyed by the
@@ -1685,7 +1800,7 @@ class StreamSession:
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
                  fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
                  horizon: Optional[float] = None, loudness: str = "given"):
-        from .engine import FastSVCError, STREAM_MAX_PUSH
+        from .engine import FastSVCError
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -1697,33 +1812,65 @@ class StreamSession:
             raise ValueError("StreamSession supports out_channels == 1 only")
         if list(getattr(signal_generator, "signal_types", ["sine"])) != ["sine"]:
             raise ValueError("StreamSession needs a signal generator whose only signal type is \"sine\"")
-        self.hop = hop = int(signal_generator.hop_size)
-        self.core = core = int(core)
-        self.context = context = -(-receptive_field_frames(cfg) // 4) * 4 if context is None else int(context)
-        self.fade = fade = int(fade)
+        self.hop = int(signal_generator.hop_size)
+        for name, value in self._check_args(cfg, self.hop, n_streams, core, context, fade, max_push, max_batch, norm, horizon,
+                                            loudness).items():
+            setattr(self, name, value)
+        self.pcm16 = bool(pcm16)
+        self._allocate(cfg)
+        self._slots: List[Optional[_Stream]] = [None] * self.n_streams        # per slot: the open stream's record
+        self._ids: Dict[int, int] = {}                                       # open id -> slot
+        self._next_id = 0
+        self.forwards = 0
+        # set to a dict to have push leave what it made there (tests): "excitation", per stream id the device tensors of
+        # its chunks' excitation in order, "forwards", per forward (its rows, the assembled excitation rows), and with
+        # loudness="audio" "lft", per stream id the device tensors of its newly final frames' loudness in order
+        self._stream_trace: Optional[Dict[str, object]] = None
+        self._closed = False
+
+    @staticmethod
+    def _check_args(cfg, hop: int, n_streams: int = 1, core: int = 32, context: Optional[int] = None, fade: int = 8,
+                    max_push: Optional[int] = None, max_batch: int = 32, norm: str = "window", horizon: Optional[float] = None,
+                    loudness: str = "given") -> Dict[str, object]:
+        """The constructor's arguments against the generator configuration ``cfg`` and the signal generator's ``hop``, with
+        no device: a ``ValueError`` for the first one that is refused, else the session's attributes they resolve to -
+        the arguments as given or defaulted, ``channels``, ``lag``, the rings' ``cap``, the floats ``_slice`` a stream takes
+        of the upload buffer (16-byte aligned) and ``_down_elems``, the samples of the download buffer (a push returns at
+        most the frames a ring holds per stream, every row's run padded to 8 samples)."""
+        from .engine import STREAM_MAX_PUSH
+        core = int(core)
+        context = -(-receptive_field_frames(cfg) // 4) * 4 if context is None else int(context)
+        fade = int(fade)
         _check_window_sizes(core, context, fade)
-        self.max_push = max_push = core if max_push is None else int(max_push)
-        self.n_streams, self.max_batch, self.pcm16 = int(n_streams), int(max_batch), bool(pcm16)
-        if self.n_streams < 1 or self.max_batch < 1:
+        max_push = core if max_push is None else int(max_push)
+        n_streams, max_batch = int(n_streams), int(max_batch)
+        if n_streams < 1 or max_batch < 1:
             raise ValueError("StreamSession needs n_streams >= 1 and max_batch >= 1")
         if not 1 <= max_push <= STREAM_MAX_PUSH:
             raise ValueError(f"max_push must be in [1, {STREAM_MAX_PUSH}], got {max_push}")
-        self.channels = C = int(cfg.in_channels)
-        self._takes_emb = bool(cfg.use_spk_emb)
+        takes_emb = bool(cfg.use_spk_emb)
         if norm not in ("window", "running"):
             raise ValueError(f"norm must be \"window\" or \"running\", got {norm!r}")
-        if norm == "running" and not self._takes_emb:
+        if norm == "running" and not takes_emb:
             raise ValueError("norm=\"running\" needs a model that takes a speaker embedding: without one nothing is normalised")
         if horizon is not None and norm != "running":
             raise ValueError("horizon forgets running statistics: it needs norm=\"running\"")
-        self.norm, self.horizon = norm, check_horizon(horizon, core)
+        horizon = check_horizon(horizon, core)
         if loudness not in ("given", "audio"):
             raise ValueError(f"loudness must be \"given\" or \"audio\", got {loudness!r}")
-        self.loudness = loudness
-        self.lag = stream_loudness_lag(hop) if loudness == "audio" else 0
-        self.cap = cap = stream_ring_frames(core, context, max_push) if loudness == "given" else \
+        lag = stream_loudness_lag(hop) if loudness == "audio" else 0
+        cap = stream_ring_frames(core, context, max_push) if loudness == "given" else \
             stream_loudness_ring_frames(core, context, max_push, hop)
-        dev, n = self.device, self.n_streams
+        C = int(cfg.in_channels)
+        return dict(core=core, context=context, fade=fade, max_push=max_push, n_streams=n_streams, max_batch=max_batch,
+                    channels=C, _takes_emb=takes_emb, norm=norm, horizon=horizon, loudness=loudness, lag=lag, cap=cap,
+                    _slice=-(-max_push * (C + 1 + hop) // 4) * 4, _down_elems=n_streams * (cap * hop + 8 * (cap // core + 2)))
+
+    def _allocate(self, cfg) -> None:
+        """The session's device and page-locked buffers, sized by what ``_check_args`` resolved (the class docstring lists
+        them)."""
+        dev, n, cap, hop, C = self.device, self.n_streams, self.cap, self.hop, self.channels
+        max_push, loudness, norm = self.max_push, self.loudness, self.norm
         self._ppg = torch.empty((n, cap, C), dtype=torch.float32, device=dev)
         self._lft = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
         self._exc = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
@@ -1736,32 +1883,21 @@ class StreamSession:
             self._audio = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
             self._peak = torch.empty((n, 2), dtype=torch.float32, device=dev)
             self._loud_scratch = torch.empty(stream_loudness_scratch_bytes(n, max_push + self.lag), dtype=torch.uint8, device=dev)
-        self._layout = StreamStitchLayout(n, hop, fade)
+        self._layout = StreamStitchLayout(n, hop, self.fade)
         self._stage = torch.empty(max(self._layout.stage_elems, 1), dtype=torch.float32, device=dev)
         self._emb = torch.zeros((n, max(int(cfg.spk_emb_size), 1)), dtype=torch.float32, device=dev)
-        self._slice = -(-max_push * (C + 1 + hop) // 4) * 4              # (every stream's slice starts 16-byte aligned)
         self._h_up = torch.empty(n * self._slice, dtype=torch.float32, pin_memory=True)
         self._d_up = torch.empty(n * self._slice, dtype=torch.float32, device=dev)
-        # a push returns at most the frames a ring holds per stream; every row's run is padded to 8 samples
         self._h_down = _PinnedSet()
-        self._h_down.get("w", (n * (cap * hop + 8 * (cap // core + 2)),))
+        self._h_down.get("w", (self._down_elems,))
         self._up_done: Optional[torch.cuda.Event] = None
         self._carry = self._norm_scratch = None
         if norm == "running":
-            plan = model.plan
+            plan = self.model.plan
             self._carry = torch.empty((n, plan.norm_carry_bytes() // 8), dtype=torch.float64, device=dev)
-            self._norm_scratch = torch.empty(max(plan.norm_running_scratch_bytes(self.max_batch, plan.padded_frames(core + 2 * context)), 1),
-                                             dtype=torch.uint8, device=dev)
+            frames = plan.padded_frames(self.core + 2 * self.context)
+            self._norm_scratch = torch.empty(max(plan.norm_running_scratch_bytes(self.max_batch, frames), 1), dtype=torch.uint8, device=dev)
         self._emb_rows: Dict[tuple, torch.Tensor] = {}                       # row slots of a forward -> their index tensor
-        self._slots: List[Optional[Dict[str, object]]] = [None] * n          # per slot: the open stream's host state
-        self._ids: Dict[int, int] = {}                                       # open id -> slot
-        self._next_id = 0
-        self.forwards = 0
-        # set to a dict to have push leave what it made there (tests): "excitation", per stream id the device tensors of
-        # its chunks' excitation in order, "forwards", per forward (its rows, the assembled excitation rows), and with
-        # loudness="audio" "lft", per stream id the device tensors of its newly final frames' loudness in order
-        self._stream_trace: Optional[Dict[str, object]] = None
-        self._closed = False
 
     latency_frames = property(lambda self: self.core + self.context + self.lag,
                               doc="the typical delay, in frames of input: core + context (+ the loudness lag with loudness=\"audio\")")
@@ -1798,7 +1934,7 @@ class StreamSession:
         has_emb = trg_emb is not None
         if has_emb and not self._takes_emb:
             raise ValueError("the model does not take a speaker embedding")
-        if any(st["emb"] != has_emb for st in self._slots if st is not None):
+        if any(st.emb != has_emb for st in self._slots if st is not None):
             raise ValueError("every open stream needs a speaker embedding, or none does")
         if (src_f0_stats is None) != (trg_f0_stats is None):
             raise ValueError("an F0 shift needs src_f0_stats and trg_f0_stats")
@@ -1811,9 +1947,8 @@ class StreamSession:
         sid = self._next_id
         self._next_id += 1
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
-        self._slots[s] = dict(id=sid, emb=has_emb, seen=0, done=0, first=True, parity=0, norm_parity=0, norm_w=0.0, seed=key,
-                              final=0, loud_parity=0,       # (loudness="audio": frames whose loudness is final; the peak entry to read)
-                              stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
+        self._slots[s] = _Stream(id=sid, slot=s, emb=has_emb, seed=key, from_audio=self.loudness == "audio",
+                                 stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
         self._ids[sid] = s
         self._layout.reset(s)
         return sid
@@ -1826,7 +1961,7 @@ class StreamSession:
             raise ValueError("norm_frames needs norm=\"running\"")
         if sid not in self._ids:
             raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
-        return float(self._slots[self._ids[sid]]["norm_w"])
+        return float(self._slots[self._ids[sid]].norm_w)
 
     def end(self, ids) -> Dict[int, np.ndarray]:
         """``push({}, end=ids)``: flush these streams and free their slots."""
@@ -1842,181 +1977,160 @@ class StreamSession:
         and their slots are free afterwards."""
         if self._closed:
             raise RuntimeError("StreamSession is closed")
-        from .engine import stream_assemble, stream_loudness, stream_push
-        hop, C, core, context = self.hop, self.channels, self.core, self.context
-        from_audio = self.loudness == "audio"
-        sig, other = ("audio", "lft") if from_audio else ("lft", "audio")     # (the chunk's third array, and the other mode's)
-        end = [int(i) for i in end]
-        # ---- validation: nothing is touched before every chunk has passed
-        for sid in list(chunks) + end:
-            if sid not in self._ids:
-                raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
-        if len(set(end)) != len(end):
-            raise ValueError("a stream is listed twice in end")
-        parts = {}
-        for sid, ch in chunks.items():
-            try:
-                ppg, f0, lft = (np.asarray(ch[key]) for key in ("ppg", "f0", sig))
-                stray = other in ch
-            except (KeyError, TypeError) as e:
-                raise ValueError(f"stream {sid}: a chunk is a dict with ppg, f0 and {sig}") from e
-            if stray:
-                raise ValueError(f"stream {sid}: the session was built with loudness=\"{self.loudness}\": a chunk carries {sig}, not {other}")
-            if ppg.ndim != 2 or ppg.shape[1] != C:
-                raise ValueError(f"stream {sid}: ppg must be (n, {C}), got {ppg.shape}")
-            n = int(ppg.shape[0])
-            if n > self.max_push:
-                raise ValueError(f"stream {sid}: {n} frames in one push, max_push is {self.max_push}")
-            if f0.shape not in ((n,), (n, 1)):
-                raise ValueError(f"stream {sid}: f0 must be ({n},) or ({n}, 1), got {f0.shape}")
-            if lft.shape not in ((n * hop,), (n * hop, 1)):
-                raise ValueError(f"stream {sid}: {sig} must be ({n * hop},) or ({n * hop}, 1), got {lft.shape}")
-            parts[sid] = (n, ppg, f0.reshape(-1), lft.reshape(-1))
-        ids = list(dict.fromkeys(list(chunks) + end))
-        dev = self.device
-        stream = torch.cuda.current_stream(dev)
-        trace = self._stream_trace
-        # ---- one upload, one stream_push
-        pushed = [sid for sid in chunks if parts[sid][0] > 0]
+        # nothing is touched before every chunk has passed
+        parts, ids, end = check_stream_chunks(chunks, end, self._ids, self.channels, self.hop, self.max_push, self.loudness)
+        pushed = [sid for sid, part in parts.items() if part[0] > 0]
         if pushed:
-            if self._up_done is not None:
-                self._up_done.synchronize()              # (the page-locked twin is still being read by the last upload)
-            h = self._h_up.numpy()
-            args = {key: [] for key in ("streams", "n", "up_off", "pos", "first", "parity", "seed")}
-            for j, sid in enumerate(pushed):
-                n, ppg, f0, lft = parts[sid]
-                st = self._slots[self._ids[sid]]
-                if st["stats"] is not None:
-                    f0 = F0Statistics().convert(np.asarray(f0, dtype=np.float64), st["stats"][0], st["stats"][1])
-                o = j * self._slice
-                h[o: o + n * C] = ppg.reshape(-1)
-                h[o + n * C: o + n * C + n] = f0
-                h[o + n * C + n: o + n * (C + 1 + hop)] = lft
-                for key, v in zip(args, (self._ids[sid], n, o, st["seen"], st["first"], st["parity"], st["seed"])):
-                    args[key].append(v)
-            used = len(pushed) * self._slice
-            self._d_up[:used].copy_(self._h_up[:used], non_blocking=True)
-            self._up_done = torch.cuda.Event()
-            self._up_done.record(stream)
-            sg = self.signal_generator
-            # (with loudness="audio" the chunk's third array is audio: the same copy appends it to the audio ring)
-            stream_push(self._d_up, args["streams"], args["n"], args["up_off"], args["pos"], args["first"], args["parity"],
-                        args["seed"], self._ppg, self._audio if from_audio else self._lft, self._exc, self._phase, self.max_push,
-                        float(sg.sample_rate), float(sg.sine_amp), float(sg.noise_amp))
-            for sid in pushed:
-                st = self._slots[self._ids[sid]]
-                n = parts[sid][0]
-                if trace is not None:
-                    idx = (torch.arange(st["seen"], st["seen"] + n, device=dev) % self.cap)
-                    trace.setdefault("excitation", {}).setdefault(sid, []).append(
-                        self._exc[self._ids[sid]].view(self.cap, hop)[idx].reshape(-1))
-                st["seen"] += n
-                st["first"] = False
-                st["parity"] ^= 1
-        # ---- loudness="audio": the frames that became final - by their audio's arrival, or by the stream's end, with or
-        # without a chunk - go from the audio ring into the lft ring, two launches for all streams
-        if from_audio:
-            args = {key: [] for key in ("streams", "first_frame", "n", "seen", "ended", "parity")}
-            for sid in ids:
-                st = self._slots[self._ids[sid]]
-                final = stream_final_frames(st["seen"], sid in end, hop)
-                if final > st["final"]:
-                    for key, v in zip(args, (self._ids[sid], st["final"], final - st["final"], st["seen"], sid in end, st["loud_parity"])):
-                        args[key].append(v)
-            if args["streams"]:
-                stream_loudness(self._audio, self._lft, self._peak, self._loud_scratch, args["streams"], args["first_frame"], args["n"],
-                                args["seen"], args["ended"], args["parity"], self.cap, self.max_push + self.lag,
-                                float(self.signal_generator.sample_rate))
-                for s, f, n in zip(args["streams"], args["first_frame"], args["n"]):
-                    st = self._slots[s]
-                    if trace is not None:
-                        idx = (torch.arange(f, f + n, device=dev) % self.cap)
-                        trace.setdefault("lft", {}).setdefault(st["id"], []).append(self._lft[s].view(self.cap, hop)[idx].reshape(-1))
-                    st["final"] = f + n
-                    st["loud_parity"] ^= 1
-        # ---- the windows that are ready now, in slot order, a stream's ascending: ready by the frames whose features are
-        # complete (all that arrived - or, with loudness="audio", the final ones)
-        count = "final" if from_audio else "seen"
-        rows = []
-        forget = []              # norm="running": per row (decay, weight, bound, the stream's weighted frames behind its core)
-        for sid in sorted(ids, key=lambda i: self._ids[i]):
-            s = self._ids[sid]
-            st = self._slots[s]
-            ended = sid in end
-            ready = stream_ready_rows(st[count], ended, core, context, st["done"])
-            w = st["norm_w"]
-            for j, (in_lo, in_hi, lo, hi) in enumerate(ready):
-                k = st["done"] + j
-                rows.append((s, k, in_lo, in_hi, lo, hi, ended and hi == st[count]))
-                if self.norm == "running" and st["emb"]:
-                    if self.horizon is None:             # (nothing forgotten: the frames up to the core's end)
-                        w = float(hi)
-                        forget.append((1.0, float(in_hi), float(in_hi), w))
-                    else:
-                        (d,), (wt,), (bd,), w = running_horizon_rows([(in_lo, in_hi, lo, hi)], self.horizon, w, core)
-                        forget.append((d, wt, bd, w))
-            st["done"] += len(ready)
+            self._append(parts, pushed)
+        if self.loudness == "audio":
+            self._finalise_loudness(ids, end)
+        streams = sorted((self._slots[self._ids[sid]] for sid in ids), key=lambda st: st.slot)
+        rows, forget = stream_push_rows(streams, end, self.core, self.context, self.norm == "running", self.horizon)
+        for r in rows:
+            self._slots[r.stream].done = r.k + 1
         # per slot, the frames whose features are complete: what the stitch layout clips a zone by and what the assembly may
         # cut rows from.  With loudness="audio" the ppg and excitation rings are `lag` frames ahead of that, and the ring
         # is sized for it (stream_loudness_ring_frames): a row still lies inside the frames they retain
-        seen = [0 if st is None else st[count] for st in self._slots]
-        for s, _, in_lo, _, _, _, _ in rows if from_audio else ():
-            if in_lo < self._slots[s]["seen"] - self.cap:
-                raise RuntimeError(f"stream slot {s}: frame {in_lo} has left the ring of {self.cap} frames")
-        pieces: Dict[int, list] = {self._ids[sid]: [] for sid in ids}
-        down = []
-        off = 0
+        seen = [0 if st is None else st.complete for st in self._slots]
+        for r in rows if self.loudness == "audio" else ():
+            if r.in_lo < self._slots[r.stream].seen - self.cap:
+                raise RuntimeError(f"stream slot {r.stream}: frame {r.in_lo} has left the ring of {self.cap} frames")
+        down, off = [], 0
         for c0 in range(0, len(rows), self.max_batch):
-            chunk = rows[c0: c0 + self.max_batch]
-            lay = self._layout.batch(chunk, seen)
-            lens = [r[3] - r[2] for r in chunk]
-            width = max(lens)
-            ppg, lft, sine = stream_assemble(self._ppg, self._lft, self._exc, seen, [r[0] for r in chunk],
-                                             [r[2] for r in chunk], lens, width)
-            if trace is not None:
-                trace.setdefault("forwards", []).append(([(self._slots[r[0]]["id"],) + tuple(r[2:6]) for r in chunk], sine.clone()))
-            emb = None
-            if self._slots[chunk[0][0]]["emb"]:
-                slots = tuple(r[0] for r in chunk)       # (the steady state repeats one tuple: its index tensor is uploaded once)
-                if slots not in self._emb_rows:
-                    if len(self._emb_rows) >= 256:
-                        self._emb_rows.clear()
-                    self._emb_rows[slots] = torch.as_tensor(slots, dtype=torch.int64, device=dev)
-                emb = self._emb.index_select(0, self._emb_rows[slots])
-            if emb is not None and self.norm == "running":
-                # window k of a stream: its core starts own_lo frames into the row, core_lo frames of the stream lie in
-                # front of it, window 0 resets the slot's carry; the slot's parity says which entry of its record is current
-                running = ([r[0] for r in chunk], [r[4] - r[2] for r in chunk], [r[5] - r[2] for r in chunk],
-                           [r[4] for r in chunk], [int(r[1] == 0) for r in chunk],
-                           [self._slots[r[0]]["norm_parity"] for r in chunk])
-                fg = forget[c0: c0 + self.max_batch]
-                decay = None if self.horizon is None else tuple([f[i] for f in fg] for i in range(3))
-                y = self.model(ppg, sine, lft, emb, lengths=lens, norm_running=running, norm_carry=self._carry,
-                               norm_scratch=self._norm_scratch, norm_decay=decay).to(torch.float32)
-                for s in dict.fromkeys(r[0] for r in chunk):         # (enqueued: the other entry is the slot's carry now)
-                    self._slots[s]["norm_parity"] ^= 1
-                for r, f in zip(chunk, fg):                          # (... and it holds this many weighted frames)
-                    self._slots[r[0]]["norm_w"] = f[3]
-            else:
-                y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
-            self.forwards += 1
-            host, off = _stitch_to_host(y, lay, self._stage, self.pcm16, self._h_down, at=off)
+            host, lay, off = self._forward_rows(rows[c0: c0 + self.max_batch], forget[c0: c0 + self.max_batch], seen, off)
             down.append((host, lay))
+        out = self._collect(ids, down)
+        for sid in end:
+            s = self._ids.pop(sid)
+            self._slots[s] = None
+            self._layout.reset(s)
+        return out
+
+    def _append(self, parts, pushed: Sequence[int]) -> None:
+        """The chunks of the streams ``pushed`` (ids, each with at least one frame; ``parts`` as ``check_stream_chunks``
+        returns them) go into the rings: waits until the last upload has left the page-locked twin, shifts the F0 of a
+        stream that has statistics, packs stream j's ppg, f0 and lft (or audio) into slice j, uploads the used slices in
+        one copy and appends them, and synthesises their excitation, in one ``stream_push``.  Reads every stream's
+        ``seen``, ``first`` and ``parity`` and leaves them advanced: ``seen`` by the chunk, the phase record's other entry
+        current.  Traces the chunks' excitation."""
+        from .engine import stream_push
+        hop, C, dev = self.hop, self.channels, self.device
+        if self._up_done is not None:
+            self._up_done.synchronize()                  # (the page-locked twin is still being read by the last upload)
+        h = self._h_up.numpy()
+        entries = []                                     # per stream (slot, n, up_off, pos, first, parity, seed), as stream_push takes them
+        for j, sid in enumerate(pushed):
+            n, ppg, f0, lft = parts[sid]
+            st = self._slots[self._ids[sid]]
+            if st.stats is not None:
+                f0 = F0Statistics().convert(np.asarray(f0, dtype=np.float64), st.stats[0], st.stats[1])
+            o = j * self._slice
+            h[o: o + n * C] = ppg.reshape(-1)
+            h[o + n * C: o + n * C + n] = f0
+            h[o + n * C + n: o + n * (C + 1 + hop)] = lft
+            entries.append((st.slot, n, o, st.seen, st.first, st.parity, st.seed))
+        used = len(pushed) * self._slice
+        self._d_up[:used].copy_(self._h_up[:used], non_blocking=True)
+        self._up_done = torch.cuda.Event()
+        self._up_done.record(torch.cuda.current_stream(dev))
+        sg = self.signal_generator
+        # (with loudness="audio" the chunk's third array is audio: the same copy appends it to the audio ring)
+        stream_push(self._d_up, *zip(*entries), self._ppg, self._audio if self.loudness == "audio" else self._lft, self._exc,
+                    self._phase, self.max_push, float(sg.sample_rate), float(sg.sine_amp), float(sg.noise_amp))
+        for sid in pushed:
+            st = self._slots[self._ids[sid]]
+            n = parts[sid][0]
+            if self._stream_trace is not None:
+                idx = (torch.arange(st.seen, st.seen + n, device=dev) % self.cap)
+                self._stream_trace.setdefault("excitation", {}).setdefault(sid, []).append(
+                    self._exc[st.slot].view(self.cap, hop)[idx].reshape(-1))
+            st.seen += n
+            st.first = False
+            st.parity ^= 1                               # (enqueued: the other entry is the slot's phase now)
+
+    def _finalise_loudness(self, ids: Sequence[int], end: Sequence[int]) -> None:
+        """``loudness="audio"``: the frames of the streams ``ids`` that became final - by their audio's arrival, or by the
+        stream's end (``end``), with or without a chunk - go from the audio ring into the lft ring: two launches for all
+        streams (``stream_loudness``), none when no frame did.  Reads every stream's ``seen``, ``final`` and
+        ``loud_parity`` and leaves ``final`` advanced and the peak record's other entry current.  Traces the frames'
+        loudness."""
+        from .engine import stream_loudness
+        entries = []                                     # per stream (slot, first_frame, n, seen, ended, parity), as stream_loudness takes them
+        for sid in ids:
+            st = self._slots[self._ids[sid]]
+            final = stream_final_frames(st.seen, sid in end, self.hop)
+            if final > st.final:
+                entries.append((st.slot, st.final, final - st.final, st.seen, sid in end, st.loud_parity))
+        if not entries:
+            return
+        stream_loudness(self._audio, self._lft, self._peak, self._loud_scratch, *zip(*entries), self.cap, self.max_push + self.lag,
+                        float(self.signal_generator.sample_rate))
+        for s, f, n, _, _, _ in entries:
+            st = self._slots[s]
+            if self._stream_trace is not None:
+                idx = (torch.arange(f, f + n, device=self.device) % self.cap)
+                self._stream_trace.setdefault("lft", {}).setdefault(st.id, []).append(
+                    self._lft[s].view(self.cap, self.hop)[idx].reshape(-1))
+            st.final = f + n
+            st.loud_parity ^= 1                          # (enqueued: the other entry is the slot's peak now)
+
+    def _forward_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], off: int):
+        """One forward over the rows ``chunk`` (at most ``max_batch``, as ``stream_push_rows`` orders them; ``forget``
+        their entries, or nothing; ``seen`` per slot the frames rows may be cut from): lays out the stitch, cuts the rows
+        from the rings (``stream_assemble``), runs the model - with ``norm="running"`` and an embedding on the slots' carry
+        records, whose other entries are current afterwards and hold the rows' weighted frames (``norm_w``) - and stitches
+        the rows into the page-locked download buffer from element ``off``.  Everything is enqueued, nothing waited for.
+        Returns ``(host, lay, off)``: the buffer's part, the batch's layout and the first element behind it.  Counts the
+        forward and traces its rows and excitation."""
+        from .engine import stream_assemble
+        lay = self._layout.batch(chunk, seen)
+        lens = [r.frames for r in chunk]
+        slots = tuple(r.stream for r in chunk)
+        ppg, lft, sine = stream_assemble(self._ppg, self._lft, self._exc, seen, slots, [r.in_lo for r in chunk], lens, max(lens))
+        if self._stream_trace is not None:
+            self._stream_trace.setdefault("forwards", []).append(
+                ([(self._slots[r.stream].id, r.in_lo, r.in_hi, r.core_lo, r.core_hi) for r in chunk], sine.clone()))
+        emb = None
+        if self._slots[slots[0]].emb:
+            if slots not in self._emb_rows:              # (the steady state repeats one tuple: its index tensor is uploaded once)
+                if len(self._emb_rows) >= 256:
+                    self._emb_rows.clear()
+                self._emb_rows[slots] = torch.as_tensor(slots, dtype=torch.int64, device=self.device)
+            emb = self._emb.index_select(0, self._emb_rows[slots])
+        if emb is not None and self.norm == "running":
+            # window k of a stream: its core starts own_lo frames into the row, core_lo frames of the stream lie in
+            # front of it, window 0 resets the slot's carry; the slot's parity says which entry of its record is current
+            running = (list(slots), [r.own_lo for r in chunk], [r.own_hi for r in chunk], [r.core_lo for r in chunk],
+                       [int(r.k == 0) for r in chunk], [self._slots[s].norm_parity for s in slots])
+            decay = None if self.horizon is None else tuple([f[i] for f in forget] for i in range(3))
+            y = self.model(ppg, sine, lft, emb, lengths=lens, norm_running=running, norm_carry=self._carry,
+                           norm_scratch=self._norm_scratch, norm_decay=decay).to(torch.float32)
+            for s in dict.fromkeys(slots):               # (enqueued: the other entry is the slot's carry now)
+                self._slots[s].norm_parity ^= 1
+            for s, f in zip(slots, forget):              # (... and it holds this many weighted frames)
+                self._slots[s].norm_w = f[3]
+        else:
+            y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
+        self.forwards += 1
+        host, off = _stitch_to_host(y, lay, self._stage, self.pcm16, self._h_down, at=off)
+        return host, lay, off
+
+    def _collect(self, ids: Sequence[int], down) -> Dict[int, np.ndarray]:
+        """Waits for the push's forwards, if any ran (one ``synchronize``), and copies every stream's runs out of their
+        download buffers ``down = [(host, lay), ...]`` -> ``{id: samples}`` for ``ids``, new arrays, empty for a stream
+        none of whose windows ran."""
+        pieces: Dict[int, list] = {self._ids[sid]: [] for sid in ids}
         if down:
-            stream.synchronize()
-            for host, lay in down:
-                h = host.numpy()
-                for (s, t_lo, t_hi), o in zip(lay["runs"], lay["dst_off"]):
-                    pieces[s].append(h[o: o + t_hi - t_lo])
+            torch.cuda.current_stream(self.device).synchronize()
+        for host, lay in down:
+            h = host.numpy()
+            for (s, t_lo, t_hi), o in zip(lay["runs"], lay["dst_off"]):
+                pieces[s].append(h[o: o + t_hi - t_lo])
         dtype = np.int16 if self.pcm16 else np.float32
         out = {}
         for sid in ids:
             ps = pieces[self._ids[sid]]
             out[sid] = np.concatenate(ps) if ps else np.empty(0, dtype=dtype)      # (a copy: never the page-locked buffer)
-        for sid in end:
-            s = self._ids.pop(sid)
-            self._slots[s] = None
-            self._layout.reset(s)
         return out
 
 

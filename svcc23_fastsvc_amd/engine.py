@@ -258,6 +258,30 @@ def load_library():
     return lib
 
 
+def _ptr(t):
+    """A tensor's device address as the library takes it; ``None`` is the null pointer."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _ints(ctype, values):
+    """The ctypes array of ``ctype`` (``c_int32``, ``c_int64``) that holds ``int(v)`` of every value; an array a caller
+    made once, of that type, passes through."""
+    if isinstance(values, ctypes.Array) and values._type_ is ctype:
+        return values
+    return (ctype * len(values))(*[int(v) for v in values])
+
+
+def _gpu_tensors(who: str, like, specs) -> None:
+    """What the wrapper ``who`` asks of its tensors, ``specs = (name, tensor, dtype, dim), ...`` in the order they are
+    checked: each on a GPU (``FastSVCError``: no CPU fallback), then of its dtype and rank, contiguous and on the device
+    of ``like`` (``ValueError``) - a tensor that was checked before, or the first of ``specs``."""
+    for name, t, dtype, dim in specs:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise FastSVCError(f"{who} needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
+        if t.dtype != dtype or not t.is_contiguous() or t.device != like.device or t.dim() != dim:
+            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {like.device}")
+
+
 def gather_padded(rows: Sequence[torch.Tensor], width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Assemble a zero-padded batch from B device tensors of shape (C, len_b) (len_b <= width; float32, unit stride
     along time, any row pitch - views of larger tensors are fine): -> (B, C, width).  One HIP launch per 64
@@ -308,13 +332,11 @@ def gather_time_major(packed: torch.Tensor, offsets: Sequence[int], lens: Sequen
         out = torch.empty((B, C, width), dtype=torch.float32, device=packed.device)
     elif tuple(out.shape) != (B, C, width) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != packed.device:
         raise ValueError(f"out must be a contiguous float32 {(B, C, width)} tensor on {packed.device}")
-    offs = (ctypes.c_int64 * B)(*[int(v) for v in offsets])
-    ls = (ctypes.c_int32 * B)(*[int(v) for v in lens])
+    offs, ls = _ints(ctypes.c_int64, offsets), _ints(ctypes.c_int32, lens)
     with torch.cuda.device(packed.device):
         stream = torch.cuda.current_stream(packed.device).cuda_stream
-        _check(lib, lib.fastsvc_gather_time_major(ctypes.c_void_p(packed.data_ptr()), packed.numel(), offs, ls,
-                                                  ctypes.c_void_p(out.data_ptr()), B, C, width, ctypes.c_void_p(stream)),
-               "fastsvc_gather_time_major")
+        _check(lib, lib.fastsvc_gather_time_major(_ptr(packed), packed.numel(), offs, ls, _ptr(out), B, C, width,
+                                                  ctypes.c_void_p(stream)), "fastsvc_gather_time_major")
     return out
 
 
@@ -342,11 +364,10 @@ def output_check(y: torch.Tensor, lens: Sequence[int], out: Optional[torch.Tenso
         raise ValueError(f"y must be a contiguous float32 (B, width) tensor with one length per row; got {tuple(y.shape)} {y.dtype}")
     B, width = int(y.shape[0]), int(y.shape[1])
     report = torch.empty((B, 4), dtype=torch.int32, device=y.device) if out is None else _report_tensor(out, B, y.device)
-    ls = (ctypes.c_int32 * B)(*[int(v) for v in lens])
+    ls = _ints(ctypes.c_int32, lens)
     with torch.cuda.device(y.device):
         stream = torch.cuda.current_stream(y.device).cuda_stream
-        _check(lib, lib.fastsvc_output_check(ctypes.c_void_p(y.data_ptr()), ls, ctypes.c_void_p(report.data_ptr()),
-                                             B, width, ctypes.c_void_p(stream)), "fastsvc_output_check")
+        _check(lib, lib.fastsvc_output_check(_ptr(y), ls, _ptr(report), B, width, ctypes.c_void_p(stream)), "fastsvc_output_check")
     return report
 
 
@@ -395,17 +416,15 @@ def pcm16_pack(y: torch.Tensor, lens: Sequence[int], offsets: Optional[Sequence[
         if report is not None:
             report.zero_()
         return out
-    offs = (ctypes.c_int64 * B)(*[int(v) for v in offsets])
-    ls = (ctypes.c_int32 * B)(*lens)
+    offs, ls = _ints(ctypes.c_int64, offsets), _ints(ctypes.c_int32, lens)
     with torch.cuda.device(y.device):
         stream = torch.cuda.current_stream(y.device).cuda_stream
         if report is not None:
-            _check(lib, lib.fastsvc_pcm16_pack_checked(ctypes.c_void_p(y.data_ptr()), ls, offs, ctypes.c_void_p(out.data_ptr()),
-                                                       out.numel(), ctypes.c_void_p(report.data_ptr()), B, width,
+            _check(lib, lib.fastsvc_pcm16_pack_checked(_ptr(y), ls, offs, _ptr(out), out.numel(), _ptr(report), B, width,
                                                        ctypes.c_void_p(stream)), "fastsvc_pcm16_pack_checked")
             return out
-        _check(lib, lib.fastsvc_pcm16_pack(ctypes.c_void_p(y.data_ptr()), ls, offs, ctypes.c_void_p(out.data_ptr()),
-                                           out.numel(), B, width, ctypes.c_void_p(stream)), "fastsvc_pcm16_pack")
+        _check(lib, lib.fastsvc_pcm16_pack(_ptr(y), ls, offs, _ptr(out), out.numel(), B, width, ctypes.c_void_p(stream)),
+               "fastsvc_pcm16_pack")
     return out
 
 
@@ -460,15 +479,12 @@ def collate_crops(wave: torch.Tensor, lft: torch.Tensor, ppg: torch.Tensor, f0: 
         else:
             outs.append(t)
     # (a session hands in the ctypes arrays it made once: a corpus has thousands of entries, a batch a few dozen)
-    offs = frame_off if isinstance(frame_off, ctypes.Array) else (ctypes.c_int64 * U)(*[int(v) for v in frame_off])
-    nfr = n_frames if isinstance(n_frames, ctypes.Array) else (ctypes.c_int32 * U)(*[int(v) for v in n_frames])
-    us = (ctypes.c_int32 * B)(*[int(v) for v in utt])
-    st = (ctypes.c_int32 * B)(*[int(v) for v in start])
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    offs, nfr = _ints(ctypes.c_int64, frame_off), _ints(ctypes.c_int32, n_frames)
+    us, st = _ints(ctypes.c_int32, utt), _ints(ctypes.c_int32, start)
     with torch.cuda.device(wave.device):
         stream = torch.cuda.current_stream(wave.device).cuda_stream
-        _check(lib, lib.fastsvc_collate_crops(ptr(wave), ptr(lft), wave.numel(), ptr(ppg), ppg.numel(), ptr(f0), f0.numel(),
-                                              ptr(emb), U, offs, nfr, us, st, *[ptr(t) for t in outs],
+        _check(lib, lib.fastsvc_collate_crops(_ptr(wave), _ptr(lft), wave.numel(), _ptr(ppg), ppg.numel(), _ptr(f0), f0.numel(),
+                                              _ptr(emb), U, offs, nfr, us, st, *[_ptr(t) for t in outs],
                                               B, D, S, hop, frames, ctx, ctypes.c_void_p(stream)), "fastsvc_collate_crops")
     return tuple(outs)
 
@@ -501,12 +517,7 @@ def fanout_assemble(ppg: torch.Tensor, lft: torch.Tensor, f0: torch.Tensor, ppg_
     named += [(n, t, torch.float64, 2) for n, t in (("src_stats", src_stats), ("spk_stats", spk_stats)) if t is not None]
     if spk_emb is not None:
         named.append(("spk_emb", spk_emb, torch.float32, 2))
-    for name, t, dtype, dim in named:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise FastSVCError(f"fanout_assemble needs GPU tensors (no CPU fallback); {name} is on " +
-                               str(getattr(t, "device", type(t))))
-        if t.dtype != dtype or not t.is_contiguous() or t.device != ppg.device or t.dim() != dim:
-            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {ppg.device}")
+    _gpu_tensors("fanout_assemble", ppg, named)
     R, U = len(utt), len(n_frames)
     C, hop, width = int(C), int(hop), int(width)
     if R == 0 or len(spk) != R or U == 0 or len(ppg_off) != U or len(lft_off) != U or len(f0_off) != U:
@@ -539,17 +550,13 @@ def fanout_assemble(ppg: torch.Tensor, lft: torch.Tensor, f0: torch.Tensor, ppg_
         else:
             outs.append(t)
     # (a session hands in the ctypes arrays it made once)
-    i64s = lambda v: v if isinstance(v, ctypes.Array) else (ctypes.c_int64 * U)(*[int(x) for x in v])      # noqa: E731
-    po, lo, fo = i64s(ppg_off), i64s(lft_off), i64s(f0_off)
-    nfr = n_frames if isinstance(n_frames, ctypes.Array) else (ctypes.c_int32 * U)(*[int(v) for v in n_frames])
-    us = (ctypes.c_int32 * R)(*[int(v) for v in utt])
-    ss = (ctypes.c_int32 * R)(*[int(v) for v in spk])
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    po, lo, fo = (_ints(ctypes.c_int64, v) for v in (ppg_off, lft_off, f0_off))
+    nfr, us, ss = (_ints(ctypes.c_int32, v) for v in (n_frames, utt, spk))
     with torch.cuda.device(ppg.device):
         stream = torch.cuda.current_stream(ppg.device).cuda_stream
-        _check(lib, lib.fastsvc_fanout_assemble(ptr(ppg), ppg.numel(), ptr(lft), lft.numel(), ptr(f0), f0.numel(), U,
-                                                po, lo, fo, nfr, ptr(src_stats), ptr(spk_stats), ptr(spk_emb), n_spk, us, ss,
-                                                *[ptr(t) for t in outs], R, C, E, hop, width, ctypes.c_void_p(stream)),
+        _check(lib, lib.fastsvc_fanout_assemble(_ptr(ppg), ppg.numel(), _ptr(lft), lft.numel(), _ptr(f0), f0.numel(), U,
+                                                po, lo, fo, nfr, _ptr(src_stats), _ptr(spk_stats), _ptr(spk_emb), n_spk, us, ss,
+                                                *[_ptr(t) for t in outs], R, C, E, hop, width, ctypes.c_void_p(stream)),
                "fastsvc_fanout_assemble")
     return tuple(outs)
 
@@ -599,14 +606,11 @@ def window_assemble(ppg: torch.Tensor, lft: torch.Tensor, sine: torch.Tensor, pp
             raise ValueError(f"out[{i}] must be a contiguous float32 {shp} tensor on {ppg.device}")
         else:
             outs.append(t)
-    po = (ctypes.c_int64 * R)(*[int(v) for v in ppg_off])
-    so = (ctypes.c_int64 * R)(*[int(v) for v in sig_off])
-    nfr = (ctypes.c_int32 * R)(*[int(v) for v in n_frames])
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    po, so, nfr = _ints(ctypes.c_int64, ppg_off), _ints(ctypes.c_int64, sig_off), _ints(ctypes.c_int32, n_frames)
     with torch.cuda.device(ppg.device):
         stream = torch.cuda.current_stream(ppg.device).cuda_stream
-        _check(lib, lib.fastsvc_window_assemble(ptr(ppg), ppg.numel(), ptr(lft), ptr(sine), lft.numel(), po, so, nfr,
-                                                *[ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
+        _check(lib, lib.fastsvc_window_assemble(_ptr(ppg), ppg.numel(), _ptr(lft), _ptr(sine), lft.numel(), po, so, nfr,
+                                                *[_ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
                "fastsvc_window_assemble")
     return tuple(outs)
 
@@ -658,16 +662,16 @@ def window_stitch(y: torch.Tensor, n_samples: Sequence[int], core_lo: Sequence[i
     if report is not None:
         n_utts = int(report.shape[0]) if isinstance(report, torch.Tensor) and report.dim() == 2 else 0
         _report_tensor(report, n_utts, y.device)
-    i32s = lambda v: (ctypes.c_int32 * B)(*[int(x) for x in v])      # noqa: E731
-    i64s = lambda v: (ctypes.c_int64 * B)(*[int(x) for x in v])      # noqa: E731
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None      # noqa: E731
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    ptr = lambda t: _ptr(t) if t is not None and t.numel() else None      # (an empty tensor goes in as the null pointer)  # noqa: E731
     with torch.cuda.device(y.device):
         stream = torch.cuda.current_stream(y.device).cuda_stream
-        _check(lib, lib.fastsvc_window_stitch(ptr(y), B, int(y.shape[1]), i32s(n_samples), i32s(core_lo), i32s(core_hi), int(half),
-                                              i32s(left_mode), i32s(right_mode), i64s(left_src), i64s(right_src),
-                                              ptr(stage), stage.numel() if stage is not None else 0, i64s(dst_off),
+        _check(lib, lib.fastsvc_window_stitch(ptr(y), B, int(y.shape[1]), _ints(i32, n_samples), _ints(i32, core_lo),
+                                              _ints(i32, core_hi), int(half), _ints(i32, left_mode), _ints(i32, right_mode),
+                                              _ints(i64, left_src), _ints(i64, right_src),
+                                              ptr(stage), stage.numel() if stage is not None else 0, _ints(i64, dst_off),
                                               ptr(out_pcm), ptr(out_float), n_dst,
-                                              i32s(utt) if report is not None else None, ptr(report), n_utts,
+                                              _ints(i32, utt) if report is not None else None, ptr(report), n_utts,
                                               ctypes.c_void_p(stream)), "fastsvc_window_stitch")
 
 
@@ -711,11 +715,7 @@ def stream_push(upload: torch.Tensor, streams: Sequence[int], n: Sequence[int], 
     nothing; fails loudly off the GPU."""
     lib = load_library()
     n_streams, cap, C, hop = _stream_rings("stream_push", ppg_ring, lft_ring, exc_ring)
-    for name, t, dtype, dim in (("upload", upload, torch.float32, 1), ("phase", phase, torch.float64, 2)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise FastSVCError(f"stream_push needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
-        if t.dtype != dtype or not t.is_contiguous() or t.device != ppg_ring.device or t.dim() != dim:
-            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {ppg_ring.device}")
+    _gpu_tensors("stream_push", ppg_ring, (("upload", upload, torch.float32, 1), ("phase", phase, torch.float64, 2)))
     if tuple(phase.shape) != (n_streams, 2):
         raise ValueError(f"phase must be ({n_streams}, 2), got {tuple(phase.shape)}")
     S = len(streams)
@@ -736,15 +736,14 @@ def stream_push(upload: torch.Tensor, streams: Sequence[int], n: Sequence[int], 
             raise ValueError(f"stream {s}: its slice [{o}, +{k * (C + 1 + hop)}) leaves the upload buffer of {upload.numel()} elements")
         if int(pos[i]) < 0:
             raise ValueError(f"stream {s}: position {int(pos[i])} out of range")
-    i32s = lambda v: (ctypes.c_int32 * S)(*[int(x) for x in v])      # noqa: E731
-    i64s = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])      # noqa: E731
-    seeds = (ctypes.c_uint64 * S)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seed])
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    seeds = _ints(ctypes.c_uint64, [int(x) & 0xFFFFFFFFFFFFFFFF for x in seed])
     with torch.cuda.device(ppg_ring.device):
         stream = torch.cuda.current_stream(ppg_ring.device).cuda_stream
-        _check(lib, lib.fastsvc_stream_push(ptr(upload), upload.numel(), S, i32s(streams), i32s(n), i64s(up_off), i64s(pos),
-                                            i32s([1 if v else 0 for v in first]), i32s([int(v) & 1 for v in parity]), seeds,
-                                            ptr(ppg_ring), ptr(lft_ring), ptr(exc_ring), ptr(phase), n_streams, cap, max_push, C, hop,
+        _check(lib, lib.fastsvc_stream_push(_ptr(upload), upload.numel(), S, _ints(i32, streams), _ints(i32, n), _ints(i64, up_off),
+                                            _ints(i64, pos), _ints(i32, [1 if v else 0 for v in first]),
+                                            _ints(i32, [int(v) & 1 for v in parity]), seeds,
+                                            _ptr(ppg_ring), _ptr(lft_ring), _ptr(exc_ring), _ptr(phase), n_streams, cap, max_push, C, hop,
                                             ctypes.c_float(float(sample_rate)), ctypes.c_float(float(sine_amp)),
                                             ctypes.c_float(float(noise_amp)), ctypes.c_void_p(stream)), "fastsvc_stream_push")
 
@@ -787,15 +786,12 @@ def stream_assemble(ppg_ring: torch.Tensor, lft_ring: torch.Tensor, exc_ring: to
             raise ValueError(f"out[{i}] must be a contiguous float32 {shp} tensor on {ppg_ring.device}")
         else:
             outs.append(t)
-    ps = (ctypes.c_int64 * n_streams)(*[int(v) for v in pos])
-    st = (ctypes.c_int32 * R)(*[int(v) for v in streams])
-    ff = (ctypes.c_int64 * R)(*[int(v) for v in first_frame])
-    nfr = (ctypes.c_int32 * R)(*[int(v) for v in n_frames])
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    ps, ff = _ints(ctypes.c_int64, pos), _ints(ctypes.c_int64, first_frame)
+    st, nfr = _ints(ctypes.c_int32, streams), _ints(ctypes.c_int32, n_frames)
     with torch.cuda.device(ppg_ring.device):
         stream = torch.cuda.current_stream(ppg_ring.device).cuda_stream
-        _check(lib, lib.fastsvc_stream_assemble(ptr(ppg_ring), ptr(lft_ring), ptr(exc_ring), n_streams, cap, ps, st, ff, nfr,
-                                                *[ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
+        _check(lib, lib.fastsvc_stream_assemble(_ptr(ppg_ring), _ptr(lft_ring), _ptr(exc_ring), n_streams, cap, ps, st, ff, nfr,
+                                                *[_ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
                "fastsvc_stream_assemble")
     return tuple(outs)
 
@@ -825,12 +821,8 @@ def stream_loudness(audio_ring: torch.Tensor, lft_ring: torch.Tensor, peak: torc
     ``scratch``: ``stream_loudness_scratch_bytes(n_streams, max_frames)`` bytes.  Anything out of range raises
     ``ValueError`` before a launch and changes nothing; fails loudly off the GPU."""
     lib = load_library()
-    for name, t, dtype, dim in (("audio_ring", audio_ring, torch.float32, 2), ("lft_ring", lft_ring, torch.float32, 2),
-                                ("peak", peak, torch.float32, 2), ("scratch", scratch, torch.uint8, 1)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise FastSVCError(f"stream_loudness needs GPU tensors (no CPU fallback); {name} is on " + str(getattr(t, "device", type(t))))
-        if t.dtype != dtype or not t.is_contiguous() or t.device != audio_ring.device or t.dim() != dim:
-            raise ValueError(f"{name} must be a contiguous {dim}-D {dtype} tensor on {audio_ring.device}")
+    _gpu_tensors("stream_loudness", audio_ring, (("audio_ring", audio_ring, torch.float32, 2), ("lft_ring", lft_ring, torch.float32, 2),
+                                                 ("peak", peak, torch.float32, 2), ("scratch", scratch, torch.uint8, 1)))
     n_streams, cap, max_frames = int(audio_ring.shape[0]), int(cap), int(max_frames)
     if cap < 4 or cap % 4 or audio_ring.shape[1] == 0 or audio_ring.shape[1] % cap or lft_ring.shape != audio_ring.shape:
         raise ValueError(f"the rings must both be (n_streams, cap * hop) with cap {cap} a multiple of 4, got "
@@ -845,14 +837,13 @@ def stream_loudness(audio_ring: torch.Tensor, lft_ring: torch.Tensor, peak: torc
     S = len(streams)
     if S == 0 or any(len(v) != S for v in (first_frame, n, seen, ended, parity)):
         raise ValueError("stream_loudness needs at least one stream and one entry per stream in every array")
-    i32s = lambda v: (ctypes.c_int32 * S)(*[int(x) for x in v])      # noqa: E731
-    i64s = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])      # noqa: E731
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
     with torch.cuda.device(audio_ring.device):
         stream = torch.cuda.current_stream(audio_ring.device).cuda_stream
-        _check(lib, lib.fastsvc_stream_loudness(ptr(audio_ring), ptr(lft_ring), ptr(peak), ptr(scratch), S, i32s(streams),
-                                                i64s(first_frame), i32s(n), i64s(seen), i32s([1 if v else 0 for v in ended]),
-                                                i32s([int(v) & 1 for v in parity]), n_streams, cap, max_frames, hop,
+        _check(lib, lib.fastsvc_stream_loudness(_ptr(audio_ring), _ptr(lft_ring), _ptr(peak), _ptr(scratch), S, _ints(i32, streams),
+                                                _ints(i64, first_frame), _ints(i32, n), _ints(i64, seen),
+                                                _ints(i32, [1 if v else 0 for v in ended]),
+                                                _ints(i32, [int(v) & 1 for v in parity]), n_streams, cap, max_frames, hop,
                                                 ctypes.c_float(float(sample_rate)), ctypes.c_void_p(stream)),
                "fastsvc_stream_loudness")
 
@@ -920,11 +911,10 @@ def norm_group_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: in
     dev = u.device
     ints = torch.tensor([group, own_lo, own_hi] + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
     scratch = torch.empty(B * C * (-(-ld // 2048)) * 16, dtype=torch.uint8, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib, lib.fastsvc_norm_group_stats(ptr(u), DTYPE_CODES[u.dtype], B, C, ld, ptr(ints[3]) if lens is not None else None,
-                                                 len_mul, ptr(ints[0]), ptr(ints[1]), ptr(ints[2]), ptr(stats), ptr(scratch),
+        _check(lib, lib.fastsvc_norm_group_stats(_ptr(u), DTYPE_CODES[u.dtype], B, C, ld, _ptr(ints[3]) if lens is not None else None,
+                                                 len_mul, _ptr(ints[0]), _ptr(ints[1]), _ptr(ints[2]), _ptr(stats), _ptr(scratch),
                                                  scratch.numel(), ctypes.c_void_p(stream)), "fastsvc_norm_group_stats")
     return stats
 
@@ -1023,8 +1013,7 @@ def norm_running_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: 
     dev = u.device
     ints = torch.tensor(list(arrays) + ([[int(v) for v in lens]] if lens is not None else []), dtype=torch.int32).to(dev)
     scratch = torch.empty(B * C * (-(-ld // 2048)) * 32, dtype=torch.uint8, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
-    lens_ptr = ptr(ints[6]) if lens is not None else None
+    lens_ptr = _ptr(ints[6]) if lens is not None else None
     name, dbl = "fastsvc_norm_running_stats", []
     if decay is not None:
         if len(decay) != 3:
@@ -1032,8 +1021,8 @@ def norm_running_stats(u: torch.Tensor, lens: Optional[Sequence[int]], len_mul: 
         name, dbl = name + "_decay", torch.tensor(check_norm_decay(*decay, arrays, lens_host), dtype=torch.float64).to(dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib, getattr(lib, name)(ptr(u), DTYPE_CODES[u.dtype], B, C, ld, lens_ptr, len_mul, *[ptr(ints[i]) for i in range(6)],
-                                       *[ptr(d) for d in dbl], ptr(carry), ptr(stats), ptr(scratch), scratch.numel(),
+        _check(lib, getattr(lib, name)(_ptr(u), DTYPE_CODES[u.dtype], B, C, ld, lens_ptr, len_mul, *[_ptr(ints[i]) for i in range(6)],
+                                       *[_ptr(d) for d in dbl], _ptr(carry), _ptr(stats), _ptr(scratch), scratch.numel(),
                                        ctypes.c_void_p(stream)), name)
     return stats
 
@@ -1488,11 +1477,10 @@ class Plan:
         elif out.dtype != torch.float32 or tuple(out.shape) != (B, cfg.out_channels, T) or out.device != dev or \
                 not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 {(B, cfg.out_channels, T)} tensor on {dev}")
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())      # noqa: E731
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            tensors = (self._h, ptr(blob), ptr(ppg), ptr(sine), ptr(lft), ptr(spk_emb), ptr(out), B, F)
-            lens_p, ws = ptr(lens_dev), (ptr(workspace), workspace.numel())
+            tensors = (self._h, _ptr(blob), _ptr(ppg), _ptr(sine), _ptr(lft), _ptr(spk_emb), _ptr(out), B, F)
+            lens_p, ws = _ptr(lens_dev), (_ptr(workspace), workspace.numel())
             if autotune:
                 ntr = ctypes.c_int32(0)
                 rc = self.lib.fastsvc_autotune(*tensors, *ws, stream, ctypes.byref(ntr))
@@ -1502,7 +1490,7 @@ class Plan:
                 need = self.norm_group_scratch_bytes(B, F) if grouped else self.norm_running_scratch_bytes(B, F)
                 if norm_scratch is None or norm_scratch.numel() * norm_scratch.element_size() < need or norm_scratch.device != dev:
                     norm_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-                scratch = (ptr(norm_scratch), norm_scratch.numel() * norm_scratch.element_size())
+                scratch = (_ptr(norm_scratch), norm_scratch.numel() * norm_scratch.element_size())
                 if override.decay is None:               # 3 (grouped) or 6 (running) arrays of B ints in one upload ...
                     host = torch.tensor(override.rows, dtype=torch.int32).reshape(-1)
                 else:                                    # (... the doubles behind the 6 B ints - an even count, so 8-byte aligned)
@@ -1515,7 +1503,7 @@ class Plan:
                 if grouped:
                     rc = self.lib.fastsvc_forward_grouped(*tensors, lens_p, *rows_p, *ws, *scratch, stream)
                 else:
-                    carry = (ptr(norm_carry), norm_carry.shape[1] * norm_carry.element_size())
+                    carry = (_ptr(norm_carry), norm_carry.shape[1] * norm_carry.element_size())
                     if override.decay is None:
                         rc = self.lib.fastsvc_forward_running(*tensors, lens_p, *rows_p, *carry, *ws, *scratch, stream)
                     else:

@@ -336,11 +336,11 @@ def test_a_refused_push_leaves_frames_carry_and_parity_alone(dev, world):
         out, at, seen_w = [], 0, []
         for i, k in enumerate(SCHEDULE[0]):
             carry = s._carry.clone().view(torch.int64)
-            state = [(st["norm_parity"], st["norm_w"]) for st in s._slots]
+            state = [(st.norm_parity, st.norm_w) for st in s._slots]
             for chunks, end in (bad[i % len(bad)], bad[(i + 2) % len(bad)]):
                 with pytest.raises(ValueError):
                     s.push(chunks, end)
-            assert torch.equal(s._carry.view(torch.int64), carry) and [(st["norm_parity"], st["norm_w"]) for st in s._slots] == state
+            assert torch.equal(s._carry.view(torch.int64), carry) and [(st.norm_parity, st.norm_w) for st in s._slots] == state
             seen_w.append(state[1][1])
             out.append(s.push({a: _chunk(feat, at, k, hop)}, end=[a] if i == len(SCHEDULE[0]) - 1 else ())[a])
             at += k

@@ -325,11 +325,11 @@ def test_a_refused_push_leaves_carry_and_parity_alone(dev, world):
         out, at = [], 0
         for i, k in enumerate(SCHEDULE[0]):
             carry = s._carry.clone().view(torch.int64)
-            parity = [st["norm_parity"] for st in s._slots]
+            parity = [st.norm_parity for st in s._slots]
             for chunks, end in (bad[i % len(bad)], bad[(i + 2) % len(bad)]):
                 with pytest.raises(ValueError):
                     s.push(chunks, end)
-            assert torch.equal(s._carry.view(torch.int64), carry) and [st["norm_parity"] for st in s._slots] == parity
+            assert torch.equal(s._carry.view(torch.int64), carry) and [st.norm_parity for st in s._slots] == parity
             out.append(s.push({a: _chunk(feat, at, k, hop)}, end=[a] if i == len(SCHEDULE[0]) - 1 else ())[a])
             at += k
         assert parity[0] == 0                            # (the idle stream never ran)
