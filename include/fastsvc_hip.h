@@ -424,7 +424,8 @@ typedef struct fastsvc_row_report {
     int32_t nonfinite;   /* NaN / +-inf among the row's first lens[b] samples */
     int32_t clipped;     /* finite samples whose PCM-16 value saturates: rint(double(y) * 32767.0) outside [-32768, 32767] */
     float   max_abs;     /* largest |y| over the row's finite samples, 0 when there is none (exact: a maximum, not a sum) */
-    int32_t reserved;    /* written as 0 */
+    int32_t reserved;    /* written as 0 by every entry point but fastsvc_stream_check, which counts the non-finite doubles
+                            of the row's InstanceNorm carry entry here */
 } fastsvc_row_report;
 
 /* Checked PCM-16 packing: writes into dst exactly the bytes the unchecked packing writes, and touches exactly the same
@@ -623,6 +624,38 @@ int fastsvc_stream_assemble(const float* ppg_ring, const float* lft_ring, const 
                             const int64_t* pos, const int32_t* stream, const int64_t* first_frame, const int32_t* n_frames,
                             float* ppg_out, float* lft_out, float* sine_out,
                             int32_t R, int32_t C, int32_t hop, int32_t width, void* stream_);
+
+/* Per-window output check of live streams (csrc/fastsvc_stream_check.hip; decode.StreamSession(checked=True)).  A window
+ * row of a stream's forward is judged on the samples it CONTRIBUTES, not on its whole length: report[r] describes
+ * y[r, span_lo[r] : span_hi[r]) of y (B, width), device float32 - the caller passes the row's emitted run together with the
+ * fade zones it stages or that a neighbour row reads (decode.stream_check_spans), so that an overflow confined to context
+ * that is never emitted (no InstanceNorm without a speaker embedding) is not reported.  nonfinite, clipped and max_abs
+ * follow fastsvc_output_check's rules exactly (one shared definition per sample): the report equals that of the span as a
+ * row of its own, bit for bit.  Any 0 <= span_lo <= span_hi <= width works; the span's first byte need not be aligned
+ * (16-byte loads over the aligned body, element loads for head and tail), and no sample outside [span_lo, span_hi) is read
+ * into the report.
+ *
+ * The fourth word (`reserved`) receives the number of non-finite doubles in the running InstanceNorm carry entry the
+ * forward just wrote for the row's stream: the entry_doubles doubles at
+ *     (char*) carry + slot[r] * carry_bytes + entry[r] * entry_doubles * 8
+ * (fastsvc_plan_norm_running's records: two entries per slot, carry_bytes >= 2 * entry_doubles * 8 per slot).  Only that
+ * entry is read - the other entry and other slots' records are legitimately uninitialised.  entry[r] == -1: no carry, the
+ * word is 0 and nothing is read; `slot` and `entry` may both be NULL (every row without a carry) and `carry` may be NULL
+ * when no entry is >= 0.  A non-finite carry implies a non-finite row by reasoning (inf sums give a NaN variance); the
+ * word makes that a checked invariant.
+ *
+ * `report` is a DEVICE array of B entries that every call OVERWRITES with plain stores: one workgroup per row reduces in
+ * registers (wave shuffles) and LDS and its first lane stores the 16 bytes - no atomics, no memset, and two calls give the
+ * same bits.  span_lo, span_hi, slot, entry are HOST arrays of B entries, read during the call (their values travel in the
+ * kernel arguments).  Everything is checked on the host BEFORE anything is enqueued: null y or report, B < 1, width < 1,
+ * span_lo > span_hi, span_hi > width, a negative value, entry outside {-1, 0, 1}, an entry >= 0 with a null or misaligned
+ * carry or a null slot, slot outside [0, n_slots), entry_doubles < 1 or carry_bytes < 2 * entry_doubles * 8 or not a
+ * multiple of 8 with an entry >= 0 - FASTSVC_E_INVALID with the row and the reason in fastsvc_last_error(), and nothing is
+ * written; a failed launch is FASTSVC_E_HIP.  One launch per 64 rows (row r's report at report + r), asynchronous on
+ * `stream_`. */
+int fastsvc_stream_check(const float* y, int32_t B, int32_t width, const int32_t* span_lo, const int32_t* span_hi,
+                         const void* carry, int64_t carry_bytes, int32_t entry_doubles, int32_t n_slots,
+                         const int32_t* slot, const int32_t* entry, fastsvc_row_report* report, void* stream_);
 
 /* Loudness of live streams from their raw audio (csrc/fastsvc_stream_loudness.hip; decode.StreamSession(loudness="audio")).
  * The stream's audio is appended to an AUDIO ring, (n_streams, cap * hop) float32 with sample p at index p % (cap * hop) -

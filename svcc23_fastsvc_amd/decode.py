@@ -23,7 +23,9 @@ than one forward takes, in buffers sized by the window.  ``--stream PUSH[,CORE[,
 dumps as N concurrent simulated LIVE streams, PUSH frames per call (``StreamSession``: features arrive chunk by chunk,
 samples come back as soon as their window has its context); ``--stream-norm running`` normalises every window by the
 statistics of all frames its stream has delivered so far, carried on the GPU, instead of by the window's own, and
-``--stream-horizon FRAMES`` forgets those statistics exponentially.
+``--stream-horizon FRAMES`` forgets those statistics exponentially; ``--checked``, ``--fallback`` and ``--storage auto`` work
+on streams too: every window is checked, and re-run in a fallback storage, before its samples or its running statistics
+are used (``StreamSession(checked=True)``).
 """
 from __future__ import annotations
 
@@ -792,6 +794,7 @@ class _Stream:
     done: int = 0                    # windows that ran
     norm_parity: int = 0             # norm="running": the carry record's current entry (flips with every forward)
     norm_w: float = 0.0              # ... and the weighted frames it holds (``running_horizon_rows``' w)
+    totals: Optional[dict] = None    # a checked session: what its windows' reports add up to since ``open``
 
     @property
     def complete(self) -> int:
@@ -867,6 +870,32 @@ def stream_push_rows(streams: Sequence[_Stream], ended, core: int, context: int,
                 w = d * w + (hi - lo) if lo else float(hi)       # (``running_horizon_rows``' w, after every window)
                 forget.append((d, wt, bd, w))
     return rows, forget
+
+
+def stream_check_spans(rows: Sequence[StreamRow], hop: int, half: int) -> Tuple[List[int], List[int]]:
+    """The samples every window row of a stream forward CONTRIBUTES, ``(lo, hi)`` per row, in samples of the row - what a
+    checked ``StreamSession`` judges a row on (``engine.stream_check``): the run it emits, the fade zone it stages for the
+    stream's next window and the zone a neighbour row blends from it, and nothing else.  With ``half`` the half zone in
+    samples (``fade * hop // 2``), window k of a stream contributes
+
+        lo = max(0, own_lo hop - (half if k > 0 else 0)),    hi = min(frames hop, own_hi hop + (0 if last else half))
+
+    - its core, grown by half a zone on every side that has a neighbour, clipped to the row (a stream may end inside a
+    zone).  A non-finite sample of a row reaches ``stitch_windows``' result exactly when it lies in the row's span; the
+    context outside it is read by the forward alone."""
+    hop, half = int(hop), int(half)
+    lo = [max(0, r.own_lo * hop - (half if r.k > 0 else 0)) for r in rows]
+    hi = [min(r.frames * hop, r.own_hi * hop + (0 if r.last else half)) for r in rows]
+    return lo, hi
+
+
+def stream_rerun_rows(rows: Sequence[StreamRow], flagged) -> List[int]:
+    """The rows of one stream forward a checked ``StreamSession`` runs again when the rows ``flagged`` (indices into
+    ``rows``) are not finite: every row, in the forward's order, of every stream that has a flagged row.  A stream's windows
+    of one forward chain through its carry record - the entry the forward leaves behind holds all of them - so they go
+    together; rows of other streams never do: their carry must stay the one their delivered samples came from."""
+    hit = {rows[int(i)].stream for i in flagged}
+    return [j for j, r in enumerate(rows) if r.stream in hit]
 
 
 def write_wav(path: str, y, sample_rate: int) -> None:
@@ -1775,7 +1804,8 @@ class StreamSession:
     starts it), plus one scratch for the power rows of the ``max_push + lag`` frames a push can finalise per stream.  A
     ``push`` is a driver over named steps, whose docstrings say what each launches: ``check_stream_chunks``, ``_append``
     (one upload, one ``stream_push``), with ``loudness="audio"`` ``_finalise_loudness`` (two ``stream_loudness`` launches, or
-    none), ``stream_push_rows`` and, per ``max_batch`` ready rows, ``_forward_rows``; ``_collect`` waits once.  A push that
+    none), ``stream_push_rows`` and, per ``max_batch`` ready rows, ``_forward_rows`` (``_run_rows``, a checked session's
+    ``_check_rows``, ``_advance_carry``, the stitch); ``_collect`` waits once.  A push that
     completes no window runs no forward (``forwards`` counts them).
 
     Excitation: the phase is carried from push to push in float64 and equals the whole-utterance scan bit for bit, so
@@ -1792,14 +1822,38 @@ class StreamSession:
     that delivers frame ``(t // core + 1) core + context - 1 + lag``, ``core + context + lag`` typical, ``2 core + context
     + lag`` worst.
 
+    ``checked=True`` is ``DecodeSession``'s safety net for streams, which makes float16 activation storage usable live: every
+    forward is judged before anything consumes it.  A stream needs that more than a file does.  With ``norm="running"`` a
+    window that overflows the storage writes inf / NaN sums into the stream's carry record, every later window reads them,
+    and the stream stays non-finite until it ends, with or without a horizon (``decay * inf`` is inf) - PCM-16 hides it, a
+    NaN becomes 0 - and with any ``norm`` the fade zone a poisoned window stages leaks into the next push.  So after the
+    model and before the stitch and the carry's flip, one launch (``engine.stream_check``, csrc/fastsvc_stream_check.hip)
+    reports every row on the samples it contributes (``stream_check_spans``: context that is never emitted costs nothing)
+    and counts the non-finite doubles of the carry entry the forward just wrote; the 16 bytes a row come down into
+    page-locked memory and are waited for - the one synchronisation a checked forward adds (``_check_rows``).  A row with
+    non-finite samples or carry is flagged, and all rows of its stream in that forward (``stream_rerun_rows``) run again in
+    the next storage of ``fallback`` (names of ``STORAGE_CODES``, or one name; plans are built at construction): cut from
+    the same rings, with the same parities and decays, so the re-run overwrites exactly those streams' carry entries,
+    and copied over their rows on the device.  Rows of other streams are never run again and keep the bits of an unchecked
+    session.  The decision is per forward, not per push: a stream's second forward of a push stages into the slot its
+    first one read.  ``last_report`` is ``{id: [dict(window, storage, tried, nonfinite, clipped, max_abs,
+    carry_nonfinite), ...]}`` for the windows that ran in the last push (empty lists included), the numbers those of the
+    run whose samples were returned; ``totals(id)`` adds them up since ``open``, and the totals of a stream that ends are
+    in that push's ``last_report["totals"][id]``.  There is no ``strict``: when the fallbacks are exhausted the samples are
+    returned as they are and the report says so - ``nonfinite > 0`` and ``tried`` lists every storage, the last one
+    included - because a live loop should not lose a push to an exception; a stream whose carry is still non-finite then
+    STAYS non-finite.  ``fallback=()`` only reports.  The model is back in its first storage after every push, also when
+    one raises.  ``checked=False`` (the default): no launch, wait, allocation or plan more than before.
+
     ``push`` validates everything before it uploads or enqueues anything: a ``ValueError`` leaves the session as it
-    was.  Not thread-safe.  ``out_channels`` must be 1 and the signal generator's only signal "sine".  Not built: checked /
-    fallback reports, graph capture of the per-push chain, several GPUs; for ``loudness="audio"`` a preset peak for
+    was, ``last_report`` included.  Not thread-safe.  ``out_channels`` must be 1 and the signal generator's only signal
+    "sine".  Not built: graph capture of the per-push chain, several GPUs; for ``loudness="audio"`` a preset peak for
     calibration, a forgetting horizon for the maximum, ppg and f0 from audio."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
                  fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
-                 horizon: Optional[float] = None, loudness: str = "given"):
+                 horizon: Optional[float] = None, loudness: str = "given", checked: bool = False,
+                 fallback: Sequence[str] = ("bfloat16",)):
         from .engine import FastSVCError
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
@@ -1814,16 +1868,22 @@ class StreamSession:
             raise ValueError("StreamSession needs a signal generator whose only signal type is \"sine\"")
         self.hop = int(signal_generator.hop_size)
         for name, value in self._check_args(cfg, self.hop, n_streams, core, context, fade, max_push, max_batch, norm, horizon,
-                                            loudness).items():
+                                            loudness, checked, fallback).items():
             setattr(self, name, value)
+        if self.checked and self.fallback and not hasattr(model, "use_activation_storage"):
+            raise ValueError("a checked session with fallback storages needs a model with use_activation_storage() "
+                             "(FastSVCGenerator); pass fallback=() to report only")
         self.pcm16 = bool(pcm16)
         self._allocate(cfg)
+        # a checked session: what the last push's windows reported, {id: [dict per window that ran]} (+ "totals")
+        self.last_report: Optional[Dict[object, object]] = None
         self._slots: List[Optional[_Stream]] = [None] * self.n_streams        # per slot: the open stream's record
         self._ids: Dict[int, int] = {}                                       # open id -> slot
         self._next_id = 0
         self.forwards = 0
         # set to a dict to have push leave what it made there (tests): "excitation", per stream id the device tensors of
-        # its chunks' excitation in order, "forwards", per forward (its rows, the assembled excitation rows), and with
+        # its chunks' excitation in order, "forwards", per forward (its rows, the assembled excitation rows), "y", per
+        # forward (its rows, a clone of the waveforms that were stitched - after a checked session's fallbacks), and with
         # loudness="audio" "lft", per stream id the device tensors of its newly final frames' loudness in order
         self._stream_trace: Optional[Dict[str, object]] = None
         self._closed = False
@@ -1831,13 +1891,18 @@ class StreamSession:
     @staticmethod
     def _check_args(cfg, hop: int, n_streams: int = 1, core: int = 32, context: Optional[int] = None, fade: int = 8,
                     max_push: Optional[int] = None, max_batch: int = 32, norm: str = "window", horizon: Optional[float] = None,
-                    loudness: str = "given") -> Dict[str, object]:
+                    loudness: str = "given", checked: bool = False, fallback: Sequence[str] = ("bfloat16",)) -> Dict[str, object]:
         """The constructor's arguments against the generator configuration ``cfg`` and the signal generator's ``hop``, with
         no device: a ``ValueError`` for the first one that is refused, else the session's attributes they resolve to -
-        the arguments as given or defaulted, ``channels``, ``lag``, the rings' ``cap``, the floats ``_slice`` a stream takes
+        the arguments as given or defaulted (``fallback`` a tuple of storage names; a string is one name), ``channels``,
+        ``lag``, the rings' ``cap``, the floats ``_slice`` a stream takes
         of the upload buffer (16-byte aligned) and ``_down_elems``, the samples of the download buffer (a push returns at
         most the frames a ring holds per stream, every row's run padded to 8 samples)."""
-        from .engine import STREAM_MAX_PUSH
+        from .engine import STORAGE_CODES, STREAM_MAX_PUSH
+        fallback = (fallback,) if isinstance(fallback, str) else tuple(fallback)
+        for name in fallback:
+            if name not in STORAGE_CODES:
+                raise ValueError(f"fallback storage must be one of {sorted(STORAGE_CODES)}, got {name!r}")
         core = int(core)
         context = -(-receptive_field_frames(cfg) // 4) * 4 if context is None else int(context)
         fade = int(fade)
@@ -1864,6 +1929,7 @@ class StreamSession:
         C = int(cfg.in_channels)
         return dict(core=core, context=context, fade=fade, max_push=max_push, n_streams=n_streams, max_batch=max_batch,
                     channels=C, _takes_emb=takes_emb, norm=norm, horizon=horizon, loudness=loudness, lag=lag, cap=cap,
+                    checked=bool(checked), fallback=fallback,
                     _slice=-(-max_push * (C + 1 + hop) // 4) * 4, _down_elems=n_streams * (cap * hop + 8 * (cap // core + 2)))
 
     def _allocate(self, cfg) -> None:
@@ -1891,13 +1957,37 @@ class StreamSession:
         self._h_down = _PinnedSet()
         self._h_down.get("w", (self._down_elems,))
         self._up_done: Optional[torch.cuda.Event] = None
-        self._carry = self._norm_scratch = None
+        self._carry = self._norm_scratch = self._report = self._h_report = None
+        plans = self._fallback_plans() if self.checked else None
         if norm == "running":
-            plan = self.model.plan
+            plans = plans or [self.model.plan]
+            plan = plans[0]
+            if any(p.norm_carry_bytes() != plan.norm_carry_bytes() for p in plans):
+                raise ValueError("the fallback storages' plans carry records of another size than the model's own")
             self._carry = torch.empty((n, plan.norm_carry_bytes() // 8), dtype=torch.float64, device=dev)
-            frames = plan.padded_frames(self.core + 2 * self.context)
-            self._norm_scratch = torch.empty(max(plan.norm_running_scratch_bytes(self.max_batch, frames), 1), dtype=torch.uint8, device=dev)
+            scratch = max(p.norm_running_scratch_bytes(self.max_batch, p.padded_frames(self.core + 2 * self.context)) for p in plans)
+            self._norm_scratch = torch.empty(max(scratch, 1), dtype=torch.uint8, device=dev)
+        if self.checked:
+            # one forward's row reports on the device and their page-locked twin (16 bytes a row)
+            self._report = torch.empty((self.max_batch, 4), dtype=torch.int32, device=dev)
+            self._h_report = torch.empty((self.max_batch, 4), dtype=torch.int32, pin_memory=True)
         self._emb_rows: Dict[tuple, torch.Tensor] = {}                       # row slots of a forward -> their index tensor
+
+    def _fallback_plans(self) -> list:
+        """A checked session: the model's own plan and that of every fallback storage, each built once here
+        (``use_activation_storage`` keeps a plan per storage) so that the first fallback of a live stream builds nothing.
+        The model is back in its first storage afterwards."""
+        model = self.model
+        plans = [model.plan]
+        first = getattr(model, "activation_storage", "float32")
+        try:
+            for name in self.fallback:
+                model.use_activation_storage(name)
+                plans.append(model.plan)
+        finally:
+            if getattr(model, "activation_storage", first) != first:
+                model.use_activation_storage(first)
+        return plans
 
     latency_frames = property(lambda self: self.core + self.context + self.lag,
                               doc="the typical delay, in frames of input: core + context (+ the loudness lag with loudness=\"audio\")")
@@ -1917,6 +2007,7 @@ class StreamSession:
         self._closed = True
         torch.cuda.current_stream(self.device).synchronize()
         self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = self._carry = self._norm_scratch = None
+        self._report = self._h_report = None
         self._audio = self._peak = self._loud_scratch = None
         self._h_up = self._d_up = self._h_down = self._up_done = None
         self._slots, self._ids = [None] * self.n_streams, {}
@@ -1949,6 +2040,8 @@ class StreamSession:
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
         self._slots[s] = _Stream(id=sid, slot=s, emb=has_emb, seed=key, from_audio=self.loudness == "audio",
                                  stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
+        if self.checked:
+            self._slots[s].totals = dict(windows=0, fell_back=0, nonfinite=0, clipped=0, max_abs=0.0, storages={})
         self._ids[sid] = s
         self._layout.reset(s)
         return sid
@@ -1996,10 +2089,15 @@ class StreamSession:
             if r.in_lo < self._slots[r.stream].seen - self.cap:
                 raise RuntimeError(f"stream slot {r.stream}: frame {r.in_lo} has left the ring of {self.cap} frames")
         down, off = [], 0
+        report = {sid: [] for sid in ids} if self.checked else None
         for c0 in range(0, len(rows), self.max_batch):
-            host, lay, off = self._forward_rows(rows[c0: c0 + self.max_batch], forget[c0: c0 + self.max_batch], seen, off)
+            host, lay, off = self._forward_rows(rows[c0: c0 + self.max_batch], forget[c0: c0 + self.max_batch], seen, off, report)
             down.append((host, lay))
         out = self._collect(ids, down)
+        if self.checked:
+            if end:                                      # (a stream that ends leaves its totals here: its slot is freed below)
+                report["totals"] = {sid: self.totals(sid) for sid in end}
+            self.last_report = report
         for sid in end:
             s = self._ids.pop(sid)
             self._slots[s] = None
@@ -2074,20 +2172,40 @@ class StreamSession:
             st.final = f + n
             st.loud_parity ^= 1                          # (enqueued: the other entry is the slot's peak now)
 
-    def _forward_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], off: int):
+    def _forward_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], off: int, report=None):
         """One forward over the rows ``chunk`` (at most ``max_batch``, as ``stream_push_rows`` orders them; ``forget``
         their entries, or nothing; ``seen`` per slot the frames rows may be cut from): lays out the stitch, cuts the rows
-        from the rings (``stream_assemble``), runs the model - with ``norm="running"`` and an embedding on the slots' carry
-        records, whose other entries are current afterwards and hold the rows' weighted frames (``norm_w``) - and stitches
-        the rows into the page-locked download buffer from element ``off``.  Everything is enqueued, nothing waited for.
-        Returns ``(host, lay, off)``: the buffer's part, the batch's layout and the first element behind it.  Counts the
-        forward and traces its rows and excitation."""
-        from .engine import stream_assemble
+        from the rings and runs the model (``_run_rows``), a checked session then decides about every row before anything
+        consumes it (``_check_rows``, which appends the rows' dicts to ``report``), the slots' carry records are made
+        current (``_advance_carry``), and the rows are stitched into the page-locked download buffer from element ``off``.
+        Without ``checked`` everything is enqueued and nothing waited for.  Returns ``(host, lay, off)``: the buffer's
+        part, the batch's layout and the first element behind it.  Traces ``"y"``: the rows and a clone of the final ``y``."""
         lay = self._layout.batch(chunk, seen)
+        y = self._run_rows(chunk, forget, seen, trace=True)
+        if self.checked:
+            self._check_rows(chunk, forget, seen, y, report)
+        if self._stream_trace is not None:
+            self._stream_trace.setdefault("y", []).append(
+                ([(self._slots[r.stream].id, r.in_lo, r.in_hi, r.core_lo, r.core_hi) for r in chunk], y.clone()))
+        self._advance_carry(chunk, forget)
+        host, off = _stitch_to_host(y, lay, self._stage, self.pcm16, self._h_down, at=off)
+        return host, lay, off
+
+    def _carries(self, chunk: Sequence[StreamRow]) -> bool:
+        """Whether the rows' streams carry running InstanceNorm sums (they all have an embedding, or none has)."""
+        return self.norm == "running" and self._slots[chunk[0].stream].emb
+
+    def _run_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], trace: bool):
+        """Cuts the rows ``chunk`` from the rings (``stream_assemble``) and runs the model in its current storage ->
+        ``y`` (rows, 1, samples) float32.  With ``norm="running"`` and an embedding the forward reads entry
+        ``norm_parity`` of the slots' carry records and writes the other one; the parities are NOT flipped here, so the
+        same rows run again - a fallback - read the same sums and simply overwrite what the first run wrote.  Counts the
+        forward and, with ``trace``, traces its rows and excitation."""
+        from .engine import stream_assemble
         lens = [r.frames for r in chunk]
         slots = tuple(r.stream for r in chunk)
         ppg, lft, sine = stream_assemble(self._ppg, self._lft, self._exc, seen, slots, [r.in_lo for r in chunk], lens, max(lens))
-        if self._stream_trace is not None:
+        if trace and self._stream_trace is not None:
             self._stream_trace.setdefault("forwards", []).append(
                 ([(self._slots[r.stream].id, r.in_lo, r.in_hi, r.core_lo, r.core_hi) for r in chunk], sine.clone()))
         emb = None
@@ -2097,7 +2215,7 @@ class StreamSession:
                     self._emb_rows.clear()
                 self._emb_rows[slots] = torch.as_tensor(slots, dtype=torch.int64, device=self.device)
             emb = self._emb.index_select(0, self._emb_rows[slots])
-        if emb is not None and self.norm == "running":
+        if self._carries(chunk):
             # window k of a stream: its core starts own_lo frames into the row, core_lo frames of the stream lie in
             # front of it, window 0 resets the slot's carry; the slot's parity says which entry of its record is current
             running = (list(slots), [r.own_lo for r in chunk], [r.own_hi for r in chunk], [r.core_lo for r in chunk],
@@ -2105,15 +2223,94 @@ class StreamSession:
             decay = None if self.horizon is None else tuple([f[i] for f in forget] for i in range(3))
             y = self.model(ppg, sine, lft, emb, lengths=lens, norm_running=running, norm_carry=self._carry,
                            norm_scratch=self._norm_scratch, norm_decay=decay).to(torch.float32)
-            for s in dict.fromkeys(slots):               # (enqueued: the other entry is the slot's carry now)
-                self._slots[s].norm_parity ^= 1
-            for s, f in zip(slots, forget):              # (... and it holds this many weighted frames)
-                self._slots[s].norm_w = f[3]
         else:
             y = self.model(ppg, sine, lft, emb, lengths=lens).to(torch.float32)
         self.forwards += 1
-        host, off = _stitch_to_host(y, lay, self._stage, self.pcm16, self._h_down, at=off)
-        return host, lay, off
+        return y
+
+    def _advance_carry(self, chunk: Sequence[StreamRow], forget) -> None:
+        """The forward over ``chunk`` is enqueued and its samples are the ones that will be delivered: with
+        ``norm="running"`` and an embedding the other entry of every slot's carry record is the current one now, and it
+        holds the rows' weighted frames (``norm_w``).  Host state only."""
+        if not self._carries(chunk):
+            return
+        slots = [r.stream for r in chunk]
+        for s in dict.fromkeys(slots):                   # (enqueued: the other entry is the slot's carry now)
+            self._slots[s].norm_parity ^= 1
+        for s, f in zip(slots, forget):                  # (... and it holds this many weighted frames)
+            self._slots[s].norm_w = f[3]
+
+    def _check_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], y: torch.Tensor, report) -> None:
+        """A checked session's decision about one forward, between the model and everything that consumes ``y`` - the
+        stitch, which stages a fade zone for the next push, and the carry record's flip.  ``stream_check`` reports every
+        row on the span it contributes (``stream_check_spans``) and, with a carry, on the entry the forward just wrote;
+        the report (16 bytes a row) comes down into page-locked memory and is WAITED for: the one synchronisation a
+        checked forward adds.  A row is flagged by non-finite samples or a non-finite carry; every row of a flagged
+        row's stream (``stream_rerun_rows``) runs again in the next storage of ``fallback`` (``storage_fallback``) - the
+        same rows cut from the same rings, the same parities and decays, so the re-run overwrites exactly those streams'
+        carry entries - is checked again and copied over its rows of ``y`` on the device.  Rows of streams that were
+        not flagged are never run again.  Appends every row's dict to ``report[id]`` and adds it to the stream's totals."""
+        from .engine import stream_check
+        lo, hi = stream_check_spans(chunk, self.hop, self._layout.half)
+        carried = self._carries(chunk)
+        rep = np.zeros((len(chunk), 4), dtype=np.int32)
+        again: List[int] = []                            # the rows to run again, by the latest reports
+
+        def check(idx, yy) -> None:
+            """Rows ``idx`` of the chunk, whose waveforms are the rows of ``yy``: their reports into ``rep``."""
+            n, kw = len(idx), {}
+            if carried:
+                kw = dict(carry=self._carry, slots=[chunk[j].stream for j in idx], entry_doubles=self._carry.shape[1] // 2,
+                          entries=[self._slots[chunk[j].stream].norm_parity ^ 1 for j in idx])
+            stream_check(yy, [lo[j] for j in idx], [hi[j] for j in idx], out=self._report[:n], **kw)
+            self._h_report[:n].copy_(self._report[:n], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            rep[idx] = self._h_report[:n].numpy()
+            bad = np.nonzero((rep[:, 0] > 0) | (rep[:, 3] > 0))[0]
+            again[:] = stream_rerun_rows(chunk, bad) if bad.size else []
+
+        def rerun(name, flagged) -> None:
+            idx = stream_rerun_rows(chunk, flagged)      # (``again``: whole streams already)
+            y2 = self._run_rows([chunk[j] for j in idx], [forget[j] for j in idx] if forget else forget, seen, trace=False)
+            check(idx, y2)
+            a = 0
+            while a < len(idx):                          # (device copies, one per run of neighbouring rows)
+                b = a + 1
+                while b < len(idx) and idx[b] == idx[b - 1] + 1:
+                    b += 1
+                y[idx[a]: idx[a] + b - a, :, :y2.shape[-1]].copy_(y2[a:b])
+                a = b
+
+        check(list(range(len(chunk))), y)
+        first = getattr(self.model, "activation_storage", "float32")
+        storage, tried, still = storage_fallback(self.model, self.fallback, len(chunk), lambda i: i in again, rerun)
+        for j in still if self.fallback else ():         # (fallbacks exhausted: ``tried`` lists every storage, the last included)
+            tried[j] = tried[j] + [storage[j]]
+        max_abs = rep[:, 2].copy().view(np.float32).tolist()
+        for j, (r, (nonfinite, clipped, _, carry_bad)) in enumerate(zip(chunk, rep.tolist())):
+            st = self._slots[r.stream]
+            d = dict(window=r.k, storage=storage[j], tried=tried[j], nonfinite=nonfinite, clipped=clipped,
+                     max_abs=max_abs[j], carry_nonfinite=carry_bad)
+            report[st.id].append(d)
+            t = st.totals
+            t["windows"] += 1
+            t["fell_back"] += int(d["storage"] != first)
+            t["nonfinite"] += d["nonfinite"]
+            t["clipped"] += d["clipped"]
+            t["max_abs"] = max(t["max_abs"], d["max_abs"])
+            t["storages"][d["storage"]] = t["storages"].get(d["storage"], 0) + 1
+
+    def totals(self, sid: int) -> Dict[str, object]:
+        """A checked session: what the windows of the open stream ``sid`` reported since ``open`` - ``windows`` that ran,
+        how many ``fell_back`` to another storage, the sums of ``nonfinite`` and ``clipped`` samples, the largest
+        ``max_abs``, and ``storages``: windows per storage their samples came from.  A copy.  (A stream that has ended:
+        the ending push's ``last_report["totals"][sid]``.)"""
+        if not self.checked:
+            raise ValueError("totals needs checked=True")
+        if sid not in self._ids:
+            raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
+        t = self._slots[self._ids[sid]].totals
+        return dict(t, storages=dict(t["storages"]))
 
     def _collect(self, ids: Sequence[int], down) -> Dict[int, np.ndarray]:
         """Waits for the push's forwards, if any ran (one ``synchronize``), and copies every stream's runs out of their
@@ -2155,10 +2352,11 @@ def main(argv=None) -> None:                                  # pragma: no cover
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--storage", default="float32", choices=["float32", "bfloat16", "float16", "auto"],
                     help="activation storage of the generator's forward (FastSVCGenerator.activation_storage); auto: float16 "
-                         "with --checked --fallback bfloat16 (needs --resident)")
+                         "with --checked --fallback bfloat16 (needs --resident; also with --stream)")
     ap.add_argument("--checked", action="store_true",
                     help="with --resident: report non-finite and clipped samples per utterance and run the batches that "
-                         "hold a non-finite utterance again in the --fallback storages (DecodeSession(checked=True))")
+                         "hold a non-finite utterance again in the --fallback storages (DecodeSession(checked=True)); with "
+                         "--stream: per window, before its samples or its running statistics are used (StreamSession(checked=True))")
     ap.add_argument("--fallback", default=None,
                     help="comma-separated storages to fall back to, in order (default with --checked: bfloat16)")
     ap.add_argument("--resident", action="store_true",
@@ -2197,9 +2395,8 @@ def main(argv=None) -> None:                                  # pragma: no cover
     ap.add_argument("--streams", type=int, default=1, help="with --stream: dumps converted side by side (default 1)")
     args = ap.parse_args(argv)
     if args.stream is not None:
-        if not args.resident or args.fanout > 1 or args.window is not None or args.checked or args.fallback is not None \
-                or args.storage == "auto":
-            ap.error("--stream works on the --resident route, without --fanout, --window, --checked and --storage auto")
+        if not args.resident or args.fanout > 1 or args.window is not None:
+            ap.error("--stream works on the --resident route, without --fanout and --window")
         try:
             parts = [int(v) for v in args.stream.split(",")]
             if not 1 <= len(parts) <= 4 or parts[0] < 1 or args.streams < 1:
@@ -2364,8 +2561,9 @@ def _main_stream(args, config, model, sg, device, files) -> None:        # pragm
     are its file."""
     embs = dict(np.load(args.spk_emb)) if args.spk_emb else {}
     hop, n, step = int(config["hop_size"]), args.stream["n_streams"], args.stream["max_push"]
-    with StreamSession(model, sg, device, **args.stream) as session:
+    with StreamSession(model, sg, device, checked=args.checked, fallback=args.fallback, **args.stream) as session:
         for trgspk in config.get("convert_to_speakers", [None]):
+            reports = []                                 # a checked session: one entry per stream, from its totals
             trg_emb = embs.get(trgspk) if config["generator_params"].get("use_spk_emb") else None
             shift = bool(args.srcf0stats and args.trgf0stats and trgspk is not None)
             trg_stats = _read_f0_mean(args.trgf0stats, trgspk) if shift else None
@@ -2387,6 +2585,8 @@ def _main_stream(args, config, model, sg, device, files) -> None:        # pragm
                                         for j in live}, end=[ids[j] for j in live if a + step >= frames[j]])
                     for j in live:
                         pieces[j].append(out[ids[j]])
+                    if args.checked:
+                        reports += [stream_totals_report(t, args.storage) for t in session.last_report.get("totals", {}).values()]
                 session.end([ids[j] for j, f in enumerate(frames) if f == 0])        # (a dump without frames: free its slot)
                 spent += time.time() - t0
                 for utt, ps in zip(utt_ids, pieces):
@@ -2395,6 +2595,17 @@ def _main_stream(args, config, model, sg, device, files) -> None:        # pragm
                     write_wav(os.path.join(args.outdir, f"{utt}_{trgspk}_gen.wav"), y, config["sampling_rate"])
             if samples:
                 print(f"{len(files)} streams -> {trgspk}: RTF = {spent / (samples / config['sampling_rate']):.5f}")
+            if args.checked:
+                print(f"{trgspk}: " + summarize_reports(reports, args.storage))
+
+
+def stream_totals_report(totals: Dict[str, object], storage: str) -> Dict[str, object]:
+    """A checked stream's totals (``StreamSession.totals``) as the one entry ``summarize_reports`` counts for an utterance:
+    it fell back when one of its windows did - ``storage`` is then the last fallback storage among its windows', in the
+    order they first ran - and its counts are the sums over its windows."""
+    others = [name for name in totals["storages"] if name != storage]
+    return dict(storage=others[-1] if others else storage, tried=[storage] if totals["fell_back"] else [],
+                nonfinite=totals["nonfinite"], clipped=totals["clipped"], max_abs=totals["max_abs"])
 
 
 def summarize_reports(reports: Sequence[Dict[str, object]], storage: str) -> str:

@@ -50,7 +50,7 @@ ABI_SYMBOLS = (
     "fastsvc_collate_launch_count", "fastsvc_collate_crops",
     "fastsvc_fanout_launch_count", "fastsvc_fanout_assemble",
     "fastsvc_window_launch_count", "fastsvc_window_assemble", "fastsvc_window_stitch",
-    "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble",
+    "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble", "fastsvc_stream_check",
     "fastsvc_stream_loudness_scratch_bytes", "fastsvc_stream_loudness",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
@@ -221,6 +221,9 @@ def load_library():
     lib.fastsvc_stream_assemble.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i64),
                                             ctypes.POINTER(i32), vp, vp, vp, i32, i32, i32, i32, vp]
     lib.fastsvc_stream_assemble.restype = ctypes.c_int
+    lib.fastsvc_stream_check.argtypes = [vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, i64, i32, i32,
+                                         ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]
+    lib.fastsvc_stream_check.restype = ctypes.c_int
     lib.fastsvc_stream_loudness_scratch_bytes.argtypes = [i32, i32]
     lib.fastsvc_stream_loudness_scratch_bytes.restype = sz
     lib.fastsvc_stream_loudness.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32),
@@ -794,6 +797,48 @@ def stream_assemble(ppg_ring: torch.Tensor, lft_ring: torch.Tensor, exc_ring: to
                                                 *[_ptr(t) for t in outs], R, C, hop, width, ctypes.c_void_p(stream)),
                "fastsvc_stream_assemble")
     return tuple(outs)
+
+
+def stream_check(y: torch.Tensor, span_lo: Sequence[int], span_hi: Sequence[int], carry: Optional[torch.Tensor] = None,
+                 slots: Optional[Sequence[int]] = None, entries: Optional[Sequence[int]] = None, entry_doubles: int = 0,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What the window rows of a live-stream forward CONTRIBUTE, per row: -> (B, 4) int32 on the device, row r the
+    ``fastsvc_row_report`` of ``y[r, span_lo[r]:span_hi[r]]`` (``decode.stream_check_spans`` gives the spans) - the bits
+    ``output_check`` gives for that span as a row of its own - and, in the fourth word, the number of non-finite doubles
+    among the ``entry_doubles`` doubles of entry ``entries[r]`` (0 or 1; -1: none, the word is 0) of slot ``slots[r]``'s
+    record in ``carry``, a contiguous 2-D device tensor with one record per row (the running InstanceNorm carry of
+    ``Model.forward(norm_running=)``: pass the entry the forward just wrote, ``parity ^ 1``).  ``y`` (B, width) or
+    (B, 1, width), float32, contiguous; any ``0 <= lo <= hi <= width``.  ``out``: a (B, 4) int32 tensor to overwrite; every
+    call overwrites with plain stores (no memset, no atomics).  One HIP launch per 64 rows on the current stream
+    (fastsvc_stream_check, csrc/fastsvc_stream_check.hip); a bad span, slot or entry raises ``ValueError`` before
+    anything is enqueued; fails loudly off the GPU."""
+    lib = load_library()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise FastSVCError("stream_check needs a GPU tensor (no CPU fallback); got " + str(getattr(y, "device", type(y))))
+    if y.dim() == 3 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous() or y.shape[0] == 0 or \
+            len(span_lo) != y.shape[0] or len(span_hi) != y.shape[0]:
+        raise ValueError(f"y must be a contiguous float32 (B, width) tensor with one span per row; got {tuple(y.shape)} {y.dtype}")
+    B, width = int(y.shape[0]), int(y.shape[1])
+    if (slots is None) != (entries is None) or (entries is not None and (len(slots) != B or len(entries) != B)):
+        raise ValueError("stream_check needs slots and entries together, one of each per row")
+    carry_bytes = n_slots = 0
+    if carry is not None:
+        if not isinstance(carry, torch.Tensor) or not carry.is_cuda:
+            raise FastSVCError("stream_check needs a GPU tensor (no CPU fallback) for carry")
+        if carry.dim() != 2 or not carry.is_contiguous() or carry.device != y.device:
+            raise ValueError(f"carry must be a contiguous 2-D tensor on {y.device}, one record per row")
+        n_slots, carry_bytes = int(carry.shape[0]), int(carry.shape[1]) * carry.element_size()
+    report = torch.empty((B, 4), dtype=torch.int32, device=y.device) if out is None else _report_tensor(out, B, y.device)
+    lo, hi = _ints(ctypes.c_int32, span_lo), _ints(ctypes.c_int32, span_hi)
+    sl = None if slots is None else _ints(ctypes.c_int32, slots)
+    en = None if entries is None else _ints(ctypes.c_int32, entries)
+    with torch.cuda.device(y.device):
+        stream = torch.cuda.current_stream(y.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_check(_ptr(y), B, width, lo, hi, _ptr(carry), carry_bytes, int(entry_doubles), n_slots,
+                                             sl, en, _ptr(report), ctypes.c_void_p(stream)), "fastsvc_stream_check")
+    return report
 
 
 STREAM_LOUDNESS_MAX_FRAMES = 2048      # frames of one stream a stream_loudness call finalises

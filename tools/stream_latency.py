@@ -27,7 +27,12 @@ to profiles/decode_stream_horizon.txt.
 32 streams at core 32 in both storages: the audio session is pushed samples and makes the loudness on the device (two more
 launches per push, csrc/fastsvc_stream_loudness.hip).  Its figures go to profiles/decode_stream_loudness.txt.
 
-    python tools/stream_latency.py [--norm [--horizon H] | --audio]"""
+--checked: the pair is StreamSession(checked=True) against StreamSession() in float16 activation storage on the same chunks, 1,
+8 and 32 streams at core 32, with norm="window" and norm="running": the checked session adds one stream_check launch, a copy
+of 16 bytes a row and ONE wait per forward (nothing falls back: the streams stay in range).  The difference is quoted next to
+the spread of the unchecked leg; nothing is gated.  Its figures go to profiles/decode_stream_checked.txt.
+
+    python tools/stream_latency.py [--norm [--horizon H] | --audio | --checked]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -276,9 +281,62 @@ def main_audio():
         f.write("\n".join(out) + "\n")
 
 
+def main_checked():
+    core, storage = 32, "float16"
+    out = [f"checked streams: one StreamSession.push that completes one window per stream (every stream delivers {core} frames), "
+           f"host to host, checked=True (one stream_check launch, 16 bytes a row copied into page-locked memory and one wait per "
+           f"forward; no window falls back) against checked=False on the same chunks, two sessions in one process, activation "
+           f"storage {storage}; context {ctx}, fade {FADE}, speaker embedding, F0 shift on, int16 out; {pushes} pushes per "
+           f"repetition, {reps} repetitions, legs alternated, median of the repetitions' means (min, max); "
+           f"{torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    m = build_model(storage)
+    for norm in ("window", "running"):
+        out.append(f"--- norm={norm}")
+        for N in (1, 8, 32):
+            src = [features(core * 8) for _ in range(N)]
+            legs = {}
+            for name in ("unchecked", "checked"):
+                s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, norm=norm, checked=name == "checked")
+                legs[name] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[])
+
+            def push(leg):
+                a = (leg["step"] % 8) * core
+                leg["step"] += 1
+                return leg["s"].push({i: dict(ppg=f["ppg"][a: a + core], f0=f["f0"][a: a + core], lft=f["lft"][a * hop: (a + core) * hop])
+                                      for i, f in zip(leg["ids"], src)})
+            for leg in legs.values():
+                for _ in range(6):                       # (fill the context, warm every shape)
+                    push(leg)
+                before = leg["s"].forwards
+                got = push(leg)
+                assert leg["s"].forwards == before + 1 and all(v.size == core * hop for v in got.values())
+            for _ in range(reps):
+                for leg in legs.values():
+                    t0 = time.perf_counter()
+                    for _ in range(pushes):
+                        push(leg)
+                    leg["t"].append((time.perf_counter() - t0) / pushes)
+            fell = sum(legs["checked"]["s"].totals(i)["fell_back"] for i in legs["checked"]["ids"])
+            for leg in legs.values():
+                leg["s"].end(leg["ids"])
+                leg["s"].close()
+            audio = N * core * hop / SR
+            mu, line_u = spread(f"{N:2d} streams, core {core:3d}: push, unchecked", legs["unchecked"]["t"], audio)
+            mc, line_c = spread(f"{N:2d} streams, core {core:3d}: push, checked", legs["checked"]["t"], audio)
+            out += [line_u, line_c, f"    checked / unchecked {mc / mu:.3f} ({(mc - mu) * 1e3:+.0f} us a push; spread of the unchecked leg "
+                                    f"{(max(legs['unchecked']['t']) - min(legs['unchecked']['t'])) * 1e6:.0f} us; {fell} windows fell back)"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream_checked.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
-    if "--audio" in argv:
+    if "--checked" in argv:
+        main_checked()
+    elif "--audio" in argv:
         main_audio()
     elif "--horizon" in argv:
         if "--norm" not in argv or argv.index("--horizon") + 1 >= len(argv):
