@@ -606,6 +606,12 @@ int fastsvc_window_stitch(const float* y, int32_t B, int32_t width, const int32_
  * launch is FASTSVC_E_HIP.  One launch per 64 entries (fastsvc_stream_launch_count(S)), none when every n[i] is 0;
  * asynchronous on `stream_`.
  *
+ * Push without f0.  exc_ring == NULL means "no f0 in the slice, no synthesis" (decode.StreamSession(f0="audio")): a slice is
+ * the time-major ppg n x C, then n x hop samples for lft_ring - the audio ring of such a session - and the launch only
+ * copies (the same 16-byte rule); phase and seed are not read and may be NULL, first and parity are checked and ignored.
+ * The excitation of those frames is made when they are final, by fastsvc_stream_f0.  With an exc_ring the launches, kernel
+ * arguments, bytes and bits are what they were.
+ *
  * Assembly.  fastsvc_window_assemble's outputs for rows cut from the rings: row r is the n_frames[r] frames from frame
  * first_frame[r] of stream stream[r], read modulo cap ->
  *   ppg_out (R, C, width)                 transposed to channel-major, every column >= n_frames written as 0
@@ -688,6 +694,58 @@ int fastsvc_stream_loudness(const float* audio_ring, float* lft_ring, float* pea
                             const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
                             const int32_t* ended, const int32_t* parity, int32_t n_streams, int32_t cap, int32_t max_frames,
                             int32_t hop, float sample_rate, void* stream_);
+
+/* F0 and excitation of live streams from their raw audio (csrc/fastsvc_stream_f0.hip; decode.StreamSession(f0="audio")).
+ * For the frames of a stream that have become FINAL - exactly the frames fastsvc_stream_loudness finalises, with the same
+ * first_frame / n / seen / ended - this call computes fastsvc_f0_extract's value from the AUDIO ring (below: YIN, a function
+ * of the frame's 2048 samples alone, so a streamed frame has the whole-file bits for every push schedule, slot and ring
+ * position, the reflected frames at the end included), shifts it, and synthesises the frames' excitation:
+ *   f0_ring   (n_streams, cap) float32: the raw F0 of frame f at index f % cap (0 = unvoiced)
+ *   f0s_ring  (n_streams, cap) float32: the F0 the excitation is made from - for a voiced frame of a stream with statistics
+ *             (float) exp((s1 / s0) * (log((double) f0) - m0) + m1), every operation a separately rounded double operation
+ *             in that order (F0Statistics.convert; within one float32 ulp of the host's, as fastsvc_fanout_assemble's), else
+ *             the raw value; unvoiced frames exactly 0
+ *   stats     HOST, 4 doubles per entry: m0, s0 (source mean and std of log F0), m1, s1 (target) - finite with s0 > 0 - or
+ *             four NaN: no shift
+ *   exc_ring  (n_streams, cap * hop), 16-byte aligned: fastsvc_stream_push's excitation of those frames, the same expressions
+ *             (csrc/fastsvc_signal.inc): the phase recurrence C_{f+1} = frac(C_f + hop * rad_f) in float64 by one lane from
+ *             phase[stream][parity[i]] - or from 0 when first_frame[i] == 0, which reads nothing - writing entry parity[i] ^ 1
+ *             (the caller alternates it per stream and call that finalises at least one frame); the noise keyed by seed[i]
+ *             and the absolute sample index.  With noise_amp == 0 the samples are bit for bit fastsvc_signal_generate's on
+ *             the whole shifted F0.
+ * 0 <= n[i] <= max_frames <= min(cap, 2048).  A stream's frames must be finalised in order, each once.  Two launches per 64
+ * entries - F0 and shift, one block per frame; then the excitation - none when every n[i] is 0; plain vector stores, no
+ * atomics; no load outside the stream's audio ring, its f0s ring and its phase entry, no store outside the stream's rows of
+ * the three rings and its phase pair.  Per-entry arrays are HOST arrays of S entries, read during the call.  Everything is
+ * checked on the host BEFORE anything is enqueued - null or misaligned pointers, sizes, lags outside [1, 1024]
+ * (fastsvc_f0_lags), threshold <= 0, n[i] > max_frames, a stream out of range or listed twice, statistics that are neither,
+ * frames that are not final or whose samples the ring no longer holds: FASTSVC_E_INVALID with the reason in
+ * fastsvc_last_error(); a failed launch is FASTSVC_E_HIP.  Asynchronous on `stream_`. */
+int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase, int32_t S,
+                      const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                      const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats,
+                      int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
+                      float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_);
+
+/* ---- F0 of whole files by YIN (csrc/fastsvc_f0.hip, csrc/fastsvc_f0.inc; de Cheveigne & Kawahara 2002) ----
+ * The recipe's F0 is pyworld.harvest's, a whole-file CPU algorithm; this is a per-frame DEFINITION that
+ * a live stream can compute as well.  Frames and conventions are fastsvc_loudness_extract's: audio (B, T) device float32,
+ * out (B, frames) float32, frames = 1 + T / hop, frame f the 2048 samples x[k] = y[reflect(f hop - 1024 + k)], no window.
+ *   tau_min = floor(sr / f0_ceil), tau_max = ceil(sr / f0_floor), 1 <= tau_min <= tau_max <= 1024 (fastsvc_f0_lags: else
+ *   FASTSVC_E_INVALID), W = 2048 - tau_max
+ *   d(tau) = sum over 1 <= j < W of (x[j] - x[j + tau])^2 for tau = 1 .. tau_max, computed directly (no FFT: no float32
+ *            cancellation); x[0] is never read - frame 0's is sample 1024 by reflection, which a live stream whose hop
+ *            divides 1024 has not received when the frame is final
+ *   d'(tau) = d(tau) tau / (d(1) + ... + d(tau));  d(1) == 0 (a constant frame: a zero denominator) -> unvoiced, no NaN
+ *   tau    = the smallest lag in [tau_min, tau_max] with d'(tau) < threshold, walked right while d'(tau + 1) < d'(tau) and
+ *            tau + 1 <= tau_max; none -> f0 = 0
+ *   parabolic interpolation of d' over tau - 1, tau, tau + 1, skipped when a neighbour lies outside [1, tau_max] or d'(tau)
+ *            is not the smallest of the three;  f0 = sr / tau_hat
+ * float32 arithmetic in an order fixed by the code (csrc/fastsvc_f0.inc), not by the launch.  One launch, no scratch, no
+ * atomics; asynchronous on `stream`. */
+int fastsvc_f0_lags(float sample_rate, float f0_floor, float f0_ceil, int32_t* tau_min, int32_t* tau_max);
+int fastsvc_f0_extract(const float* audio, float* out, int32_t B, int32_t T, int32_t hop, float sample_rate, float f0_floor,
+                       float f0_ceil, float threshold, void* stream);
 
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa

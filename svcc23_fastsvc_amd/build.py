@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libfastsvc_hip.so")
 # the stamped diagnostic build (--timeline) is a separate file: loaded only when FASTSVC_HIP_LIB names it
 TIMELINE_LIB_PATH = os.path.join(PKG_DIR, "libfastsvc_hip_timeline.so")
-SOURCES = ["fastsvc_kernels.hip", "fastsvc_hx.hip", "fastsvc_wx.hip", "fastsvc_cond.hip", "fastsvc_plan.cpp", "fastsvc_signal.hip", "fastsvc_loudness.hip", "fastsvc_stftloss.hip", "fastsvc_convgrad.hip", "fastsvc_filmnorm.hip", "fastsvc_gconv.hip", "fastsvc_decodeio.hip", "fastsvc_pack.hip", "fastsvc_collate.hip", "fastsvc_fanout.hip", "fastsvc_window.hip", "fastsvc_stream.hip", "fastsvc_stream_loudness.hip", "fastsvc_stream_check.hip", "fastsvc_normgroup.hip"]
+SOURCES = ["fastsvc_kernels.hip", "fastsvc_hx.hip", "fastsvc_wx.hip", "fastsvc_cond.hip", "fastsvc_plan.cpp", "fastsvc_signal.hip", "fastsvc_loudness.hip", "fastsvc_stftloss.hip", "fastsvc_convgrad.hip", "fastsvc_filmnorm.hip", "fastsvc_gconv.hip", "fastsvc_decodeio.hip", "fastsvc_pack.hip", "fastsvc_collate.hip", "fastsvc_fanout.hip", "fastsvc_window.hip", "fastsvc_stream.hip", "fastsvc_stream_loudness.hip", "fastsvc_f0.hip", "fastsvc_stream_f0.hip", "fastsvc_stream_check.hip", "fastsvc_normgroup.hip"]
 HEADERS = [os.path.join(CSRC, "fastsvc_kernels.h"), os.path.join(ROOT, "include", "fastsvc_hip.h")]
 ARCH = "gfx950"
 
@@ -71,6 +71,10 @@ UNITS = [
     ("fastsvc_stream.hip", [], "stream.o"),
     # (live streams' loudness from raw audio: fastsvc_loudness.hip's flags - the two share the frame's arithmetic, bit for bit)
     ("fastsvc_stream_loudness.hip", [], "stream_loudness.o"),
+    # (F0 by YIN, whole files and live streams: the two share the frame's arithmetic, bit for bit - fastsvc_f0.inc spells out
+    # its fused multiply-adds and turns contraction off itself, so the flags are the default ones)
+    ("fastsvc_f0.hip", [], "f0.o"),
+    ("fastsvc_stream_f0.hip", [], "stream_f0.o"),
     # (live streams' per-window output check: fastsvc_decodeio.hip's flags - the two share the per-sample report rules)
     ("fastsvc_stream_check.hip", [], "stream_check.o"),
     # (grouped InstanceNorm sums: the partial sums once per activation storage, the pool with the float32 unit)

@@ -4,7 +4,9 @@
 //   stream_push       per stream, n frames (0 allowed) of one packed upload buffer - time-major ppg n x C, then f0 n,
 //                     then lft n x hop - are appended to the stream's RINGS: ppg (cap x C, time-major), lft (cap x hop)
 //                     and the excitation (cap x hop), which the same launch synthesises.  Frame p of a stream lives at
-//                     ring index p % cap; a chunk is at most cap frames, so it wraps at most once.
+//                     ring index p % cap; a chunk is at most cap frames, so it wraps at most once.  With a null exc_ring
+//                     the slice holds no f0 - ppg, then n x hop samples - and the launch only copies (stream_append_kernel):
+//                     a session that makes the F0 itself synthesises when the frames are final (fastsvc_stream_f0.hip).
 //   stream_assemble   fastsvc_window_assemble's outputs for rows (stream, first_frame, n_frames) read from the rings
 //                     modulo cap: ppg transposed to channel-major, lft and the excitation copied, the tails zero.
 //
@@ -141,6 +143,31 @@ void stream_push_kernel(PushArgs a, PushDims d, const float* __restrict__ up, fl
                 }
             }
         }
+    }
+}
+
+// The push of a session that makes the F0 itself (StreamSession(f0="audio")): the slice is ppg n x C, then audio n x hop -
+// no f0 - and nothing is synthesised: the excitation is made when the frames are final (fastsvc_stream_f0.hip).  The
+// copies are stream_push_kernel's, through ring_put4.
+__global__ __launch_bounds__(256)
+void stream_append_kernel(PushArgs a, PushDims d, const float* __restrict__ up, float* __restrict__ ppg_ring,
+                          float* __restrict__ sig_ring) {
+    const int b = blockIdx.y;
+    const int n = a.n[b];
+    if (n == 0) return;                             // (uniform per block)
+    const int slot = a.slot[b];
+    const int C = d.C, hop = d.hop, cap = d.cap;
+    const float* src = up + a.up_off[b];
+    const float* sig = src + (long)n * C;
+    const long p0 = a.pos[b] % cap;
+    const long np = (long)n * C, ns = (long)n * hop;
+    const long gp = (np + 3) / 4, gs = (ns + 3) / 4;
+    const long ring_p = (long)cap * C, ring_s = (long)cap * hop;
+    float* rp = ppg_ring + slot * ring_p;
+    float* rs = sig_ring + slot * ring_s;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < gp + gs; g += (long)gridDim.x * 256) {
+        if (g < gp) ring_put4(src, rp, ring_p, p0 * C, np, g);
+        else ring_put4(sig, rs, ring_s, p0 * hop, ns, g - gp);
     }
 }
 
@@ -316,13 +343,15 @@ int fastsvc_stream_push(const float* upload, int64_t upload_elems, int32_t S, co
                         const uint64_t* seed, float* ppg_ring, float* lft_ring, float* exc_ring, double* phase,
                         int32_t n_streams, int32_t cap, int32_t max_push, int32_t C, int32_t hop,
                         float sample_rate, float sine_amp, float noise_amp, void* stream_) {
-    if (!upload || !stream || !n || !up_off || !pos || !first || !parity || !seed || !phase)
+    // a null exc_ring: no f0 in the slices and no synthesis (phase and seed are then not read and may be null)
+    const bool synth = exc_ring != nullptr;
+    if (!upload || !stream || !n || !up_off || !pos || !first || !parity || (synth && (!seed || !phase)))
         return invalid("fastsvc_stream_push: null pointer");
-    if (const int rc = check_rings("fastsvc_stream_push", ppg_ring, lft_ring, exc_ring, n_streams, cap, C, hop)) return rc;
+    if (const int rc = check_rings("fastsvc_stream_push", ppg_ring, lft_ring, synth ? exc_ring : lft_ring, n_streams, cap, C, hop)) return rc;
     if (S < 1 || upload_elems < 0 || max_push < 1 || max_push > SP_MAX_PUSH || max_push > cap || !(sample_rate > 0.f))
         return invalid("fastsvc_stream_push: size out of range (S %ld, max_push %ld: at most %ld and at most cap %ld)", S, max_push,
                        SP_MAX_PUSH, cap);
-    if ((reinterpret_cast<uintptr_t>(upload) & 3) || (reinterpret_cast<uintptr_t>(phase) & 7))
+    if ((reinterpret_cast<uintptr_t>(upload) & 3) || (synth && (reinterpret_cast<uintptr_t>(phase) & 7)))
         return invalid("fastsvc_stream_push: misaligned pointer");
     int64_t most = 0;
     for (int i = 0; i < S; ++i) {
@@ -331,7 +360,7 @@ int fastsvc_stream_push(const float* upload, int64_t upload_elems, int32_t S, co
         for (int j = 0; j < i; ++j)
             if (stream[j] == s) return invalid("fastsvc_stream_push: stream %ld is pushed twice in one call", s);
         if (k < 0 || k > max_push) return invalid("fastsvc_stream_push: stream %ld: %ld frames, outside [0, max_push %ld]", s, k, max_push);
-        const int64_t need = k * ((int64_t)C + 1 + hop);
+        const int64_t need = k * ((int64_t)C + (synth ? 1 : 0) + hop);
         if (up_off[i] < 0 || up_off[i] > upload_elems || need > upload_elems - up_off[i])
             return invalid("fastsvc_stream_push: stream %ld: its slice [%ld, +%ld) leaves the upload buffer of %ld elements", s, up_off[i],
                            need, upload_elems);
@@ -340,7 +369,7 @@ int fastsvc_stream_push(const float* upload, int64_t upload_elems, int32_t S, co
         most = k > most ? k : most;
     }
     if (most == 0) return FASTSVC_OK;               // (nothing to append: no launch)
-    const int64_t groups = (most * C + 3) / 4 + 2 * ((most * hop + 3) / 4);
+    const int64_t groups = (most * C + 3) / 4 + (synth ? 2 : 1) * ((most * hop + 3) / 4);
     int64_t gx = (groups + 255) / 256;
     gx = gx > SP_MAX_BLOCKS ? SP_MAX_BLOCKS : gx;
     PushDims d;
@@ -356,7 +385,11 @@ int fastsvc_stream_push(const float* upload, int64_t upload_elems, int32_t S, co
             a.flags[i] = on ? (first[b0 + i] | (parity[b0 + i] << 1)) : 0;
             a.up_off[i] = on ? (long)up_off[b0 + i] : 0;
             a.pos[i] = on ? (long)pos[b0 + i] : 0;
-            a.seed[i] = on ? (unsigned long long)seed[b0 + i] : 0ull;
+            a.seed[i] = on && synth ? (unsigned long long)seed[b0 + i] : 0ull;
+        }
+        if (!synth) {
+            hipLaunchKernelGGL(stream_append_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, hs, a, d, upload, ppg_ring, lft_ring);
+            continue;
         }
         hipLaunchKernelGGL(stream_push_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, hs, a, d, upload, ppg_ring, lft_ring,
                            exc_ring, phase);

@@ -1,0 +1,255 @@
+// fastsvc_stream_f0.hip - the F0 and the excitation of live streams from their raw audio, on gfx950
+// (decode.StreamSession(f0="audio")): the frames of a stream that have become FINAL - the frames fastsvc_stream_loudness
+// finalises in the same push - get their F0 by YIN from the stream's audio ring, the Gaussian log-F0 shift, and their
+// excitation, straight into the stream's excitation ring.
+//
+// The function is fastsvc_f0_extract's, frame by frame: fastsvc_f0.inc is one text for both, and the value
+// is a function of the frame's 2048 samples alone, so a streamed frame has the whole-file bits for every push schedule,
+// slot and ring position.  There is no running state in the estimator.
+//
+//   stream_f0_frames    one block per (stream, newly final frame): reads the AUDIO ring (sample p at p % (cap hop)),
+//                       writes the raw F0 to f0_ring[slot][f % cap], then the shifted F0 - F0Statistics.convert in float64
+//                       for voiced frames of a stream that has statistics, else the raw value - to f0s_ring
+//   stream_f0_excite    blocks per stream: one lane runs the phase recurrence C_{f+1} = frac(C_f + hop rad_f) over the
+//                       call's frames from phase[slot][parity] into LDS (fastsvc_stream.hip's rule: reads entry `parity`,
+//                       block 0 writes entry `parity ^ 1`; first_frame == 0 starts at 0 and reads nothing), then all lanes
+//                       write the samples with fastsvc_signal.inc's closed form into exc_ring, the noise keyed by the seed
+//                       and the ABSOLUTE sample index - stream_push_kernel's excitation part, from the shifted F0 ring
+//
+// The second launch reads what the first wrote: two launches, ordered by the stream.  Descriptors travel IN the kernel
+// arguments, 64 streams per launch.  Plain vector stores, no atomics, no tunables.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "fastsvc_hip.h"
+
+namespace fastsvc {
+int set_last_error(int code, const char* msg);      // fastsvc_plan.cpp: the text fastsvc_last_error() returns
+}
+
+namespace {
+
+#include "fastsvc_loudness.inc"    // LD_NFFT, reflect_index
+#include "fastsvc_f0.inc"          // the per-frame estimator, shared with fastsvc_f0.hip
+#include "fastsvc_signal.inc"      // frame_rad, phase_step, sine_sample: shared with fastsvc_signal.hip and fastsvc_stream.hip
+
+constexpr int SF_MAX = 64;                          // streams per launch (the arguments hold their descriptors)
+constexpr int SF_MAX_FRAMES = 2048;                 // frames of one stream a call finalises (their prefixes: 16 KiB of LDS)
+constexpr int SF_MAX_BLOCKS = 64;                   // blocks per stream of the excitation launch (grid-stride beyond)
+
+struct F0Args {
+    long first[SF_MAX];                             // the stream's first frame of this call
+    long samples[SF_MAX];                           // samples the stream's audio ring has received
+    int n[SF_MAX];                                  // frames of this call
+    int slot[SF_MAX];
+    int flags[SF_MAX];                              // bit 0: the stream's first frame is among them (the phase starts at 0);
+};                                                  // bit 1: the phase entry to read; bit 2: ended; bit 3: has statistics
+
+struct F0Seeds {                                    // (the excitation launch alone takes them: the arguments stay under 4 KiB)
+    unsigned long long seed[SF_MAX];
+};
+
+struct F0Shift {                                    // F0Statistics.convert's constants: source mean, std ratio, target mean
+    double m0[SF_MAX], ratio[SF_MAX], m1[SF_MAX];
+};
+
+struct F0Dims {
+    int hop, cap;
+    float sine_amp, noise_amp;
+};
+
+// F0Statistics.convert for one frame (fastsvc_fanout.hip's ShiftF0): every operation a separately rounded double operation
+__device__ __forceinline__ float shift_f0(float f, double m0, double ratio, double m1) {
+    #pragma clang fp contract(off)
+    if (!(f > 0.f)) return 0.f;
+    const double l = log((double)f);
+    const double d = l - m0;
+    const double q = ratio * d;
+    const double s = q + m1;
+    return (float)exp(s);
+}
+
+__global__ __launch_bounds__(256)
+void stream_f0_frames_kernel(F0Args a, F0Shift sh, F0Dims d, F0Params p, const float* __restrict__ audio_ring,
+                             float* __restrict__ f0_ring, float* __restrict__ f0s_ring) {
+    __shared__ __attribute__((aligned(16))) float x[LD_NFFT];
+    __shared__ float dn[F0_MAX_LAG + 2];
+    __shared__ float res;
+    __shared__ int wmin[4];
+    const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (j >= a.n[b]) return;                        // (uniform per block)
+    const int slot = a.slot[b], flags = a.flags[b];
+    const long ring_len = (long)d.cap * d.hop, T = a.samples[b];
+    const bool ended = (flags & 4) != 0;
+    const float* ring = audio_ring + slot * ring_len;
+    const long f = a.first[b] + j;
+    const long base = f * d.hop - LD_NFFT / 2;
+    for (int k = tid; k < LD_NFFT; k += 256) {
+        long i = base + k;
+        if (ended) i = reflect_index<long>(i, T);
+        else if (i < 0) i = -i;
+        // (a frame that is final before the end reads [f hop - 1024, f hop + 1024) < T; only frame 0's element 0 mirrors
+        // to sample 1024, which may not have arrived when hop divides 1024 - the estimator never reads x[0])
+        x[k] = i < T ? ring[i % ring_len] : 0.f;
+    }
+    const float v = f0_frame_value(x, dn, &res, wmin, p, tid);
+    if (tid == 0) {
+        const long at = (long)slot * d.cap + f % d.cap;
+        f0_ring[at] = v;
+        f0s_ring[at] = (flags & 8) ? shift_f0(v, sh.m0[b], sh.ratio[b], sh.m1[b]) : v;
+    }
+}
+
+__global__ __launch_bounds__(256)
+void stream_f0_excite_kernel(F0Args a, F0Seeds sd, F0Dims d, float sr, const float* __restrict__ f0s_ring, float* __restrict__ exc_ring,
+                             double* __restrict__ phase) {
+    __shared__ double pre[SF_MAX_FRAMES];
+    __shared__ float f0v[SF_MAX_FRAMES];
+    const int b = blockIdx.y;
+    const int n = a.n[b];
+    if (n == 0) return;                             // (uniform per block)
+    const int slot = a.slot[b], flags = a.flags[b];
+    const int hop = d.hop, cap = d.cap;
+    const long first = a.first[b];
+    const float* fr = f0s_ring + (long)slot * cap;
+    for (int f = threadIdx.x; f < n; f += 256) f0v[f] = fr[(first + f) % cap];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double c = (flags & 1) ? 0.0 : phase[2 * slot + ((flags >> 1) & 1)];
+        for (int f = 0; f < n; ++f) {
+            pre[f] = c;
+            c = phase_step(c, frame_rad(f0v[f], sr), hop);
+        }
+        if (blockIdx.x == 0) phase[2 * slot + (((flags >> 1) & 1) ^ 1)] = c;
+    }
+    __syncthreads();
+    const long ring_s = (long)cap * hop, ns = (long)n * hop;
+    float* re = exc_ring + slot * ring_s;
+    const long p0 = first % cap;
+    const uint64_t t0 = (uint64_t)first * (uint64_t)hop;            // the call's first sample in the stream
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < (ns + 3) / 4; g += (long)gridDim.x * 256) {
+        const long k0 = 4 * g;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        #pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const long k = k0 + e;
+            if (k >= ns) break;
+            const int q = (int)(k / hop);
+            const int i = (int)(k - (long)q * hop);
+            v[e] = sine_sample(f0v[q], pre[q], i, sr, d.sine_amp, d.noise_amp, sd.seed[b], t0 + (uint64_t)k);
+        }
+        long d0 = p0 * hop + k0;
+        if (d0 >= ring_s) d0 -= ring_s;
+        if (k0 + 4 <= ns && d0 + 4 <= ring_s && (reinterpret_cast<uintptr_t>(re + d0) & 15) == 0) {
+            *reinterpret_cast<float4*>(re + d0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            #pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (k0 + e >= ns) break;
+                long x = d0 + e;
+                if (x >= ring_s) x -= ring_s;
+                re[x] = v[e];
+            }
+        }
+    }
+}
+
+int invalid(const char* fmt, long a = 0, long b = 0, long c = 0, long e = 0) {
+    char buf[240];
+    snprintf(buf, sizeof buf, fmt, a, b, c, e);
+    return fastsvc::set_last_error(FASTSVC_E_INVALID, buf);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase, int32_t S,
+                      const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                      const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats,
+                      int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
+                      float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_) {
+    if (!audio_ring || !f0_ring || !f0s_ring || !exc_ring || !phase || !stream || !first_frame || !n || !seen || !ended ||
+            !parity || !seed || !stats)
+        return invalid("fastsvc_stream_f0: null pointer");
+    if (S < 1 || n_streams < 1 || cap < 4 || (cap & 3) || hop < 1 || (int64_t)cap * hop > INT32_MAX || max_frames < 1 ||
+            max_frames > SF_MAX_FRAMES || max_frames > cap || !(sample_rate > 0.f) ||
+            (int64_t)n_streams * cap * hop > ((int64_t)1 << 40))
+        return invalid("fastsvc_stream_f0: size out of range (S %ld, cap %ld: a multiple of 4, hop %ld, max_frames %ld: at most cap)",
+                       S, cap, hop, max_frames);
+    if ((reinterpret_cast<uintptr_t>(audio_ring) & 3) || (reinterpret_cast<uintptr_t>(f0_ring) & 3) ||
+            (reinterpret_cast<uintptr_t>(f0s_ring) & 3) || (reinterpret_cast<uintptr_t>(exc_ring) & 15) ||
+            (reinterpret_cast<uintptr_t>(phase) & 7))
+        return invalid("fastsvc_stream_f0: misaligned pointer (the excitation ring: 16 bytes, the phase: 8)");
+    if (!(threshold > 0.f)) return invalid("fastsvc_stream_f0: threshold must be > 0");
+    F0Params p;
+    if (const int rc = fastsvc_f0_lags(sample_rate, f0_floor, f0_ceil, &p.tau_min, &p.tau_max)) return rc;
+    p.sr = sample_rate; p.threshold = threshold;
+    const int64_t ring_len = (int64_t)cap * hop;
+    int64_t most = 0;
+    for (int i = 0; i < S; ++i) {
+        const int64_t s = stream[i], k = n[i], f = first_frame[i], q = seen[i];
+        if (s < 0 || s >= n_streams) return invalid("fastsvc_stream_f0: entry %ld: stream %ld outside [0, %ld)", i, s, n_streams);
+        for (int j = 0; j < i; ++j)
+            if (stream[j] == s) return invalid("fastsvc_stream_f0: stream %ld is listed twice in one call", s);
+        if (k < 0 || k > max_frames)
+            return invalid("fastsvc_stream_f0: stream %ld: %ld frames, outside [0, max_frames %ld]", s, k, max_frames);
+        if (f < 0 || q < 0 || q > ((int64_t)1 << 40) || f + k > q)
+            return invalid("fastsvc_stream_f0: stream %ld: frames [%ld, +%ld) of %ld seen", s, f, k, q);
+        if ((ended[i] & ~1) || (parity[i] & ~1)) return invalid("fastsvc_stream_f0: stream %ld: ended and parity are 0 or 1", s);
+        const double* st = stats + 4 * i;               // (source mean, source std, target mean, target std), or four NaN: no shift
+        auto finite = [](double v) { return v == v && v > -1e300 && v < 1e300; };
+        const bool none = st[0] != st[0] && st[1] != st[1] && st[2] != st[2] && st[3] != st[3];
+        if (!none && !(finite(st[0]) && finite(st[1]) && finite(st[2]) && finite(st[3]) && st[1] > 0.0))
+            return invalid("fastsvc_stream_f0: stream %ld: statistics are four finite values with a source std > 0, or four NaN for none", s);
+        if (k == 0) continue;
+        // every frame is final: it reads up to (f + k - 1) hop + 1023, or the stream has ended and these are its last frames
+        if (ended[i] ? f + k != q : (f + k - 1) * hop + LD_NFFT / 2 > q * hop)
+            return invalid("fastsvc_stream_f0: stream %ld: frames [%ld, +%ld) are not final with %ld frames seen", s, f, k, q);
+        // ... and the ring still holds what the first of them reads: from sample max(0, f hop - 1024) on
+        const int64_t lowest = f * hop > LD_NFFT / 2 ? f * hop - LD_NFFT / 2 : 0;
+        if (lowest < q * hop - ring_len)
+            return invalid("fastsvc_stream_f0: stream %ld: frame %ld reads samples the ring of %ld no longer holds (%ld frames seen)",
+                           s, f, ring_len, q);
+        most = k > most ? k : most;
+    }
+    if (most == 0) return FASTSVC_OK;               // (nothing became final: no launch)
+    F0Dims d;
+    d.hop = hop; d.cap = cap; d.sine_amp = sine_amp; d.noise_amp = noise_amp;
+    hipStream_t hs = static_cast<hipStream_t>(stream_);
+    for (int b0 = 0; b0 < S; b0 += SF_MAX) {
+        const int nb = S - b0 < SF_MAX ? S - b0 : SF_MAX;
+        F0Args a;
+        F0Shift sh;
+        F0Seeds sd;
+        int grid = 0;
+        for (int i = 0; i < SF_MAX; ++i) {
+            const bool on = i < nb;
+            const double* st = stats + 4 * (b0 + (on ? i : 0));
+            const bool shift = on && st[0] == st[0];
+            a.n[i] = on ? n[b0 + i] : 0;
+            a.slot[i] = on ? stream[b0 + i] : 0;
+            a.first[i] = on ? (long)first_frame[b0 + i] : 0;
+            a.samples[i] = on ? (long)seen[b0 + i] * hop : 0;
+            sd.seed[i] = on ? (unsigned long long)seed[b0 + i] : 0ull;
+            a.flags[i] = on ? ((first_frame[b0 + i] == 0 ? 1 : 0) | (parity[b0 + i] << 1) | (ended[b0 + i] << 2) | (shift ? 8 : 0)) : 0;
+            sh.m0[i] = shift ? st[0] : 0.0;
+            sh.ratio[i] = shift ? st[3] / st[1] : 1.0;      // (one double division, as numpy does it on the host)
+            sh.m1[i] = shift ? st[2] : 0.0;
+            grid = a.n[i] > grid ? a.n[i] : grid;
+        }
+        if (grid == 0) continue;
+        int64_t gx = (((int64_t)grid * hop + 3) / 4 + 255) / 256;
+        gx = gx > SF_MAX_BLOCKS ? SF_MAX_BLOCKS : gx;
+        hipLaunchKernelGGL(stream_f0_frames_kernel, dim3((unsigned)grid, (unsigned)nb), dim3(256), 0, hs, a, sh, d, p, audio_ring,
+                           f0_ring, f0s_ring);
+        hipLaunchKernelGGL(stream_f0_excite_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, hs, a, sd, d, sample_rate, f0s_ring,
+                           exc_ring, phase);
+    }
+    return hipGetLastError() == hipSuccess ? FASTSVC_OK
+                                           : fastsvc::set_last_error(FASTSVC_E_HIP, "fastsvc_stream_f0: launch failed");
+}
+
+}  // extern "C"

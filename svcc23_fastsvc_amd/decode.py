@@ -788,7 +788,7 @@ class _Stream:
     from_audio: bool = False         # the session makes the loudness (loudness="audio")
     seen: int = 0                    # frames that have arrived
     first: bool = True               # nothing has arrived: the sine phase starts at 0
-    parity: int = 0                  # the phase record's current entry (flips with every stream_push)
+    parity: int = 0                  # the phase record's current entry (flips with every stream_push; f0="audio": stream_f0)
     final: int = 0                   # loudness="audio": frames whose loudness is final
     loud_parity: int = 0             # the peak record's current entry (flips with every stream_loudness)
     done: int = 0                    # windows that ran
@@ -803,14 +803,20 @@ class _Stream:
         return self.final if self.from_audio else self.seen
 
 
-def check_stream_chunks(chunks, end, open_ids, channels: int, hop: int, max_push: int, loudness: str = "given"):
+def check_stream_chunks(chunks, end, open_ids, channels: int, hop: int, max_push: int, loudness: str = "given",
+                        f0: str = "given"):
     """Everything ``StreamSession.push`` refuses, on the host alone: ``chunks = {id: dict(ppg, f0, lft | audio)}`` and the
-    ids in ``end`` against the open ids, the ppg channels, ``hop``, ``max_push`` and the session's ``loudness`` mode.
-    Returns ``(parts, ids, end)``: ``parts[id] = (n, ppg (n, C), f0 (n,), lft or audio (n hop,))`` as numpy arrays in the
-    order of ``chunks``, ``ids`` every id of ``chunks`` and ``end`` once, in that order, and ``end`` as a list of ints.
-    A ``ValueError`` names the first thing wrong; nothing is changed."""
+    ids in ``end`` against the open ids, the ppg channels, ``hop``, ``max_push`` and the session's ``loudness`` and ``f0``
+    modes.  Returns ``(parts, ids, end)``: ``parts[id] = (n, ppg (n, C), f0 (n,), lft or audio (n hop,))`` as numpy arrays
+    in the order of ``chunks``, ``ids`` every id of ``chunks`` and ``end`` once, in that order, and ``end`` as a list of
+    ints.  With ``f0="audio"`` (which needs ``loudness="audio"``) a chunk is ``dict(ppg, audio)``: an ``f0`` key is
+    refused like any other mode's array, and ``parts[id][2]`` is None.  A ``ValueError`` names the first thing wrong;
+    nothing is changed."""
     C, hop = int(channels), int(hop)
     sig, other = ("audio", "lft") if loudness == "audio" else ("lft", "audio")     # (the chunk's third array, and the other mode's)
+    own_f0 = f0 == "audio"
+    if own_f0 and loudness != "audio":
+        raise ValueError("f0=\"audio\" needs loudness=\"audio\": the audio ring exists only there")
     end = [int(i) for i in end]
     for sid in list(chunks) + end:
         if sid not in open_ids:
@@ -820,22 +826,25 @@ def check_stream_chunks(chunks, end, open_ids, channels: int, hop: int, max_push
     parts = {}
     for sid, ch in chunks.items():
         try:
-            ppg, f0, lft = (np.asarray(ch[key]) for key in ("ppg", "f0", sig))
-            stray = other in ch
+            ppg, lft = (np.asarray(ch[key]) for key in ("ppg", sig))
+            pitch = None if own_f0 else np.asarray(ch["f0"])
+            stray, stray_f0 = other in ch, own_f0 and "f0" in ch
         except (KeyError, TypeError) as e:
-            raise ValueError(f"stream {sid}: a chunk is a dict with ppg, f0 and {sig}") from e
+            raise ValueError(f"stream {sid}: a chunk is a dict with ppg{'' if own_f0 else ', f0'} and {sig}") from e
         if stray:
             raise ValueError(f"stream {sid}: the session was built with loudness=\"{loudness}\": a chunk carries {sig}, not {other}")
+        if stray_f0:
+            raise ValueError(f"stream {sid}: the session was built with f0=\"audio\": it makes the F0 from the audio, a chunk carries none")
         if ppg.ndim != 2 or ppg.shape[1] != C:
             raise ValueError(f"stream {sid}: ppg must be (n, {C}), got {ppg.shape}")
         n = int(ppg.shape[0])
         if n > max_push:
             raise ValueError(f"stream {sid}: {n} frames in one push, max_push is {max_push}")
-        if f0.shape not in ((n,), (n, 1)):
-            raise ValueError(f"stream {sid}: f0 must be ({n},) or ({n}, 1), got {f0.shape}")
+        if pitch is not None and pitch.shape not in ((n,), (n, 1)):
+            raise ValueError(f"stream {sid}: f0 must be ({n},) or ({n}, 1), got {pitch.shape}")
         if lft.shape not in ((n * hop,), (n * hop, 1)):
             raise ValueError(f"stream {sid}: {sig} must be ({n * hop},) or ({n * hop}, 1), got {lft.shape}")
-        parts[sid] = (n, ppg, f0.reshape(-1), lft.reshape(-1))
+        parts[sid] = (n, ppg, None if pitch is None else pitch.reshape(-1), lft.reshape(-1))
     return parts, list(dict.fromkeys(list(chunks) + end)), end
 
 
@@ -1792,7 +1801,29 @@ class StreamSession:
     ``lag = stream_loudness_lag(hop)`` frames after it arrived (6 at hop 160) or at the stream's end; window k is ready
     when ``stream_ready_rows(final, ...)`` says so, ``final = stream_final_frames(seen, ended, hop)`` in ``seen``'s place,
     so a stream's rows are still ``window_plan([F], core, context)`` and stitching, running norms and horizons are
-    untouched.  ppg and f0 still come from outside.  ``"given"`` (the default): launches, bytes and bits as before.
+    untouched.  ``"given"`` (the default): launches, bytes and bits as before.
+
+    ``f0="audio"`` (needs ``loudness="audio"``) makes the F0 from that audio as well: a chunk is ``dict(ppg, audio)`` and
+    nothing else.  The recipe's F0 is ``pyworld.harvest``'s, a whole-file CPU algorithm; here the F0 is a DEFINITION, like
+    the running loudness floor: YIN (de Cheveigne & Kawahara 2002) per frame on the loudness frame ``x[k] = y[f hop - 1024
+    + k]``, ``k < 2048``, no window, reflection at 0 and - once the stream has ended - at ``F hop``.  With ``tau_min =
+    floor(sr / f0_ceil)``, ``tau_max = ceil(sr / f0_floor)`` (70 and 343 at 24 kHz with the defaults 340 and 70 Hz; ``tau_max
+    > 1024`` is a ``ValueError``) and ``W = 2048 - tau_max``: ``d(tau) = sum over 1 <= j < W of (x[j] - x[j + tau])^2`` for
+    ``tau = 1..tau_max``, computed directly in float32 (no FFT: no cancellation; ``x[0]`` is never read - frame 0's is sample
+    1024 by reflection, which has not arrived when the frame is final and hop divides 1024 - the loudness weights it by a
+    Hann zero); ``d'(tau) = d(tau) tau / (d(1) + ... + d(tau))``, and a constant frame (``d(1) == 0``) is unvoiced: no NaN;
+    the smallest ``tau`` in ``[tau_min, tau_max]`` with ``d'(tau) < f0_threshold`` (0.15), walked right while ``d'`` falls,
+    refined by a parabola through its neighbours (skipped at the range's ends and when ``d'(tau)`` is not the smallest of
+    the three); ``f0 = sr / tau_hat``, 0 when no lag qualifies.  The value is a function of the frame's 2048 samples alone -
+    no running state, no departure from the whole-file function ``f0_extract`` (svcc23_fastsvc_amd/f0.py), whose bits a
+    streamed frame has for every push schedule, slot and ring position.  The float64 reference is within 0.01 % of steady
+    harmonic tones at 70.5 - 339 Hz, calls 1e-3 white noise and digital silence unvoiced on every frame, and is within 0.8
+    % of a 110 -> 220 Hz glide over 0.4 s.  A frame's F0 is final when its loudness is, so the excitation
+    of a chunk is no longer made by the push that delivers it: ``_finalise_f0`` (two ``stream_f0`` launches,
+    csrc/fastsvc_stream_f0.hip) writes the raw F0 and the shifted F0 into two rings of ``cap`` frames and synthesises the
+    frames' excitation from the carried phase; the F0 shift of ``src_f0_stats`` / ``trg_f0_stats`` runs there, on the
+    device, in float64 (within one float32 ulp of ``F0Statistics.convert``).  Ring sizes, ``lag`` and latencies are
+    ``loudness="audio"``'s.  ``"given"`` (the default): launches, kernel arguments, bytes and bits as before.
 
     State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
     ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
@@ -1804,7 +1835,8 @@ class StreamSession:
     starts it), plus one scratch for the power rows of the ``max_push + lag`` frames a push can finalise per stream.  A
     ``push`` is a driver over named steps, whose docstrings say what each launches: ``check_stream_chunks``, ``_append``
     (one upload, one ``stream_push``), with ``loudness="audio"`` ``_finalise_loudness`` (two ``stream_loudness`` launches, or
-    none), ``stream_push_rows`` and, per ``max_batch`` ready rows, ``_forward_rows`` (``_run_rows``, a checked session's
+    none) and with ``f0="audio"`` ``_finalise_f0`` (two ``stream_f0`` launches when a frame became final),
+    ``stream_push_rows`` and, per ``max_batch`` ready rows, ``_forward_rows`` (``_run_rows``, a checked session's
     ``_check_rows``, ``_advance_carry``, the stitch); ``_collect`` waits once.  A push that
     completes no window runs no forward (``forwards`` counts them).
 
@@ -1812,7 +1844,8 @@ class StreamSession:
     with ``noise_amp == 0`` the streamed excitation IS ``signal_generator`` on the whole f0.  The noise is keyed by the
     stream's ``seed`` (mixed with the generator's) and the absolute sample index: it depends neither on the slot nor on
     the push sizes - and is another draw than ``signal_generator``'s, as ``convert_many``'s already is.  The F0 shift is
-    ``F0Statistics.convert`` on the host per chunk, as in ``DecodeSession.convert``.
+    ``F0Statistics.convert`` on the host per chunk, as in ``DecodeSession.convert`` (``f0="audio"``: on the device, when
+    the frames are final).
 
     Latency, in frames of input (``latency_frames``, ``latency_frames_max``): a sample of frame t is returned by the
     push that delivers frame ``(t // core + 1) core + context - 1`` - its window's last context frame; the last ``fade /
@@ -1848,12 +1881,15 @@ class StreamSession:
     ``push`` validates everything before it uploads or enqueues anything: a ``ValueError`` leaves the session as it
     was, ``last_report`` included.  Not thread-safe.  ``out_channels`` must be 1 and the signal generator's only signal
     "sine".  Not built: graph capture of the per-push chain, several GPUs; for ``loudness="audio"`` a preset peak for
-    calibration, a forgetting horizon for the maximum, ppg and f0 from audio."""
+    calibration, a forgetting horizon for the maximum, ppg from audio (it needs an ASR model that lives outside this
+    repository); ``f0="audio"`` without ``loudness="audio"``; octave-error smoothing across frames (the estimator is per
+    frame on purpose); a command-line flag for ``f0="audio"`` (the feature dumps hold no audio)."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
                  fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
                  horizon: Optional[float] = None, loudness: str = "given", checked: bool = False,
-                 fallback: Sequence[str] = ("bfloat16",)):
+                 fallback: Sequence[str] = ("bfloat16",), f0: str = "given", f0_floor: float = 70.0, f0_ceil: float = 340.0,
+                 f0_threshold: float = 0.15):
         from .engine import FastSVCError
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
@@ -1868,7 +1904,8 @@ class StreamSession:
             raise ValueError("StreamSession needs a signal generator whose only signal type is \"sine\"")
         self.hop = int(signal_generator.hop_size)
         for name, value in self._check_args(cfg, self.hop, n_streams, core, context, fade, max_push, max_batch, norm, horizon,
-                                            loudness, checked, fallback).items():
+                                            loudness, checked, fallback, f0, f0_floor, f0_ceil, f0_threshold,
+                                            float(signal_generator.sample_rate)).items():
             setattr(self, name, value)
         if self.checked and self.fallback and not hasattr(model, "use_activation_storage"):
             raise ValueError("a checked session with fallback storages needs a model with use_activation_storage() "
@@ -1884,21 +1921,24 @@ class StreamSession:
         # set to a dict to have push leave what it made there (tests): "excitation", per stream id the device tensors of
         # its chunks' excitation in order, "forwards", per forward (its rows, the assembled excitation rows), "y", per
         # forward (its rows, a clone of the waveforms that were stitched - after a checked session's fallbacks), and with
-        # loudness="audio" "lft", per stream id the device tensors of its newly final frames' loudness in order
+        # loudness="audio" "lft", per stream id the device tensors of its newly final frames' loudness in order; with
+        # f0="audio" "f0" and "f0_shifted", likewise the frames' raw and shifted F0 (and "excitation" is per finalisation)
         self._stream_trace: Optional[Dict[str, object]] = None
         self._closed = False
 
     @staticmethod
     def _check_args(cfg, hop: int, n_streams: int = 1, core: int = 32, context: Optional[int] = None, fade: int = 8,
                     max_push: Optional[int] = None, max_batch: int = 32, norm: str = "window", horizon: Optional[float] = None,
-                    loudness: str = "given", checked: bool = False, fallback: Sequence[str] = ("bfloat16",)) -> Dict[str, object]:
+                    loudness: str = "given", checked: bool = False, fallback: Sequence[str] = ("bfloat16",), f0: str = "given",
+                    f0_floor: float = 70.0, f0_ceil: float = 340.0, f0_threshold: float = 0.15,
+                    sample_rate: float = 24000.0) -> Dict[str, object]:
         """The constructor's arguments against the generator configuration ``cfg`` and the signal generator's ``hop``, with
         no device: a ``ValueError`` for the first one that is refused, else the session's attributes they resolve to -
         the arguments as given or defaulted (``fallback`` a tuple of storage names; a string is one name), ``channels``,
         ``lag``, the rings' ``cap``, the floats ``_slice`` a stream takes
         of the upload buffer (16-byte aligned) and ``_down_elems``, the samples of the download buffer (a push returns at
         most the frames a ring holds per stream, every row's run padded to 8 samples)."""
-        from .engine import STORAGE_CODES, STREAM_MAX_PUSH
+        from .engine import STORAGE_CODES, STREAM_MAX_PUSH, f0_lags
         fallback = (fallback,) if isinstance(fallback, str) else tuple(fallback)
         for name in fallback:
             if name not in STORAGE_CODES:
@@ -1923,13 +1963,22 @@ class StreamSession:
         horizon = check_horizon(horizon, core)
         if loudness not in ("given", "audio"):
             raise ValueError(f"loudness must be \"given\" or \"audio\", got {loudness!r}")
+        if f0 not in ("given", "audio"):
+            raise ValueError(f"f0 must be \"given\" or \"audio\", got {f0!r}")
+        if f0 == "audio":
+            if loudness != "audio":
+                raise ValueError("f0=\"audio\" needs loudness=\"audio\": the audio ring exists only there")
+            f0_lags(sample_rate, f0_floor, f0_ceil)      # (ValueError: tau_max > 1024, or no lag at all)
+            if not float(f0_threshold) > 0.0:
+                raise ValueError(f"f0_threshold must be > 0, got {f0_threshold}")
         lag = stream_loudness_lag(hop) if loudness == "audio" else 0
         cap = stream_ring_frames(core, context, max_push) if loudness == "given" else \
             stream_loudness_ring_frames(core, context, max_push, hop)
         C = int(cfg.in_channels)
         return dict(core=core, context=context, fade=fade, max_push=max_push, n_streams=n_streams, max_batch=max_batch,
                     channels=C, _takes_emb=takes_emb, norm=norm, horizon=horizon, loudness=loudness, lag=lag, cap=cap,
-                    checked=bool(checked), fallback=fallback,
+                    checked=bool(checked), fallback=fallback, f0=f0, f0_floor=float(f0_floor), f0_ceil=float(f0_ceil),
+                    f0_threshold=float(f0_threshold),
                     _slice=-(-max_push * (C + 1 + hop) // 4) * 4, _down_elems=n_streams * (cap * hop + 8 * (cap // core + 2)))
 
     def _allocate(self, cfg) -> None:
@@ -1949,6 +1998,11 @@ class StreamSession:
             self._audio = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
             self._peak = torch.empty((n, 2), dtype=torch.float32, device=dev)
             self._loud_scratch = torch.empty(stream_loudness_scratch_bytes(n, max_push + self.lag), dtype=torch.uint8, device=dev)
+        self._f0_raw = self._f0_shift = None
+        if self.f0 == "audio":
+            # the raw and the shifted F0 of the final frames (frame f at f % cap): what the excitation was made from
+            self._f0_raw = torch.empty((n, cap), dtype=torch.float32, device=dev)
+            self._f0_shift = torch.empty((n, cap), dtype=torch.float32, device=dev)
         self._layout = StreamStitchLayout(n, hop, self.fade)
         self._stage = torch.empty(max(self._layout.stage_elems, 1), dtype=torch.float32, device=dev)
         self._emb = torch.zeros((n, max(int(cfg.spk_emb_size), 1)), dtype=torch.float32, device=dev)
@@ -2008,7 +2062,7 @@ class StreamSession:
         torch.cuda.current_stream(self.device).synchronize()
         self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = self._carry = self._norm_scratch = None
         self._report = self._h_report = None
-        self._audio = self._peak = self._loud_scratch = None
+        self._audio = self._peak = self._loud_scratch = self._f0_raw = self._f0_shift = None
         self._h_up = self._d_up = self._h_down = self._up_done = None
         self._slots, self._ids = [None] * self.n_streams, {}
 
@@ -2071,12 +2125,15 @@ class StreamSession:
         if self._closed:
             raise RuntimeError("StreamSession is closed")
         # nothing is touched before every chunk has passed
-        parts, ids, end = check_stream_chunks(chunks, end, self._ids, self.channels, self.hop, self.max_push, self.loudness)
+        parts, ids, end = check_stream_chunks(chunks, end, self._ids, self.channels, self.hop, self.max_push, self.loudness,
+                                              self.f0)
         pushed = [sid for sid, part in parts.items() if part[0] > 0]
         if pushed:
             self._append(parts, pushed)
         if self.loudness == "audio":
-            self._finalise_loudness(ids, end)
+            final = self._finalise_loudness(ids, end)
+            if self.f0 == "audio" and final:
+                self._finalise_f0(final)
         streams = sorted((self._slots[self._ids[sid]] for sid in ids), key=lambda st: st.slot)
         rows, forget = stream_push_rows(streams, end, self.core, self.context, self.norm == "running", self.horizon)
         for r in rows:
@@ -2110,22 +2167,28 @@ class StreamSession:
         stream that has statistics, packs stream j's ppg, f0 and lft (or audio) into slice j, uploads the used slices in
         one copy and appends them, and synthesises their excitation, in one ``stream_push``.  Reads every stream's
         ``seen``, ``first`` and ``parity`` and leaves them advanced: ``seen`` by the chunk, the phase record's other entry
-        current.  Traces the chunks' excitation."""
+        current.  Traces the chunks' excitation.  With ``f0="audio"`` the slices hold ppg and audio only, the one
+        ``stream_push`` copies and synthesises nothing, and only ``seen`` advances: ``_finalise_f0`` owns the phase record
+        and the trace."""
         from .engine import stream_push
         hop, C, dev = self.hop, self.channels, self.device
         if self._up_done is not None:
             self._up_done.synchronize()                  # (the page-locked twin is still being read by the last upload)
         h = self._h_up.numpy()
         entries = []                                     # per stream (slot, n, up_off, pos, first, parity, seed), as stream_push takes them
+        own_f0 = self.f0 == "audio"                     # (no f0 in the slice, nothing synthesised: ``_finalise_f0`` does that)
         for j, sid in enumerate(pushed):
             n, ppg, f0, lft = parts[sid]
             st = self._slots[self._ids[sid]]
-            if st.stats is not None:
-                f0 = F0Statistics().convert(np.asarray(f0, dtype=np.float64), st.stats[0], st.stats[1])
             o = j * self._slice
             h[o: o + n * C] = ppg.reshape(-1)
-            h[o + n * C: o + n * C + n] = f0
-            h[o + n * C + n: o + n * (C + 1 + hop)] = lft
+            if own_f0:
+                h[o + n * C: o + n * (C + hop)] = lft
+            else:
+                if st.stats is not None:
+                    f0 = F0Statistics().convert(np.asarray(f0, dtype=np.float64), st.stats[0], st.stats[1])
+                h[o + n * C: o + n * C + n] = f0
+                h[o + n * C + n: o + n * (C + 1 + hop)] = lft
             entries.append((st.slot, n, o, st.seen, st.first, st.parity, st.seed))
         used = len(pushed) * self._slice
         self._d_up[:used].copy_(self._h_up[:used], non_blocking=True)
@@ -2133,11 +2196,15 @@ class StreamSession:
         self._up_done.record(torch.cuda.current_stream(dev))
         sg = self.signal_generator
         # (with loudness="audio" the chunk's third array is audio: the same copy appends it to the audio ring)
-        stream_push(self._d_up, *zip(*entries), self._ppg, self._audio if self.loudness == "audio" else self._lft, self._exc,
-                    self._phase, self.max_push, float(sg.sample_rate), float(sg.sine_amp), float(sg.noise_amp))
+        stream_push(self._d_up, *zip(*entries), self._ppg, self._audio if self.loudness == "audio" else self._lft,
+                    None if own_f0 else self._exc, None if own_f0 else self._phase, self.max_push, float(sg.sample_rate),
+                    float(sg.sine_amp), float(sg.noise_amp))
         for sid in pushed:
             st = self._slots[self._ids[sid]]
             n = parts[sid][0]
+            if own_f0:
+                st.seen += n
+                continue
             if self._stream_trace is not None:
                 idx = (torch.arange(st.seen, st.seen + n, device=dev) % self.cap)
                 self._stream_trace.setdefault("excitation", {}).setdefault(sid, []).append(
@@ -2151,7 +2218,7 @@ class StreamSession:
         stream's end (``end``), with or without a chunk - go from the audio ring into the lft ring: two launches for all
         streams (``stream_loudness``), none when no frame did.  Reads every stream's ``seen``, ``final`` and
         ``loud_parity`` and leaves ``final`` advanced and the peak record's other entry current.  Traces the frames'
-        loudness."""
+        loudness.  Returns the entries it finalised, ``(slot, first_frame, n, seen, ended, parity)`` per stream."""
         from .engine import stream_loudness
         entries = []                                     # per stream (slot, first_frame, n, seen, ended, parity), as stream_loudness takes them
         for sid in ids:
@@ -2160,7 +2227,7 @@ class StreamSession:
             if final > st.final:
                 entries.append((st.slot, st.final, final - st.final, st.seen, sid in end, st.loud_parity))
         if not entries:
-            return
+            return entries
         stream_loudness(self._audio, self._lft, self._peak, self._loud_scratch, *zip(*entries), self.cap, self.max_push + self.lag,
                         float(self.signal_generator.sample_rate))
         for s, f, n, _, _, _ in entries:
@@ -2171,6 +2238,32 @@ class StreamSession:
                     self._lft[s].view(self.cap, self.hop)[idx].reshape(-1))
             st.final = f + n
             st.loud_parity ^= 1                          # (enqueued: the other entry is the slot's peak now)
+        return entries
+
+    def _finalise_f0(self, final) -> None:
+        """``f0="audio"``: the frames ``_finalise_loudness`` just finalised (``final``, its entries) get their F0 from the
+        audio ring, the F0 shift of a stream that has statistics - on the device, in float64 - and their excitation: two
+        launches for all streams (``stream_f0``).  Reads every stream's ``parity`` and leaves the phase record's other
+        entry current.  Traces the frames' raw F0 (``"f0"``), shifted F0 (``"f0_shifted"``) and ``"excitation"``."""
+        from .engine import stream_f0
+        sg = self.signal_generator
+        slots, first, n, seen, ended, _ = zip(*final)
+        sts = [self._slots[s] for s in slots]
+        stream_f0(self._audio, self._f0_raw, self._f0_shift, self._exc, self._phase, slots, first, n, seen, ended,
+                  [st.parity for st in sts], [st.seed for st in sts],
+                  [None if st.stats is None else (*st.stats[0][:2], *st.stats[1][:2]) for st in sts], self.cap,
+                  self.max_push + self.lag, float(sg.sample_rate), self.f0_floor, self.f0_ceil, self.f0_threshold,
+                  float(sg.sine_amp), float(sg.noise_amp))
+        for st, f, k in zip(sts, first, n):
+            if self._stream_trace is not None:
+                idx = (torch.arange(f, f + k, device=self.device) % self.cap)
+                tr = self._stream_trace
+                tr.setdefault("f0", {}).setdefault(st.id, []).append(self._f0_raw[st.slot][idx])
+                tr.setdefault("f0_shifted", {}).setdefault(st.id, []).append(self._f0_shift[st.slot][idx])
+                tr.setdefault("excitation", {}).setdefault(st.id, []).append(
+                    self._exc[st.slot].view(self.cap, self.hop)[idx].reshape(-1))
+            st.first = False
+            st.parity ^= 1                               # (enqueued: the other entry is the slot's phase now)
 
     def _forward_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], off: int, report=None):
         """One forward over the rows ``chunk`` (at most ``max_batch``, as ``stream_push_rows`` orders them; ``forget``

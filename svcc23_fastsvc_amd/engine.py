@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "fastsvc_window_launch_count", "fastsvc_window_assemble", "fastsvc_window_stitch",
     "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble", "fastsvc_stream_check",
     "fastsvc_stream_loudness_scratch_bytes", "fastsvc_stream_loudness",
+    "fastsvc_stream_f0", "fastsvc_f0_lags", "fastsvc_f0_extract",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -230,6 +231,14 @@ def load_library():
                                             ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, i32, i32, i32,
                                             ctypes.c_float, vp]
     lib.fastsvc_stream_loudness.restype = ctypes.c_int
+    lib.fastsvc_stream_f0.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                      ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32] + [ctypes.c_float] * 6 + [vp]
+    lib.fastsvc_stream_f0.restype = ctypes.c_int
+    lib.fastsvc_f0_lags.argtypes = [ctypes.c_float] * 3 + [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.fastsvc_f0_lags.restype = ctypes.c_int
+    lib.fastsvc_f0_extract.argtypes = [vp, vp, i32, i32, i32] + [ctypes.c_float] * 4 + [vp]
+    lib.fastsvc_f0_extract.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -704,8 +713,8 @@ def _stream_rings(who: str, ppg_ring, lft_ring, exc_ring):
 
 def stream_push(upload: torch.Tensor, streams: Sequence[int], n: Sequence[int], up_off: Sequence[int], pos: Sequence[int],
                 first: Sequence[int], parity: Sequence[int], seed: Sequence[int], ppg_ring: torch.Tensor, lft_ring: torch.Tensor,
-                exc_ring: torch.Tensor, phase: torch.Tensor, max_push: int, sample_rate: float, sine_amp: float,
-                noise_amp: float) -> None:
+                exc_ring: Optional[torch.Tensor], phase: Optional[torch.Tensor], max_push: int, sample_rate: float,
+                sine_amp: float, noise_amp: float) -> None:
     """Append chunks to the rings of live streams and synthesise their excitation, by ONE HIP launch per 64 streams on
     the current stream (fastsvc_stream_push, csrc/fastsvc_stream.hip; none when every chunk is empty).
 
@@ -714,13 +723,19 @@ def stream_push(upload: torch.Tensor, streams: Sequence[int], n: Sequence[int], 
     then f0 ``n``, then lft ``n x hop``.  ``ppg_ring (n_streams, cap, C)``, ``lft_ring`` / ``exc_ring (n_streams, cap *
     hop)``: frame p of a stream at index ``p % cap``.  ``phase (n_streams, 2)`` float64: the push reads entry
     ``parity[i]`` (or starts at 0 when ``first[i]``) and writes entry ``parity[i] ^ 1``.  ``seed[i]`` keys the noise
-    together with the absolute sample index.  Anything out of range raises ``ValueError`` before a launch and changes
-    nothing; fails loudly off the GPU."""
+    together with the absolute sample index.  ``exc_ring=None`` (and ``phase=None``): the slices hold NO f0 - ppg ``n x
+    C``, then ``n x hop`` samples for ``lft_ring`` - and nothing is synthesised (``StreamSession(f0="audio")``, whose
+    excitation ``stream_f0`` makes when the frames are final).  Anything out of range raises ``ValueError`` before a launch
+    and changes nothing; fails loudly off the GPU."""
     lib = load_library()
-    n_streams, cap, C, hop = _stream_rings("stream_push", ppg_ring, lft_ring, exc_ring)
-    _gpu_tensors("stream_push", ppg_ring, (("upload", upload, torch.float32, 1), ("phase", phase, torch.float64, 2)))
-    if tuple(phase.shape) != (n_streams, 2):
+    synth = exc_ring is not None
+    if not synth and phase is not None:
+        raise ValueError("stream_push without an exc_ring synthesises nothing: it takes no phase")
+    n_streams, cap, C, hop = _stream_rings("stream_push", ppg_ring, lft_ring, exc_ring if synth else lft_ring)
+    _gpu_tensors("stream_push", ppg_ring, (("upload", upload, torch.float32, 1),) + ((("phase", phase, torch.float64, 2),) if synth else ()))
+    if synth and tuple(phase.shape) != (n_streams, 2):
         raise ValueError(f"phase must be ({n_streams}, 2), got {tuple(phase.shape)}")
+    per_frame = C + (1 if synth else 0) + hop
     S = len(streams)
     max_push = int(max_push)
     if S == 0 or any(len(v) != S for v in (n, up_off, pos, first, parity, seed)):
@@ -735,8 +750,8 @@ def stream_push(upload: torch.Tensor, streams: Sequence[int], n: Sequence[int], 
             raise ValueError(f"stream {s} outside [0, {n_streams})")
         if not 0 <= k <= max_push:
             raise ValueError(f"stream {s}: {k} frames, outside [0, max_push {max_push}]")
-        if o < 0 or o + k * (C + 1 + hop) > upload.numel():
-            raise ValueError(f"stream {s}: its slice [{o}, +{k * (C + 1 + hop)}) leaves the upload buffer of {upload.numel()} elements")
+        if o < 0 or o + k * per_frame > upload.numel():
+            raise ValueError(f"stream {s}: its slice [{o}, +{k * per_frame}) leaves the upload buffer of {upload.numel()} elements")
         if int(pos[i]) < 0:
             raise ValueError(f"stream {s}: position {int(pos[i])} out of range")
     i32, i64 = ctypes.c_int32, ctypes.c_int64
@@ -891,6 +906,75 @@ def stream_loudness(audio_ring: torch.Tensor, lft_ring: torch.Tensor, peak: torc
                                                 _ints(i32, [int(v) & 1 for v in parity]), n_streams, cap, max_frames, hop,
                                                 ctypes.c_float(float(sample_rate)), ctypes.c_void_p(stream)),
                "fastsvc_stream_loudness")
+
+
+F0_MAX_LAG = 1024           # the largest lag: half the 2048-sample frame
+
+
+def f0_lags(sample_rate: float, f0_floor: float = 70.0, f0_ceil: float = 340.0) -> Tuple[int, int]:
+    """The lags the YIN estimator searches, ``(tau_min, tau_max) = (floor(sr / f0_ceil), ceil(sr / f0_floor))`` with the
+    three taken as float32 (what the kernels get): (70, 343) at 24 kHz with the defaults.  ``ValueError`` unless ``1 <=
+    tau_min <= tau_max <= 1024`` - the frame is 2048 samples and the difference function sums over ``2048 - tau_max``.  Host
+    arithmetic only: fastsvc_f0_lags (csrc/fastsvc_f0.hip) computes the same two and refuses the same."""
+    sr, lo, hi = (float(np.float32(v)) for v in (sample_rate, f0_floor, f0_ceil))
+    if not (sr > 0.0 and lo > 0.0 and hi >= lo and sr / lo < 1e6):
+        raise ValueError(f"F0 search range needs sample_rate > 0 and 0 < f0_floor <= f0_ceil, got {sample_rate}, {f0_floor}, {f0_ceil}")
+    tau_min, tau_max = int(math.floor(sr / hi)), int(math.ceil(sr / lo))
+    if tau_min < 1 or tau_max > F0_MAX_LAG or tau_min > tau_max:
+        raise ValueError(f"F0 lags [{tau_min}, {tau_max}] outside [1, {F0_MAX_LAG}]: f0_ceil {f0_ceil} above the sample rate, or "
+                         f"f0_floor {f0_floor} below sample_rate / {F0_MAX_LAG}")
+    return tau_min, tau_max
+
+
+def stream_f0(audio_ring: torch.Tensor, f0_ring: torch.Tensor, f0s_ring: torch.Tensor, exc_ring: torch.Tensor, phase: torch.Tensor,
+              streams: Sequence[int], first_frame: Sequence[int], n: Sequence[int], seen: Sequence[int], ended: Sequence[int],
+              parity: Sequence[int], seed: Sequence[int], stats: Sequence[Optional[Sequence[float]]], cap: int, max_frames: int,
+              sample_rate: float, f0_floor: float, f0_ceil: float, threshold: float, sine_amp: float, noise_amp: float) -> None:
+    """The F0 (YIN, ``f0_extract``'s function frame by frame), its Gaussian log-F0 shift and the excitation of the frames of
+    live streams that have become final, from their audio rings, by TWO HIP launches per 64 streams on the current stream
+    (fastsvc_stream_f0, csrc/fastsvc_stream_f0.hip; none when every ``n[i]`` is 0).
+
+    ``audio_ring`` and ``exc_ring`` are ``(n_streams, cap * hop)``, ``f0_ring`` (raw) and ``f0s_ring`` (shifted) ``(n_streams,
+    cap)``: frame f at index ``f % cap``.  Entry i takes the ``n[i]`` frames from ``first_frame[i]`` of stream ``streams[i]``
+    with ``seen[i]`` frames arrived and ``ended[i]`` - ``stream_loudness``'s entries.  ``stats[i]``: ``(m0, s0, m1, s1)``, the
+    source's and the target's mean and std of log F0, or None for no shift.  ``phase (n_streams, 2)`` float64: read at entry
+    ``parity[i]`` (or started at 0 when ``first_frame[i] == 0``), written at ``parity[i] ^ 1``; ``seed[i]`` keys the noise with
+    the absolute sample index.  Anything out of range raises ``ValueError`` before a launch and changes nothing; fails loudly
+    off the GPU."""
+    lib = load_library()
+    _gpu_tensors("stream_f0", audio_ring, (("audio_ring", audio_ring, torch.float32, 2), ("f0_ring", f0_ring, torch.float32, 2),
+                                           ("f0s_ring", f0s_ring, torch.float32, 2), ("exc_ring", exc_ring, torch.float32, 2),
+                                           ("phase", phase, torch.float64, 2)))
+    n_streams, cap, max_frames = int(audio_ring.shape[0]), int(cap), int(max_frames)
+    if cap < 4 or cap % 4 or audio_ring.shape[1] == 0 or audio_ring.shape[1] % cap or exc_ring.shape != audio_ring.shape:
+        raise ValueError(f"audio_ring and exc_ring must both be (n_streams, cap * hop) with cap {cap} a multiple of 4, got "
+                         f"{tuple(audio_ring.shape)} and {tuple(exc_ring.shape)}")
+    hop = int(audio_ring.shape[1]) // cap
+    if tuple(f0_ring.shape) != (n_streams, cap) or tuple(f0s_ring.shape) != (n_streams, cap) or tuple(phase.shape) != (n_streams, 2):
+        raise ValueError(f"f0_ring and f0s_ring must be ({n_streams}, {cap}) and phase ({n_streams}, 2)")
+    if not 1 <= max_frames <= min(cap, STREAM_LOUDNESS_MAX_FRAMES):
+        raise ValueError(f"max_frames must be in [1, min(cap {cap}, {STREAM_LOUDNESS_MAX_FRAMES})], got {max_frames}")
+    f0_lags(sample_rate, f0_floor, f0_ceil)
+    S = len(streams)
+    if S == 0 or any(len(v) != S for v in (first_frame, n, seen, ended, parity, seed, stats)):
+        raise ValueError("stream_f0 needs at least one stream and one entry per stream in every array")
+    flat = []
+    for st in stats:
+        flat += [float("nan")] * 4 if st is None else [float(v) for v in st]
+    if len(flat) != 4 * S:
+        raise ValueError("stats entries are (m0, s0, m1, s1) or None")
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    with torch.cuda.device(audio_ring.device):
+        stream = torch.cuda.current_stream(audio_ring.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_f0(_ptr(audio_ring), _ptr(f0_ring), _ptr(f0s_ring), _ptr(exc_ring), _ptr(phase), S,
+                                          _ints(i32, streams), _ints(i64, first_frame), _ints(i32, n), _ints(i64, seen),
+                                          _ints(i32, [1 if v else 0 for v in ended]), _ints(i32, [int(v) & 1 for v in parity]),
+                                          _ints(ctypes.c_uint64, [int(x) & 0xFFFFFFFFFFFFFFFF for x in seed]),
+                                          (ctypes.c_double * len(flat))(*flat), n_streams, cap, max_frames, hop,
+                                          ctypes.c_float(float(sample_rate)), ctypes.c_float(float(f0_floor)),
+                                          ctypes.c_float(float(f0_ceil)), ctypes.c_float(float(threshold)),
+                                          ctypes.c_float(float(sine_amp)), ctypes.c_float(float(noise_amp)), ctypes.c_void_p(stream)),
+               "fastsvc_stream_f0")
 
 
 def check_norm_groups(norm_groups, lens: Sequence[int]):

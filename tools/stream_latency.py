@@ -27,6 +27,11 @@ to profiles/decode_stream_horizon.txt.
 32 streams at core 32 in both storages: the audio session is pushed samples and makes the loudness on the device (two more
 launches per push, csrc/fastsvc_stream_loudness.hip).  Its figures go to profiles/decode_stream_loudness.txt.
 
+--f0: the pair is StreamSession(f0="audio") against StreamSession(f0="given"), both with loudness="audio", on the same ppg and
+audio, 1, 8 and 32 streams at core 32 in both storages: the f0 session is pushed no F0 and makes it, its shift and the
+excitation on the device when the frames are final (two more launches per push, csrc/fastsvc_stream_f0.hip).  Reported, not
+gated.  Its figures go to profiles/decode_stream_f0.txt.
+
 --checked: the pair is StreamSession(checked=True) against StreamSession() in float16 activation storage on the same chunks, 1,
 8 and 32 streams at core 32, with norm="window" and norm="running": the checked session adds one stream_check launch, a copy
 of 16 bytes a row and ONE wait per forward (nothing falls back: the streams stay in range).  The difference is quoted next to
@@ -281,6 +286,66 @@ def main_audio():
         f.write("\n".join(out) + "\n")
 
 
+def main_f0():
+    core = 32
+    lag = Dc.stream_loudness_lag(hop)
+    out = [f"stream F0: one StreamSession.push that completes one window per stream (every stream delivers {core} frames), host to "
+           f"host, f0=audio (the chunk carries ppg and {core} x {hop} samples of audio; the push finalises {core} frames of F0 by YIN, "
+           f"their F0 shift and their excitation per stream on the device, {lag} frames behind the audio: two more launches, "
+           f"csrc/fastsvc_stream_f0.hip) against f0=given (the chunk carries the F0, shifted on the host; the push synthesises the "
+           f"excitation), both with loudness=audio on the same ppg and audio, two sessions in one process; context {ctx}, fade "
+           f"{FADE}, speaker embedding, F0 shift on, int16 out; {pushes} pushes per repetition, {reps} repetitions, legs alternated, "
+           f"median of the repetitions' means (min, max); {torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    t = np.arange(core * 8 * hop) / SR
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for N in (1, 8, 32):
+            src = [features(core * 8) for _ in range(N)]
+            for i, f in enumerate(src):                  # (a voiced tone per stream over a little noise)
+                ph = 2.0 * np.pi * (110.0 + 7.0 * i) * t
+                f["audio"] = (0.3 * np.sin(ph) + 0.1 * np.sin(2.0 * ph) + 0.01 * rng.standard_normal(t.size)).astype(np.float32)[:, None]
+            legs = {}
+            for name in ("given", "audio"):
+                s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, loudness="audio", f0=name)
+                legs[name] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[])
+
+            def push(leg, name):
+                a = (leg["step"] % 8) * core
+                leg["step"] += 1
+                chunks = {}
+                for i, f in zip(leg["ids"], src):
+                    chunks[i] = {"ppg": f["ppg"][a: a + core], "audio": f["audio"][a * hop: (a + core) * hop]}
+                    if name == "given":
+                        chunks[i]["f0"] = f["f0"][a: a + core]
+                return leg["s"].push(chunks)
+            for name, leg in legs.items():
+                for _ in range(6):                       # (fill the context, warm every shape)
+                    push(leg, name)
+                before = leg["s"].forwards
+                got = push(leg, name)
+                assert leg["s"].forwards == before + 1 and all(v.size == core * hop for v in got.values())
+            for _ in range(reps):
+                for name, leg in legs.items():
+                    t0 = time.perf_counter()
+                    for _ in range(pushes):
+                        push(leg, name)
+                    leg["t"].append((time.perf_counter() - t0) / pushes)
+            for leg in legs.values():
+                leg["s"].end(leg["ids"])
+                leg["s"].close()
+            audio = N * core * hop / SR
+            mg, line_g = spread(f"{N:2d} streams, core {core:3d}: push, f0=given", legs["given"]["t"], audio)
+            ma, line_a = spread(f"{N:2d} streams, core {core:3d}: push, f0=audio", legs["audio"]["t"], audio)
+            out += [line_g, line_a, f"    audio / given {ma / mg:.3f} ({(ma - mg) * 1e3:+.0f} us a push; spread of the given leg "
+                                    f"{(max(legs['given']['t']) - min(legs['given']['t'])) * 1e6:.0f} us)"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream_f0.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 def main_checked():
     core, storage = 32, "float16"
     out = [f"checked streams: one StreamSession.push that completes one window per stream (every stream delivers {core} frames), "
@@ -336,6 +401,8 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     if "--checked" in argv:
         main_checked()
+    elif "--f0" in argv:
+        main_f0()
     elif "--audio" in argv:
         main_audio()
     elif "--horizon" in argv:
