@@ -727,6 +727,35 @@ int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, 
                       int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
                       float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_);
 
+/* fastsvc_stream_f0 for calls in which a stream runs SOURCE STATISTICS (decode.RunningF0Stats): a live stream
+ * has no corpus to take the source's mean and std of log F0 from, so they are defined causally, per frame, and carried on the
+ * device.  Everything is fastsvc_stream_f0's - arguments, rings, phase, checks - plus:
+ *   running       HOST, 6 doubles per entry: prior mean m_p, prior std s_p > 0, prior weight n0 > 0 (frames), decay g in
+ *                 (0, 1] (exp(-1 / horizon), or exactly 1: nothing is forgotten), target mean m_t, target std s_t - all
+ *                 finite - or six NaN: the entry runs none, and `stats` says what it gets, as in fastsvc_stream_f0.  An entry
+ *                 with running statistics has four NaN in `stats`.
+ *   stats_record  device, (n_streams, 2, 4) doubles, 8-byte aligned: per stream two entries of (w, S1, S2, voiced frames).
+ *                 The call reads entry parity[i] - or starts from zeros when first_frame[i] == 0, which reads nothing, so the
+ *                 record is never zeroed and a reused slot is fresh - and writes entry parity[i] ^ 1: the phase record's bit.
+ * The rule, frame by frame in order, for a final frame with raw F0 v: v <= 0 gives 0 and leaves the state alone; else, every
+ * operation a separately rounded double operation,
+ *   d = log((double) v) - m_p;   w = w g + 1;   S1 = S1 g + d;   S2 = S2 g + d d;   N = n0 + w;   mu = S1 / N
+ *   var = (n0 s_p s_p + S2) / N - mu mu;   f0s = (float) exp((s_t / sqrt(var)) (d - mu) + m_t)
+ * so a frame is shifted by the statistics of the voiced frames up to and including itself, blended with a prior that counts as
+ * n0 frames; var >= n0 s_p^2 / N > 0 (Cauchy-Schwarz): no NaN, no floor.  The value depends on the stream's frames alone, not
+ * on how they fall into calls.  One launch more than fastsvc_stream_f0 per 64 entries, between its two - one block per stream
+ * with running statistics and frames in the call: all lanes take d, one lane runs the three sums in frame order, all lanes
+ * shift and overwrite f0s_ring, 256 frames a tile - and none more when no entry of the 64 has any; plain vector stores, no
+ * atomics; no load or store outside the stream's rows of f0_ring, f0s_ring and its record pair.  Checked on the host before
+ * anything is enqueued, in addition: a null or misaligned record, null `running`, constants that are not finite, s_p <= 0,
+ * n0 <= 0, g outside (0, 1], an entry with both kinds of statistics: FASTSVC_E_INVALID. */
+int fastsvc_stream_f0_running(const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase,
+                              double* stats_record, int32_t S, const int32_t* stream, const int64_t* first_frame,
+                              const int32_t* n, const int64_t* seen, const int32_t* ended, const int32_t* parity,
+                              const uint64_t* seed, const double* stats, const double* running, int32_t n_streams, int32_t cap,
+                              int32_t max_frames, int32_t hop, float sample_rate, float f0_floor, float f0_ceil, float threshold,
+                              float sine_amp, float noise_amp, void* stream_);
+
 /* ---- F0 of whole files by YIN (csrc/fastsvc_f0.hip, csrc/fastsvc_f0.inc; de Cheveigne & Kawahara 2002) ----
  * The recipe's F0 is pyworld.harvest's, a whole-file CPU algorithm; this is a per-frame DEFINITION that
  * a live stream can compute as well.  Frames and conventions are fastsvc_loudness_extract's: audio (B, T) device float32,

@@ -16,8 +16,15 @@
 //                       write the samples with fastsvc_signal.inc's closed form into exc_ring, the noise keyed by the seed
 //                       and the ABSOLUTE sample index - stream_push_kernel's excitation part, from the shifted F0 ring
 //
-// The second launch reads what the first wrote: two launches, ordered by the stream.  Descriptors travel IN the kernel
-// arguments, 64 streams per launch.  Plain vector stores, no atomics, no tunables.
+//   stream_f0_running   (fastsvc_stream_f0_running alone, between the two) one block per stream that runs SOURCE STATISTICS
+//                       (decode.RunningF0Stats) and has frames in the call: all lanes read the call's raw F0 from f0_ring
+//                       and take d = log f0 - m_p in float64, one lane runs the recurrence of the three sums (w, S1, S2) in
+//                       frame order from rec[slot][parity] into LDS, all lanes shift their frame by the statistics up to
+//                       and including it and overwrite f0s_ring; 256 frames a tile, the state carried from tile to tile,
+//                       the block writes rec[slot][parity ^ 1] (first_frame == 0 starts from zeros and reads nothing)
+//
+// Every launch reads what the one before wrote: two launches (three with running statistics), ordered by the stream.
+// Descriptors travel IN the kernel arguments, 64 streams per launch.  Plain vector stores, no atomics, no tunables.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -69,6 +76,82 @@ __device__ __forceinline__ float shift_f0(float f, double m0, double ratio, doub
     const double q = ratio * d;
     const double s = q + m1;
     return (float)exp(s);
+}
+
+constexpr int SF_TILE = 256;                        // frames of one stream the running shift holds in LDS at a time
+
+struct RunArgs {                                    // per BLOCK of the running shift: a stream that runs statistics and has frames
+    double mp[SF_MAX], n0[SF_MAX], prior[SF_MAX];   // prior mean, prior weight in frames, n0 s_p s_p
+    double g[SF_MAX], mt[SF_MAX], st[SF_MAX];       // decay per voiced frame, target mean and std
+    int pos[SF_MAX];                                // the first frame's place in the rings: first % cap
+    int slot[SF_MAX];
+    int nf[SF_MAX];                                 // frames << 2 | bit 1: the record entry to read | bit 0: start from zeros
+};
+static_assert(sizeof(RunArgs) + 64 <= 4096, "a kernel takes at most 4 KiB of arguments");
+
+// The running source statistics: a final voiced frame with d = log f0 - m_p updates w = w g + 1, S1 = S1 g + d,
+// S2 = S2 g + d d and is shifted by mu = S1 / (n0 + w), var = (n0 s_p^2 + S2) / (n0 + w) - mu^2 - itself included; an unvoiced
+// frame is 0 and leaves the state alone.  Every operation a separately rounded double operation, as in shift_f0.
+__global__ __launch_bounds__(SF_TILE)
+void stream_f0_running_kernel(RunArgs r, int cap, const float* __restrict__ f0_ring, float* __restrict__ f0s_ring,
+                              double* __restrict__ rec) {
+    #pragma clang fp contract(off)
+    __shared__ double sd[SF_TILE], sw[SF_TILE], s1[SF_TILE], s2[SF_TILE];
+    __shared__ unsigned char voiced[SF_TILE];
+    __shared__ double state[4];                     // w, S1, S2, voiced frames: carried from tile to tile
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = r.nf[b] >> 2, flags = r.nf[b] & 3, slot = r.slot[b], pos = r.pos[b];
+    const double mp = r.mp[b], n0 = r.n0[b], prior = r.prior[b], g = r.g[b], mt = r.mt[b], st = r.st[b];
+    const float* raw = f0_ring + (long)slot * cap;
+    float* out = f0s_ring + (long)slot * cap;
+    double* mine = rec + (long)slot * 8;
+    if (tid < 4) state[tid] = (flags & 1) ? 0.0 : mine[4 * (flags >> 1) + tid];
+    for (int t0 = 0; t0 < n; t0 += SF_TILE) {       // (n is uniform per block)
+        const int f = t0 + tid;
+        const int at = (pos + f) % cap;
+        const float v = f < n ? raw[at] : 0.f;
+        const bool on = v > 0.f;
+        const double d = on ? log((double)v) - mp : 0.0;
+        sd[tid] = d;
+        voiced[tid] = on ? 1 : 0;
+        __syncthreads();
+        if (tid == 0) {
+            double w = state[0], a1 = state[1], a2 = state[2], count = state[3];
+            const int m = n - t0 < SF_TILE ? n - t0 : SF_TILE;
+            for (int j = 0; j < m; ++j) {
+                if (voiced[j]) {
+                    const double dj = sd[j];
+                    const double wg = w * g, a1g = a1 * g, a2g = a2 * g, dd = dj * dj;
+                    w = wg + 1.0;
+                    a1 = a1g + dj;
+                    a2 = a2g + dd;
+                    count = count + 1.0;
+                }
+                sw[j] = w; s1[j] = a1; s2[j] = a2;
+            }
+            state[0] = w; state[1] = a1; state[2] = a2; state[3] = count;
+        }
+        __syncthreads();
+        if (f < n) {
+            float res = 0.f;
+            if (on) {
+                const double N = n0 + sw[tid];
+                const double mu = s1[tid] / N;
+                const double e2 = prior + s2[tid];
+                const double m2 = e2 / N;
+                const double mumu = mu * mu;
+                const double var = m2 - mumu;       // >= n0 s_p^2 / N > 0 by Cauchy-Schwarz
+                const double ratio = st / sqrt(var);
+                const double c = d - mu;
+                const double q = ratio * c;
+                const double s = q + mt;
+                res = (float)exp(s);
+            }
+            out[at] = res;
+        }
+        __syncthreads();                            // (the next tile overwrites the sums)
+    }
+    if (tid < 4) mine[4 * ((flags >> 1) ^ 1) + tid] = state[tid];
 }
 
 __global__ __launch_bounds__(256)
@@ -156,34 +239,36 @@ void stream_f0_excite_kernel(F0Args a, F0Seeds sd, F0Dims d, float sr, const flo
     }
 }
 
-int invalid(const char* fmt, long a = 0, long b = 0, long c = 0, long e = 0) {
-    char buf[240];
-    snprintf(buf, sizeof buf, fmt, a, b, c, e);
+int invalid(const char* who, const char* fmt, long a = 0, long b = 0, long c = 0, long e = 0) {
+    char buf[280];
+    const int at = snprintf(buf, sizeof buf, "%s: ", who);
+    snprintf(buf + at, sizeof buf - at, fmt, a, b, c, e);
     return fastsvc::set_last_error(FASTSVC_E_INVALID, buf);
 }
 
-}  // namespace
+bool is_finite(double v) { return v == v && v > -1e300 && v < 1e300; }
 
-extern "C" {
-
-int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase, int32_t S,
-                      const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
-                      const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats,
-                      int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
-                      float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_) {
+// Both entry points: `who` names the one that was called.  fastsvc_stream_f0 passes no record and no running constants, and
+// then this validates, fills and launches exactly what it always did.
+int stream_f0_run(const char* who, const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase,
+                  double* rec, int32_t S, const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                  const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats, const double* running,
+                  int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
+                  float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_) {
     if (!audio_ring || !f0_ring || !f0s_ring || !exc_ring || !phase || !stream || !first_frame || !n || !seen || !ended ||
             !parity || !seed || !stats)
-        return invalid("fastsvc_stream_f0: null pointer");
+        return invalid(who, "null pointer");
     if (S < 1 || n_streams < 1 || cap < 4 || (cap & 3) || hop < 1 || (int64_t)cap * hop > INT32_MAX || max_frames < 1 ||
             max_frames > SF_MAX_FRAMES || max_frames > cap || !(sample_rate > 0.f) ||
             (int64_t)n_streams * cap * hop > ((int64_t)1 << 40))
-        return invalid("fastsvc_stream_f0: size out of range (S %ld, cap %ld: a multiple of 4, hop %ld, max_frames %ld: at most cap)",
+        return invalid(who, "size out of range (S %ld, cap %ld: a multiple of 4, hop %ld, max_frames %ld: at most cap)",
                        S, cap, hop, max_frames);
     if ((reinterpret_cast<uintptr_t>(audio_ring) & 3) || (reinterpret_cast<uintptr_t>(f0_ring) & 3) ||
             (reinterpret_cast<uintptr_t>(f0s_ring) & 3) || (reinterpret_cast<uintptr_t>(exc_ring) & 15) ||
             (reinterpret_cast<uintptr_t>(phase) & 7))
-        return invalid("fastsvc_stream_f0: misaligned pointer (the excitation ring: 16 bytes, the phase: 8)");
-    if (!(threshold > 0.f)) return invalid("fastsvc_stream_f0: threshold must be > 0");
+        return invalid(who, "misaligned pointer (the excitation ring: 16 bytes, the phase: 8)");
+    if (reinterpret_cast<uintptr_t>(rec) & 7) return invalid(who, "misaligned pointer (the statistics record: 8 bytes)");
+    if (!(threshold > 0.f)) return invalid(who, "threshold must be > 0");
     F0Params p;
     if (const int rc = fastsvc_f0_lags(sample_rate, f0_floor, f0_ceil, &p.tau_min, &p.tau_max)) return rc;
     p.sr = sample_rate; p.threshold = threshold;
@@ -191,27 +276,35 @@ int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, 
     int64_t most = 0;
     for (int i = 0; i < S; ++i) {
         const int64_t s = stream[i], k = n[i], f = first_frame[i], q = seen[i];
-        if (s < 0 || s >= n_streams) return invalid("fastsvc_stream_f0: entry %ld: stream %ld outside [0, %ld)", i, s, n_streams);
+        if (s < 0 || s >= n_streams) return invalid(who, "entry %ld: stream %ld outside [0, %ld)", i, s, n_streams);
         for (int j = 0; j < i; ++j)
-            if (stream[j] == s) return invalid("fastsvc_stream_f0: stream %ld is listed twice in one call", s);
+            if (stream[j] == s) return invalid(who, "stream %ld is listed twice in one call", s);
         if (k < 0 || k > max_frames)
-            return invalid("fastsvc_stream_f0: stream %ld: %ld frames, outside [0, max_frames %ld]", s, k, max_frames);
+            return invalid(who, "stream %ld: %ld frames, outside [0, max_frames %ld]", s, k, max_frames);
         if (f < 0 || q < 0 || q > ((int64_t)1 << 40) || f + k > q)
-            return invalid("fastsvc_stream_f0: stream %ld: frames [%ld, +%ld) of %ld seen", s, f, k, q);
-        if ((ended[i] & ~1) || (parity[i] & ~1)) return invalid("fastsvc_stream_f0: stream %ld: ended and parity are 0 or 1", s);
+            return invalid(who, "stream %ld: frames [%ld, +%ld) of %ld seen", s, f, k, q);
+        if ((ended[i] & ~1) || (parity[i] & ~1)) return invalid(who, "stream %ld: ended and parity are 0 or 1", s);
         const double* st = stats + 4 * i;               // (source mean, source std, target mean, target std), or four NaN: no shift
-        auto finite = [](double v) { return v == v && v > -1e300 && v < 1e300; };
         const bool none = st[0] != st[0] && st[1] != st[1] && st[2] != st[2] && st[3] != st[3];
-        if (!none && !(finite(st[0]) && finite(st[1]) && finite(st[2]) && finite(st[3]) && st[1] > 0.0))
-            return invalid("fastsvc_stream_f0: stream %ld: statistics are four finite values with a source std > 0, or four NaN for none", s);
+        if (!none && !(is_finite(st[0]) && is_finite(st[1]) && is_finite(st[2]) && is_finite(st[3]) && st[1] > 0.0))
+            return invalid(who, "stream %ld: statistics are four finite values with a source std > 0, or four NaN for none", s);
+        if (running) {                                  // (m_p, s_p, n0, g, m_t, s_t), or six NaN: the stream runs no statistics
+            const double* ru = running + 6 * i;
+            bool off = true, fin = true;
+            for (int e = 0; e < 6; ++e) { off = off && ru[e] != ru[e]; fin = fin && is_finite(ru[e]); }
+            if (!off && !(fin && ru[1] > 0.0 && ru[2] > 0.0 && ru[3] > 0.0 && ru[3] <= 1.0))
+                return invalid(who, "stream %ld: running statistics are six finite values (prior mean, prior std > 0, prior frames "
+                                    "> 0, decay in (0, 1], target mean, target std), or six NaN for none", s);
+            if (!off && !none) return invalid(who, "stream %ld: given statistics and running statistics exclude each other", s);
+        }
         if (k == 0) continue;
         // every frame is final: it reads up to (f + k - 1) hop + 1023, or the stream has ended and these are its last frames
         if (ended[i] ? f + k != q : (f + k - 1) * hop + LD_NFFT / 2 > q * hop)
-            return invalid("fastsvc_stream_f0: stream %ld: frames [%ld, +%ld) are not final with %ld frames seen", s, f, k, q);
+            return invalid(who, "stream %ld: frames [%ld, +%ld) are not final with %ld frames seen", s, f, k, q);
         // ... and the ring still holds what the first of them reads: from sample max(0, f hop - 1024) on
         const int64_t lowest = f * hop > LD_NFFT / 2 ? f * hop - LD_NFFT / 2 : 0;
         if (lowest < q * hop - ring_len)
-            return invalid("fastsvc_stream_f0: stream %ld: frame %ld reads samples the ring of %ld no longer holds (%ld frames seen)",
+            return invalid(who, "stream %ld: frame %ld reads samples the ring of %ld no longer holds (%ld frames seen)",
                            s, f, ring_len, q);
         most = k > most ? k : most;
     }
@@ -224,7 +317,8 @@ int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, 
         F0Args a;
         F0Shift sh;
         F0Seeds sd;
-        int grid = 0;
+        RunArgs ra;
+        int grid = 0, nrun = 0;
         for (int i = 0; i < SF_MAX; ++i) {
             const bool on = i < nb;
             const double* st = stats + 4 * (b0 + (on ? i : 0));
@@ -239,17 +333,62 @@ int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, 
             sh.ratio[i] = shift ? st[3] / st[1] : 1.0;      // (one double division, as numpy does it on the host)
             sh.m1[i] = shift ? st[2] : 0.0;
             grid = a.n[i] > grid ? a.n[i] : grid;
+            const double* ru = running ? running + 6 * (b0 + (on ? i : 0)) : nullptr;
+            if (ru && on && a.n[i] > 0 && ru[0] == ru[0]) {
+                ra.mp[nrun] = ru[0]; ra.n0[nrun] = ru[2]; ra.prior[nrun] = ru[2] * ru[1] * ru[1];
+                ra.g[nrun] = ru[3]; ra.mt[nrun] = ru[4]; ra.st[nrun] = ru[5];
+                ra.pos[nrun] = (int)(first_frame[b0 + i] % cap);
+                ra.slot[nrun] = a.slot[i];
+                ra.nf[nrun] = (a.n[i] << 2) | (parity[b0 + i] << 1) | (first_frame[b0 + i] == 0 ? 1 : 0);
+                ++nrun;
+            }
         }
         if (grid == 0) continue;
         int64_t gx = (((int64_t)grid * hop + 3) / 4 + 255) / 256;
         gx = gx > SF_MAX_BLOCKS ? SF_MAX_BLOCKS : gx;
         hipLaunchKernelGGL(stream_f0_frames_kernel, dim3((unsigned)grid, (unsigned)nb), dim3(256), 0, hs, a, sh, d, p, audio_ring,
                            f0_ring, f0s_ring);
+        if (nrun) {
+            for (int i = nrun; i < SF_MAX; ++i) {       // (entries no block reads)
+                ra.mp[i] = ra.n0[i] = ra.prior[i] = ra.g[i] = ra.mt[i] = ra.st[i] = 0.0;
+                ra.pos[i] = ra.slot[i] = ra.nf[i] = 0;
+            }
+            hipLaunchKernelGGL(stream_f0_running_kernel, dim3((unsigned)nrun), dim3(SF_TILE), 0, hs, ra, (int)cap, f0_ring, f0s_ring, rec);
+        }
         hipLaunchKernelGGL(stream_f0_excite_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, hs, a, sd, d, sample_rate, f0s_ring,
                            exc_ring, phase);
     }
-    return hipGetLastError() == hipSuccess ? FASTSVC_OK
-                                           : fastsvc::set_last_error(FASTSVC_E_HIP, "fastsvc_stream_f0: launch failed");
+    if (hipGetLastError() == hipSuccess) return FASTSVC_OK;
+    char buf[80];
+    snprintf(buf, sizeof buf, "%s: launch failed", who);
+    return fastsvc::set_last_error(FASTSVC_E_HIP, buf);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase, int32_t S,
+                      const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                      const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats,
+                      int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
+                      float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_) {
+    return stream_f0_run("fastsvc_stream_f0", audio_ring, f0_ring, f0s_ring, exc_ring, phase, nullptr, S, stream, first_frame, n,
+                         seen, ended, parity, seed, stats, nullptr, n_streams, cap, max_frames, hop, sample_rate, f0_floor,
+                         f0_ceil, threshold, sine_amp, noise_amp, stream_);
+}
+
+int fastsvc_stream_f0_running(const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase,
+                              double* stats_record, int32_t S, const int32_t* stream, const int64_t* first_frame,
+                              const int32_t* n, const int64_t* seen, const int32_t* ended, const int32_t* parity,
+                              const uint64_t* seed, const double* stats, const double* running, int32_t n_streams, int32_t cap,
+                              int32_t max_frames, int32_t hop, float sample_rate, float f0_floor, float f0_ceil, float threshold,
+                              float sine_amp, float noise_amp, void* stream_) {
+    const char* who = "fastsvc_stream_f0_running";
+    if (!stats_record || !running) return invalid(who, "null pointer (the statistics record or the running constants)");
+    return stream_f0_run(who, audio_ring, f0_ring, f0s_ring, exc_ring, phase, stats_record, S, stream, first_frame, n, seen, ended,
+                         parity, seed, stats, running, n_streams, cap, max_frames, hop, sample_rate, f0_floor, f0_ceil, threshold,
+                         sine_amp, noise_amp, stream_);
 }
 
 }  // extern "C"

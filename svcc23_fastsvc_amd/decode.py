@@ -62,6 +62,85 @@ class F0Statistics:
         return cvf0
 
 
+@dataclass(frozen=True)
+class RunningF0Stats:
+    """Source F0 statistics a live stream makes for itself: pass it to ``StreamSession.open`` as ``src_f0_stats`` where a
+    ``[mean, std]`` of log F0 over a corpus goes, which a live microphone does not have (``StreamSession``'s docstring and
+    DESIGN.md 4.10 have the rule).  ``prior``: ``[mean, std]`` of log F0 the stream starts from, finite with ``std > 0``, or
+    None for the target's statistics - the stream then begins almost unshifted; ``prior_frames``: the voiced frames the prior
+    counts as, finite and ``> 0`` (it is never forgotten); ``horizon``: None, or the voiced frames after which a frame counts
+    with 1 / e, finite and ``>= 1``.  Immutable; a ``ValueError`` for anything else."""
+    prior: Optional[Tuple[float, float]] = None
+    prior_frames: float = 100.0
+    horizon: Optional[float] = None
+
+    def __post_init__(self):
+        if self.prior is not None:
+            try:
+                mean, std = (float(v) for v in self.prior)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"prior must be None or [mean, std] of log F0, got {self.prior!r}") from e
+            if not (math.isfinite(mean) and math.isfinite(std) and std > 0.0):
+                raise ValueError(f"prior must be a finite [mean, std] with std > 0, got {self.prior!r}")
+            object.__setattr__(self, "prior", (mean, std))
+        try:
+            frames = float(self.prior_frames)
+            horizon = None if self.horizon is None else float(self.horizon)
+        except (TypeError, ValueError) as e:
+            raise ValueError("prior_frames and horizon must be numbers") from e
+        if not (math.isfinite(frames) and frames > 0.0):
+            raise ValueError(f"prior_frames must be finite and > 0, got {self.prior_frames!r}")
+        if horizon is not None and not (math.isfinite(horizon) and horizon >= 1.0):
+            raise ValueError(f"horizon must be None or finite and >= 1 (voiced frames), got {self.horizon!r}")
+        object.__setattr__(self, "prior_frames", frames)
+        object.__setattr__(self, "horizon", horizon)
+
+    @property
+    def decay(self) -> float:
+        """``g``: what a voiced frame multiplies the sums before it by - ``exp(-1 / horizon)``, exactly 1.0 without one."""
+        return 1.0 if self.horizon is None else math.exp(-1.0 / self.horizon)
+
+    def constants(self, trg_f0_stats: Sequence[float]) -> Tuple[float, float, float, float, float, float]:
+        """The rule's six constants for a target ``[mean, std]``: ``(m_p, s_p, n0, g, m_t, s_t)``."""
+        try:
+            m_t, s_t = (float(v) for v in list(trg_f0_stats)[:2])
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"trg_f0_stats must be [mean, std] of log F0, got {trg_f0_stats!r}") from e
+        if not (math.isfinite(m_t) and math.isfinite(s_t)):
+            raise ValueError(f"trg_f0_stats must be finite, got {trg_f0_stats!r}")
+        m_p, s_p = (m_t, s_t) if self.prior is None else self.prior
+        if not s_p > 0.0:
+            raise ValueError(f"without a prior the target's std is the prior's and must be > 0, got {s_p}")
+        return m_p, s_p, self.prior_frames, self.decay, m_t, s_t
+
+
+def running_f0_convert(f0: np.ndarray, running: RunningF0Stats, trg_f0_stats: Sequence[float]) -> np.ndarray:
+    """The running shift of a whole F0 track on the host - for ``RunningF0Stats`` what ``F0Statistics.convert`` is for fixed
+    statistics, and what a stream opened with ``running`` applies frame by frame on the device.  Frames in order, from ``(w,
+    S1, S2) = (0, 0, 0)``; an unvoiced frame (``f0 <= 0``) is 0 and changes nothing; a voiced one, every operation a separately
+    rounded float64 operation::
+
+        d = log(f0) - m_p;  w = w g + 1;  S1 = S1 g + d;  S2 = S2 g + d d;  N = n0 + w;  mu = S1 / N
+        var = (n0 s_p s_p + S2) / N - mu mu;  out = exp((s_t / sqrt(var)) (d - mu) + m_t)
+
+    Returns float64 (the device rounds it to float32)."""
+    m_p, s_p, n0, g, m_t, s_t = running.constants(trg_f0_stats)
+    f0 = np.asarray(f0).reshape(-1)
+    out = np.zeros(f0.size)
+    voiced = f0 > 0
+    d = np.log(f0[voiced].astype(np.float64)) - m_p
+    mu, var = np.empty(d.size), np.empty(d.size)
+    prior = n0 * s_p * s_p
+    w = s1 = s2 = 0.0
+    for k, dk in enumerate(d.tolist()):              # (Python floats: IEEE doubles, one rounding per operation)
+        w, s1, s2 = w * g + 1.0, s1 * g + dk, s2 * g + dk * dk
+        N = n0 + w
+        m = s1 / N
+        mu[k], var[k] = m, (prior + s2) / N - m * m
+    out[voiced] = np.exp((s_t / np.sqrt(var)) * (d - mu) + m_t)
+    return out
+
+
 def convert_f0_device(f0: torch.Tensor, orgf0stats: Sequence[float], tarf0stats: Sequence[float]) -> torch.Tensor:
     """``F0Statistics.convert`` on a device tensor of any shape (float64 inside, like numpy)."""
     f = f0.to(torch.float64)
@@ -795,6 +874,7 @@ class _Stream:
     norm_parity: int = 0             # norm="running": the carry record's current entry (flips with every forward)
     norm_w: float = 0.0              # ... and the weighted frames it holds (``running_horizon_rows``' w)
     totals: Optional[dict] = None    # a checked session: what its windows' reports add up to since ``open``
+    running: Optional[tuple] = None  # RunningF0Stats' six constants (m_p, s_p, n0, g, m_t, s_t): the record at ``parity`` is its state
 
     @property
     def complete(self) -> int:
@@ -1825,6 +1905,32 @@ class StreamSession:
     device, in float64 (within one float32 ulp of ``F0Statistics.convert``).  Ring sizes, ``lag`` and latencies are
     ``loudness="audio"``'s.  ``"given"`` (the default): launches, kernel arguments, bytes and bits as before.
 
+    ``open(trg_emb, src_f0_stats=RunningF0Stats(prior, prior_frames, horizon), trg_f0_stats=[m_t, s_t])`` (``f0="audio"``
+    sessions) makes the source statistics of the F0 shift from the stream itself - a live microphone has no corpus to take
+    them from.  Like the running loudness floor it is a DEFINITION: with the prior ``(m_p, s_p)`` (None: the target's), its
+    weight ``n0 = prior_frames``, ``g = exp(-1 / horizon)`` (one ``math.exp`` at ``open``; exactly 1.0 without a horizon) and the
+    state ``(w, S1, S2) = (0, 0, 0)`` at ``open``, the final frames are taken in order: raw F0 ``v <= 0`` gives 0 and leaves the
+    state alone - silence neither counts nor forgets - and a voiced frame, in float64, every operation rounded separately::
+
+        d = log(v) - m_p;  w = w g + 1;  S1 = S1 g + d;  S2 = S2 g + d d;  N = n0 + w;  mu = S1 / N
+        var = (n0 s_p s_p + S2) / N - mu mu;  out = (float) exp((s_t / sqrt(var)) (d - mu) + m_t)
+
+    Frame f is shifted by the statistics of the voiced frames ``<= f``, itself included, blended with a prior that counts as
+    ``n0`` frames and is never forgotten; the voiced frame j voiced frames back counts with ``g^j``.  ``var >= n0 s_p^2 / N > 0``
+    (Cauchy-Schwarz): no NaN, no division by zero, no floor parameter.  Without a horizon ``m_p + mu`` and ``var`` tend to the
+    mean and population variance of the source's log F0, so the output tends to ``F0Statistics.convert(f0, estimate([f0 so
+    far]), trg)`` - on 3000 frames wandering between 120 and 200 Hz the last fifth is within 9.0e-3 relative of ``convert`` with
+    the whole track's ``estimate`` for ``prior_frames=1`` and 1.56e-1 for 100 (8.97e-2 and 4.06e-1 with ``horizon=200``: the
+    prior keeps its share for ever, so a horizon wants a small ``prior_frames``).  With prior = target a stream
+    begins almost unshifted and moves to the target's register as evidence arrives.  The value depends on the stream's
+    frames alone, not on push sizes, slot or ring position.  On the device: a float64 record ``(n_streams, 2, 4)`` of ``(w, S1,
+    S2, voiced frames)`` - allocated with ``f0="audio"``, never zeroed, a stream's frame 0 starts from zeros, addressed by the
+    phase record's parity - and ONE more launch between the F0 and the excitation in a push where a stream with running
+    statistics got final frames (``stream_f0_running``); streams with list statistics or none keep their meaning, and a
+    push without a running stream its launches, kernel arguments and bytes.  All three kinds may be open at once.
+    ``f0_stats(id)`` reads the record back; ``running_f0_convert`` is the rule on the host.  Within one float32 ulp of the
+    float64 reference over the traced raw F0 (0 measured).
+
     State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
     ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
     upload buffer with a page-locked twin and one page-locked download buffer; with ``norm="running"`` per stream one
@@ -1835,7 +1941,8 @@ class StreamSession:
     starts it), plus one scratch for the power rows of the ``max_push + lag`` frames a push can finalise per stream.  A
     ``push`` is a driver over named steps, whose docstrings say what each launches: ``check_stream_chunks``, ``_append``
     (one upload, one ``stream_push``), with ``loudness="audio"`` ``_finalise_loudness`` (two ``stream_loudness`` launches, or
-    none) and with ``f0="audio"`` ``_finalise_f0`` (two ``stream_f0`` launches when a frame became final),
+    none) and with ``f0="audio"`` ``_finalise_f0`` (two ``stream_f0`` launches when a frame became final, three with running F0
+    statistics),
     ``stream_push_rows`` and, per ``max_batch`` ready rows, ``_forward_rows`` (``_run_rows``, a checked session's
     ``_check_rows``, ``_advance_carry``, the stitch); ``_collect`` waits once.  A push that
     completes no window runs no forward (``forwards`` counts them).
@@ -1883,7 +1990,8 @@ class StreamSession:
     "sine".  Not built: graph capture of the per-push chain, several GPUs; for ``loudness="audio"`` a preset peak for
     calibration, a forgetting horizon for the maximum, ppg from audio (it needs an ASR model that lives outside this
     repository); ``f0="audio"`` without ``loudness="audio"``; octave-error smoothing across frames (the estimator is per
-    frame on purpose); a command-line flag for ``f0="audio"`` (the feature dumps hold no audio)."""
+    frame on purpose); a command-line flag for ``f0="audio"`` (the feature dumps hold no audio); for ``RunningF0Stats`` a std
+    floor or a mean-only mode, and ``f0="given"`` sessions (the host shifts per chunk there)."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
                  fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
@@ -1998,11 +2106,14 @@ class StreamSession:
             self._audio = torch.empty((n, cap * hop), dtype=torch.float32, device=dev)
             self._peak = torch.empty((n, 2), dtype=torch.float32, device=dev)
             self._loud_scratch = torch.empty(stream_loudness_scratch_bytes(n, max_push + self.lag), dtype=torch.uint8, device=dev)
-        self._f0_raw = self._f0_shift = None
+        self._f0_raw = self._f0_shift = self._f0_rec = None
         if self.f0 == "audio":
             # the raw and the shifted F0 of the final frames (frame f at f % cap): what the excitation was made from
             self._f0_raw = torch.empty((n, cap), dtype=torch.float32, device=dev)
             self._f0_shift = torch.empty((n, cap), dtype=torch.float32, device=dev)
+            # running source statistics: per stream two parity entries of (w, S1, S2, voiced frames), never zeroed - a stream's
+            # first frame starts from zeros - addressed by the phase record's ``parity``
+            self._f0_rec = torch.empty((n, 2, 4), dtype=torch.float64, device=dev)
         self._layout = StreamStitchLayout(n, hop, self.fade)
         self._stage = torch.empty(max(self._layout.stage_elems, 1), dtype=torch.float32, device=dev)
         self._emb = torch.zeros((n, max(int(cfg.spk_emb_size), 1)), dtype=torch.float32, device=dev)
@@ -2062,15 +2173,16 @@ class StreamSession:
         torch.cuda.current_stream(self.device).synchronize()
         self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = self._carry = self._norm_scratch = None
         self._report = self._h_report = None
-        self._audio = self._peak = self._loud_scratch = self._f0_raw = self._f0_shift = None
+        self._audio = self._peak = self._loud_scratch = self._f0_raw = self._f0_shift = self._f0_rec = None
         self._h_up = self._d_up = self._h_down = self._up_done = None
         self._slots, self._ids = [None] * self.n_streams, {}
 
-    def open(self, trg_emb=None, src_f0_stats: Optional[Sequence[float]] = None, trg_f0_stats: Optional[Sequence[float]] = None,
-             seed: int = 0) -> int:
+    def open(self, trg_emb=None, src_f0_stats=None, trg_f0_stats: Optional[Sequence[float]] = None, seed: int = 0) -> int:
         """A new stream in a free slot -> its id (ids are never reused; a slot is, after ``end``).  ``trg_emb``: the target
         speaker's embedding or None - every open stream must agree on having one, because a forward takes ``spk_emb`` for
-        all its rows or for none.  ``src_f0_stats`` and ``trg_f0_stats`` ([mean, std] of log F0): both or neither."""
+        all its rows or for none.  ``src_f0_stats`` and ``trg_f0_stats`` ([mean, std] of log F0): both or neither; a
+        ``RunningF0Stats`` as ``src_f0_stats`` (``f0="audio"`` sessions) makes the stream run its own source statistics.  A
+        ``ValueError`` leaves the session as it was."""
         if self._closed:
             raise RuntimeError("StreamSession is closed")
         free = [s for s in range(self.n_streams) if self._slots[s] is None]
@@ -2083,6 +2195,12 @@ class StreamSession:
             raise ValueError("every open stream needs a speaker embedding, or none does")
         if (src_f0_stats is None) != (trg_f0_stats is None):
             raise ValueError("an F0 shift needs src_f0_stats and trg_f0_stats")
+        running = None
+        if isinstance(src_f0_stats, RunningF0Stats):
+            if self.f0 != "audio":
+                raise ValueError("running F0 statistics need a session with f0=\"audio\": with f0=\"given\" the host shifts "
+                                 "every chunk (not built)")
+            running, src_f0_stats, trg_f0_stats = src_f0_stats.constants(trg_f0_stats), None, None
         s = free[0]
         if has_emb:
             e = np.asarray(trg_emb, dtype=np.float32).reshape(-1)
@@ -2093,7 +2211,8 @@ class StreamSession:
         self._next_id += 1
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
         self._slots[s] = _Stream(id=sid, slot=s, emb=has_emb, seed=key, from_audio=self.loudness == "audio",
-                                 stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)))
+                                 stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)),
+                                 running=running)
         if self.checked:
             self._slots[s].totals = dict(windows=0, fell_back=0, nonfinite=0, clipped=0, max_abs=0.0, storages={})
         self._ids[sid] = s
@@ -2109,6 +2228,32 @@ class StreamSession:
         if sid not in self._ids:
             raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
         return float(self._slots[self._ids[sid]].norm_w)
+
+    def f0_stats(self, sid: int) -> Dict[str, float]:
+        """What a stream opened with ``RunningF0Stats`` knows of its source after the frames that are final: ``dict(mean, std,
+        voiced_frames, weight, observed_mean, observed_std)``.  ``mean`` and ``std`` are the statistics of log F0 the last
+        final voiced frame was shifted with (``m_p + mu``, ``sqrt(var)``: the prior's before the first one); ``weight`` is
+        ``w``, ``voiced_frames`` their count; ``observed_mean`` and ``observed_std`` are the same without the prior (``m_p +
+        S1 / w``, ``sqrt(S2 / w - (S1 / w)^2)``), NaN while ``w == 0`` - what to save for a speaker and hand back as ``prior``
+        with a large ``prior_frames`` next time.  Reads the stream's current record on the device: one download of 32 bytes
+        and a WAIT for everything enqueued before it - for the end of a conversation, not for the push loop.  ``ValueError``
+        for a stream that is not open or runs no statistics."""
+        if sid not in self._ids:
+            raise ValueError(f"stream {sid} is not open (unknown, or it has ended)")
+        st = self._slots[self._ids[sid]]
+        if st.running is None:
+            raise ValueError(f"stream {sid} was not opened with RunningF0Stats")
+        m_p, s_p, n0, _, _, _ = st.running
+        # (before the stream's first final frame the record holds whatever the slot's last stream left: the state is zeros)
+        w, s1, s2, count = (0.0,) * 4 if st.first else self._f0_rec[st.slot, st.parity].cpu().tolist()
+        N = n0 + w
+        mu = s1 / N
+        out = dict(mean=m_p + mu, std=math.sqrt((n0 * s_p * s_p + s2) / N - mu * mu), voiced_frames=int(count), weight=w,
+                   observed_mean=float("nan"), observed_std=float("nan"))
+        if w > 0.0:
+            om = s1 / w
+            out["observed_mean"], out["observed_std"] = m_p + om, math.sqrt(max(s2 / w - om * om, 0.0))
+        return out
 
     def end(self, ids) -> Dict[int, np.ndarray]:
         """``push({}, end=ids)``: flush these streams and free their slots."""
@@ -2243,17 +2388,22 @@ class StreamSession:
     def _finalise_f0(self, final) -> None:
         """``f0="audio"``: the frames ``_finalise_loudness`` just finalised (``final``, its entries) get their F0 from the
         audio ring, the F0 shift of a stream that has statistics - on the device, in float64 - and their excitation: two
-        launches for all streams (``stream_f0``).  Reads every stream's ``parity`` and leaves the phase record's other
-        entry current.  Traces the frames' raw F0 (``"f0"``), shifted F0 (``"f0_shifted"``) and ``"excitation"``."""
-        from .engine import stream_f0
+        launches for all streams (``stream_f0``), three (``stream_f0_running``) when one of them runs its source statistics,
+        whose record is read and written like the phase's.  Reads every stream's ``parity`` and leaves the phase record's
+        other entry current.  Traces the frames' raw F0 (``"f0"``), shifted F0 (``"f0_shifted"``) and ``"excitation"``."""
+        from .engine import stream_f0, stream_f0_running
         sg = self.signal_generator
         slots, first, n, seen, ended, _ = zip(*final)
         sts = [self._slots[s] for s in slots]
-        stream_f0(self._audio, self._f0_raw, self._f0_shift, self._exc, self._phase, slots, first, n, seen, ended,
-                  [st.parity for st in sts], [st.seed for st in sts],
-                  [None if st.stats is None else (*st.stats[0][:2], *st.stats[1][:2]) for st in sts], self.cap,
-                  self.max_push + self.lag, float(sg.sample_rate), self.f0_floor, self.f0_ceil, self.f0_threshold,
+        rings = (self._audio, self._f0_raw, self._f0_shift, self._exc, self._phase)
+        entries = (slots, first, n, seen, ended, [st.parity for st in sts], [st.seed for st in sts],
+                   [None if st.stats is None else (*st.stats[0][:2], *st.stats[1][:2]) for st in sts])
+        consts = (self.cap, self.max_push + self.lag, float(sg.sample_rate), self.f0_floor, self.f0_ceil, self.f0_threshold,
                   float(sg.sine_amp), float(sg.noise_amp))
+        if any(st.running is not None for st in sts):
+            stream_f0_running(*rings, self._f0_rec, *entries, [st.running for st in sts], *consts)
+        else:
+            stream_f0(*rings, *entries, *consts)
         for st, f, k in zip(sts, first, n):
             if self._stream_trace is not None:
                 idx = (torch.arange(f, f + k, device=self.device) % self.cap)

@@ -52,7 +52,7 @@ ABI_SYMBOLS = (
     "fastsvc_window_launch_count", "fastsvc_window_assemble", "fastsvc_window_stitch",
     "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble", "fastsvc_stream_check",
     "fastsvc_stream_loudness_scratch_bytes", "fastsvc_stream_loudness",
-    "fastsvc_stream_f0", "fastsvc_f0_lags", "fastsvc_f0_extract",
+    "fastsvc_stream_f0", "fastsvc_stream_f0_running", "fastsvc_f0_lags", "fastsvc_f0_extract",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -235,6 +235,11 @@ def load_library():
                                       ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64),
                                       ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32] + [ctypes.c_float] * 6 + [vp]
     lib.fastsvc_stream_f0.restype = ctypes.c_int
+    lib.fastsvc_stream_f0_running.argtypes = [vp, vp, vp, vp, vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64),
+                                              ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32] + [ctypes.c_float] * 6 + [vp]
+    lib.fastsvc_stream_f0_running.restype = ctypes.c_int
     lib.fastsvc_f0_lags.argtypes = [ctypes.c_float] * 3 + [ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.fastsvc_f0_lags.restype = ctypes.c_int
     lib.fastsvc_f0_extract.argtypes = [vp, vp, i32, i32, i32] + [ctypes.c_float] * 4 + [vp]
@@ -926,6 +931,38 @@ def f0_lags(sample_rate: float, f0_floor: float = 70.0, f0_ceil: float = 340.0) 
     return tau_min, tau_max
 
 
+def _stream_f0_args(who: str, audio_ring, f0_ring, f0s_ring, exc_ring, phase, streams, first_frame, n, seen, ended, parity, seed,
+                    stats, cap: int, max_frames: int, sample_rate: float, f0_floor: float, f0_ceil: float):
+    """What ``stream_f0`` and ``stream_f0_running`` check on the host, and the arguments the two entry points share from ``S``
+    to ``stats`` and from ``n_streams`` to ``hop``: -> (S .. stats as ctypes, (n_streams, cap, max_frames, hop))."""
+    _gpu_tensors(who, audio_ring, (("audio_ring", audio_ring, torch.float32, 2), ("f0_ring", f0_ring, torch.float32, 2),
+                                   ("f0s_ring", f0s_ring, torch.float32, 2), ("exc_ring", exc_ring, torch.float32, 2),
+                                   ("phase", phase, torch.float64, 2)))
+    n_streams, cap, max_frames = int(audio_ring.shape[0]), int(cap), int(max_frames)
+    if cap < 4 or cap % 4 or audio_ring.shape[1] == 0 or audio_ring.shape[1] % cap or exc_ring.shape != audio_ring.shape:
+        raise ValueError(f"audio_ring and exc_ring must both be (n_streams, cap * hop) with cap {cap} a multiple of 4, got "
+                         f"{tuple(audio_ring.shape)} and {tuple(exc_ring.shape)}")
+    hop = int(audio_ring.shape[1]) // cap
+    if tuple(f0_ring.shape) != (n_streams, cap) or tuple(f0s_ring.shape) != (n_streams, cap) or tuple(phase.shape) != (n_streams, 2):
+        raise ValueError(f"f0_ring and f0s_ring must be ({n_streams}, {cap}) and phase ({n_streams}, 2)")
+    if not 1 <= max_frames <= min(cap, STREAM_LOUDNESS_MAX_FRAMES):
+        raise ValueError(f"max_frames must be in [1, min(cap {cap}, {STREAM_LOUDNESS_MAX_FRAMES})], got {max_frames}")
+    f0_lags(sample_rate, f0_floor, f0_ceil)
+    S = len(streams)
+    if S == 0 or any(len(v) != S for v in (first_frame, n, seen, ended, parity, seed, stats)):
+        raise ValueError(f"{who} needs at least one stream and one entry per stream in every array")
+    flat = []
+    for st in stats:
+        flat += [float("nan")] * 4 if st is None else [float(v) for v in st]
+    if len(flat) != 4 * S:
+        raise ValueError("stats entries are (m0, s0, m1, s1) or None")
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    per = (S, _ints(i32, streams), _ints(i64, first_frame), _ints(i32, n), _ints(i64, seen),
+           _ints(i32, [1 if v else 0 for v in ended]), _ints(i32, [int(v) & 1 for v in parity]),
+           _ints(ctypes.c_uint64, [int(x) & 0xFFFFFFFFFFFFFFFF for x in seed]), (ctypes.c_double * len(flat))(*flat))
+    return per, (n_streams, cap, max_frames, hop)
+
+
 def stream_f0(audio_ring: torch.Tensor, f0_ring: torch.Tensor, f0s_ring: torch.Tensor, exc_ring: torch.Tensor, phase: torch.Tensor,
               streams: Sequence[int], first_frame: Sequence[int], n: Sequence[int], seen: Sequence[int], ended: Sequence[int],
               parity: Sequence[int], seed: Sequence[int], stats: Sequence[Optional[Sequence[float]]], cap: int, max_frames: int,
@@ -942,39 +979,54 @@ def stream_f0(audio_ring: torch.Tensor, f0_ring: torch.Tensor, f0s_ring: torch.T
     the absolute sample index.  Anything out of range raises ``ValueError`` before a launch and changes nothing; fails loudly
     off the GPU."""
     lib = load_library()
-    _gpu_tensors("stream_f0", audio_ring, (("audio_ring", audio_ring, torch.float32, 2), ("f0_ring", f0_ring, torch.float32, 2),
-                                           ("f0s_ring", f0s_ring, torch.float32, 2), ("exc_ring", exc_ring, torch.float32, 2),
-                                           ("phase", phase, torch.float64, 2)))
-    n_streams, cap, max_frames = int(audio_ring.shape[0]), int(cap), int(max_frames)
-    if cap < 4 or cap % 4 or audio_ring.shape[1] == 0 or audio_ring.shape[1] % cap or exc_ring.shape != audio_ring.shape:
-        raise ValueError(f"audio_ring and exc_ring must both be (n_streams, cap * hop) with cap {cap} a multiple of 4, got "
-                         f"{tuple(audio_ring.shape)} and {tuple(exc_ring.shape)}")
-    hop = int(audio_ring.shape[1]) // cap
-    if tuple(f0_ring.shape) != (n_streams, cap) or tuple(f0s_ring.shape) != (n_streams, cap) or tuple(phase.shape) != (n_streams, 2):
-        raise ValueError(f"f0_ring and f0s_ring must be ({n_streams}, {cap}) and phase ({n_streams}, 2)")
-    if not 1 <= max_frames <= min(cap, STREAM_LOUDNESS_MAX_FRAMES):
-        raise ValueError(f"max_frames must be in [1, min(cap {cap}, {STREAM_LOUDNESS_MAX_FRAMES})], got {max_frames}")
-    f0_lags(sample_rate, f0_floor, f0_ceil)
-    S = len(streams)
-    if S == 0 or any(len(v) != S for v in (first_frame, n, seen, ended, parity, seed, stats)):
-        raise ValueError("stream_f0 needs at least one stream and one entry per stream in every array")
-    flat = []
-    for st in stats:
-        flat += [float("nan")] * 4 if st is None else [float(v) for v in st]
-    if len(flat) != 4 * S:
-        raise ValueError("stats entries are (m0, s0, m1, s1) or None")
-    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    per, dims = _stream_f0_args("stream_f0", audio_ring, f0_ring, f0s_ring, exc_ring, phase, streams, first_frame, n, seen, ended,
+                                parity, seed, stats, cap, max_frames, sample_rate, f0_floor, f0_ceil)
     with torch.cuda.device(audio_ring.device):
         stream = torch.cuda.current_stream(audio_ring.device).cuda_stream
-        _check(lib, lib.fastsvc_stream_f0(_ptr(audio_ring), _ptr(f0_ring), _ptr(f0s_ring), _ptr(exc_ring), _ptr(phase), S,
-                                          _ints(i32, streams), _ints(i64, first_frame), _ints(i32, n), _ints(i64, seen),
-                                          _ints(i32, [1 if v else 0 for v in ended]), _ints(i32, [int(v) & 1 for v in parity]),
-                                          _ints(ctypes.c_uint64, [int(x) & 0xFFFFFFFFFFFFFFFF for x in seed]),
-                                          (ctypes.c_double * len(flat))(*flat), n_streams, cap, max_frames, hop,
+        _check(lib, lib.fastsvc_stream_f0(_ptr(audio_ring), _ptr(f0_ring), _ptr(f0s_ring), _ptr(exc_ring), _ptr(phase), *per, *dims,
                                           ctypes.c_float(float(sample_rate)), ctypes.c_float(float(f0_floor)),
                                           ctypes.c_float(float(f0_ceil)), ctypes.c_float(float(threshold)),
                                           ctypes.c_float(float(sine_amp)), ctypes.c_float(float(noise_amp)), ctypes.c_void_p(stream)),
                "fastsvc_stream_f0")
+
+
+def stream_f0_running(audio_ring: torch.Tensor, f0_ring: torch.Tensor, f0s_ring: torch.Tensor, exc_ring: torch.Tensor,
+                      phase: torch.Tensor, record: Optional[torch.Tensor], streams: Sequence[int], first_frame: Sequence[int],
+                      n: Sequence[int], seen: Sequence[int], ended: Sequence[int], parity: Sequence[int], seed: Sequence[int],
+                      stats: Sequence[Optional[Sequence[float]]], running: Sequence[Optional[Sequence[float]]], cap: int,
+                      max_frames: int, sample_rate: float, f0_floor: float, f0_ceil: float, threshold: float, sine_amp: float,
+                      noise_amp: float) -> None:
+    """``stream_f0`` for a call in which a stream runs source statistics (``decode.RunningF0Stats``): THREE HIP launches per 64
+    streams of which one has them, two otherwise (fastsvc_stream_f0_running, csrc/fastsvc_stream_f0.hip).
+
+    Everything is ``stream_f0``'s, plus ``running[i]``: ``(m_p, s_p, n0, g, m_t, s_t)`` - the prior's mean, std and weight in
+    frames, the decay per voiced frame and the target's mean and std - or None for an entry that runs none (``stats[i]`` then
+    says what it gets; an entry has one kind or neither), and ``record (n_streams, 2, 4)`` float64, per stream two entries of
+    ``(w, S1, S2, voiced frames)``: read at entry ``parity[i]`` (or started from zeros when ``first_frame[i] == 0``), written at
+    ``parity[i] ^ 1``, like ``phase``.  The rule is in include/fastsvc_hip.h.  Anything out of range - a missing record, ``s_p <=
+    0``, ``n0 <= 0``, ``g`` outside (0, 1], a value that is not finite - raises ``ValueError`` before a launch and changes
+    nothing; fails loudly off the GPU."""
+    lib = load_library()
+    per, dims = _stream_f0_args("stream_f0_running", audio_ring, f0_ring, f0s_ring, exc_ring, phase, streams, first_frame, n, seen,
+                                ended, parity, seed, stats, cap, max_frames, sample_rate, f0_floor, f0_ceil)
+    if record is not None:                           # (none is the library's to refuse)
+        _gpu_tensors("stream_f0_running", audio_ring, (("record", record, torch.float64, 3),))
+        if tuple(record.shape) != (dims[0], 2, 4):
+            raise ValueError(f"record must be ({dims[0]}, 2, 4), got {tuple(record.shape)}")
+    flat = []
+    for ru in running:
+        flat += [float("nan")] * 6 if ru is None else [float(v) for v in ru]
+    if len(flat) != 6 * per[0]:
+        raise ValueError("running entries are (m_p, s_p, n0, g, m_t, s_t) or None, one per stream")
+    with torch.cuda.device(audio_ring.device):
+        stream = torch.cuda.current_stream(audio_ring.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_f0_running(_ptr(audio_ring), _ptr(f0_ring), _ptr(f0s_ring), _ptr(exc_ring), _ptr(phase),
+                                                  _ptr(record), *per, (ctypes.c_double * len(flat))(*flat), *dims,
+                                                  ctypes.c_float(float(sample_rate)), ctypes.c_float(float(f0_floor)),
+                                                  ctypes.c_float(float(f0_ceil)), ctypes.c_float(float(threshold)),
+                                                  ctypes.c_float(float(sine_amp)), ctypes.c_float(float(noise_amp)),
+                                                  ctypes.c_void_p(stream)),
+               "fastsvc_stream_f0_running")
 
 
 def check_norm_groups(norm_groups, lens: Sequence[int]):

@@ -37,7 +37,12 @@ gated.  Its figures go to profiles/decode_stream_f0.txt.
 of 16 bytes a row and ONE wait per forward (nothing falls back: the streams stay in range).  The difference is quoted next to
 the spread of the unchecked leg; nothing is gated.  Its figures go to profiles/decode_stream_checked.txt.
 
-    python tools/stream_latency.py [--norm [--horizon H] | --audio | --checked]"""
+--f0-stats: the pair is f0=audio streams opened with RunningF0Stats() (source statistics run on the device: one more launch
+per push in which a frame became final, stream_f0_running_kernel) against the same streams opened with list statistics -
+the path as it was - on the same ppg and audio, 1, 8 and 32 streams at core 32 in both storages.  Reported, not gated.  Its
+figures go to profiles/decode_stream_f0_stats.txt.
+
+    python tools/stream_latency.py [--norm [--horizon H] | --audio | --f0 | --f0-stats | --checked]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -346,6 +351,65 @@ def main_f0():
         f.write("\n".join(out) + "\n")
 
 
+def main_f0_stats():
+    core = 32
+    lag = Dc.stream_loudness_lag(hop)
+    trg = [5.3, 1.0]
+    out = [f"stream F0 statistics: one StreamSession.push that completes one window per stream (every stream delivers {core} "
+           f"frames), host to host, streams opened with RunningF0Stats() (the push finalises {core} frames per stream, {lag} frames "
+           f"behind the audio: F0 by YIN, the running source statistics and their shift - one more launch, "
+           f"stream_f0_running_kernel - and the excitation) against the same streams opened with list statistics (the shift inside "
+           f"the F0 launch), both loudness=audio, f0=audio on the same ppg and audio, two sessions in one process; context {ctx}, "
+           f"fade {FADE}, speaker embedding, int16 out; {pushes} pushes per repetition, {reps} repetitions, legs alternated, median "
+           f"of the repetitions' means (min, max); {torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    t = np.arange(core * 8 * hop) / SR
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for N in (1, 8, 32):
+            src = [features(core * 8) for _ in range(N)]
+            for i, f in enumerate(src):                  # (a voiced tone per stream over a little noise)
+                ph = 2.0 * np.pi * (110.0 + 7.0 * i) * t
+                f["audio"] = (0.3 * np.sin(ph) + 0.1 * np.sin(2.0 * ph) + 0.01 * rng.standard_normal(t.size)).astype(np.float32)[:, None]
+            legs = {}
+            for name, stats in (("list", [5.0, 1.0]), ("running", Dc.RunningF0Stats())):
+                s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, loudness="audio", f0="audio")
+                legs[name] = dict(s=s, ids=[s.open(emb, stats, trg, seed=i) for i in range(N)], step=0, t=[])
+
+            def push(leg):
+                a = (leg["step"] % 8) * core
+                leg["step"] += 1
+                return leg["s"].push({i: {"ppg": f["ppg"][a: a + core], "audio": f["audio"][a * hop: (a + core) * hop]}
+                                      for i, f in zip(leg["ids"], src)})
+            for leg in legs.values():
+                for _ in range(6):                       # (fill the context, warm every shape)
+                    push(leg)
+                before = leg["s"].forwards
+                got = push(leg)
+                assert leg["s"].forwards == before + 1 and all(v.size == core * hop for v in got.values())
+            for _ in range(reps):
+                for leg in legs.values():
+                    t0 = time.perf_counter()
+                    for _ in range(pushes):
+                        push(leg)
+                    leg["t"].append((time.perf_counter() - t0) / pushes)
+            voiced = legs["running"]["s"].f0_stats(legs["running"]["ids"][0])["voiced_frames"]
+            for leg in legs.values():
+                leg["s"].end(leg["ids"])
+                leg["s"].close()
+            audio = N * core * hop / SR
+            ml, line_l = spread(f"{N:2d} streams, core {core:3d}: push, list statistics", legs["list"]["t"], audio)
+            mr, line_r = spread(f"{N:2d} streams, core {core:3d}: push, RunningF0Stats()", legs["running"]["t"], audio)
+            out += [line_l, line_r, f"    running / list {mr / ml:.3f} ({(mr - ml) * 1e3:+.0f} us a push; spread of the list leg "
+                                    f"{(max(legs['list']['t']) - min(legs['list']['t'])) * 1e6:.0f} us; stream 0 counted {voiced} "
+                                    f"voiced frames)"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream_f0_stats.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 def main_checked():
     core, storage = 32, "float16"
     out = [f"checked streams: one StreamSession.push that completes one window per stream (every stream delivers {core} frames), "
@@ -401,6 +465,8 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     if "--checked" in argv:
         main_checked()
+    elif "--f0-stats" in argv:
+        main_f0_stats()
     elif "--f0" in argv:
         main_f0()
     elif "--audio" in argv:
