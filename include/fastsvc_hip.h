@@ -776,6 +776,52 @@ int fastsvc_f0_lags(float sample_rate, float f0_floor, float f0_ceil, int32_t* t
 int fastsvc_f0_extract(const float* audio, float* out, int32_t B, int32_t T, int32_t hop, float sample_rate, float f0_floor,
                        float f0_ceil, float threshold, void* stream);
 
+/* ---- Fixed-lag Viterbi F0 tracking over YIN candidates (decode.F0Track) ----
+ * A DEFINITION like the estimator above: the value of frame f is a function of the audio of the frames <= f + lag alone.
+ *
+ * fastsvc_f0_candidates: out (B, frames, 4, 2) float32, per frame up to four (tau_hat, s), the rest (0, inf).  With d' as
+ * above, a lag t in [max(tau_min, 2), tau_max] is a candidate when d'(t) < cand_threshold, d'(t) < d'(t - 1) and t == tau_max
+ * or d'(t) <= d'(t + 1); the four with the smallest d' are kept (ties: the smaller lag), in ascending lag, each with the
+ * parabola above under its conditions as tau_hat, and s = d'(t).  A constant frame has none.  One launch, one workgroup per
+ * frame: the lanes flag local minima, four rounds of a block-wide minimum over the key (bits of d', lag), one lane refines.
+ *
+ * fastsvc_f0_track: cands (B, frames, 4, 2) -> out (B, frames) float32; scratch: fastsvc_f0_track_scratch_bytes(B, frames)
+ * bytes of device memory (5 backpointers and the best state per frame).  Viterbi over the states {candidate 0..3, unvoiced},
+ * all float64, every operation rounded separately:
+ *   local cost   c_k = s_k + lag_bias ((tau_hat_k - tau_hat_0) / tau_max); unvoiced: `unvoiced`; an absent state: +inf
+ *   transition   unvoiced -> unvoiced 0; voiced <-> unvoiced switch_cost; voiced a -> voiced b jump (|ta - tb| / min(ta, tb))
+ *   recurrence   frame 0: C = local; then C'[j] = (min over a of C[a] + tr(a, j)) + local[j], ties to the smallest a, which is
+ *                the backpointer; absent states take no part; then min_j C'[j] is subtracted from every state
+ *   output       e = min(f + lag, frames - 1); the state at e is the argmin of C_e (ties: the smallest index), followed back
+ *                to f; f0 = sample_rate / tau_hat in float32, 0 when unvoiced
+ * One launch, one workgroup per row: one lane runs the recurrence, then all lanes trace back at most `lag` steps each.
+ * lag in [0, 64], costs finite and >= 0, tau_max in [1, 1024]: else FASTSVC_E_INVALID.  Asynchronous on `stream`. */
+int fastsvc_f0_candidates(const float* audio, float* out, int32_t B, int32_t T, int32_t hop, float sample_rate, float f0_floor,
+                          float f0_ceil, float cand_threshold, void* stream);
+int64_t fastsvc_f0_track_scratch_bytes(int32_t B, int32_t frames);
+int fastsvc_f0_track(const float* cands, float* out, void* scratch, int32_t B, int32_t frames, int32_t tau_max, float sample_rate,
+                     int32_t lag, double lag_bias, double jump, double switch_cost, double unvoiced, void* stream);
+
+/* fastsvc_stream_f0_running with TRACKING (csrc/fastsvc_stream_f0.hip): the newly final frames [first_frame, + n) get their
+ * candidates into cand_ring (n_streams, cap, 4, 2) float32 - frame f at f % cap - the recurrence advances over them from
+ * track_record (n_streams, 2, 8) doubles (entry track_parity[i] is read, or nothing when first_frame[i] == 0; the other is
+ * written; 5 of the 8 are used) and leaves backpointers and best states in bp_ring (n_streams, cap, 8) bytes; the frames
+ * [emit_first, + emit_n) - up to frame max(0, first_frame + n - lag) before the end, first_frame + n at the end, which the call
+ * checks - get the tracked raw F0 in f0_ring and its static shift in f0s_ring, and the running shift (`running` and
+ * stats_record, both or neither may be null) and the excitation run over THEM: `parity` addresses the phase and the statistics
+ * record as before and flips with a call that emits.  An entry may have n[i] == 0 and still emit (a stream that ends in a
+ * call that finalises nothing).  Per 64 entries the launches are: the frames launch in candidate mode (when an entry has new
+ * frames), the tracker (one block per stream), the running shift (when an entry runs statistics and emits) and the excitation
+ * (when an entry emits) - ONE launch more than the untracked call.  Plain vector stores, no atomics. */
+int fastsvc_stream_f0_tracked(const float* audio_ring, float* cand_ring, void* bp_ring, float* f0_ring, float* f0s_ring,
+                              float* exc_ring, double* phase, double* stats_record, double* track_record, int32_t S,
+                              const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                              const int32_t* ended, const int32_t* parity, const int32_t* track_parity, const int64_t* emit_first,
+                              const int32_t* emit_n, const uint64_t* seed, const double* stats, const double* running,
+                              int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
+                              float f0_ceil, float cand_threshold, int32_t lag, double lag_bias, double jump, double switch_cost,
+                              double unvoiced, float sine_amp, float noise_amp, void* stream_);
+
 /* ---- the producer of the generator's loudness input ----
  * Replaces loudness_extract(audio, sampling_rate, hop_length) (harana/bin/preprocess_fastsvc.py:60-75; librosa
  * 0.8.1 stft n_fft 2048 / periodic Hann / reflect padding, perceptual (A) weighting with the 80 dB floor below

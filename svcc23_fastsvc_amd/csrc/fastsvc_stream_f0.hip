@@ -23,7 +23,19 @@
 //                       and including it and overwrite f0s_ring; 256 frames a tile, the state carried from tile to tile,
 //                       the block writes rec[slot][parity ^ 1] (first_frame == 0 starts from zeros and reads nothing)
 //
-// Every launch reads what the one before wrote: two launches (three with running statistics), ordered by the stream.
+//   With TRACKING (fastsvc_stream_f0_tracked alone; decode.F0Track) the frames launch runs in candidate mode
+//   and a tracker launch follows it:
+//   stream_f0_cands     one block per (stream, newly final frame): the frame and d' as above, then the frame's four
+//                       candidates (fastsvc_f0.inc) into cand_ring[slot][f % cap] in place of the pick
+//   stream_f0_track     one block per stream with new frames or frames to emit: one lane advances the Viterbi recurrence over
+//                       the new frames from track_rec[slot][parity] (first_frame == 0 starts fresh and reads nothing) and
+//                       leaves backpointers and best states in bp_ring, then all lanes trace the frames to emit - `lag`
+//                       behind the final ones, all of them at the end - back at most `lag` steps and write the tracked raw F0
+//                       to f0_ring and its static shift to f0s_ring.  stream_f0_running and stream_f0_excite then run over the
+//                       EMITTED frames.
+//
+// Every launch reads what the one before wrote: two launches (three with running statistics, one more with tracking), ordered
+// by the stream.
 // Descriptors travel IN the kernel arguments, 64 streams per launch.  Plain vector stores, no atomics, no tunables.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -154,6 +166,104 @@ void stream_f0_running_kernel(RunArgs r, int cap, const float* __restrict__ f0_r
     if (tid < 4) mine[4 * ((flags >> 1) ^ 1) + tid] = state[tid];
 }
 
+// Frame f of entry b's stream from its audio ring into x (LDS); the caller's estimator synchronises.
+__device__ __forceinline__ void stream_frame_load(float* x, const float* __restrict__ audio_ring, const F0Args& a, const F0Dims& d,
+                                                  int b, long f, int tid) {
+    const long ring_len = (long)d.cap * d.hop, T = a.samples[b];
+    const bool ended = (a.flags[b] & 4) != 0;
+    const float* ring = audio_ring + a.slot[b] * ring_len;
+    const long base = f * d.hop - LD_NFFT / 2;
+    for (int k = tid; k < LD_NFFT; k += 256) {
+        long i = base + k;
+        if (ended) i = reflect_index<long>(i, T);
+        else if (i < 0) i = -i;
+        // (a frame that is final before the end reads [f hop - 1024, f hop + 1024) < T; only frame 0's element 0 mirrors
+        // to sample 1024, which may not have arrived when hop divides 1024 - the estimator never reads x[0])
+        x[k] = i < T ? ring[i % ring_len] : 0.f;
+    }
+}
+
+// The frames kernel in CANDIDATE mode (a session with decode.F0Track): the same frame, the same d', and the frame's four
+// candidates into the stream's candidate ring (frame f at f % cap, 8 floats) in place of the pick.
+__global__ __launch_bounds__(256)
+void stream_f0_cands_kernel(F0Args a, F0Dims d, F0Params p, float cand_threshold, const float* __restrict__ audio_ring,
+                            float* __restrict__ cand_ring) {
+    __shared__ __attribute__((aligned(16))) float x[LD_NFFT];
+    __shared__ float dn[F0_MAX_LAG + 2];
+    __shared__ unsigned long long kmin[4];
+    const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (j >= a.n[b]) return;                        // (uniform per block)
+    const long f = a.first[b] + j;
+    stream_frame_load(x, audio_ring, a, d, b, f, tid);
+    f0_frame_dn(x, dn, p, tid);
+    f0_frame_candidates(dn, kmin, cand_threshold, p, tid, cand_ring + ((long)a.slot[b] * d.cap + f % d.cap) * 2 * F0_CANDS);
+}
+
+struct TrackArgs {                                  // per entry of a tracked call
+    long first[SF_MAX];                             // the first newly final frame: the recurrence advances over [first, first + n)
+    long efirst[SF_MAX];                            // the first frame to emit: [efirst, efirst + en) get their tracked F0
+    int n[SF_MAX], en[SF_MAX];
+    int slot[SF_MAX];
+    int flags[SF_MAX];                              // bit 0: the tracker record's entry to read; bit 3: has statistics
+};
+static_assert(sizeof(TrackArgs) + sizeof(F0Shift) + sizeof(F0Track) + 96 <= 4096, "a kernel takes at most 4 KiB of arguments");
+
+// The tracker of live streams: one block per entry with new frames or frames to emit.  One lane advances the
+// recurrence over the new frames from rec[slot][parity] (5 doubles: C of the last frame, normalised; first == 0 starts fresh
+// and reads nothing) with the lags of frame first - 1 from the candidate ring, leaves backpointers and best state in
+// bp_ring (frame f at f % cap, F0_BP_BYTES bytes) and C in rec[slot][parity ^ 1]; then every lane traces its frames to emit
+// back from frame min(f + lag, first + n - 1) and writes the tracked raw F0 and its static shift.
+__global__ __launch_bounds__(256)
+void stream_f0_track_kernel(TrackArgs a, F0Shift sh, F0Track t, int cap, const float* __restrict__ cand_ring,
+                            unsigned char* __restrict__ bp_ring, double* __restrict__ rec, float* __restrict__ f0_ring,
+                            float* __restrict__ f0s_ring) {
+    #pragma clang fp contract(off)
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = a.n[b], en = a.en[b];
+    if (n == 0 && en == 0) return;                  // (uniform per block)
+    const int slot = a.slot[b], flags = a.flags[b];
+    const long first = a.first[b], efirst = a.efirst[b];
+    const float* cd = cand_ring + (long)slot * cap * 2 * F0_CANDS;
+    unsigned char* bp = bp_ring + (long)slot * cap * F0_BP_BYTES;
+    if (tid == 0 && n > 0) {
+        double C[F0_STATES], tau[F0_CANDS], ptau[F0_CANDS] = {0.0, 0.0, 0.0, 0.0}, local[F0_STATES];
+        double* mine = rec + (long)slot * 2 * 8;
+        if (first > 0) {
+            const double* from = mine + 8 * (flags & 1);
+            #pragma unroll
+            for (int j = 0; j < F0_STATES; ++j) C[j] = from[j];
+            f0_track_local(cd + ((first - 1) % cap) * 2 * F0_CANDS, t, ptau, local);
+        }
+        for (int i = 0; i < n; ++i) {
+            const long f = first + i, at = f % cap;
+            unsigned char back[F0_STATES];
+            f0_track_local(cd + at * 2 * F0_CANDS, t, tau, local);
+            const int best = f0_track_step(C, ptau, tau, local, f == 0, t, back);
+            #pragma unroll
+            for (int j = 0; j < F0_STATES; ++j) bp[at * F0_BP_BYTES + j] = back[j];
+            bp[at * F0_BP_BYTES + F0_STATES] = (unsigned char)best;
+            #pragma unroll
+            for (int k = 0; k < F0_CANDS; ++k) ptau[k] = tau[k];
+        }
+        double* to = mine + 8 * ((flags & 1) ^ 1);
+        #pragma unroll
+        for (int j = 0; j < F0_STATES; ++j) to[j] = C[j];
+    }
+    __threadfence_block();
+    __syncthreads();
+    const long last = first + n - 1;                // the newest final frame
+    for (int i = tid; i < en; i += 256) {
+        const long f = efirst + i;
+        const long e = f + t.lag < last ? f + t.lag : last;
+        int s = bp[(e % cap) * F0_BP_BYTES + F0_STATES] & 7;      // (& 7: a byte of the ring never indexes outside its frame)
+        for (long g = e; g > f; --g) s = bp[(g % cap) * F0_BP_BYTES + s] & 7;
+        const float v = s < F0_CANDS ? t.sr / cd[(f % cap) * 2 * F0_CANDS + 2 * s] : 0.f;
+        const long at = (long)slot * cap + f % cap;
+        f0_ring[at] = v;
+        f0s_ring[at] = (flags & 8) ? shift_f0(v, sh.m0[b], sh.ratio[b], sh.m1[b]) : v;
+    }
+}
+
 __global__ __launch_bounds__(256)
 void stream_f0_frames_kernel(F0Args a, F0Shift sh, F0Dims d, F0Params p, const float* __restrict__ audio_ring,
                              float* __restrict__ f0_ring, float* __restrict__ f0s_ring) {
@@ -164,19 +274,8 @@ void stream_f0_frames_kernel(F0Args a, F0Shift sh, F0Dims d, F0Params p, const f
     const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     if (j >= a.n[b]) return;                        // (uniform per block)
     const int slot = a.slot[b], flags = a.flags[b];
-    const long ring_len = (long)d.cap * d.hop, T = a.samples[b];
-    const bool ended = (flags & 4) != 0;
-    const float* ring = audio_ring + slot * ring_len;
     const long f = a.first[b] + j;
-    const long base = f * d.hop - LD_NFFT / 2;
-    for (int k = tid; k < LD_NFFT; k += 256) {
-        long i = base + k;
-        if (ended) i = reflect_index<long>(i, T);
-        else if (i < 0) i = -i;
-        // (a frame that is final before the end reads [f hop - 1024, f hop + 1024) < T; only frame 0's element 0 mirrors
-        // to sample 1024, which may not have arrived when hop divides 1024 - the estimator never reads x[0])
-        x[k] = i < T ? ring[i % ring_len] : 0.f;
-    }
+    stream_frame_load(x, audio_ring, a, d, b, f, tid);
     const float v = f0_frame_value(x, dn, &res, wmin, p, tid);
     if (tid == 0) {
         const long at = (long)slot * d.cap + f % d.cap;
@@ -248,9 +347,22 @@ int invalid(const char* who, const char* fmt, long a = 0, long b = 0, long c = 0
 
 bool is_finite(double v) { return v == v && v > -1e300 && v < 1e300; }
 
-// Both entry points: `who` names the one that was called.  fastsvc_stream_f0 passes no record and no running constants, and
-// then this validates, fills and launches exactly what it always did.
-int stream_f0_run(const char* who, const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase,
+// What fastsvc_stream_f0_tracked adds to the other two entry points: the tracker's rings and record, per entry the record's
+// parity and the frames to emit, and the tracker's constants.
+struct TrackCall {
+    float* cand_ring;
+    unsigned char* bp_ring;
+    double* rec;
+    const int32_t* parity;
+    const int64_t* emit_first;
+    const int32_t* emit_n;
+    float cand_threshold;
+    F0Track t;
+};
+
+// All entry points: `who` names the one that was called.  fastsvc_stream_f0 passes no record, no running constants and no
+// tracker, and then this validates, fills and launches exactly what it always did.
+int stream_f0_run(const char* who, const TrackCall* tk, const float* audio_ring, float* f0_ring, float* f0s_ring, float* exc_ring, double* phase,
                   double* rec, int32_t S, const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
                   const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats, const double* running,
                   int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
@@ -297,6 +409,14 @@ int stream_f0_run(const char* who, const float* audio_ring, float* f0_ring, floa
                                     "> 0, decay in (0, 1], target mean, target std), or six NaN for none", s);
             if (!off && !none) return invalid(who, "stream %ld: given statistics and running statistics exclude each other", s);
         }
+        if (tk) {                                       // the frames to emit: up to `lag` behind the final ones, all at the end
+            const int64_t ef = tk->emit_first[i], en = tk->emit_n[i];
+            const int64_t upto = ended[i] ? f + k : (f + k > tk->t.lag ? f + k - tk->t.lag : 0);
+            if (tk->parity[i] & ~1) return invalid(who, "stream %ld: the tracker's parity is 0 or 1", s);
+            if (ef < 0 || en < 0 || en > max_frames || ef + en != upto || f + k - ef > cap || (ended[i] && f + k != q))
+                return invalid(who, "stream %ld: emits frames [%ld, +%ld), not up to frame %ld", s, ef, en, upto);
+            most = en > most ? en : most;
+        }
         if (k == 0) continue;
         // every frame is final: it reads up to (f + k - 1) hop + 1023, or the stream has ended and these are its last frames
         if (ended[i] ? f + k != q : (f + k - 1) * hop + LD_NFFT / 2 > q * hop)
@@ -318,7 +438,8 @@ int stream_f0_run(const char* who, const float* audio_ring, float* f0_ring, floa
         F0Shift sh;
         F0Seeds sd;
         RunArgs ra;
-        int grid = 0, nrun = 0;
+        TrackArgs ta;
+        int grid = 0, nrun = 0, gnew = 0;
         for (int i = 0; i < SF_MAX; ++i) {
             const bool on = i < nb;
             const double* st = stats + 4 * (b0 + (on ? i : 0));
@@ -332,22 +453,47 @@ int stream_f0_run(const char* who, const float* audio_ring, float* f0_ring, floa
             sh.m0[i] = shift ? st[0] : 0.0;
             sh.ratio[i] = shift ? st[3] / st[1] : 1.0;      // (one double division, as numpy does it on the host)
             sh.m1[i] = shift ? st[2] : 0.0;
-            grid = a.n[i] > grid ? a.n[i] : grid;
+            if (tk) {
+                // the tracker takes the newly final frames; everything behind it - the running shift, the excitation - the
+                // emitted ones, as if they were the call's
+                ta.first[i] = a.first[i]; ta.n[i] = a.n[i]; ta.slot[i] = a.slot[i];
+                ta.efirst[i] = on ? (long)tk->emit_first[b0 + i] : 0;
+                ta.en[i] = on ? tk->emit_n[b0 + i] : 0;
+                ta.flags[i] = on ? (tk->parity[b0 + i] | (shift ? 8 : 0)) : 0;
+                gnew = a.n[i] > gnew ? a.n[i] : gnew;
+            }
+            const long efirst = tk ? ta.efirst[i] : a.first[i];
+            const int en = tk ? ta.en[i] : a.n[i];
+            grid = en > grid ? en : grid;
             const double* ru = running ? running + 6 * (b0 + (on ? i : 0)) : nullptr;
-            if (ru && on && a.n[i] > 0 && ru[0] == ru[0]) {
+            if (ru && on && en > 0 && ru[0] == ru[0]) {
                 ra.mp[nrun] = ru[0]; ra.n0[nrun] = ru[2]; ra.prior[nrun] = ru[2] * ru[1] * ru[1];
                 ra.g[nrun] = ru[3]; ra.mt[nrun] = ru[4]; ra.st[nrun] = ru[5];
-                ra.pos[nrun] = (int)(first_frame[b0 + i] % cap);
+                ra.pos[nrun] = (int)(efirst % cap);
                 ra.slot[nrun] = a.slot[i];
-                ra.nf[nrun] = (a.n[i] << 2) | (parity[b0 + i] << 1) | (first_frame[b0 + i] == 0 ? 1 : 0);
+                ra.nf[nrun] = (en << 2) | (parity[b0 + i] << 1) | (efirst == 0 ? 1 : 0);
                 ++nrun;
+            }
+        }
+        if (tk) {
+            if (gnew == 0 && grid == 0) continue;
+            if (gnew)
+                hipLaunchKernelGGL(stream_f0_cands_kernel, dim3((unsigned)gnew, (unsigned)nb), dim3(256), 0, hs, a, d, p,
+                                   tk->cand_threshold, audio_ring, tk->cand_ring);
+            hipLaunchKernelGGL(stream_f0_track_kernel, dim3((unsigned)nb), dim3(256), 0, hs, ta, sh, tk->t, (int)cap, tk->cand_ring,
+                               tk->bp_ring, tk->rec, f0_ring, f0s_ring);
+            for (int i = 0; i < SF_MAX; ++i) {          // the excitation runs over the emitted frames
+                a.first[i] = ta.efirst[i];
+                a.n[i] = ta.en[i];
+                a.flags[i] = (a.flags[i] & ~1) | (i < nb && ta.efirst[i] == 0 ? 1 : 0);
             }
         }
         if (grid == 0) continue;
         int64_t gx = (((int64_t)grid * hop + 3) / 4 + 255) / 256;
         gx = gx > SF_MAX_BLOCKS ? SF_MAX_BLOCKS : gx;
-        hipLaunchKernelGGL(stream_f0_frames_kernel, dim3((unsigned)grid, (unsigned)nb), dim3(256), 0, hs, a, sh, d, p, audio_ring,
-                           f0_ring, f0s_ring);
+        if (!tk)
+            hipLaunchKernelGGL(stream_f0_frames_kernel, dim3((unsigned)grid, (unsigned)nb), dim3(256), 0, hs, a, sh, d, p, audio_ring,
+                               f0_ring, f0s_ring);
         if (nrun) {
             for (int i = nrun; i < SF_MAX; ++i) {       // (entries no block reads)
                 ra.mp[i] = ra.n0[i] = ra.prior[i] = ra.g[i] = ra.mt[i] = ra.st[i] = 0.0;
@@ -373,7 +519,7 @@ int fastsvc_stream_f0(const float* audio_ring, float* f0_ring, float* f0s_ring, 
                       const int32_t* ended, const int32_t* parity, const uint64_t* seed, const double* stats,
                       int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
                       float f0_ceil, float threshold, float sine_amp, float noise_amp, void* stream_) {
-    return stream_f0_run("fastsvc_stream_f0", audio_ring, f0_ring, f0s_ring, exc_ring, phase, nullptr, S, stream, first_frame, n,
+    return stream_f0_run("fastsvc_stream_f0", nullptr, audio_ring, f0_ring, f0s_ring, exc_ring, phase, nullptr, S, stream, first_frame, n,
                          seen, ended, parity, seed, stats, nullptr, n_streams, cap, max_frames, hop, sample_rate, f0_floor,
                          f0_ceil, threshold, sine_amp, noise_amp, stream_);
 }
@@ -386,9 +532,40 @@ int fastsvc_stream_f0_running(const float* audio_ring, float* f0_ring, float* f0
                               float sine_amp, float noise_amp, void* stream_) {
     const char* who = "fastsvc_stream_f0_running";
     if (!stats_record || !running) return invalid(who, "null pointer (the statistics record or the running constants)");
-    return stream_f0_run(who, audio_ring, f0_ring, f0s_ring, exc_ring, phase, stats_record, S, stream, first_frame, n, seen, ended,
+    return stream_f0_run(who, nullptr, audio_ring, f0_ring, f0s_ring, exc_ring, phase, stats_record, S, stream, first_frame, n, seen, ended,
                          parity, seed, stats, running, n_streams, cap, max_frames, hop, sample_rate, f0_floor, f0_ceil, threshold,
                          sine_amp, noise_amp, stream_);
+}
+
+int fastsvc_stream_f0_tracked(const float* audio_ring, float* cand_ring, void* bp_ring, float* f0_ring, float* f0s_ring,
+                              float* exc_ring, double* phase, double* stats_record, double* track_record, int32_t S,
+                              const int32_t* stream, const int64_t* first_frame, const int32_t* n, const int64_t* seen,
+                              const int32_t* ended, const int32_t* parity, const int32_t* track_parity, const int64_t* emit_first,
+                              const int32_t* emit_n, const uint64_t* seed, const double* stats, const double* running,
+                              int32_t n_streams, int32_t cap, int32_t max_frames, int32_t hop, float sample_rate, float f0_floor,
+                              float f0_ceil, float cand_threshold, int32_t lag, double lag_bias, double jump, double switch_cost,
+                              double unvoiced, float sine_amp, float noise_amp, void* stream_) {
+    const char* who = "fastsvc_stream_f0_tracked";
+    if (!cand_ring || !bp_ring || !track_record || !track_parity || !emit_first || !emit_n)
+        return invalid(who, "null pointer (the tracker's rings, record, parity or frames to emit)");
+    if (running && !stats_record) return invalid(who, "null pointer (running constants without a statistics record)");
+    if ((reinterpret_cast<uintptr_t>(cand_ring) & 3) || (reinterpret_cast<uintptr_t>(track_record) & 7))
+        return invalid(who, "misaligned pointer (the candidate ring: 4 bytes, the tracker record: 8)");
+    const double costs[4] = {lag_bias, jump, switch_cost, unvoiced};
+    for (double c : costs)
+        if (!(c >= 0.0 && is_finite(c))) return invalid(who, "the tracker's costs are finite and >= 0");
+    if (lag < 0 || lag > F0_TRACK_MAX_LAG) return invalid(who, "lag %ld outside [0, %ld]", lag, F0_TRACK_MAX_LAG);
+    TrackCall tk;
+    tk.cand_ring = cand_ring; tk.bp_ring = static_cast<unsigned char*>(bp_ring); tk.rec = track_record;
+    tk.parity = track_parity; tk.emit_first = emit_first; tk.emit_n = emit_n; tk.cand_threshold = cand_threshold;
+    tk.t.lag_bias = lag_bias; tk.t.jump = jump; tk.t.sw = switch_cost; tk.t.unvoiced = unvoiced; tk.t.sr = sample_rate; tk.t.lag = lag;
+    int32_t tau_min = 0, tau_max = 0;
+    if (const int rc = fastsvc_f0_lags(sample_rate, f0_floor, f0_ceil, &tau_min, &tau_max)) return rc;
+    tk.t.tau_max = (double)tau_max;
+    // (the threshold of the per-frame pick has no part here: the unvoiced state's cost takes its place)
+    return stream_f0_run(who, &tk, audio_ring, f0_ring, f0s_ring, exc_ring, phase, stats_record, S, stream, first_frame, n, seen,
+                         ended, parity, seed, stats, running, n_streams, cap, max_frames, hop, sample_rate, f0_floor, f0_ceil,
+                         cand_threshold, sine_amp, noise_amp, stream_);
 }
 
 }  // extern "C"

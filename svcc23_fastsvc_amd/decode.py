@@ -141,6 +141,111 @@ def running_f0_convert(f0: np.ndarray, running: RunningF0Stats, trg_f0_stats: Se
     return out
 
 
+F0_CANDIDATES = 4             # K: the candidates a frame offers the tracker - a constant of the definition, not a parameter
+F0_TRACK_MAX_LAG = 64
+
+
+@dataclass(frozen=True)
+class F0Track:
+    """Fixed-lag Viterbi tracking of the F0 over YIN candidates: pass it to ``StreamSession(f0="audio", f0_track=...)`` or
+    ``f0_extract(track=...)`` (DESIGN.md 4.10 and ``f0_track_rule`` have the rule).  ``lag``: the frames the tracker looks
+    ahead, ``0 <= lag <= 64`` - the value of frame f is a function of the audio of the frames ``<= f + lag`` alone, and a live
+    stream delivers it ``lag`` frames later; ``cand_threshold > 0``: d' a local minimum must lie under to be a candidate;
+    ``lag_bias``: what a candidate costs per ``tau_max`` of lag above the frame's smallest-lag candidate (it keeps the tracker
+    off a sub-harmonic); ``jump``: the cost of an octave between voiced frames; ``switch``: of a change of voicing;
+    ``unvoiced``: the unvoiced state's cost per frame, or None for the session's ``f0_threshold``.  Costs are finite and ``>=
+    0``.  Immutable; a ``ValueError`` for anything else."""
+    lag: int = 8
+    cand_threshold: float = 0.5
+    lag_bias: float = 0.2
+    jump: float = 1.0
+    switch: float = 0.3
+    unvoiced: Optional[float] = None
+
+    def __post_init__(self):
+        try:
+            lag = int(self.lag)
+            if lag != self.lag:
+                raise ValueError
+            costs = {k: float(getattr(self, k)) for k in ("cand_threshold", "lag_bias", "jump", "switch")}
+            if self.unvoiced is not None:
+                costs["unvoiced"] = float(self.unvoiced)
+        except (TypeError, ValueError) as e:
+            raise ValueError("F0Track needs an integer lag and numbers for its costs") from e
+        if not 0 <= lag <= F0_TRACK_MAX_LAG:
+            raise ValueError(f"lag must be in [0, {F0_TRACK_MAX_LAG}] frames, got {self.lag!r}")
+        for k, v in costs.items():
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{k} must be finite and >= 0, got {getattr(self, k)!r}")
+            object.__setattr__(self, k, v)
+        if not costs["cand_threshold"] > 0.0:
+            raise ValueError(f"cand_threshold must be > 0, got {self.cand_threshold!r}")
+        object.__setattr__(self, "lag", lag)
+
+
+def f0_track_rule(cands, tau_max: int, sample_rate: float, track: F0Track, unvoiced: float) -> np.ndarray:
+    """The tracker on the host - for ``F0Track`` what ``running_f0_convert`` is for the running statistics, and what
+    fastsvc_f0_track and a tracked stream compute on the device.  ``cands (F, 4, 2)``: per frame up to four ``(tau_hat, s)`` in
+    ascending lag, absent entries ``(0, inf)`` (``f0.f0_candidates``).  Viterbi over the states {candidate 0..3, 4 = unvoiced},
+    in float64 (Python floats: one rounding per operation)::
+
+        local[k] = s_k + lag_bias ((tau_hat_k - tau_hat_0) / tau_max);  local[4] = unvoiced;  absent: inf
+        tr(4, 4) = 0;  tr(a, 4) = tr(4, b) = switch;  tr(a, b) = jump (|ta - tb| / min(ta, tb))
+        C_0 = local;  C'[j] = (min over a of C[a] + tr(a, j)) + local[j], ties to the smallest a (the backpointer; absent
+        states take no part);  C = C' - min C'
+
+    Frame f: the argmin of ``C_e`` (ties: the smallest index), ``e = min(f + lag, F - 1)``, followed back to f; ``f0 =
+    sample_rate / tau_hat`` or 0 when unvoiced, in the dtype of ``cands`` (float32 candidates: the device's bits).  Returns
+    ``(F,)`` of that dtype."""
+    cands = np.asarray(cands)
+    if cands.ndim != 3 or cands.shape[1:] != (F0_CANDIDATES, 2):
+        raise ValueError(f"cands must be (F, {F0_CANDIDATES}, 2), got {cands.shape}")
+    dtype = cands.dtype if cands.dtype in (np.float32, np.float64) else np.dtype(np.float64)
+    F, K, inf = cands.shape[0], F0_CANDIDATES, float("inf")
+    tmax, bias, jump, sw, uv, lag = float(int(tau_max)), track.lag_bias, track.jump, track.switch, float(unvoiced), track.lag
+    back = np.zeros((F, K + 1), dtype=np.int64)
+    best = np.zeros(F, dtype=np.int64)
+    C, ptau = [], []
+    for f in range(F):
+        tau = [float(v) for v in cands[f, :, 0]]
+        sc = [float(v) for v in cands[f, :, 1]]
+        local = [sc[k] + bias * ((tau[k] - tau[0]) / tmax) if sc[k] < inf else inf for k in range(K)] + [uv]
+        if f == 0:
+            nxt = list(local)
+        else:
+            nxt = []
+            for j in range(K + 1):
+                top, src = inf, 0
+                for a in range(K + 1) if local[j] < inf else ():
+                    if not C[a] < inf:
+                        continue
+                    if a == K and j == K:
+                        tr = 0.0
+                    elif a == K or j == K:
+                        tr = sw
+                    else:
+                        tr = jump * (abs(ptau[a] - tau[j]) / min(ptau[a], tau[j]))
+                    v = C[a] + tr
+                    if v < top:
+                        top, src = v, a
+                nxt.append(top + local[j])
+                back[f, j] = src
+            m = min(nxt)
+            nxt = [v - m for v in nxt]
+        C, ptau = nxt, tau
+        best[f] = min(range(K + 1), key=lambda j: (C[j], j))
+    out = np.zeros(F, dtype=dtype)
+    sr = dtype.type(sample_rate)
+    for f in range(F):
+        e = min(f + lag, F - 1)
+        st = best[e]
+        for g in range(e, f, -1):
+            st = back[g, st]
+        if st < K:
+            out[f] = sr / cands[f, st, 0].astype(dtype)
+    return out
+
+
 def convert_f0_device(f0: torch.Tensor, orgf0stats: Sequence[float], tarf0stats: Sequence[float]) -> torch.Tensor:
     """``F0Statistics.convert`` on a device tensor of any shape (float64 inside, like numpy)."""
     f = f0.to(torch.float64)
@@ -762,6 +867,27 @@ def stream_loudness_ring_frames(core: int, context: int, max_push: int, hop: int
     return -(-max(frames, samples) // 4) * 4
 
 
+def stream_tracked_frames(final: int, ended: bool, track_lag: int) -> int:
+    """Frames of a live stream whose TRACKED F0 is final when ``final`` frames have their candidates (``f0_track=F0Track(lag=
+    track_lag)``): frame f needs the frames up to ``f + track_lag``, so ``max(0, final - track_lag)`` before the end and all of
+    them once the stream has ended."""
+    final = int(final)
+    return final if ended else max(0, final - int(track_lag))
+
+
+def stream_track_ring_frames(core: int, context: int, max_push: int, hop: int, track_lag: int) -> int:
+    """``stream_loudness_ring_frames`` for a session that tracks its F0 ``track_lag`` frames behind the final frames.  The
+    FRAMES bound: the oldest window that has not run lacks a TRACKED frame, ``tracked < (k + 1) core + context``, and ``seen <=
+    tracked + lag + track_lag`` - ``stream_ring_frames(core, context, max_push + lag + track_lag)``; the candidates and
+    backpointers a frame's trace reads, the ``track_lag`` frames after it, lie inside that.  The SAMPLES bound is unchanged:
+    candidates are made when a frame is final, as the F0 was."""
+    core, context, max_push, hop = int(core), int(context), int(max_push), int(hop)
+    lag = stream_loudness_lag(hop)
+    frames = stream_ring_frames(core, context, max_push + lag + int(track_lag))
+    samples = -(-((max_push + lag) * hop + LOUDNESS_HALF_FRAME) // hop)
+    return -(-max(frames, samples) // 4) * 4
+
+
 class StreamRow(NamedTuple):
     """Window ``k`` of the live stream in slot ``stream`` as a row of a forward: it reads the stream's frames ``[in_lo,
     in_hi)``, owns ``[core_lo, core_hi)`` of them, and is the stream's ``last`` window or not.  The row type of
@@ -875,12 +1001,15 @@ class _Stream:
     norm_w: float = 0.0              # ... and the weighted frames it holds (``running_horizon_rows``' w)
     totals: Optional[dict] = None    # a checked session: what its windows' reports add up to since ``open``
     running: Optional[tuple] = None  # RunningF0Stats' six constants (m_p, s_p, n0, g, m_t, s_t): the record at ``parity`` is its state
+    track: bool = False              # the session tracks its F0 (f0_track): the excitation exists for the tracked frames only
+    tracked: int = 0                 # ... frames whose tracked F0 and excitation are made (``parity`` flips with a call that makes some)
+    track_parity: int = 0            # the tracker record's current entry (flips with every call that has newly final frames)
 
     @property
     def complete(self) -> int:
         """Frames whose features are complete - what a window is ready by: all that arrived or, when the session makes the
-        loudness, those whose loudness is final."""
-        return self.final if self.from_audio else self.seen
+        loudness, those whose loudness is final or, when it tracks the F0, those whose tracked F0 is."""
+        return self.tracked if self.track else self.final if self.from_audio else self.seen
 
 
 def check_stream_chunks(chunks, end, open_ids, channels: int, hop: int, max_push: int, loudness: str = "given",
@@ -1931,6 +2060,20 @@ class StreamSession:
     ``f0_stats(id)`` reads the record back; ``running_f0_convert`` is the rule on the host.  Within one float32 ulp of the
     float64 reference over the traced raw F0 (0 measured).
 
+    ``f0_track=F0Track(lag=8, ...)`` (needs ``f0="audio"``) replaces the per-frame pick by fixed-lag Viterbi over YIN candidates
+    (``F0Track``, ``f0_track_rule`` and DESIGN.md 4.10 have the rule): per frame up to four local minima of d' under
+    ``cand_threshold``, across frames Viterbi over {4 candidates, unvoiced} in float64, the state of frame f traced back from the
+    best state of frame ``min(f + lag, F - 1)`` - the value of frame f is a function of the audio of the frames ``<= f + lag``
+    alone, so it does not depend on push sizes, slots or ring positions and equals ``f0_extract(track=...)``'s whole-file
+    function over the stream's frames.  A frame's tracked F0, shift and excitation are made ``lag`` frames after it is final
+    (all at the stream's end, also when that push finalises nothing): windows are ready by the TRACKED frames
+    (``stream_tracked_frames``), ``latency_frames`` and ``latency_frames_max`` grow by ``lag`` and the rings hold
+    ``stream_track_ring_frames`` frames.  ``_finalise_f0_tracked`` is one ``stream_f0_tracked``: the frames launch in candidate mode
+    into a candidate ring, one block per stream for the recurrence (its costs in a float64 parity pair, backpointers in a
+    ring) and the trace, then the running statistics and the excitation over the EMITTED frames.  All three kinds of F0
+    statistics work with it.  Voicing has hysteresis at the edges of a voiced stretch.  ``None`` (the default): launches,
+    kernel arguments, bytes and bits as before.
+
     State on the device, allocated once: per stream a ring of ``stream_ring_frames(core, context, max_push)`` frames of
     ppg, lft and excitation, the sine phase (float64) and two fade slots; an embedding table ``(n_streams, E)``; one
     upload buffer with a page-locked twin and one page-locked download buffer; with ``norm="running"`` per stream one
@@ -1989,15 +2132,15 @@ class StreamSession:
     was, ``last_report`` included.  Not thread-safe.  ``out_channels`` must be 1 and the signal generator's only signal
     "sine".  Not built: graph capture of the per-push chain, several GPUs; for ``loudness="audio"`` a preset peak for
     calibration, a forgetting horizon for the maximum, ppg from audio (it needs an ASR model that lives outside this
-    repository); ``f0="audio"`` without ``loudness="audio"``; octave-error smoothing across frames (the estimator is per
-    frame on purpose); a command-line flag for ``f0="audio"`` (the feature dumps hold no audio); for ``RunningF0Stats`` a std
+    repository); ``f0="audio"`` without ``loudness="audio"``; a command-line flag for ``f0="audio"`` (the feature
+    dumps hold no audio); for ``f0_track`` candidates beyond 4, a learned prior and tracking for ``f0="given"``; for ``RunningF0Stats`` a std
     floor or a mean-only mode, and ``f0="given"`` sessions (the host shifts per chunk there)."""
 
     def __init__(self, model, signal_generator, device, n_streams: int = 1, core: int = 32, context: Optional[int] = None,
                  fade: int = 8, max_push: Optional[int] = None, pcm16: bool = True, max_batch: int = 32, norm: str = "window",
                  horizon: Optional[float] = None, loudness: str = "given", checked: bool = False,
                  fallback: Sequence[str] = ("bfloat16",), f0: str = "given", f0_floor: float = 70.0, f0_ceil: float = 340.0,
-                 f0_threshold: float = 0.15):
+                 f0_threshold: float = 0.15, f0_track: Optional[F0Track] = None):
         from .engine import FastSVCError
         self.model, self.signal_generator = model, signal_generator
         self.device = torch.device(device)
@@ -2013,7 +2156,7 @@ class StreamSession:
         self.hop = int(signal_generator.hop_size)
         for name, value in self._check_args(cfg, self.hop, n_streams, core, context, fade, max_push, max_batch, norm, horizon,
                                             loudness, checked, fallback, f0, f0_floor, f0_ceil, f0_threshold,
-                                            float(signal_generator.sample_rate)).items():
+                                            float(signal_generator.sample_rate), f0_track).items():
             setattr(self, name, value)
         if self.checked and self.fallback and not hasattr(model, "use_activation_storage"):
             raise ValueError("a checked session with fallback storages needs a model with use_activation_storage() "
@@ -2039,14 +2182,14 @@ class StreamSession:
                     max_push: Optional[int] = None, max_batch: int = 32, norm: str = "window", horizon: Optional[float] = None,
                     loudness: str = "given", checked: bool = False, fallback: Sequence[str] = ("bfloat16",), f0: str = "given",
                     f0_floor: float = 70.0, f0_ceil: float = 340.0, f0_threshold: float = 0.15,
-                    sample_rate: float = 24000.0) -> Dict[str, object]:
+                    sample_rate: float = 24000.0, f0_track: Optional[F0Track] = None) -> Dict[str, object]:
         """The constructor's arguments against the generator configuration ``cfg`` and the signal generator's ``hop``, with
         no device: a ``ValueError`` for the first one that is refused, else the session's attributes they resolve to -
         the arguments as given or defaulted (``fallback`` a tuple of storage names; a string is one name), ``channels``,
         ``lag``, the rings' ``cap``, the floats ``_slice`` a stream takes
         of the upload buffer (16-byte aligned) and ``_down_elems``, the samples of the download buffer (a push returns at
         most the frames a ring holds per stream, every row's run padded to 8 samples)."""
-        from .engine import STORAGE_CODES, STREAM_MAX_PUSH, f0_lags
+        from .engine import STORAGE_CODES, STREAM_LOUDNESS_MAX_FRAMES, STREAM_MAX_PUSH, f0_lags
         fallback = (fallback,) if isinstance(fallback, str) else tuple(fallback)
         for name in fallback:
             if name not in STORAGE_CODES:
@@ -2079,14 +2222,24 @@ class StreamSession:
             f0_lags(sample_rate, f0_floor, f0_ceil)      # (ValueError: tau_max > 1024, or no lag at all)
             if not float(f0_threshold) > 0.0:
                 raise ValueError(f"f0_threshold must be > 0, got {f0_threshold}")
+        if f0_track is not None:
+            if not isinstance(f0_track, F0Track):
+                raise ValueError(f"f0_track must be None or an F0Track, got {f0_track!r}")
+            if f0 != "audio":
+                raise ValueError("f0_track tracks the F0 the session makes: it needs f0=\"audio\" (tracking a given F0 is not built)")
         lag = stream_loudness_lag(hop) if loudness == "audio" else 0
+        track_lag = 0 if f0_track is None else f0_track.lag
         cap = stream_ring_frames(core, context, max_push) if loudness == "given" else \
-            stream_loudness_ring_frames(core, context, max_push, hop)
+            stream_loudness_ring_frames(core, context, max_push, hop) if f0_track is None else \
+            stream_track_ring_frames(core, context, max_push, hop, track_lag)
+        if f0_track is not None and max_push + lag + track_lag > STREAM_LOUDNESS_MAX_FRAMES:
+            raise ValueError(f"max_push + the loudness lag + the tracker's lag must be at most {STREAM_LOUDNESS_MAX_FRAMES} frames, "
+                             f"got {max_push + lag + track_lag}")
         C = int(cfg.in_channels)
         return dict(core=core, context=context, fade=fade, max_push=max_push, n_streams=n_streams, max_batch=max_batch,
                     channels=C, _takes_emb=takes_emb, norm=norm, horizon=horizon, loudness=loudness, lag=lag, cap=cap,
                     checked=bool(checked), fallback=fallback, f0=f0, f0_floor=float(f0_floor), f0_ceil=float(f0_ceil),
-                    f0_threshold=float(f0_threshold),
+                    f0_threshold=float(f0_threshold), f0_track=f0_track, track_lag=track_lag,
                     _slice=-(-max_push * (C + 1 + hop) // 4) * 4, _down_elems=n_streams * (cap * hop + 8 * (cap // core + 2)))
 
     def _allocate(self, cfg) -> None:
@@ -2114,6 +2267,14 @@ class StreamSession:
             # running source statistics: per stream two parity entries of (w, S1, S2, voiced frames), never zeroed - a stream's
             # first frame starts from zeros - addressed by the phase record's ``parity``
             self._f0_rec = torch.empty((n, 2, 4), dtype=torch.float64, device=dev)
+        self._f0_cand = self._f0_back = self._f0_track_rec = None
+        if self.f0_track is not None:
+            # the tracker: the final frames' candidates (frame f at f % cap: 4 x (tau_hat, s)), their backpointers and best
+            # state (8 bytes a frame) and per stream two parity entries of the recurrence's costs (5 of 8 doubles), never
+            # zeroed - a stream's first frame starts fresh - addressed by ``track_parity``
+            self._f0_cand = torch.empty((n, cap, 4, 2), dtype=torch.float32, device=dev)
+            self._f0_back = torch.empty((n, cap, 8), dtype=torch.uint8, device=dev)
+            self._f0_track_rec = torch.empty((n, 2, 8), dtype=torch.float64, device=dev)
         self._layout = StreamStitchLayout(n, hop, self.fade)
         self._stage = torch.empty(max(self._layout.stage_elems, 1), dtype=torch.float32, device=dev)
         self._emb = torch.zeros((n, max(int(cfg.spk_emb_size), 1)), dtype=torch.float32, device=dev)
@@ -2154,10 +2315,12 @@ class StreamSession:
                 model.use_activation_storage(first)
         return plans
 
-    latency_frames = property(lambda self: self.core + self.context + self.lag,
-                              doc="the typical delay, in frames of input: core + context (+ the loudness lag with loudness=\"audio\")")
-    latency_frames_max = property(lambda self: 2 * self.core + self.context + self.lag,
-                                  doc="the worst delay (the last fade / 2 frames of a core): 2 core + context (+ the loudness lag)")
+    latency_frames = property(lambda self: self.core + self.context + self.lag + self.track_lag,
+                              doc="the typical delay, in frames of input: core + context (+ the loudness lag with loudness=\"audio\""
+                                  ", + the tracker's lag with f0_track)")
+    latency_frames_max = property(lambda self: 2 * self.core + self.context + self.lag + self.track_lag,
+                                  doc="the worst delay (the last fade / 2 frames of a core): 2 core + context (+ the loudness lag, + "
+                                      "the tracker's lag)")
 
     def __enter__(self):
         return self
@@ -2174,6 +2337,7 @@ class StreamSession:
         self._ppg = self._lft = self._exc = self._phase = self._stage = self._emb = self._carry = self._norm_scratch = None
         self._report = self._h_report = None
         self._audio = self._peak = self._loud_scratch = self._f0_raw = self._f0_shift = self._f0_rec = None
+        self._f0_cand = self._f0_back = self._f0_track_rec = None
         self._h_up = self._d_up = self._h_down = self._up_done = None
         self._slots, self._ids = [None] * self.n_streams, {}
 
@@ -2212,7 +2376,7 @@ class StreamSession:
         key = (int(getattr(self.signal_generator, "seed", 0)) * 0x9E3779B97F4A7C15 + int(seed)) & 0xFFFFFFFFFFFFFFFF
         self._slots[s] = _Stream(id=sid, slot=s, emb=has_emb, seed=key, from_audio=self.loudness == "audio",
                                  stats=None if src_f0_stats is None else (list(src_f0_stats), list(trg_f0_stats)),
-                                 running=running)
+                                 running=running, track=self.f0_track is not None)
         if self.checked:
             self._slots[s].totals = dict(windows=0, fell_back=0, nonfinite=0, clipped=0, max_abs=0.0, storages={})
         self._ids[sid] = s
@@ -2277,7 +2441,9 @@ class StreamSession:
             self._append(parts, pushed)
         if self.loudness == "audio":
             final = self._finalise_loudness(ids, end)
-            if self.f0 == "audio" and final:
+            if self.f0_track is not None:
+                self._finalise_f0_tracked(final, ids, end)
+            elif self.f0 == "audio" and final:
                 self._finalise_f0(final)
         streams = sorted((self._slots[self._ids[sid]] for sid in ids), key=lambda st: st.slot)
         rows, forget = stream_push_rows(streams, end, self.core, self.context, self.norm == "running", self.horizon)
@@ -2414,6 +2580,56 @@ class StreamSession:
                     self._exc[st.slot].view(self.cap, self.hop)[idx].reshape(-1))
             st.first = False
             st.parity ^= 1                               # (enqueued: the other entry is the slot's phase now)
+
+    def _finalise_f0_tracked(self, final, ids: Sequence[int], end: Sequence[int]) -> None:
+        """``_finalise_f0`` of a session with ``f0_track``: the frames ``_finalise_loudness`` just finalised (``final``) get their
+        CANDIDATES from the audio ring and advance the tracker, and the frames whose tracked F0 became final with them
+        (``stream_tracked_frames``: ``track_lag`` behind, all at a stream's end - also of a stream that ends in a push that
+        finalises nothing) get it, its shift and their excitation: one ``stream_f0_tracked`` (the frames launch in candidate
+        mode, the tracker, the running shift when a stream runs statistics, the excitation), or nothing when no stream has
+        either.  Leaves ``tracked`` advanced, the tracker record's other entry current for a stream with new frames and the
+        phase (and statistics) record's for a stream that emitted.  Traces the new frames' ``"f0_candidates"`` and the emitted
+        frames' tracked raw F0 (``"f0"``), ``"f0_shifted"`` and ``"excitation"``."""
+        from .engine import stream_f0_tracked
+        sg, tk = self.signal_generator, self.f0_track
+        new = {e[0]: (e[1], e[2]) for e in final}        # slot -> (first newly final frame, how many)
+        work = []
+        for sid in ids:
+            st = self._slots[self._ids[sid]]
+            first, n = new.get(st.slot, (st.final, 0))
+            emit = stream_tracked_frames(st.final, sid in end, tk.lag) - st.tracked
+            if n or emit:
+                work.append((st, first, n, sid in end, emit))
+        if not work:
+            return
+        sts = [w[0] for w in work]
+        running = [st.running for st in sts] if any(st.running is not None for st in sts) else None
+        stream_f0_tracked(self._audio, self._f0_cand, self._f0_back, self._f0_raw, self._f0_shift, self._exc, self._phase,
+                          self._f0_rec if running is not None else None, self._f0_track_rec,
+                          [st.slot for st in sts], [w[1] for w in work], [w[2] for w in work], [st.seen for st in sts],
+                          [w[3] for w in work], [st.parity for st in sts], [st.track_parity for st in sts],
+                          [st.tracked for st in sts], [w[4] for w in work], [st.seed for st in sts],
+                          [None if st.stats is None else (*st.stats[0][:2], *st.stats[1][:2]) for st in sts], running,
+                          self.cap, self.max_push + self.lag + self.track_lag, float(sg.sample_rate), self.f0_floor, self.f0_ceil,
+                          tk.cand_threshold, tk.lag, tk.lag_bias, tk.jump, tk.switch,
+                          self.f0_threshold if tk.unvoiced is None else tk.unvoiced, float(sg.sine_amp), float(sg.noise_amp))
+        for st, first, n, _, emit in work:
+            tr = self._stream_trace
+            if tr is not None and n:
+                idx = (torch.arange(first, first + n, device=self.device) % self.cap)
+                tr.setdefault("f0_candidates", {}).setdefault(st.id, []).append(self._f0_cand[st.slot][idx])
+            if tr is not None and emit:
+                idx = (torch.arange(st.tracked, st.tracked + emit, device=self.device) % self.cap)
+                tr.setdefault("f0", {}).setdefault(st.id, []).append(self._f0_raw[st.slot][idx])
+                tr.setdefault("f0_shifted", {}).setdefault(st.id, []).append(self._f0_shift[st.slot][idx])
+                tr.setdefault("excitation", {}).setdefault(st.id, []).append(
+                    self._exc[st.slot].view(self.cap, self.hop)[idx].reshape(-1))
+            if n:
+                st.track_parity ^= 1                     # (enqueued: the other entry is the slot's tracker state now)
+            if emit:
+                st.tracked += emit
+                st.first = False
+                st.parity ^= 1                           # (enqueued: the other entry is the slot's phase now)
 
     def _forward_rows(self, chunk: Sequence[StreamRow], forget, seen: Sequence[int], off: int, report=None):
         """One forward over the rows ``chunk`` (at most ``max_batch``, as ``stream_push_rows`` orders them; ``forget``

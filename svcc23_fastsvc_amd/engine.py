@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     "fastsvc_stream_launch_count", "fastsvc_stream_push", "fastsvc_stream_assemble", "fastsvc_stream_check",
     "fastsvc_stream_loudness_scratch_bytes", "fastsvc_stream_loudness",
     "fastsvc_stream_f0", "fastsvc_stream_f0_running", "fastsvc_f0_lags", "fastsvc_f0_extract",
+    "fastsvc_f0_candidates", "fastsvc_f0_track_scratch_bytes", "fastsvc_f0_track", "fastsvc_stream_f0_tracked",
     "fastsvc_stft_loss_scratch_bytes", "fastsvc_stft_loss_forward", "fastsvc_stft_loss_backward",
     "fastsvc_conv1d_forward", "fastsvc_conv1d_backward_weight", "fastsvc_conv1d_backward_weight_scratch_bytes",
     "fastsvc_film_norm_forward", "fastsvc_film_norm_backward", "fastsvc_weight_norm_forward", "fastsvc_weight_norm_backward",
@@ -244,6 +245,19 @@ def load_library():
     lib.fastsvc_f0_lags.restype = ctypes.c_int
     lib.fastsvc_f0_extract.argtypes = [vp, vp, i32, i32, i32] + [ctypes.c_float] * 4 + [vp]
     lib.fastsvc_f0_extract.restype = ctypes.c_int
+    lib.fastsvc_f0_candidates.argtypes = [vp, vp, i32, i32, i32] + [ctypes.c_float] * 4 + [vp]
+    lib.fastsvc_f0_candidates.restype = ctypes.c_int
+    lib.fastsvc_f0_track_scratch_bytes.argtypes = [i32, i32]
+    lib.fastsvc_f0_track_scratch_bytes.restype = i64
+    lib.fastsvc_f0_track.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_float, i32] + [ctypes.c_double] * 4 + [vp]
+    lib.fastsvc_f0_track.restype = ctypes.c_int
+    lib.fastsvc_stream_f0_tracked.argtypes = [vp] * 9 + [i32, ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                              ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                              ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32] + [ctypes.c_float] * 4 + \
+        [i32] + [ctypes.c_double] * 4 + [ctypes.c_float] * 2 + [vp]
+    lib.fastsvc_stream_f0_tracked.restype = ctypes.c_int
     lib.fastsvc_autotune.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, ctypes.POINTER(i32)]
     lib.fastsvc_autotune.restype = ctypes.c_int
     lib.fastsvc_tuned_count.argtypes = [vp]
@@ -1027,6 +1041,57 @@ def stream_f0_running(audio_ring: torch.Tensor, f0_ring: torch.Tensor, f0s_ring:
                                                   ctypes.c_float(float(sine_amp)), ctypes.c_float(float(noise_amp)),
                                                   ctypes.c_void_p(stream)),
                "fastsvc_stream_f0_running")
+
+
+def stream_f0_tracked(audio_ring: torch.Tensor, cand_ring: torch.Tensor, bp_ring: torch.Tensor, f0_ring: torch.Tensor,
+                      f0s_ring: torch.Tensor, exc_ring: torch.Tensor, phase: torch.Tensor, record: Optional[torch.Tensor],
+                      track_record: torch.Tensor, streams: Sequence[int], first_frame: Sequence[int], n: Sequence[int],
+                      seen: Sequence[int], ended: Sequence[int], parity: Sequence[int], track_parity: Sequence[int],
+                      emit_first: Sequence[int], emit_n: Sequence[int], seed: Sequence[int],
+                      stats: Sequence[Optional[Sequence[float]]], running: Optional[Sequence[Optional[Sequence[float]]]], cap: int,
+                      max_frames: int, sample_rate: float, f0_floor: float, f0_ceil: float, cand_threshold: float, lag: int,
+                      lag_bias: float, jump: float, switch: float, unvoiced: float, sine_amp: float, noise_amp: float) -> None:
+    """``stream_f0_running`` with fixed-lag Viterbi tracking (``decode.F0Track``; fastsvc_stream_f0_tracked,
+    csrc/fastsvc_stream_f0.hip): the newly final frames ``[first_frame[i], + n[i])`` get their candidates into ``cand_ring
+    (n_streams, cap, 4, 2)`` float32 and advance the recurrence, whose state lives in ``track_record (n_streams, 2, 8)``
+    float64 (entry ``track_parity[i]`` read, the other written) and whose backpointers in ``bp_ring (n_streams, cap, 8)`` uint8;
+    the frames ``[emit_first[i], + emit_n[i])`` get the tracked raw F0, the shift (``stats`` / ``running`` with ``record``, which
+    may both be None) and the excitation.  The rule is in include/fastsvc_hip.h.  Anything out of range raises ``ValueError``
+    before a launch and changes nothing; fails loudly off the GPU."""
+    lib = load_library()
+    who = "stream_f0_tracked"
+    per, dims = _stream_f0_args(who, audio_ring, f0_ring, f0s_ring, exc_ring, phase, streams, first_frame, n, seen, ended, parity,
+                                seed, stats, cap, max_frames, sample_rate, f0_floor, f0_ceil)
+    S, n_streams = per[0], dims[0]
+    _gpu_tensors(who, audio_ring, (("cand_ring", cand_ring, torch.float32, 4), ("bp_ring", bp_ring, torch.uint8, 3),
+                                   ("track_record", track_record, torch.float64, 3)))
+    if tuple(cand_ring.shape) != (n_streams, cap, 4, 2) or tuple(bp_ring.shape) != (n_streams, cap, 8) or \
+            tuple(track_record.shape) != (n_streams, 2, 8):
+        raise ValueError(f"cand_ring must be ({n_streams}, {cap}, 4, 2), bp_ring ({n_streams}, {cap}, 8) and track_record "
+                         f"({n_streams}, 2, 8)")
+    if any(len(v) != S for v in (track_parity, emit_first, emit_n)):
+        raise ValueError(f"{who} needs one entry per stream in every array")
+    flat = None
+    if running is not None:
+        _gpu_tensors(who, audio_ring, (("record", record, torch.float64, 3),))
+        if tuple(record.shape) != (n_streams, 2, 4):
+            raise ValueError(f"record must be ({n_streams}, 2, 4), got {tuple(record.shape)}")
+        flat = []
+        for ru in running:
+            flat += [float("nan")] * 6 if ru is None else [float(v) for v in ru]
+        if len(flat) != 6 * S:
+            raise ValueError("running entries are (m_p, s_p, n0, g, m_t, s_t) or None, one per stream")
+        flat = (ctypes.c_double * len(flat))(*flat)
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    with torch.cuda.device(audio_ring.device):
+        stream = torch.cuda.current_stream(audio_ring.device).cuda_stream
+        _check(lib, lib.fastsvc_stream_f0_tracked(
+            _ptr(audio_ring), _ptr(cand_ring), _ptr(bp_ring), _ptr(f0_ring), _ptr(f0s_ring), _ptr(exc_ring), _ptr(phase),
+            _ptr(record) if running is not None else None, _ptr(track_record), *per[:7],
+            _ints(i32, [int(v) & 1 for v in track_parity]), _ints(i64, emit_first), _ints(i32, emit_n), per[7], per[8], flat, *dims,
+            ctypes.c_float(float(sample_rate)), ctypes.c_float(float(f0_floor)), ctypes.c_float(float(f0_ceil)),
+            ctypes.c_float(float(cand_threshold)), int(lag), float(lag_bias), float(jump), float(switch), float(unvoiced),
+            ctypes.c_float(float(sine_amp)), ctypes.c_float(float(noise_amp)), ctypes.c_void_p(stream)), "fastsvc_stream_f0_tracked")
 
 
 def check_norm_groups(norm_groups, lens: Sequence[int]):

@@ -42,7 +42,12 @@ per push in which a frame became final, stream_f0_running_kernel) against the sa
 the path as it was - on the same ppg and audio, 1, 8 and 32 streams at core 32 in both storages.  Reported, not gated.  Its
 figures go to profiles/decode_stream_f0_stats.txt.
 
-    python tools/stream_latency.py [--norm [--horizon H] | --audio | --f0 | --f0-stats | --checked]"""
+--f0-track: the pair is f0=audio streams in a session with f0_track=F0Track() (the frames launch makes candidates, one more
+launch runs the fixed-lag Viterbi tracker, stream_f0_track_kernel; the windows run 8 frames later) against the same streams
+with f0_track=None - the path as it was - on the same ppg and audio, 1, 8 and 32 streams at core 32 in both storages.
+Reported, not gated.  Its figures go to profiles/decode_stream_f0_track.txt.
+
+    python tools/stream_latency.py [--norm [--horizon H] | --audio | --f0 | --f0-stats | --f0-track | --checked]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -410,6 +415,66 @@ def main_f0_stats():
         f.write("\n".join(out) + "\n")
 
 
+def main_f0_track():
+    core = 32
+    lag = Dc.stream_loudness_lag(hop)
+    track = Dc.F0Track()
+    out = [f"stream F0 tracking: one StreamSession.push that completes one window per stream (every stream delivers {core} "
+           f"frames), host to host, f0_track=F0Track() (the push finalises {core} frames per stream, {lag} frames behind the audio: "
+           f"their YIN candidates, the Viterbi recurrence over them and the trace of the frames {track.lag} behind - one more "
+           f"launch, stream_f0_track_kernel - their shift and the excitation) against f0_track=None (the per-frame pick inside the "
+           f"frames launch), both loudness=audio, f0=audio on the same ppg and audio, two sessions in one process; context {ctx}, "
+           f"fade {FADE}, speaker embedding, F0 shift on, int16 out; {pushes} pushes per repetition, {reps} repetitions, legs "
+           f"alternated, median of the repetitions' means (min, max); {torch.cuda.get_device_name(0)}"]
+    print(out[0], flush=True)
+    t = np.arange(core * 8 * hop) / SR
+    for storage in ("float32", "bfloat16"):
+        m = build_model(storage)
+        out.append(f"--- activation storage {storage}")
+        for N in (1, 8, 32):
+            src = [features(core * 8) for _ in range(N)]
+            for i, f in enumerate(src):                  # (a voiced tone per stream over a little noise)
+                ph = 2.0 * np.pi * (110.0 + 7.0 * i) * t
+                f["audio"] = (0.3 * np.sin(ph) + 0.1 * np.sin(2.0 * ph) + 0.01 * rng.standard_normal(t.size)).astype(np.float32)[:, None]
+            legs = {}
+            for name, tk in (("untracked", None), ("tracked", track)):
+                s = Dc.StreamSession(m, sg, dev, n_streams=N, core=core, fade=FADE, max_push=core, loudness="audio", f0="audio",
+                                     f0_track=tk)
+                legs[name] = dict(s=s, ids=[s.open(emb, [5.0, 1.0], [5.3, 1.0], seed=i) for i in range(N)], step=0, t=[])
+
+            def push(leg):
+                a = (leg["step"] % 8) * core
+                leg["step"] += 1
+                return leg["s"].push({i: {"ppg": f["ppg"][a: a + core], "audio": f["audio"][a * hop: (a + core) * hop]}
+                                      for i, f in zip(leg["ids"], src)})
+            for leg in legs.values():
+                for _ in range(6):                       # (fill the context, warm every shape)
+                    push(leg)
+                before = leg["s"].forwards
+                got = push(leg)
+                assert leg["s"].forwards == before + 1 and all(v.size == core * hop for v in got.values())
+            for _ in range(reps):
+                for leg in legs.values():
+                    t0 = time.perf_counter()
+                    for _ in range(pushes):
+                        push(leg)
+                    leg["t"].append((time.perf_counter() - t0) / pushes)
+            latency = [legs[k]["s"].latency_frames for k in ("untracked", "tracked")]
+            for leg in legs.values():
+                leg["s"].end(leg["ids"])
+                leg["s"].close()
+            audio = N * core * hop / SR
+            mu, line_u = spread(f"{N:2d} streams, core {core:3d}: push, f0_track=None", legs["untracked"]["t"], audio)
+            mt, line_t = spread(f"{N:2d} streams, core {core:3d}: push, f0_track=F0Track()", legs["tracked"]["t"], audio)
+            out += [line_u, line_t, f"    tracked / untracked {mt / mu:.3f} ({(mt - mu) * 1e3:+.0f} us a push; spread of the untracked leg "
+                                    f"{(max(legs['untracked']['t']) - min(legs['untracked']['t'])) * 1e6:.0f} us; latency "
+                                    f"{latency[0]} -> {latency[1]} frames)"]
+            print("\n".join(out[-3:]), flush=True)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "decode_stream_f0_track.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 def main_checked():
     core, storage = 32, "float16"
     out = [f"checked streams: one StreamSession.push that completes one window per stream (every stream delivers {core} frames), "
@@ -465,6 +530,8 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     if "--checked" in argv:
         main_checked()
+    elif "--f0-track" in argv:
+        main_f0_track()
     elif "--f0-stats" in argv:
         main_f0_stats()
     elif "--f0" in argv:
